@@ -3,12 +3,19 @@
 
     GiB/s of plaintext, AES-256-GCM, 16 GiB stream per GPU, bit-exact tag
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path (fused AES-CTR + GHASH kernel, fold/combine kernels, 16-byte tag to
 host) over the whole resident workload.
+
+A plain run sets up, warms up, times --steps steps, checks the tags against the committed fixtures and prints the line
+(`ms_per_step`: wall milliseconds of one timed step).  --full adds what takes passes of its own: the CPU baseline
+(`cpu_baseline`, skipped with --no-cpu-baseline) and, after the timed steps, `roofline` (per-launch HIP-event timing, shader
+clock, the formulation's ceiling, the copy kernel, the PMC traffic of this build).  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy: the output data (a fixed, seeded sample of 4 KiB pieces when it exceeds 8 MiB) with
+its byte offsets, and the tags with their indices.
 
   N = 1   configs[2] of BASELINE.json ("cfg3"): ONE AES-256-GCM message of 16 GiB, SplitMix64 plaintext seed
           0xAE5C0003, already resident in HBM; ciphertext written to a second 16 GiB buffer.  The tag of the first
@@ -157,6 +164,65 @@ def sclk_from_trace(trace, waves_per_wg):
         if t1 > t0 and kc:
             v.append((kc * 1024.0 / waves_per_wg) / ((t1 - t0) * 10e-9) / 1e6)
     return round(statistics.median(v), 0) if v else None
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_SEED = 0xD0D0                     # the sample of a large output is fixed: same arguments, same bytes compared
+DUMP_CHUNK = 4096                      # bytes per sampled piece of a data buffer
+DUMP_DATA_BYTES = 8 << 20              # at most this many bytes of a data buffer (as float32: 32 MiB)
+DUMP_TAGS = 1 << 16                    # at most this many tags (as float32: 4 MiB)
+
+
+def _seeded_rows(n, k, seed):
+    """about k of the n indices [0, n) -- all of them when n <= k, else the first, the last and a seeded draw -- sorted"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, size=k - 2)])).astype(np.int64)
+
+
+def sample_data(d_buf, nbytes, offset=0, seed=DUMP_SEED):
+    """what a caller would download from bytes [offset, offset + nbytes) of a device buffer: all of it when it is at most
+    DUMP_DATA_BYTES, else DUMP_CHUNK-byte pieces at fixed, seeded places -> (float32 values 0 .. 255, float64 byte offsets)"""
+    import numpy as np
+    if nbytes <= DUMP_DATA_BYTES:
+        return np.frombuffer(bytes(d_buf.download(nbytes, offset)), dtype=np.uint8).astype(np.float32), np.array([0.0])
+    rows = _seeded_rows(nbytes // DUMP_CHUNK, DUMP_DATA_BYTES // DUMP_CHUNK, seed)
+    out = np.empty((len(rows), DUMP_CHUNK), dtype=np.float32)
+    for i, r in enumerate(rows):
+        out[i] = np.frombuffer(bytes(d_buf.download(DUMP_CHUNK, offset + int(r) * DUMP_CHUNK)), dtype=np.uint8)
+    return out, rows.astype(np.float64) * DUMP_CHUNK
+
+
+def sample_tags(tags, seed=DUMP_SEED):
+    """16-byte tags (one bytes object, back to back) -> (float32 [k, 16], float64 tag indices): all of them, or a fixed, seeded
+    sample of DUMP_TAGS"""
+    import numpy as np
+    t = np.frombuffer(tags, dtype=np.uint8).reshape(-1, 16)
+    rows = _seeded_rows(len(t), DUMP_TAGS, seed + 1)
+    return t[rows].astype(np.float32), rows.astype(np.float64)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy (float32 / float64), 64 MB at most in all"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        np.save(os.path.join(d, name + ".npy"), a)
+    assert total <= 64 << 20, total
+    log("bench.py: wrote %d arrays (%d bytes) to %s" % (len(arrays), total, d))
+
+
+def data_arrays(role, d_buf, nbytes, tags, offset=0):
+    """the outputs of a step: a sample of its data (`role`: ciphertext or plaintext) and its tags"""
+    data, data_off = sample_data(d_buf, nbytes, offset)
+    t, t_idx = sample_tags(tags)
+    return {role: data, role + "_offsets": data_off, "tags": t, "tags_index": t_idx}
 
 
 # ------------------------------------------------------------------------------------------------ self-launch
@@ -407,11 +473,14 @@ def run_cfg5(args, rank, world, dev, ex, cpu_base):
         if tag_ok is not None:
             tag_ok = bool(ok)
     value = n * N * pkt * args.steps / dt / GiB
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, data_arrays("plaintext" if args.decrypt else "ciphertext", d_pt if args.decrypt else d_ct, pkt * n,
+                                                    bytes(d_tags.download())))
 
-    # ---- the kernel's own duration: HIP events on the stream it is launched on (the NULL stream), separate short pass
+    # ---- the kernel's own duration: HIP events on the stream it is launched on (the NULL stream), separate short pass (--full)
     tm = lib.Timer(device=dev)
     k_ms = []
-    for _ in range(min(5, max(1, args.steps))):
+    for _ in range(min(5, max(1, args.steps)) if args.full else 0):
         tm.start(None)
         step()
         tm.stop(None)
@@ -419,7 +488,7 @@ def run_cfg5(args, rank, world, dev, ex, cpu_base):
     # ---- the formulation's ceiling: the same kernel without the data's loads and stores (aesgcm_batch_ceiling_probe_dev; 8 lanes per packet only), same process,
     #      same clocks -- how far the launch is from what per-packet aes_kexp + T-table AES + Shoup GHASH cost by themselves on this chip (round-4 verdict, Next 2)
     c_ms = []
-    if not args.decrypt and not args.batch_lanes and lib.batch_shape(n, pkt, device=dev) == 8:
+    if args.full and not args.decrypt and not args.batch_lanes and lib.batch_shape(n, pkt, device=dev) == 8:
         try:
             lib.batch_ceiling_probe_dev(n, kb, d_keys.ptr, d_ivs.ptr, pkt, d_tags.ptr, device=dev)
             lib.dev_sync(dev)
@@ -432,7 +501,8 @@ def run_cfg5(args, rank, world, dev, ex, cpu_base):
             log("bench.py: cfg5 ceiling probe failed: %r" % (e,))
             c_ms = []
     tm.close()
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         avg_s = statistics.mean(k_ms) / 1e3
         alg_bytes = n * (2 * pkt + kb + 12 + 16)                  # per packet: data read + written, key, IV, tag
         achieved = alg_bytes / avg_s
@@ -457,6 +527,7 @@ def run_cfg5(args, rank, world, dev, ex, cpu_base):
                                                "avg_launch_ms": round(c_s * 1e3, 4), "gib_per_s": round(n * pkt / c_s / GiB, 1), "alg_gb_per_s": round(alg_bytes / c_s / 1e9, 1),
                                                "frac_of_hbm_peak": round(alg_bytes / c_s / HBM_PEAK_BYTES_PER_S, 4)}
             roofline["achieved_over_ceiling"] = round(c_s / avg_s, 4)
+    if rank == 0:
         line = {
             "metric": "GiB/s plaintext, AES-%d-GCM, %d independent %d-byte packets, per-packet key/IV, bit-exact tags" % (key_bits, n * N, pkt),
             "value": round(value, 3), "unit": "GiB/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -469,8 +540,10 @@ def run_cfg5(args, rank, world, dev, ex, cpu_base):
                        "packets_per_gpu": n, "pkt_len": pkt, "key_bits": key_bits, "mpkt_per_s": round(n * N * args.steps / dt / 1e6, 2),
                        "parallelism": "single" if N == 1 else "replicas%d" % N,
                        "exchange": None if ex is None else {"backend": ex.name, "ranks_seen": ex.world, "use": "barrier and max-over-ranks timing only", "torch": "not imported"}},
-            "tag_ok": tag_ok, "tags_sha256": tags_sha, "roofline": roofline,
+            "tag_ok": tag_ok, "tags_sha256": tags_sha,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if cpu_base is not None:
             line["cpu_baseline"] = cpu_base
         emit(line)
@@ -565,9 +638,12 @@ def run_msgs(args, rank, world, dev, ex, cpu_base):
         dt = ex.allreduce(dt, "max")
         tag_ok = bool(ex.allreduce(1.0 if tag_ok else 0.0, "min"))
     value = n * N * size * args.steps / dt / GiB
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, data_arrays("plaintext" if args.decrypt else "ciphertext", d_pt if args.decrypt else d_ct, size * n,
+                                                    bytes(d_tags.download())))
     tm = lib.Timer(device=dev)
     k_ms = []
-    for _ in range(min(5, max(1, args.steps))):
+    for _ in range(min(5, max(1, args.steps)) if args.full else 0):
         tm.start(ctx.stream())
         step()
         tm.stop(ctx.stream())
@@ -575,12 +651,6 @@ def run_msgs(args, rank, world, dev, ex, cpu_base):
     tm.close()
     if rank != 0:
         return tag_ok
-    avg_s = statistics.mean(k_ms) / 1e3
-    alg_bytes = n * (2 * size + 12 + 16 + al)
-    achieved = alg_bytes / avg_s
-    so_sha = sha256_file(SO)
-    pm = pmc_summary("rows_1m") if (n, N, size, key_bits, al) == (cfg["n_pkts"], 1, cfg["pkt_len"], cfg["key_bits"], 0) and not args.decrypt and not args.scattered else {}
-    same_build = bool(pm) and pm.get("so_sha256") == so_sha
     nr = key_bits // 32 + 6
     line = {
         "metric": "GiB/s plaintext, AES-%d-GCM, %d messages of %d bytes%s under one key as %s, bit-exact tags" % (key_bits, n * N, size, " with %d bytes of AAD each" % al if al else "",
@@ -593,13 +663,20 @@ def run_msgs(args, rank, world, dev, ex, cpu_base):
                    "parallelism": "single" if N == 1 else "replicas%d" % N,
                    "exchange": None if ex is None else {"backend": ex.name, "ranks_seen": ex.world, "use": "barrier and max-over-ranks timing only", "torch": "not imported"}},
         "tag_ok": tag_ok, "tags_checked": len(sample),
-        "roofline": {"bound": "hbm", "kernel": ("k_rows<%d,%d> + k_rows_close (the rows of all messages through k_body's row loop; one call)" % (nr, int(args.decrypt))) if shape == lib.SHAPE_ROWS else "the packet kernels",
-                     "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
-                     "traffic": pm.get("hbm_bytes_per_launch") if same_build else None, "traffic_source": "profiles/pmc_rows_1m.json" if pm else None,
-                     "traffic_build": {"pmc_so_sha256": pm.get("so_sha256"), "running_so_sha256": so_sha, "running_git": git_head(), "match": same_build},
-                     "alg_bytes_per_launch": alg_bytes, "launches_timed": len(k_ms), "avg_launch_ms": round(avg_s * 1e3, 4),
-                     "timing": "HIP events on the context's stream around each call (both launches) in a separate %d-step pass after the timed region" % len(k_ms)},
     }
+    if args.full:
+        avg_s = statistics.mean(k_ms) / 1e3
+        alg_bytes = n * (2 * size + 12 + 16 + al)
+        achieved = alg_bytes / avg_s
+        so_sha = sha256_file(SO)
+        pm = pmc_summary("rows_1m") if (n, N, size, key_bits, al) == (cfg["n_pkts"], 1, cfg["pkt_len"], cfg["key_bits"], 0) and not args.decrypt and not args.scattered else {}
+        same_build = bool(pm) and pm.get("so_sha256") == so_sha
+        line["roofline"] = {"bound": "hbm", "kernel": ("k_rows<%d,%d> + k_rows_close (the rows of all messages through k_body's row loop; one call)" % (nr, int(args.decrypt))) if shape == lib.SHAPE_ROWS else "the packet kernels",
+                            "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
+                            "traffic": pm.get("hbm_bytes_per_launch") if same_build else None, "traffic_source": "profiles/pmc_rows_1m.json" if pm else None,
+                            "traffic_build": {"pmc_so_sha256": pm.get("so_sha256"), "running_so_sha256": so_sha, "running_git": git_head(), "match": same_build},
+                            "alg_bytes_per_launch": alg_bytes, "launches_timed": len(k_ms), "avg_launch_ms": round(avg_s * 1e3, 4),
+                            "timing": "HIP events on the context's stream around each call (both launches) in a separate %d-step pass after the timed region" % len(k_ms)}
     if cpu_base is not None:
         line["cpu_baseline"] = cpu_base
     emit(line)
@@ -704,48 +781,54 @@ def run_frames(args, rank, world, dev, ex, cpu_base):
     else:
         total_all = float(total)
     value = total_all * args.steps / dt / GiB
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, data_arrays("plaintext" if args.decrypt else "ciphertext", d_pt if args.decrypt else d_ct, total,
+                                                    bytes(d_tags.download())))
     tm = lib.Timer(device=dev)
     k_ms, c_ms = [], []
-    for _ in range(min(7, max(1, args.steps))):
-        tm.start(ctx.stream()); step(); tm.stop(ctx.stream())
-        k_ms.append(tm.ms())
-    if not args.decrypt:
-        try:
-            ctx.frames_ceiling_probe_dev(n, d_ivs.ptr, d_doff.ptr, d_tags.ptr, **akw)
-            lib.dev_sync(dev)
-            for _ in range(min(7, max(1, args.steps))):
-                tm.start(ctx.stream()); ctx.frames_ceiling_probe_dev(n, d_ivs.ptr, d_doff.ptr, d_tags.ptr, **akw); tm.stop(ctx.stream())
-                c_ms.append(tm.ms())
-            probe_route = ctx.last_route()
-        except lib.AesGcmError as e:
-            log("bench.py: frames ceiling probe failed: %r" % (e,))
-            c_ms = []
+    if args.full:                                               # per-call timing and the ceiling of the formulation: passes of their own
+        for _ in range(min(7, max(1, args.steps))):
+            tm.start(ctx.stream()); step(); tm.stop(ctx.stream())
+            k_ms.append(tm.ms())
+        if not args.decrypt:
+            try:
+                ctx.frames_ceiling_probe_dev(n, d_ivs.ptr, d_doff.ptr, d_tags.ptr, **akw)
+                lib.dev_sync(dev)
+                for _ in range(min(7, max(1, args.steps))):
+                    tm.start(ctx.stream()); ctx.frames_ceiling_probe_dev(n, d_ivs.ptr, d_doff.ptr, d_tags.ptr, **akw); tm.stop(ctx.stream())
+                    c_ms.append(tm.ms())
+                probe_route = ctx.last_route()
+            except lib.AesGcmError as e:
+                log("bench.py: frames ceiling probe failed: %r" % (e,))
+                c_ms = []
     tm.close()
     if rank != 0:
         return tag_ok
-    avg_s = statistics.mean(k_ms) / 1e3
-    alg_bytes = int(2 * total + n * (al + 12 + 16))
-    achieved = alg_bytes / avg_s
-    so_sha = sha256_file(SO)
-    pm = pmc_summary("frames") if standard and N == 1 else {}
-    same_build = bool(pm) and pm.get("so_sha256") == so_sha
-    nr = key_bits // 32 + 6
-    lanes = int(route["lanes"])
-    kname = ("k_pktl<%d,%d,0>" % (nr, int(args.decrypt))) if lanes == 1 else ("k_pktg<%d,%d,%d>" % (nr, int(args.decrypt), {4: 2, 8: 3, 16: 4, 64: 6}.get(lanes, 0))) if lanes else "k_rows (the device sent every frame by rows)"
-    roofline = {"bound": "hbm", "kernel": "%s: %d lane(s) per frame, frames taken by falling size class (k_len_hist / _scan / _scatter in front; the device's route: mark %d, %d of %d frames to the packet kernels)"
-                                          % (kname, lanes, route["route_min"], route["n_small"], n),
-                "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
-                "traffic": pm.get("hbm_bytes_per_launch") if same_build else None, "traffic_source": "profiles/pmc_frames.json" if pm else None,
-                "traffic_build": {"pmc_so_sha256": pm.get("so_sha256"), "running_so_sha256": so_sha, "running_git": git_head(), "match": same_build},
-                "alg_bytes_per_launch": alg_bytes, "alg_bytes": "per frame 2 x length + %d (AAD) + 12 (IV) + 16 (tag)" % al, "launches_timed": len(k_ms), "avg_launch_ms": round(avg_s * 1e3, 4),
-                "timing": "HIP events on the context's stream around each call (the sort, the packet kernel, the empty row launches) in a separate %d-step pass after the timed region" % len(k_ms),
-                "lds_busy_frac": (pm.get("lds") or {}).get("lds_busy_frac") if same_build else None}
-    if c_ms:
-        c_s = statistics.mean(c_ms) / 1e3
-        roofline["formulation_ceiling"] = {"kernel": "the same call with the packet kernel in its PROBE form (%d lane(s) per frame: the instruction stream without the data's loads and stores; IVs, offsets, AAD and tags still move)" % int(probe_route["lanes"]),
-                                           "avg_launch_ms": round(c_s * 1e3, 4), "gib_per_s": round(total / c_s / GiB, 1), "alg_gb_per_s": round(alg_bytes / c_s / 1e9, 1),
-                                           "frac_of_hbm_peak": round(alg_bytes / c_s / HBM_PEAK_BYTES_PER_S, 4)}
-        roofline["achieved_over_ceiling"] = round(c_s / avg_s, 4)
+    roofline = None
+    if args.full:
+        avg_s = statistics.mean(k_ms) / 1e3
+        alg_bytes = int(2 * total + n * (al + 12 + 16))
+        achieved = alg_bytes / avg_s
+        so_sha = sha256_file(SO)
+        pm = pmc_summary("frames") if standard and N == 1 else {}
+        same_build = bool(pm) and pm.get("so_sha256") == so_sha
+        nr = key_bits // 32 + 6
+        lanes = int(route["lanes"])
+        kname = ("k_pktl<%d,%d,0>" % (nr, int(args.decrypt))) if lanes == 1 else ("k_pktg<%d,%d,%d>" % (nr, int(args.decrypt), {4: 2, 8: 3, 16: 4, 64: 6}.get(lanes, 0))) if lanes else "k_rows (the device sent every frame by rows)"
+        roofline = {"bound": "hbm", "kernel": "%s: %d lane(s) per frame, frames taken by falling size class (k_len_hist / _scan / _scatter in front; the device's route: mark %d, %d of %d frames to the packet kernels)"
+                                              % (kname, lanes, route["route_min"], route["n_small"], n),
+                    "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
+                    "traffic": pm.get("hbm_bytes_per_launch") if same_build else None, "traffic_source": "profiles/pmc_frames.json" if pm else None,
+                    "traffic_build": {"pmc_so_sha256": pm.get("so_sha256"), "running_so_sha256": so_sha, "running_git": git_head(), "match": same_build},
+                    "alg_bytes_per_launch": alg_bytes, "alg_bytes": "per frame 2 x length + %d (AAD) + 12 (IV) + 16 (tag)" % al, "launches_timed": len(k_ms), "avg_launch_ms": round(avg_s * 1e3, 4),
+                    "timing": "HIP events on the context's stream around each call (the sort, the packet kernel, the empty row launches) in a separate %d-step pass after the timed region" % len(k_ms),
+                    "lds_busy_frac": (pm.get("lds") or {}).get("lds_busy_frac") if same_build else None}
+        if c_ms:
+            c_s = statistics.mean(c_ms) / 1e3
+            roofline["formulation_ceiling"] = {"kernel": "the same call with the packet kernel in its PROBE form (%d lane(s) per frame: the instruction stream without the data's loads and stores; IVs, offsets, AAD and tags still move)" % int(probe_route["lanes"]),
+                                               "avg_launch_ms": round(c_s * 1e3, 4), "gib_per_s": round(total / c_s / GiB, 1), "alg_gb_per_s": round(alg_bytes / c_s / 1e9, 1),
+                                               "frac_of_hbm_peak": round(alg_bytes / c_s / HBM_PEAK_BYTES_PER_S, 4)}
+            roofline["achieved_over_ceiling"] = round(c_s / avg_s, 4)
     line = {
         "metric": "GiB/s plaintext, AES-%d-GCM, %d frames of 64 .. 1514 bytes with %d bytes of AAD each under one key (offset arrays, one call), bit-exact tags" % (key_bits, n * N, al),
         "value": round(value, 3), "unit": "GiB/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -756,8 +839,10 @@ def run_frames(args, rank, world, dev, ex, cpu_base):
                    "frames_per_gpu": n, "bytes_per_gpu": total, "mean_frame_bytes": round(total / n, 1), "aad_bytes": al, "key_bits": key_bits, "mframes_per_s": round(n * N * args.steps / dt / 1e6, 2),
                    "parallelism": "single" if N == 1 else "replicas%d" % N,
                    "exchange": None if ex is None else {"backend": ex.name, "ranks_seen": ex.world, "use": "barrier and max-over-ranks timing only", "torch": "not imported"}},
-        "tag_ok": tag_ok, "tags_checked": len(sample), "roofline": roofline,
+        "tag_ok": tag_ok, "tags_checked": len(sample),
     }
+    if roofline is not None:
+        line["roofline"] = roofline
     if cpu_base is not None:
         line["cpu_baseline"] = cpu_base
     emit(line)
@@ -797,12 +882,17 @@ def run_inflight(args, dev):
     # the queued and the waited form run the same launches; tests/test_gpu_cyclic.py and tests/test_gpu_inflight.py hold both to the oracle)
     ref = [ctxs[0].encrypt_dev(ivs[r], d_pt.ptr + r * size, size, d_ct.ptr + r * size) for r in range(R)]
     pending = [None] * K
+    last_i = [-1] * K
     bad = [0]
+    last = [-1, None, None]                                      # the latest message collected: its number, ring slot and tag
 
     def collect(j):
         if pending[j] is not None:
-            if ctxs[j].last_tag() != ref[pending[j]]:
+            t = ctxs[j].last_tag()
+            if t != ref[pending[j]]:
                 bad[0] += 1
+            if last_i[j] > last[0]:
+                last[:] = [last_i[j], pending[j], t]
             pending[j] = None
 
     def run(n, i0):
@@ -810,7 +900,7 @@ def run_inflight(args, dev):
             j, r = i % K, i % R
             collect(j)
             ctxs[j].encrypt_dev(ivs[r], d_pt.ptr + r * size, size, d_ct.ptr + r * size, want_tag=False)
-            pending[j] = r
+            pending[j], last_i[j] = r, i
         for j in range(K):
             collect(j)
         return i0 + n
@@ -825,19 +915,8 @@ def run_inflight(args, dev):
     lib.dev_sync(dev)
     dt = time.perf_counter() - t0
     value = size * steps / dt / GiB
-    # the kernel alone: HIP events around each launch on its stream, ONE context, launches back to back, waited
-    c0 = ctxs[0]
-    c0.timing_enable(True)
-    c0.timing_read(reset=True)
-    for r in range(min(R, 8)):
-        c0.encrypt_dev(ivs[r], d_pt.ptr + r * size, size, d_ct.ptr + r * size)
-    lib.dev_sync(dev)
-    n_launch, kernel_ms = c0.timing_read(reset=True)
-    c0.timing_enable(False)
-    avg_s = kernel_ms / 1e3 / max(n_launch, 1)
-    _, body_blocks = c0.split(size, 0)
-    blocks = body_blocks if body_blocks else size // 16
-    achieved = 32 * blocks / avg_s if avg_s > 0 else 0.0
+    if args.dump_outputs:                                        # the last message of the timed region: its ciphertext and its tag
+        dump_outputs(args.dump_outputs, data_arrays("ciphertext", d_ct, size, last[2], offset=last[1] * size))
     line = {
         "metric": "GiB/s plaintext, AES-%d-GCM, %.6g MiB messages, %d in flight, bit-exact tags" % (key_bits, size / (1 << 20), K),
         "value": round(value, 3), "unit": "GiB/s", "n_gpus": 1, "steps": steps, "warmup": warm,
@@ -846,12 +925,26 @@ def run_inflight(args, dev):
                                "the host slot), ring of %d message buffers = %.3g GiB, SplitMix64 PT seed 0xAE5C0003, empty AAD" % (key_bits, size, K, R, size * R / GiB),
                    "bytes_per_message": size, "inflight": K, "ring": R, "half_shape": {-1: "library rule (when another context has a message under way)", 0: "never", 1: "always"}[args.half], "context_options": args.opt, "parallelism": "single", "key_bits": key_bits, "us_per_message": round(dt / steps * 1e6, 2)},
         "tag_ok": bad[0] == 0, "tags_checked": steps + warm, "tags_wrong": bad[0],
-        "roofline": {"bound": "hbm", "kernel": "%s<%d,ENC> (fused AES-CTR + GHASH), one message at a time" % ("k_body" if body_blocks else "k_main", key_bits // 32 + 6),
-                     "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
-                     "traffic": None, "alg_bytes_per_launch": 32 * blocks, "launches_timed": n_launch, "avg_launch_ms": round(avg_s * 1e3, 5),
-                     "sustained_frac": round(2 * size * steps / dt / HBM_PEAK_BYTES_PER_S, 4),
-                     "timing": "HIP events on the launch stream, one context, waited calls, separate pass after the timed region"},
     }
+    if args.full:
+        # the kernel alone: HIP events around each launch on its stream, ONE context, launches back to back, waited
+        c0 = ctxs[0]
+        c0.timing_enable(True)
+        c0.timing_read(reset=True)
+        for r in range(min(R, 8)):
+            c0.encrypt_dev(ivs[r], d_pt.ptr + r * size, size, d_ct.ptr + r * size)
+        lib.dev_sync(dev)
+        n_launch, kernel_ms = c0.timing_read(reset=True)
+        c0.timing_enable(False)
+        avg_s = kernel_ms / 1e3 / max(n_launch, 1)
+        _, body_blocks = c0.split(size, 0)
+        blocks = body_blocks if body_blocks else size // 16
+        achieved = 32 * blocks / avg_s if avg_s > 0 else 0.0
+        line["roofline"] = {"bound": "hbm", "kernel": "%s<%d,ENC> (fused AES-CTR + GHASH), one message at a time" % ("k_body" if body_blocks else "k_main", key_bits // 32 + 6),
+                            "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
+                            "traffic": None, "alg_bytes_per_launch": 32 * blocks, "launches_timed": n_launch, "avg_launch_ms": round(avg_s * 1e3, 5),
+                            "sustained_frac": round(2 * size * steps / dt / HBM_PEAK_BYTES_PER_S, 4),
+                            "timing": "HIP events on the launch stream, one context, waited calls, separate pass after the timed region"}
     emit(line)
     if bad[0]:
         log("PARITY FAILURE: %d of %d queued tags differ from the waited call's" % (bad[0], steps + warm))
@@ -952,26 +1045,35 @@ def run_single_process(args):
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     sync_all()
     dt = time.perf_counter() - t0
     value = per_gpu * N * args.steps / dt / GiB
+    if args.dump_outputs:                                         # device 0's ciphertext and every message's tag
+        dump_outputs(args.dump_outputs, data_arrays("ciphertext", d_ct[0], per_gpu, b"".join(last)))
 
-    ctx0 = mg.context(0)                                          # device 0's fused kernel under HIP events, separate short pass
-    ctx0.timing_enable(True)
-    ctx0.timing_read(reset=True)
-    for _ in range(min(3, max(1, args.steps))):
-        step()
-    sync_all()
-    n_launch, kernel_ms = ctx0.timing_read(reset=True)
-    ctx0.timing_enable(False)
+    ctx0 = mg.context(0)
     m0 = plans[0][0]
     _, body_blocks = ctx0.split(m0["len"], m0["first_block"])
-    blocks_per_launch = body_blocks if body_blocks else m0["len"] // 16
-    avg_s = kernel_ms / 1e3 / max(n_launch, 1)
-    alg_bytes = 32 * blocks_per_launch
-    achieved = alg_bytes / avg_s if avg_s > 0 else 0.0
     geo = ctx0.geometry(body=bool(body_blocks))
+    roofline = None
+    if args.full:                                                 # device 0's fused kernel under HIP events, separate short pass
+        ctx0.timing_enable(True)
+        ctx0.timing_read(reset=True)
+        for _ in range(min(3, max(1, args.steps))):
+            step()
+        sync_all()
+        n_launch, kernel_ms = ctx0.timing_read(reset=True)
+        ctx0.timing_enable(False)
+        blocks_per_launch = body_blocks if body_blocks else m0["len"] // 16
+        avg_s = kernel_ms / 1e3 / max(n_launch, 1)
+        alg_bytes = 32 * blocks_per_launch
+        achieved = alg_bytes / avg_s if avg_s > 0 else 0.0
+        roofline = {"bound": "hbm", "kernel": "%s<%d,ENC> (fused AES-CTR + GHASH), device 0" % ("k_body" if body_blocks else "k_main", key_bits // 32 + 6),
+                    "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
+                    "traffic": None, "alg_bytes_per_launch": alg_bytes, "launches_timed": n_launch, "avg_launch_ms": round(avg_s * 1e3, 4),
+                    "timing": "HIP events on device 0's launch stream in a separate pass after the timed region",
+                    "traffic_build": {"running_so_sha256": sha256_file(SO), "running_git": git_head()}}
     line = {
         "metric": "GiB/s plaintext, AES-%d-GCM %.3g GiB stream, bit-exact tag" % (key_bits, cfg["gib"]),
         "value": round(value, 3), "unit": "GiB/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -983,12 +1085,9 @@ def run_single_process(args):
                    "workgroups": geo["workgroups"], "wg_lanes": geo["wg_lanes"], "lds_bytes_per_wg": geo["lds_bytes"],
                    "exchange": {"backend": "rccl (single process)", "ranks_seen": mg.n_ranks, "init": "ncclCommInitAll", "torch": "not imported"}},
         "tag_ok": tag_ok, "validated": validated, "tags": [t.hex() for t in tags],
-        "roofline": {"bound": "hbm", "kernel": "%s<%d,ENC> (fused AES-CTR + GHASH), device 0" % ("k_body" if body_blocks else "k_main", key_bits // 32 + 6),
-                     "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK_BYTES_PER_S / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_BYTES_PER_S, 4),
-                     "traffic": None, "alg_bytes_per_launch": alg_bytes, "launches_timed": n_launch, "avg_launch_ms": round(avg_s * 1e3, 4),
-                     "timing": "HIP events on device 0's launch stream in a separate pass after the timed region",
-                     "traffic_build": {"running_so_sha256": sha256_file(SO), "running_git": git_head()}},
     }
+    if roofline is not None:
+        line["roofline"] = roofline
     emit(line)
     ok = mg.n_ranks == N and tag_ok is not False and validated
     mg.close()
@@ -1011,7 +1110,13 @@ def main(argv=None):
     ap.add_argument("--scattered", action="store_true", help="--config msgs: the same messages through aesgcm_messages_crypt_dev (device arrays of addresses and lengths: messages wherever they live)")
     ap.add_argument("--aad-len", type=int, default=None, help="--config msgs: bytes of AAD per message (a header: 13 for TLS-shaped records; default none); --config frames: default 28")
     ap.add_argument("--decrypt", action="store_true", help="time decrypt + authenticate instead of encrypt (N = 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure as well: the CPU baseline (before the GPU is touched) and, after the timed steps, the passes of "
+                         "their own behind `roofline` (per-launch HIP-event timing, shader clock, the formulation's ceiling, the copy kernel, the PMC traffic of this build)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, 64 MB at most): the output data "
+                         "(all of it, or %d-byte pieces at fixed, seeded places), their byte offsets, the tags and their indices" % DUMP_CHUNK)
     ap.add_argument("--backend", default="rccl", choices=("rccl", "nccl", "file", "gloo"),
                     help="exchange for N > 1: rccl (= nccl, the product: RCCL inside the library) or file (= gloo of round 1: "
                          "debug, partials through the host, for several ranks on ONE GPU; needs --allow-file-exchange)")
@@ -1050,6 +1155,9 @@ def main(argv=None):
     if args.gib_per_gpu is not None and not args.gib_per_gpu > 0:
         log("bench.py: --gib-per-gpu must be positive")
         return 2
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        log("bench.py: --steps must be at least 1 and --warmup at least 0")
+        return 2
     est_ms = None
     if args.config == "frames":                                  # ~1.4 ms per 2^20 frames
         est_ms = 1.4 * (args.n_pkts or CONFIGS["frames"]["n_pkts"]) / (1 << 20) / max(args.gpus, 1)
@@ -1083,9 +1191,9 @@ def main(argv=None):
         log("bench.py: --emulate-rank R --of W runs on one GPU (--gpus 1), 0 <= R < W, stream configs only")
         return 2
 
-    # ---- CPU baseline FIRST: its worker processes are forked before this process touches the GPU
+    # ---- CPU baseline FIRST (--full): its worker processes are forked before this process touches the GPU
     cpu_base = None
-    if N == 1 and rank == 0 and not args.no_cpu_baseline and emu is None:
+    if args.full and N == 1 and rank == 0 and not args.no_cpu_baseline and emu is None:
         try:
             cpu_base = cpu_baseline(args.config)
         except Exception as e:                                  # the baseline must never break the bench line
@@ -1303,7 +1411,7 @@ def main(argv=None):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
 
@@ -1315,27 +1423,31 @@ def main(argv=None):
 
     total_bytes = per_gpu * N * args.steps
     value = total_bytes / dt / GiB
+    if args.dump_outputs and rank == 0:                            # this rank's output buffer and every message's tag
+        dump_outputs(args.dump_outputs, data_arrays("plaintext" if args.decrypt else "ciphertext", d_pt if args.decrypt else d_ct, per_gpu, b"".join(last)))
 
-    # ---- separate short pass with timing mode ON: HIP events around each launch of the fused kernel on its own
-    # stream (ONE context, so the launches do not overlap), the per-workgroup trace (shader clock), then the same
-    # instruction stream without HBM traffic
-    ctx.timing_enable(True)
-    ctx.timing_read(reset=True)
-    for _ in range(min(3, max(1, args.steps))):
-        step([ctx])
-    lib.dev_sync(dev)
-    n_launch, kernel_ms = ctx.timing_read(reset=True)
-    sclk = None
     if ctx.split(msgs[0]["len"], msgs[0]["first_block"])[1]:
         geo = ctx.geometry(body=True)                              # the timed kernel is k_body: report ITS launch geometry
-    if rank == 0:
-        try:
-            sclk = sclk_from_trace(ctx.wg_trace(), geo["wg_lanes"] // 64)
-        except Exception as e:
-            log("trace failed: %r" % (e,))
-    ctx.timing_enable(False)
+    if args.full:
+        # ---- separate short pass with timing mode ON: HIP events around each launch of the fused kernel on its own
+        # stream (ONE context, so the launches do not overlap), the per-workgroup trace (shader clock), then the same
+        # instruction stream without HBM traffic
+        ctx.timing_enable(True)
+        ctx.timing_read(reset=True)
+        for _ in range(min(3, max(1, args.steps))):
+            step([ctx])
+        lib.dev_sync(dev)
+        n_launch, kernel_ms = ctx.timing_read(reset=True)
+        sclk = None
+        if rank == 0:
+            try:
+                sclk = sclk_from_trace(ctx.wg_trace(), geo["wg_lanes"] // 64)
+            except Exception as e:
+                log("trace failed: %r" % (e,))
+        ctx.timing_enable(False)
 
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         # the timed kernel: k_body over the aligned middle of each range when the library splits it, else k_main over all of it
         _, body_blocks = ctx.split(msgs[0]["len"], msgs[0]["first_block"])
         blocks_per_launch = body_blocks if body_blocks else (per_gpu // M) // 16
@@ -1392,6 +1504,7 @@ def main(argv=None):
                     "lds_busy_frac": (pm.get("lds") or {}).get("lds_busy_frac") if same_build else None,
                     "formulation_ceiling": ceiling,
                     "measured_copy_kernel": {"value": copy_gbps, "unit": "GB/s read+write", "frac_of_copy": (round(achieved / 1e9 / copy_gbps, 4) if copy_gbps else None)}}
+    if rank == 0:
         line = {
             "metric": "GiB/s plaintext, AES-%d-GCM %.3g GiB stream, bit-exact tag" % (key_bits, cfg["gib"]),
             "value": round(value, 3), "unit": "GiB/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -1402,8 +1515,9 @@ def main(argv=None):
                        "workgroups": geo["workgroups"], "wg_lanes": geo["wg_lanes"], "lds_bytes_per_wg": geo["lds_bytes"],
                        "exchange": None if ex is None else {"backend": ex.name, "ranks_seen": ex.world, "torch": "not imported"}},
             "tag_ok": tag_ok, "ct_head_tail_ok": ct_ok, "selfcheck": selfcheck, "tags": [t.hex() for t in tags],
-            "roofline": roofline,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if emu is not None:
             line["emulated"] = {"rank": R, "of": W, "what": "ONE GPU runs rank %d's step of the %d-GPU cfg4 job: its shard of every message at the real "
                                 "first_block, a device copy in place of the RCCL all-gather, every finalize; `value` is this one rank's GiB/s "

@@ -12,7 +12,7 @@ for LIB in "$@"; do
   N=$(basename $LIB .so)
   for LG in ${BATCH_AB_LGS:-3 4}; do
     T=${N}_lg$LG
-    ( cd $REPO && AESGCM_LIB=$LIB AESGCM_LIB_DEBUG=$LIB timeout 300 python3 bench.py --config cfg5 --batch-lanes $((1 << LG)) --no-cpu-baseline $EXTRA > $O/bench_$T.json 2> $O/bench_$T.err )
+    ( cd $REPO && AESGCM_LIB=$LIB AESGCM_LIB_DEBUG=$LIB timeout 300 python3 bench.py --config cfg5 --batch-lanes $((1 << LG)) --full --no-cpu-baseline $EXTRA > $O/bench_$T.json 2> $O/bench_$T.err )
     ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ab_$T && \
       AESGCM_LIB=$LIB AESGCM_LIB_DEBUG=$LIB timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d /tmp/ab_$T/sq -- python3 $REPO/bench.py --config cfg5 --batch-lanes $((1 << LG)) --steps 4 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null 2> $O/pmc_$T.err; \
       AESGCM_LIB=$LIB AESGCM_LIB_DEBUG=$LIB timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d /tmp/ab_$T/grbm -- python3 $REPO/bench.py --config cfg5 --batch-lanes $((1 << LG)) --steps 4 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null 2>> $O/pmc_$T.err; \

@@ -7,7 +7,7 @@ SIZES=${@:-1 4 16 64 256}
 for M in $SIZES; do
   for K in ${INFLIGHT_KS:-1 2 4}; do
     G=$(python3 -c "print($M/1024)")
-    timeout 300 python3 bench.py --gib-per-gpu $G --inflight $K --no-cpu-baseline ${INFLIGHT_ARGS:-} > $O/inflight_${M}m_k$K.json 2> $O/inflight_${M}m_k$K.err
+    timeout 300 python3 bench.py --gib-per-gpu $G --inflight $K --full --no-cpu-baseline ${INFLIGHT_ARGS:-} > $O/inflight_${M}m_k$K.json 2> $O/inflight_${M}m_k$K.err
     python3 - $O/inflight_${M}m_k$K.json $M $K <<'PY'
 import json, sys
 try:

@@ -18,7 +18,7 @@ bash profiles/collect.sh mixed_u 'k_rows<' profiles/mixed_bench.py --only mixed 
 bash profiles/collect.sh mixed_u_1m 'k_rows<' profiles/mixed_bench.py --only mixed --n 16384 --max-len 1048576 > $O/collect_mixed_u_1m.txt 2>&1
 # (the counters of THIS library first, so that the bench lines behind them carry roofline.traffic: bench.py reads profiles/pmc_<tag>.json only when its hash is the running library's)
 for t in cfg2_n1 cfg3_n1 cfg5_n1 rows_1m frames; do cp gpurun_out/prof_$t/pmc_$t.json profiles/ 2>/dev/null; done
-b() { n=$1; shift; timeout 900 python bench.py "$@" > $O/bench_$n.json 2> $O/bench_$n.err; }
+b() { n=$1; shift; timeout 900 python bench.py --full "$@" > $O/bench_$n.json 2> $O/bench_$n.err; }
 b default
 b cfg2 --config cfg2
 b dec --decrypt --no-cpu-baseline

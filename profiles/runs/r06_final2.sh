@@ -3,7 +3,7 @@
 # another box than r06_final.sh's.  -> profiles/r06/second_box/
 O=$PWD/gpurun_out/r06_final2; mkdir -p $O
 sha256sum aes-gcm-128-192-256-bits_amd/libaesgcm_hip.so > $O/so_sha256.txt
-b() { n=$1; shift; timeout 900 python bench.py "$@" > $O/bench_$n.json 2> $O/bench_$n.err; }
+b() { n=$1; shift; timeout 900 python bench.py --full "$@" > $O/bench_$n.json 2> $O/bench_$n.err; }
 b default
 b cfg2 --config cfg2
 b cfg5 --config cfg5

@@ -49,6 +49,45 @@ def test_bench_single_process_queues_its_messages_without_a_host_sync_per_messag
     assert seen[9][2] > seen[4][2]                                      # ... while the collectives do
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """bench.py over the fake runtime: a plain run prints the headline line without `roofline` / `cpu_baseline` and makes fewer launches than the same run
+    with --full; --steps sets the timed steps; --dump-outputs writes the last step's outputs as float32 / float64 .npy files (64 MB at most), the same
+    arrays from run to run"""
+    import json
+    import re
+    import numpy as np
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"), FAKEHIP_REPORT="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    runs = {}
+    for name, extra in (("plain", []), ("again", []), ("full", ["--full", "--no-cpu-baseline"])):
+        out = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gib-per-gpu", "0.0625", "--steps", "4", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / name)] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and {"metric", "value", "unit", "higher_is_better", "dtype"} <= set(line)
+        m = re.search(r"fakehip: syncs=(\d+) launches=(\d+)", out.stderr)
+        assert m, out.stderr[-2000:]
+        runs[name] = (line, int(m.group(2)))
+    assert "roofline" not in runs["plain"][0] and "cpu_baseline" not in runs["plain"][0] and "roofline" in runs["full"][0]
+    assert runs["plain"][1] < runs["full"][1]
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files == ["ciphertext.npy", "ciphertext_offsets.npy", "tags.npy", "tags_index.npy"]
+    total = 0
+    for f in files:
+        a = np.load(tmp_path / "plain" / f)
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        total += a.nbytes
+        for other in ("again", "full"):
+            assert np.array_equal(a, np.load(tmp_path / other / f)), (f, other)
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "plain" / "ciphertext.npy").shape[1] == 4096 and np.load(tmp_path / "plain" / "tags.npy").shape == (1, 16)
+
+
 @pytest.mark.parametrize("n", [2, 4])
 def test_bench_ranks_each_keep_to_their_own_device(n):
     """bench.py --gpus N the way the driver's launcher would not even have to: the parent starts N rank processes itself (one per device, LOCAL_RANK = device), the

@@ -62,7 +62,7 @@ def test_last_tag_of_a_waited_call_and_of_nothing_enqueued(hip, orc):
 def test_bench_inflight_line(hip, orc):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gib-per-gpu", str(4 / 1024), "--inflight", "2", "--ring-gib", "0.03125",
-                        "--steps", "64", "--warmup", "8", "--no-cpu-baseline"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                        "--steps", "64", "--warmup", "8", "--full", "--no-cpu-baseline"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["tag_ok"] is True and line["tags_checked"] == 72 and line["config"]["inflight"] == 2 and line["config"]["ring"] == 8

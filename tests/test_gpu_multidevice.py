@@ -247,7 +247,7 @@ def test_two_rank_bench_over_rccl(two, orc):
 
 
 def test_single_process_fallback_path(two, orc):
-    rc, line, err = _bench(["--single-process"])
+    rc, line, err = _bench(["--single-process", "--full"])
     assert rc == 0, err[-4000:]
     ex = line["config"]["exchange"]
     assert ex["backend"] == "rccl (single process)" and ex["ranks_seen"] == 2 and ex["init"] == "ncclCommInitAll"

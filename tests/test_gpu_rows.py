@@ -391,7 +391,7 @@ def test_bench_line_of_the_messages_config(aad_len, scattered):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "msgs", "--n-pkts", "300", "--pkt-len", str(65536 + 1024 * 3 + 17), "--steps", "3", "--warmup", "1",
-                          "--aad-len", str(aad_len), "--no-cpu-baseline"] + (["--scattered"] if scattered else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                          "--aad-len", str(aad_len), "--full", "--no-cpu-baseline"] + (["--scattered"] if scattered else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["tag_ok"] is True and line["config"]["shape"] == "rows" and line["unit"] == "GiB/s" and line["n_gpus"] == 1 and line["config"]["aad_bytes"] == aad_len and line["config"]["scattered"] == scattered

@@ -53,7 +53,7 @@ def test_cfg5_replicas_produce_the_same_tags_as_one_gpu(hip):
     """bench.py --config cfg5: N ranks are replicas of 2^k / N packets with no collective on the data path; the SHA-256 over all
     tags (rank 0 concatenates every rank's) must equal the one-GPU run's over the same packets, and the first 64 tags the fixture's"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "AESGCM_RDZV_DIR")}
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg5", "--n-pkts", "65536", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg5", "--n-pkts", "65536", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     one = subprocess.run(base, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     two = subprocess.run(base + ["--gpus", "2", "--one-device", "--backend", "file", "--allow-file-exchange"], env=env, cwd=ROOT,
