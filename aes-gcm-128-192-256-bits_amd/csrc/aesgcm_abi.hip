@@ -77,6 +77,7 @@ int aesgcm_ctx_destroy(aesgcm_ctx *c) {
     { std::lock_guard<std::mutex> lk(g_mu); g_ctxs.erase(std::remove(g_ctxs.begin(), g_ctxs.end(), c), g_ctxs.end()); }
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->ev_session) { hipEventSynchronize(c->ev_session); hipEventDestroy(c->ev_session); }      // (a session's last chunk may be on a caller's stream)
     for (auto &e : c->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (c->km) { hipMemset(c->km, 0, sizeof(KeyMaterial)); hipFree(c->km); }
@@ -529,10 +530,28 @@ int aesgcm_shard_finalize_dev(aesgcm_ctx *c, const uint8_t iv[12], const void *d
 
 // ---------------------------------------------------------------- streaming
 // state Y (c->d_tag[1]) = polynomial of everything absorbed so far: sum X_i H^(n-1-i); the bookkeeping is aesgcm_ctx::StreamState (aesgcm_internal.h)
+// A session's steps may come on different streams -- aesgcm_stream_update_dev on the caller's, every other step on the context's -- and the context's stream is not
+// ordered behind a caller's.  So every step makes its stream WAIT (on the device) for the session's event before it enqueues anything, and records the event on that
+// stream behind what it enqueued: the steps of a session run in the order they were called, whichever streams they came on.
+static int session_wait(aesgcm_ctx *c, hipStream_t st) {
+    if (c->ev_session) HIPCHK(hipStreamWaitEvent(st, c->ev_session, 0));
+    return AESGCM_OK;
+}
+static int session_mark(aesgcm_ctx *c, hipStream_t st) {
+    if (!c->ev_session) HIPCHK(hipEventCreateWithFlags(&c->ev_session, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->ev_session, st));
+    return AESGCM_OK;
+}
+// A step whose absorb failed part-way may have advanced Y without the bookkeeping: the session is over (ESTATE until aesgcm_stream_begin / _import)
+static int session_broken(aesgcm_ctx *c, int rc) { c->s.active = false; return rc; }
+
 int aesgcm_stream_begin(aesgcm_ctx *c, const uint8_t iv[12], int decrypt) {
     if (!c || !iv) return AESGCM_EARG;
     HIPCHK(hipSetDevice(c->device));
-    return stream_open(c, iv, decrypt, c->stream);
+    int rc;
+    if ((rc = session_wait(c, c->stream))) return rc;             // (an abandoned session's last chunk may still be absorbing into Y)
+    if ((rc = stream_open(c, iv, decrypt, c->stream))) return rc;
+    return session_mark(c, c->stream);
 }
 
 int aesgcm_stream_aad(aesgcm_ctx *c, const uint8_t *aad, size_t len) {
@@ -542,10 +561,12 @@ int aesgcm_stream_aad(aesgcm_ctx *c, const uint8_t *aad, size_t len) {
     if (check_lengths(c->s.aad_len + len, 0)) return AESGCM_ETOOLONG;
     HIPCHK(hipSetDevice(c->device));
     int rc;
+    if ((rc = session_wait(c, c->stream))) return rc;
     if ((rc = stage_in(c, aad, len, nullptr, 0))) return rc;
-    if ((rc = stream_absorb(c, c->st_aad, len, c->st_in, 0, c->st_out, 0))) return rc;
+    if ((rc = stream_absorb(c, c->st_aad, len, c->st_in, 0, c->st_out, 0))) return session_broken(c, rc);
     c->s.aad_len += len;
     if (len & 15) c->s.ragged = true;
+    if ((rc = session_mark(c, c->stream))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return AESGCM_OK;
 }
@@ -558,19 +579,21 @@ int aesgcm_stream_update(aesgcm_ctx *c, const uint8_t *in, size_t len, uint8_t *
     if (check_lengths(c->s.aad_len, c->s.len + len)) return AESGCM_ETOOLONG;
     HIPCHK(hipSetDevice(c->device));
     int rc;
+    if ((rc = session_wait(c, c->stream))) return rc;
     if ((rc = stage_in(c, nullptr, 0, in, len))) return rc;
     c->s.ragged = false;
-    if ((rc = stream_absorb(c, nullptr, 0, c->st_in, len, c->st_out, c->s.len / 16))) return rc;
+    if ((rc = stream_absorb(c, nullptr, 0, c->st_in, len, c->st_out, c->s.len / 16))) return session_broken(c, rc);
     c->s.data = true;
     c->s.len += len;
     if (len & 15) c->s.ragged = true;
+    if ((rc = session_mark(c, c->stream))) return rc;
     HIPCHK(hipMemcpyAsync(out, c->st_out, len, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return AESGCM_OK;
 }
 
 // The same step on DEVICE pointers, asynchronous on `stream` (round 6): a chunk of any size -- it takes the launch structure a shard of that size takes -- of a message
-// whose total length nobody knows yet.  The chunks of one session must be stream-ordered (one stream, or the caller orders them), as every call on a context.
+// whose total length nobody knows yet.  The chunks of one session may come on different streams: the library orders them (session_wait / session_mark above).
 int aesgcm_stream_update_dev(aesgcm_ctx *c, const void *d_in, size_t len, void *d_out, void *stream) {
     if (!c || (len && (!d_in || !d_out))) return AESGCM_EARG;
     if (!c->s.active) return AESGCM_ESTATE;
@@ -579,22 +602,24 @@ int aesgcm_stream_update_dev(aesgcm_ctx *c, const void *d_in, size_t len, void *
     if (check_lengths(c->s.aad_len, c->s.len + len)) return AESGCM_ETOOLONG;
     if (((uintptr_t)d_in | (uintptr_t)d_out) & 15) return AESGCM_EALIGN;
     HIPCHK(hipSetDevice(c->device));
-    const bool was_ragged = c->s.ragged;
+    hipStream_t st = pick_stream(c, stream);
+    int rc;
+    if ((rc = session_wait(c, st))) return rc;
+    if ((rc = stream_absorb(c, nullptr, 0, d_in, len, d_out, c->s.len / 16, st, true))) return session_broken(c, rc);
     c->s.ragged = false;
-    const int rc = stream_absorb(c, nullptr, 0, d_in, len, d_out, c->s.len / 16, pick_stream(c, stream), true);
-    if (rc) { c->s.ragged = was_ragged; return rc; }
     c->s.data = true;
     c->s.len += len;
     if (len & 15) c->s.ragged = true;
-    return AESGCM_OK;
+    return session_mark(c, st);
 }
 
 int aesgcm_stream_final(aesgcm_ctx *c, uint8_t tag[16]) {
     if (!c || !tag) return AESGCM_EARG;
     if (!c->s.active) return AESGCM_ESTATE;
     HIPCHK(hipSetDevice(c->device));
-    int rc = enqueue_combine(c, plan_combine_final(c->d_tag + 1, c->s.iv, c->s.aad_len, c->s.len, c->d_tag), c->stream);
-    if (rc) return rc;
+    int rc;
+    if ((rc = session_wait(c, c->stream))) return rc;
+    if ((rc = enqueue_combine(c, plan_combine_final(c->d_tag + 1, c->s.iv, c->s.aad_len, c->s.len, c->d_tag), c->stream))) return rc;
     if ((rc = fetch_tag(c, c->stream, tag))) return rc;
     c->s.active = false;
     return AESGCM_OK;
@@ -605,7 +630,8 @@ int aesgcm_stream_final(aesgcm_ctx *c, uint8_t tag[16]) {
 //   [0] version 1   [1] direction (1 = decrypt)   [2] bit 0: data has begun, bit 1: the last chunk was ragged   [3] 0
 //   [4, 16) IV      [16, 24) AAD bytes so far     [24, 32) data bytes so far (the next counter is 2 + this / 16)      [32, 48) Y, in the library's form (the RTL's Y / H)
 //   [48, 56) GHASH blocks so far    [56, 60) key check: the first four bytes of E_K(A5 .. A5) -- NOT key material (H = E_K(0) is, and stays out)   [60, 64) sum check over [0, 60)
-// No key, no H, no table.  Y itself is a secret-dependent value of the same kind as a tag before its final XOR: treat the blob like the message's tag-in-progress.
+// No key and no table -- but the blob is EQUIVALENT TO H, the authentication key: Y together with the public AAD or ciphertext gives it (after two blocks X0, X1,
+// Y = X0 H ^ X1, so H = (Y ^ X1) X0^-1), and H lets anyone forge tags under this key.  Protect the blob like the key itself.
 #define STREAM_BLOB_VERSION 1
 static u32 blob_sum(const uint8_t *b) { u32 s = 0x5EC0DE5u; for (int i = 0; i < 60; i++) s = (s << 5 | s >> 27) ^ b[i]; return s; }
 static int key_check(aesgcm_ctx *c, uint8_t out[4]) {
@@ -624,10 +650,12 @@ int aesgcm_stream_export(aesgcm_ctx *c, uint8_t blob[64]) {
     blob[0] = STREAM_BLOB_VERSION; blob[1] = c->s.dec ? 1 : 0; blob[2] = (uint8_t)((c->s.data ? 1 : 0) | (c->s.ragged ? 2 : 0));
     memcpy(blob + 4, c->s.iv, 12);
     memcpy(blob + 16, &c->s.aad_len, 8); memcpy(blob + 24, &c->s.len, 8); memcpy(blob + 48, &c->s.blocks, 8);
-    // everything this session enqueued -- on the context's stream or, for aesgcm_stream_update_dev, on the caller's -- before Y is read
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(blob + 32, c->d_tag + 1, 16, hipMemcpyDeviceToHost));
-    int rc = key_check(c, blob + 56);
+    // Y behind everything this session enqueued -- on the context's stream or, for aesgcm_stream_update_dev, on a caller's (the session's event): no other work waited for
+    int rc;
+    if ((rc = session_wait(c, c->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(blob + 32, c->d_tag + 1, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = key_check(c, blob + 56);
     if (rc) return rc;
     const u32 sum = blob_sum(blob);
     memcpy(blob + 60, &sum, 4);
@@ -648,8 +676,13 @@ int aesgcm_stream_import(aesgcm_ctx *c, const uint8_t blob[64]) {
     st.active = true; st.dec = blob[1]; st.data = (blob[2] & 1) != 0; st.ragged = (blob[2] & 2) != 0;
     memcpy(st.iv, blob + 4, 12);
     memcpy(&st.aad_len, blob + 16, 8); memcpy(&st.len, blob + 24, 8); memcpy(&st.blocks, blob + 48, 8);
-    if (check_lengths(st.aad_len, st.len) || st.blocks != (st.aad_len + 15) / 16 + (st.len + 15) / 16 || (!st.ragged && (st.len & 15)) || (st.data ? false : st.len != 0)) return AESGCM_EARG;
+    // (the ragged bit is what the lengths say: the last chunk of the kind under way -- data once it has begun, else AAD -- was ragged.  A blob that claims aligned AAD of
+    // a ragged length would let aesgcm_stream_aad absorb as if block-aligned: a wrong tag, and the sum check is no signature)
+    if (check_lengths(st.aad_len, st.len) || st.blocks != (st.aad_len + 15) / 16 + (st.len + 15) / 16 || (!st.ragged && (st.len & 15)) || (st.data ? false : st.len != 0) ||
+        st.ragged != ((((st.data ? st.len : st.aad_len) & 15)) != 0)) return AESGCM_EARG;
+    if ((rc = session_wait(c, c->stream))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_tag + 1, blob + 32, 16, hipMemcpyHostToDevice, c->stream));
+    if ((rc = session_mark(c, c->stream))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->s = st;
     return AESGCM_OK;
@@ -684,7 +717,7 @@ int aesgcm_messages_crypt_dev(aesgcm_ctx *c, int decrypt, size_t n_msgs, const v
     k.ivs = r.ivs; k.tags = r.tags; k.expect = r.expect; k.auth = d_auth;
     k.aligned = 1;                                                                      // per message: its two addresses decide (pkt_info)
     const int rc = packets_rows(c, decrypt, r, pick_stream(c, stream), &k);
-    if (!rc && decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_msgs, nullptr, 0, nullptr, d_auth, pick_stream(c, stream), (const u64 *)d_out_ptr, d_len);
+    if (!rc && decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_msgs, nullptr, 0, nullptr, d_auth, pick_stream(c, stream), (const u64 *)d_out_ptr, d_len, r.hdr);      // (r.hdr: nothing behind a refused call)
     return rc;
 }
 
@@ -718,7 +751,7 @@ int aesgcm_packets_crypt_dev(aesgcm_ctx *c, int decrypt, size_t n_pkts, const vo
         r.data_off = (const u64 *)d_data_off; r.aad_off = (const u64 *)d_aad_off;
         r.n_pkts = (u32)n_pkts; r.pkt_len = routed ? 0u : (u32)pkt_len; r.aad_len = (u32)aad_len;
         const int rc = packets_rows(c, decrypt, r, pick_stream(c, stream), routed ? &p : nullptr);
-        if (!rc && decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_pkts, d_out, pkt_len, (const u64 *)d_data_off, d_auth, pick_stream(c, stream));
+        if (!rc && decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_pkts, d_out, pkt_len, (const u64 *)d_data_off, d_auth, pick_stream(c, stream), nullptr, nullptr, r.hdr);
         return rc;
     }
     const u32 n_cu = (u32)c->G / 2;                                                 // c->G = two workgroups per CU

@@ -749,11 +749,15 @@ int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktP
                 HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
                 HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
             }
+            // after the fork a failing launch still joins before the call returns: the caller's stream is then ordered behind whatever reached the side stream
+            // (the scratch stays marked dirty: the next call clears it on that stream)
+#define FORKCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { if (rows_st != st) { hipEventRecord(c->ev_join, rows_st); hipStreamWaitEvent(st, c->ev_join, 0); } \
+                                                                      return hip_fail(_e, #call); } } while (0)
             if (!probe) {
                 HIPCHK(hipEventRecord(c->ev_fork, st));
                 HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
                 rows_st = c->side;
-                HIPCHK(klaunch_rows_plan(rows_st, p, true, c->rows_block, (u32)ROWS_NB_CAP, r.plan_part, reinterpret_cast<u32 *>(c->h_tag_dev + 2)));
+                FORKCHK(klaunch_rows_plan(rows_st, p, true, c->rows_block, (u32)ROWS_NB_CAP, r.plan_part, reinterpret_cast<u32 *>(c->h_tag_dev + 2)));
             }
             // every shape the count of small messages -- anything up to n -- could ask for; all but the one k_len_scan named return before they stage a table
             const u32 lg_min = cfg.force_lg != 0xFFu ? cfg.force_lg : route_pick_lg(n_cu, n), lg_max = cfg.force_lg != 0xFFu ? cfg.force_lg : 4u;
@@ -764,12 +768,12 @@ int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktP
                     const u32 waves_per_wg = AESGCM_PKTL_WG / 64, nb = (u32)((n + 63) / 64);
                     u32 w = (nb + waves_per_wg - 1) / waves_per_wg;
                     if (w > n_cu) w = n_cu;
-                    HIPCHK(klaunch_pktl(c->nr, decrypt, false, w, st, c->km, c->tables, *k));
+                    FORKCHK(klaunch_pktl(c->nr, decrypt, false, w, st, c->km, c->tables, *k));
                 } else {
                     const u32 P = 64u >> lg, waves_per_wg = (u32)PKTG_WG(lg) / 64, nb = (u32)((n + P - 1) / P);
                     u32 w = (nb + waves_per_wg - 1) / waves_per_wg;
                     if (w > n_cu) w = n_cu;
-                    HIPCHK(klaunch_pktg(c->nr, decrypt, (int)lg, w, st, c->km, c->tables, *k));
+                    FORKCHK(klaunch_pktg(c->nr, decrypt, (int)lg, w, st, c->km, c->tables, *k));
                 }
             }
             if (probe) { c->rows_dirty = false; return AESGCM_OK; }           // (nothing of the row path ran: its scratch is at rest)
@@ -778,11 +782,12 @@ int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktP
         }
     }
     p.prio_rows = c->cyc_prio;
-    if (wgs) HIPCHK(klaunch_rows(c->nr, decrypt, wgs, rows_st, c->km, c->tables, p));                          // (fixed-size records of no bytes and no AAD have no units: their tags are the closing's alone)
+    if (wgs) FORKCHK(klaunch_rows(c->nr, decrypt, wgs, rows_st, c->km, c->tables, p));                          // (fixed-size records of no bytes and no AAD have no units: their tags are the closing's alone)
     size_t close_lanes = p.slot_cap > n ? p.slot_cap : n;                                                    // a lane per record slot and per message; the lanes stride, so the grid is capped (and with offset arrays most slots of the worst case are never given out)
     if (close_lanes > (size_t)4096 * ROWS_CLOSE_WG) close_lanes = (size_t)4096 * ROWS_CLOSE_WG;
-    HIPCHK(klaunch_rows_close(decrypt, (unsigned)((close_lanes + ROWS_CLOSE_WG - 1) / ROWS_CLOSE_WG), rows_st, c->km, c->tables, p));
+    FORKCHK(klaunch_rows_close(decrypt, (unsigned)((close_lanes + ROWS_CLOSE_WG - 1) / ROWS_CLOSE_WG), rows_st, c->km, c->tables, p));
     if (rows_st != st) { HIPCHK(hipEventRecord(c->ev_join, rows_st)); HIPCHK(hipStreamWaitEvent(st, c->ev_join, 0)); }      // the join
+#undef FORKCHK
     c->rows_dirty = false;
     return AESGCM_OK;
 }
@@ -810,11 +815,15 @@ bool packets_by_rows(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len) {
     return true;
 }
 
+thread_local const RowsHdr *g_wipe_hdr = nullptr;
 // zero the output of every packet whose d_auth[] entry is 0 (behind the launch that wrote it, on the same stream)
-int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr, const u32 *d_len) {
+int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr, const u32 *d_len, const RowsHdr *hdr) {
     if (!n_pkts || !d_auth || (!d_out && !d_len)) return AESGCM_OK;
     HIPCHK(hipSetDevice(device));
-    HIPCHK(klaunch_wipe_failed(st, (unsigned char *)d_out, d_auth, d_data_off, (u32)n_pkts, (u32)pkt_len, d_out_ptr, d_len));
+    g_wipe_hdr = hdr;
+    const hipError_t e = klaunch_wipe_failed(st, (unsigned char *)d_out, d_auth, d_data_off, (u32)n_pkts, (u32)pkt_len, d_out_ptr, d_len);
+    g_wipe_hdr = nullptr;
+    HIPCHK(e);
     return AESGCM_OK;
 }
 

@@ -74,6 +74,10 @@ hipError_t klaunch_rows_plan(hipStream_t st, const RowsParams &p, bool routed, u
 hipError_t klaunch_rows(int nr, int dec, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p);
 hipError_t klaunch_rows_close(int dec, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p);
 hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr = nullptr, const u32 *len_arr = nullptr);
+// The header of the call a wipe follows (nothing behind a refused call: aesgcm_rows.h wipe_failed_lane), or NULL.  Set by wipe_failed around its launch and read by
+// klaunch_wipe_failed: it travels beside the launcher's arguments so that the launcher keeps the signature every runtime the host side links against provides
+// (the kernels' and the fake runtime of tests/fake_hip, in every version of that directory).
+extern thread_local const RowsHdr *g_wipe_hdr;
 
 // ---------------------------------------------------------------- host runtime (aesgcm_host.hip)
 extern thread_local char g_err[256];
@@ -146,6 +150,7 @@ struct aesgcm_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev_sync = nullptr;      // aesgcm_ctx_wait: marks "everything enqueued so far on this context's stream"
     hipEvent_t ev_fused = nullptr;     // aesgcm_ctx_wait_fused: recorded behind every fused-kernel launch once somebody has asked for it
+    hipEvent_t ev_session = nullptr;   // the streaming session's last step, recorded on whichever stream it was enqueued on (aesgcm_abi.hip "streaming"); created on first use
     // host-API staging
     unsigned char *st_in = nullptr, *st_out = nullptr, *st_aad = nullptr;
     size_t st_in_cap = 0, st_out_cap = 0, st_aad_cap = 0;
@@ -227,7 +232,7 @@ size_t rows_carve(unsigned char *base, size_t slots, size_t n, RowsScratch *r);
 int rows_scratch(aesgcm_ctx *c, size_t slots, size_t n, hipStream_t st, RowsScratch *r);
 int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktParams *k = nullptr);
 bool packets_by_rows(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len);
-int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr = nullptr, const u32 *d_len = nullptr);
+int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr = nullptr, const u32 *d_len = nullptr, const RowsHdr *hdr = nullptr);
 int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchParams &p, void *stream);
 void pipeline_release(aesgcm_ctx *c);
 int pipeline_prepare(aesgcm_ctx *c, size_t chunk);

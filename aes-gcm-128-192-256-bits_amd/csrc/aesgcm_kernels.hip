@@ -1651,19 +1651,10 @@ __global__ __launch_bounds__(1024) void k_rows_plan_base(const RowsPlan a) {
     if (m < a.n) a.slot_base[m] = (u32)(a.part[2u * a.nwg + blockIdx.x] + before);
 }
 
-// k_wipe_failed: a wave per packet; packets whose auth[] says 0 get their output bytes zeroed (context option "wipe_on_auth_fail", aesgcm_wipe_failed_dev)
-__global__ __launch_bounds__(256) void k_wipe_failed(unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr) {
-    const u32 pkt = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (pkt >= n_pkts || auth[pkt]) return;
-    u64 lo = data_off ? data_off[pkt] : (u64)pkt * pkt_len, hi = data_off ? data_off[pkt + 1] : lo + pkt_len;
-    if (len_arr) { lo = out_ptr[pkt]; hi = lo + len_arr[pkt]; }                 // the scattered form: addresses (out is NULL)
-    unsigned char *p = reinterpret_cast<unsigned char *>((uintptr_t)out + lo);
-    const u64 len = hi - lo, head = len < 16 ? len : ((16u - ((uintptr_t)p & 15u)) & 15u);
-    if (lane < head) p[lane] = 0;
-    const u64 nvec = (len - head) / 16;
-    for (u64 i = lane; i < nvec; i += 64) gstore16(p + head + 16 * i, make_uint4(0, 0, 0, 0));
-    const u64 done = head + 16 * nvec;
-    if (done + lane < len) p[done + lane] = 0;
+// k_wipe_failed: a wave per packet; packets whose auth[] says 0 get their output bytes zeroed (context option "wipe_on_auth_fail", aesgcm_wipe_failed_dev).  Nothing
+// behind a refused call (hdr->bad), nothing outside a range a call could have written (aesgcm_rows.h wipe_failed_lane)
+__global__ __launch_bounds__(256) void k_wipe_failed(unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr, const RowsHdr *hdr) {
+    wipe_failed_lane(out, auth, data_off, n_pkts, pkt_len, out_ptr, len_arr, hdr, blockIdx.x * 4u + (threadIdx.x >> 6), threadIdx.x & 63u);
 }
 
 // ================================================================================================
@@ -1873,6 +1864,6 @@ hipError_t klaunch_rows_close(int dec, unsigned wgs, hipStream_t st, const KeyMa
     return hipGetLastError();
 }
 hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr) {
-    hipLaunchKernelGGL(k_wipe_failed, dim3((n_pkts + 3u) / 4u), dim3(256), 0, st, out, auth, data_off, n_pkts, pkt_len, out_ptr, len_arr);
+    hipLaunchKernelGGL(k_wipe_failed, dim3((n_pkts + 3u) / 4u), dim3(256), 0, st, out, auth, data_off, n_pkts, pkt_len, out_ptr, len_arr, g_wipe_hdr);      // (g_wipe_hdr: aesgcm_internal.h)
     return hipGetLastError();
 }

@@ -79,6 +79,33 @@ HD void pkt_place_scattered(const RowsHdr *h, u32 pkt, u64 *doff, u64 *ooff, u64
     *aoff = aad_ptr ? aad_ptr[pkt] : 0; *aad_len = aad_ptr ? alen_arr[pkt] : 0u;
 }
 #define ROWS_LEN_LIMIT (1ull << 28)           /* a message's data and its AAD: each below this (include/aesgcm.h) */
+// k_wipe_failed (context option "wipe_on_auth_fail", aesgcm_wipe_failed_dev), one packet: where its output lies -- out + *lo, *len bytes; in the scattered form
+// (len_arr) out is NULL and *lo an address -- or false: leave it untouched.  A range that falls (hi < lo) or holds ROWS_LEN_LIMIT bytes or more is one no call
+// could have written (the lengths k_len_hist / k_rows_plan refuse; aesgcm_wipe_failed_dev gets offsets no kernel has checked), never a range to zero.
+HD bool wipe_range(const u64 *data_off, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr, u32 pkt, u64 *lo, u64 *len) {
+    u64 a, b;
+    if (len_arr) { a = out_ptr[pkt]; b = a + len_arr[pkt]; }
+    else if (data_off) { a = data_off[pkt]; b = data_off[pkt + 1]; }
+    else { a = (u64)pkt * pkt_len; b = a + pkt_len; }
+    if (b < a || b - a >= ROWS_LEN_LIMIT) return false;
+    *lo = a; *len = b - a;
+    return true;
+}
+// k_wipe_failed's lane `lane` of the wave of packet `pkt`.  hdr (NULL for aesgcm_wipe_failed_dev): the header of the call the wipe follows -- a refused call
+// (hdr->bad) ran nothing, so its d_auth holds whatever the caller left there and nothing is wiped.
+HD void wipe_failed_lane(unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr,
+                         const RowsHdr *hdr, u32 pkt, u32 lane) {
+    if (hdr && hdr->bad) return;
+    u64 lo, len;
+    if (pkt >= n_pkts || auth[pkt] || !wipe_range(data_off, pkt_len, out_ptr, len_arr, pkt, &lo, &len)) return;
+    unsigned char *p = reinterpret_cast<unsigned char *>((uintptr_t)out + lo);
+    const u64 head = len < 16 ? len : ((16u - ((uintptr_t)p & 15u)) & 15u);
+    if (lane < head) p[lane] = 0;
+    const u64 nvec = (len - head) / 16;
+    for (u64 i = lane; i < nvec; i += 64) gstore16(p + head + 16 * i, make_uint4(0, 0, 0, 0));
+    const u64 done = head + 16 * nvec;
+    if (done + lane < len) p[done + lane] = 0;
+}
 #define ROWS_ST_OK 0u
 #define ROWS_ST_PLAN_FIT 1u                   /* AESGCM_STATUS_PLAN: the plan does not fit the scratch the host sized for it */
 #define ROWS_ST_LENGTH 2u                     /* AESGCM_STATUS_LENGTH: a length of 2^28 bytes or more, or offsets that do not rise (detail: the first such message) */

@@ -652,7 +652,7 @@ class Context:
         _chk(self._lib.aesgcm_stream_update_dev(self._c, d_in, nbytes, d_out, stream))
 
     def stream_export(self):
-        """aesgcm_stream_export -> the 64-byte state of the open session (no key in it); the session stays open"""
+        """aesgcm_stream_export -> the 64-byte state of the open session; the session stays open.  No key in it, but it gives H with the public data: keep it like the key"""
         b = ctypes.create_string_buffer(64)
         _chk(self._lib.aesgcm_stream_export(self._c, b))
         return b.raw

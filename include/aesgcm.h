@@ -343,7 +343,9 @@ AESGCM_API int aesgcm_batch_crypt_dev(int device, int decrypt, size_t n_pkts, si
                            void *d_tags, const void *d_expect_tags, int *d_auth, void *stream);
 
 /* Zero the output of every packet whose d_auth entry is 0: what the context option "wipe_on_auth_fail" does behind aesgcm_packets_crypt_dev, for callers of the
- * context-free batch entry points (fixed-size records: d_data_off = NULL).  Asynchronous on `stream`, which must be the stream the decrypt call ran on. */
+ * context-free batch entry points (fixed-size records: d_data_off = NULL).  Asynchronous on `stream`, which must be the stream the decrypt call ran on.
+ * Bound: a packet whose range falls (d_data_off[p + 1] < d_data_off[p]) or is 2^28 bytes or more long -- a length no call of this library accepts -- is left
+ * untouched, whatever its d_auth entry says; so is every packet behind a context call that was refused (aesgcm_ctx_status). */
 AESGCM_API int aesgcm_wipe_failed_dev(int device, size_t n_pkts, void *d_out, size_t pkt_len, const uint64_t *d_data_off, const int *d_auth, void *stream);
 
 /* Measurement support: the batch kernel's instruction stream without the data's loads and stores (keys, IVs and tags still move) over n_pkts virtual packets of
@@ -372,7 +374,8 @@ AESGCM_API int aesgcm_packets_shape(const aesgcm_ctx *ctx, size_t n_pkts, size_t
 /* Variable-length form (MACsec-shaped traffic like the reference's README vectors: short frames with a
  * per-frame header as AAD, README.md:251-257): packet p occupies bytes [d_data_off[p], d_data_off[p+1]) of
  * in/out and, when d_aad_off != NULL, bytes [d_aad_off[p], d_aad_off[p+1]) of aad.  Offset arrays have
- * n_pkts + 1 uint64 entries in device memory.  Each packet < 2^28 bytes.  Packets whose data offset is a
+ * n_pkts + 1 uint64 entries in device memory.  Each packet < 2^28 bytes, and offsets must rise: the caller's to ensure -- unlike the context's offset-array calls,
+ * this entry point does NOT check the lengths on the device (nothing refuses a call with a longer packet or falling offsets).  Packets whose data offset is a
  * multiple of 16 take the aligned fast path.  From 262144 packets (AES-128; 98304 for the longer keys) the launch takes them by falling
  * length class, as aesgcm_packets_crypt_dev does (scratch: 4 bytes per packet, kept per device). */
 AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts, size_t key_len, const void *d_keys, const void *d_ivs,
@@ -389,17 +392,18 @@ AESGCM_API int aesgcm_stream_begin(aesgcm_ctx *ctx, const uint8_t iv[12], int de
 AESGCM_API int aesgcm_stream_aad(aesgcm_ctx *ctx, const uint8_t *aad, size_t len);
 AESGCM_API int aesgcm_stream_update(aesgcm_ctx *ctx, const uint8_t *in, size_t len, uint8_t *out);
 AESGCM_API int aesgcm_stream_final(aesgcm_ctx *ctx, uint8_t tag[16]);
-/* The same step on DEVICE pointers (round 6): d_in / d_out 16-byte aligned, may alias; asynchronous on `stream` (NULL = the context's own; the chunks of one session must be
- * stream-ordered, as every call on a context).  A chunk of any size takes the launch structure a shard of that size takes, so a message of unknown total length that is
+/* The same step on DEVICE pointers (round 6): d_in / d_out 16-byte aligned, may alias; asynchronous on `stream` (NULL = the context's own).  The steps of one session
+ * may come on different streams: the library orders them itself (each step's stream waits on the device for the session's previous step; no host synchronisation).  A chunk of any size takes the launch structure a shard of that size takes, so a message of unknown total length that is
  * already on the GPU runs at the rate of aesgcm_shard_crypt_dev.  Every chunk but the last a multiple of 16 bytes. */
 AESGCM_API int aesgcm_stream_update_dev(aesgcm_ctx *ctx, const void *d_in, size_t len, void *d_out, void *stream);
 /* The state of the open session as 64 bytes the caller can keep, move and pick up again -- in another context of the same key, on another device, in another process
  * (SURVEY.md 5 "checkpoint / resume", 8(f2)): what the RTL holds in its Y register (src/gcm_ghash.vhd:174-186) and its counter (src/aes_icb.vhd:97-100) and cannot hand out.
  * blob: version, direction, IV, AAD and data bytes so far, GHASH blocks so far, the running GHASH value (in the library's form: the RTL's Y divided by H), a four-byte key
- * check (E_K of a constant block; NOT key material -- no key, no H and no table is in the blob) and a sum check.  The running GHASH value depends on the key and the data
- * like a tag before its final XOR: handle the blob as you would the tag-in-progress.  aesgcm_stream_export waits for everything the session has enqueued (a device
+ * check (E_K of a constant block) and a sum check (not cryptographic).  No key and no table is in the blob, but it is EQUIVALENT TO THE AUTHENTICATION KEY H: the
+ * running GHASH value together with the public AAD or ciphertext gives H (after two blocks X0, X1 it is X0 H ^ X1), and H forges tags under this key.  Protect the blob
+ * like the key.  aesgcm_stream_export waits for everything the session has enqueued (on the context's stream and on any stream a chunk came on; no device-wide
  * synchronisation) and leaves the session open; aesgcm_stream_import opens a session in `ctx` at exactly that point (AESGCM_ESTATE if one is open already; AESGCM_EARG for
- * a blob that is damaged, of another version, or exported under another key), after which aesgcm_stream_aad / _update / _update_dev / _final go on as if nothing had happened. */
+ * a blob that is damaged, of another version, exported under another key, or whose fields disagree -- e.g. the ragged bit and the lengths), after which aesgcm_stream_aad / _update / _update_dev / _final go on as if nothing had happened. */
 #define AESGCM_STREAM_STATE_BYTES 64
 AESGCM_API int aesgcm_stream_export(aesgcm_ctx *ctx, uint8_t blob[AESGCM_STREAM_STATE_BYTES]);
 AESGCM_API int aesgcm_stream_import(aesgcm_ctx *ctx, const uint8_t blob[AESGCM_STREAM_STATE_BYTES]);

@@ -8,7 +8,10 @@
 //   * a stream, event or allocation is used only while the device it belongs to is current;
 //   * every pointer a launch carries (key material, tables, data, scratch, dispensers) lives on the device of the launch, its stream belongs to that device;
 //   * a collective runs on the device and stream of its communicator's rank;
-//   * host synchronisations are counted (the queued multi-GPU path must have none per message).
+//   * host synchronisations are counted (the queued multi-GPU path must have none per message), device-wide ones apart;
+//   * STREAM ORDER: every stream keeps a vector clock (its own count of enqueued operations, and what it has waited for through events), so a test can ask whether
+//     one stream is ordered behind another (fake_ordered_behind), or have every operation on another stream checked against a watched one (fake_watch);
+//   * fault injection: fake_fail_launch(k) makes the k-th kernel launch after a reset fail, to drive the library's error paths.
 // To keep the host logic running, a launch that would publish a tag and its generation number to the pinned host slot publishes the number (no tag).
 #include <hip/hip_runtime.h>
 
@@ -34,12 +37,14 @@ thread_local int cur = 0;
 struct Alloc { size_t size; int dev; };                     // dev -2 = pinned host memory (valid everywhere)
 std::map<uintptr_t, Alloc> allocs;
 struct FakeStream { int dev; };
-struct FakeEvent { int dev; };
+struct FakeEvent { int dev; std::map<const void *, long> clock; };      // clock: the stream clock it captured when it was last recorded
 std::set<void *> live_streams, live_events;
 FakeStream null_stream[FAKE_DEVICES] = {{0}, {1}, {2}, {3}};
 std::vector<std::string> violations, log_lines;
 unsigned touched = 0, attrs = 0;                              // bit masks of devices
-long n_sync = 0, n_launch = 0, n_collective = 0;
+long n_sync = 0, n_dev_sync = 0, n_launch = 0, n_collective = 0, fail_at = 0;
+std::map<const void *, std::map<const void *, long>> clocks;  // per stream: its own count of enqueued operations and the counts of the others it is ordered behind
+const void *watched = nullptr;
 
 void note(const char *fmt, ...) {
     char b[512]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
@@ -63,6 +68,14 @@ void chk_ptr(const char *what, const char *name, const void *p) {
     if (d >= 0 && d != cur) bad("%s: %s lives on device %d, current device is %d", what, name, d, cur);
 }
 int stream_dev(hipStream_t s) { return s ? reinterpret_cast<FakeStream *>(s)->dev : cur; }
+const void *stream_key(hipStream_t s) { return s ? (const void *)s : (const void *)&null_stream[cur]; }
+// an operation enqueued on s: with a watched stream, s must already be ordered behind everything the watched stream holds
+void enqueue(const char *what, hipStream_t s) {
+    const void *k = stream_key(s);
+    if (watched && k != watched && clocks[k][watched] < clocks[watched][watched])
+        bad("%s: enqueued on a stream not ordered behind the watched stream (%ld of its %ld operations)", what, clocks[k][watched], clocks[watched][watched]);
+    ++clocks[k][k];
+}
 void chk_stream(const char *what, hipStream_t s) {
     if (s && !live_streams.count((void *)s)) { bad("%s: unknown stream", what); return; }
     if (stream_dev(s) != cur) bad("%s: stream of device %d used while device %d is current", what, stream_dev(s), cur);
@@ -73,11 +86,24 @@ void publish(void *slot, unsigned long long gen) { if (slot) __atomic_store_n(re
 }  // namespace
 
 // ---------------------------------------------------------------- what the test reads
-EXPORT void fake_reset(void) { std::lock_guard<std::mutex> lk(mu); violations.clear(); log_lines.clear(); touched = 0; n_sync = n_launch = n_collective = 0; }   // (attrs stays: set once per device and process)
+EXPORT void fake_reset(void) { std::lock_guard<std::mutex> lk(mu); violations.clear(); log_lines.clear(); touched = 0; n_sync = n_dev_sync = n_launch = n_collective = fail_at = 0; clocks.clear(); watched = nullptr; }   // (attrs stays: set once per device and process)
 EXPORT unsigned fake_touched(void) { return touched; }
 EXPORT unsigned fake_attrs(void) { return attrs; }
 EXPORT long fake_syncs(void) { return n_sync; }
 EXPORT long fake_launches(void) { return n_launch; }
+EXPORT long fake_device_syncs(void) { return n_dev_sync; }                    // hipDeviceSynchronize calls (also counted in fake_syncs)
+EXPORT void fake_fail_launch(long k) { std::lock_guard<std::mutex> lk(mu); fail_at = k; }      // the k-th launch from now on (counted since the last reset) fails; 0 = none
+// 1: stream a is ordered behind every operation enqueued on stream b since the last reset (NULL: the current device's null stream)
+EXPORT int fake_ordered_behind(hipStream_t a, hipStream_t b) { std::lock_guard<std::mutex> lk(mu); return clocks[stream_key(a)][stream_key(b)] >= clocks[stream_key(b)][stream_key(b)] ? 1 : 0; }
+// from now on every operation enqueued on another stream must be ordered behind what s holds at that moment (a violation otherwise); NULL: stop watching
+// 1: stream a is ordered behind every operation enqueued on any stream since the last reset
+EXPORT int fake_ordered_behind_all(hipStream_t a) {
+    std::lock_guard<std::mutex> lk(mu);
+    auto &mine = clocks[stream_key(a)];
+    for (auto &kv : clocks) if (mine[kv.first] < kv.second[kv.first]) return 0;
+    return 1;
+}
+EXPORT void fake_watch(hipStream_t s) { std::lock_guard<std::mutex> lk(mu); watched = s ? stream_key(s) : nullptr; }
 EXPORT long fake_collectives(void) { return n_collective; }
 EXPORT int fake_violations(char *buf, size_t n) {
     std::lock_guard<std::mutex> lk(mu);
@@ -104,7 +130,7 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int d) {
     p->multiProcessorCount = 256;
     return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { std::lock_guard<std::mutex> lk(mu); touch(); ++n_sync; return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { std::lock_guard<std::mutex> lk(mu); touch(); ++n_sync; ++n_dev_sync; return hipSuccess; }
 hipError_t hipMalloc(void **p, size_t n) {
     std::lock_guard<std::mutex> lk(mu);
     touch();
@@ -138,7 +164,7 @@ static hipError_t copy(const char *what, void *dst, const void *src, size_t n, h
     std::lock_guard<std::mutex> lk(mu);
     touch();
     chk_ptr(what, "dst", dst); chk_ptr(what, "src", src);
-    if (async) chk_stream(what, st);
+    if (async) { chk_stream(what, st); enqueue(what, st); }
     if (n) memmove(dst, src, n);
     return hipSuccess;
 }
@@ -147,7 +173,7 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind, h
 hipError_t hipMemset(void *dst, int v, size_t n) { std::lock_guard<std::mutex> lk(mu); touch(); chk_ptr("hipMemset", "dst", dst); memset(dst, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t st) {
     std::lock_guard<std::mutex> lk(mu);
-    touch(); chk_ptr("hipMemsetAsync", "dst", dst); chk_stream("hipMemsetAsync", st);
+    touch(); chk_ptr("hipMemsetAsync", "dst", dst); chk_stream("hipMemsetAsync", st); enqueue("hipMemsetAsync", st);
     memset(dst, v, n);
     return hipSuccess;
 }
@@ -171,7 +197,7 @@ hipError_t hipStreamSynchronize(hipStream_t s) { std::lock_guard<std::mutex> lk(
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
     std::lock_guard<std::mutex> lk(mu);
     touch();
-    FakeEvent *f = new FakeEvent{cur};
+    FakeEvent *f = new FakeEvent{cur, {}};
     live_events.insert(f);
     *e = reinterpret_cast<hipEvent_t>(f);
     return hipSuccess;
@@ -182,14 +208,26 @@ static void chk_event(const char *what, hipEvent_t e) {
     if (!live_events.count((void *)e)) { bad("%s: unknown event", what); return; }
     if (reinterpret_cast<FakeEvent *>(e)->dev != cur) bad("%s: event of device %d used while device %d is current", what, reinterpret_cast<FakeEvent *>(e)->dev, cur);
 }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { std::lock_guard<std::mutex> lk(mu); touch(); chk_event("hipEventRecord", e); chk_stream("hipEventRecord", s); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(mu); touch(); chk_event("hipEventRecord", e); chk_stream("hipEventRecord", s);
+    if (live_events.count((void *)e)) reinterpret_cast<FakeEvent *>(e)->clock = clocks[stream_key(s)];
+    return hipSuccess;
+}
 hipError_t hipEventSynchronize(hipEvent_t e) { std::lock_guard<std::mutex> lk(mu); touch(); chk_event("hipEventSynchronize", e); ++n_sync; return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { std::lock_guard<std::mutex> lk(mu); chk_event("hipEventElapsedTime", a); chk_event("hipEventElapsedTime", b); *ms = 1.0f; return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamWaitEvent", s); chk_event("hipStreamWaitEvent", e); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamWaitEvent", s); chk_event("hipStreamWaitEvent", e);
+    if (live_events.count((void *)e)) {
+        auto &mine = clocks[stream_key(s)];
+        for (auto &kv : reinterpret_cast<FakeEvent *>(e)->clock) if (mine[kv.first] < kv.second) mine[kv.first] = kv.second;
+    }
+    return hipSuccess;
+}
 }  // extern "C"
 
 // ---------------------------------------------------------------- launchers (csrc/aesgcm_internal.h): record, check, launch nothing
-#define LAUNCH(what, st) std::lock_guard<std::mutex> lk(mu); touch(); ++n_launch; chk_stream(what, st); const char *W = what; (void)W
+#define LAUNCH(what, st) std::lock_guard<std::mutex> lk(mu); touch(); ++n_launch; if (fail_at && n_launch == fail_at) return hipErrorLaunchFailure; \
+                         chk_stream(what, st); enqueue(what, st); const char *W = what; (void)W
 // kernels that ask for more dynamic LDS than the default cap: the attribute must have been set on THIS device
 #define BIG_LDS() do { if (!((attrs >> cur) & 1u)) bad("%s launched on device %d before its LDS attributes were set there", W, cur); } while (0)
 #define P(x) chk_ptr(W, #x, x)
@@ -253,7 +291,10 @@ static void rows_ptrs(const char *W, const KeyMaterial *km, const RowsParams &p)
 }
 hipError_t klaunch_rows(int, int, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) { LAUNCH("k_rows", st); BIG_LDS(); P(tb); rows_ptrs(W, km, p); return hipSuccess; }
 hipError_t klaunch_rows_close(int, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) { LAUNCH("k_rows_close", st); P(tb); rows_ptrs(W, km, p); return hipSuccess; }
-hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32, u32, const u64 *out_ptr, const u32 *len_arr) { LAUNCH("k_wipe_failed", st); P(out); P(auth); P(data_off); P(out_ptr); P(len_arr); return hipSuccess; }
+hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32, u32, const u64 *out_ptr, const u32 *len_arr) {
+    LAUNCH("k_wipe_failed", st); P(out); P(auth); P(data_off); P(out_ptr); P(len_arr); P(g_wipe_hdr);      // (the call's header: beside the arguments, aesgcm_internal.h)
+    return hipSuccess;
+}
 
 // ---------------------------------------------------------------- RCCL (reached by csrc/aesgcm_comm.hip through dlopen of this very library)
 struct FakeComm { int dev, rank, n; };

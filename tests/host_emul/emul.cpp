@@ -983,6 +983,83 @@ static void test_rows(int key_len, u64 seed, u32 waves, u32 force_d, int var, co
     }
 }
 
+// emulated k_wipe_failed: every lane of its grid (a wave per packet, four waves per workgroup) through wipe_failed_lane, the kernel's own code
+static void emu_wipe_failed(unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr, const RowsHdr *hdr) {
+    for (u32 b = 0; b < (n_pkts + 3u) / 4u; b++)
+        for (u32 t = 0; t < 256; t++) wipe_failed_lane(out, auth, data_off, n_pkts, pkt_len, out_ptr, len_arr, hdr, b * 4u + (t >> 6), t & 63u);
+}
+static unsigned char wipe_mark(size_t i) { return (unsigned char)((i * 131u + 7u) | 1u); }      // never zero
+// one wipe over a heap buffer of exactly `sz` bytes (out = its byte `mis`) filled with wipe_mark: afterwards exactly the ranges `zeroed` (relative to out) are zeros.
+// Offsets that fall, gaps of 2^29 and lengths of 2^28 point far outside the buffer: a wipe that went there is a heap overflow the sanitizer build reports.
+static void wipe_case(const char *name, size_t sz, u32 mis, const std::vector<u64> &doff, const std::vector<int> &auth, const std::vector<std::pair<u64, u64>> &zeroed,
+                      u32 pkt_len = 0, bool refused = false) {
+    unsigned char *buf = (unsigned char *)malloc(sz);
+    for (size_t i = 0; i < sz; i++) buf[i] = wipe_mark(i);
+    RowsHdr hdr;
+    memset(&hdr, 0, sizeof hdr);
+    hdr.bad = refused ? 1u : 0u;
+    const u32 n = (u32)auth.size();
+    emu_wipe_failed(buf + mis, auth.data(), doff.empty() ? nullptr : doff.data(), n, pkt_len, nullptr, nullptr, refused ? &hdr : nullptr);
+    std::vector<unsigned char> want(sz);
+    for (size_t i = 0; i < sz; i++) want[i] = wipe_mark(i);
+    for (auto &z : zeroed) memset(want.data() + mis + z.first, 0, z.second - z.first);
+    size_t first = sz;
+    for (size_t i = 0; i < sz && first == sz; i++) if (buf[i] != want[i]) first = i;
+    CHECK(first == sz, "wipe %s: byte %zu of %zu is %02x, wanted %02x", name, first, sz, first < sz ? buf[first] : 0, first < sz ? want[first] : 0);
+    free(buf);
+}
+static void test_wipe() {
+    const u64 G29 = 1ull << 29, L28 = 1ull << 28;
+    // offsets that fall: packet 1 (100 -> 40) and packet 4 (250 -> 0) are left alone whatever auth says; packet 3 [200, 250) is zeroed
+    wipe_case("falling", 300, 0, {0, 100, 40, 200, 250, 0}, {1, 0, 1, 0, 0}, {{200, 250}});
+    wipe_case("falling by one", 64, 0, {0, 30, 29, 64}, {0, 0, 0}, {{0, 30}, {29, 64}});
+    // a gap of 2^29 bytes: packet 1 seems to be 2^29 bytes long (never wiped), packet 0 is
+    wipe_case("gap", 128, 0, {0, 64, 64 + G29, 64 + G29 + 10}, {0, 0, 1}, {{0, 64}});
+    // fixed-size records: 2^28 bytes each is beyond the bound (aesgcm_wipe_failed_dev), 100 bytes from an odd address are not
+    wipe_case("pkt_len 2^28", 64, 0, {}, {0}, {}, (u32)L28);
+    wipe_case("pkt_len 100", 311, 3, {}, {0, 1, 0}, {{0, 100}, {200, 300}}, 100);
+    // odd byte addresses, lengths around 16-byte boundaries, zero-length packets between them and at the very end of the buffer
+    for (u32 mis : {1u, 3u, 7u, 8u, 15u}) {
+        const std::vector<u64> lens = {1, 15, 16, 17, 0, 31, 33, 0, 1000, 4097, 2, 0};
+        std::vector<u64> doff = {0};
+        for (u64 l : lens) doff.push_back(doff.back() + l);
+        std::vector<int> auth;
+        std::vector<std::pair<u64, u64>> z;
+        for (size_t i = 0; i < lens.size(); i++) {
+            auth.push_back((int)((i + mis) % 3 == 0));
+            if (!auth.back() && lens[i]) z.push_back({doff[i], doff[i + 1]});
+        }
+        wipe_case("odd addresses", mis + doff.back(), mis, doff, auth, z);
+    }
+    // a refused call (hdr->bad): every verdict zero, nothing wiped; the same call not refused wipes everything
+    wipe_case("refused", 4200, 5, {0, 1000, 1000, 3000, 4100}, {0, 0, 0, 0}, {}, 0, true);
+    wipe_case("not refused", 4200, 5, {0, 1000, 1000, 3000, 4100}, {0, 0, 0, 0}, {{0, 4100}});
+    // the scattered form (aesgcm_messages_crypt_dev): addresses and 32-bit lengths; 2^28 bytes is left alone, 2^28 - 1 bytes is wiped to the last byte
+    {
+        const size_t sa = 64, sb = L28 - 1;
+        unsigned char *a = (unsigned char *)malloc(sa), *b = (unsigned char *)malloc(sb);
+        for (size_t i = 0; i < sa; i++) a[i] = wipe_mark(i);
+        memset(b, 0xEE, sb);
+        const u64 ptr[5] = {(u64)(uintptr_t)a, (u64)(uintptr_t)b, (u64)(uintptr_t)(a + sa), (u64)(uintptr_t)(a + 5), (u64)(uintptr_t)(a + 40)};
+        const u32 len[5] = {(u32)L28, (u32)(L28 - 1), 0, 17, 0xFFFFFFFFu};
+        const int auth[5] = {0, 0, 0, 0, 0};
+        emu_wipe_failed(nullptr, auth, nullptr, 5, 0, ptr, len, nullptr);
+        size_t bad_a = sa, bad_b = sb;
+        for (size_t i = 0; i < sa && bad_a == sa; i++) if (a[i] != ((i >= 5 && i < 22) ? 0 : wipe_mark(i))) bad_a = i;
+        static const unsigned char zeros[4096] = {};
+        for (size_t i = 0; i < sb && bad_b == sb; i += 4096) if (memcmp(b + i, zeros, sb - i < 4096 ? sb - i : 4096)) bad_b = i;
+        CHECK(bad_a == sa && bad_b == sb, "wipe scattered: first wrong byte %zu (of 64), %zu (of 2^28 - 1)", bad_a, bad_b);
+        RowsHdr hdr;
+        memset(&hdr, 0, sizeof hdr);
+        hdr.bad = 1;
+        for (size_t i = 0; i < sa; i++) a[i] = wipe_mark(i);
+        emu_wipe_failed(nullptr, auth, nullptr, 5, 0, ptr, len, &hdr);
+        for (size_t i = 0; i < sa && bad_a == sa; i++) if (a[i] != wipe_mark(i)) bad_a = i;
+        CHECK(bad_a == sa, "wipe scattered, refused: byte %zu written", bad_a);
+        free(a); free(b);
+    }
+}
+
 int main(int argc, char **argv) {
     int level = argc > 1 ? atoi(argv[1]) : 1;
     init_tables();
@@ -1022,6 +1099,7 @@ int main(int argc, char **argv) {
     test_body(16, 1, 16 * 64, 16 * 64 * 5 + 16, 113, true);         // AAD fills its row exactly (no front padding), one whole block behind the body
     test_body(32, 1, 1, 16 * 64 * 3 + 1, 114, true);                 // one byte of AAD, one byte behind the body
     test_batch_pieces();
+    test_wipe();
     test_packets(16, 61); test_packets(24, 62); test_packets(32, 63);
     // many messages by rows: offset arrays with every kind of length (empty, shorter than a block, tails of 63 blocks + 15 bytes = two tail rows, whole super-rows,
     // 1 .. 3 rows behind them), AAD of none / a ragged block / more than a row; fixed-size records; one block per wave for few and for many waves (cuts in the

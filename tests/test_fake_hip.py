@@ -23,6 +23,19 @@ def test_host_side_keeps_to_its_device_on_four_fake_devices():
     assert out.returncode == 0 and "FAKE HIP OK" in out.stdout, out.stdout[-3000:]
 
 
+def test_stream_order_and_error_paths_on_the_fake_runtime():
+    """tests/fake_hip/order_drive.py: a streaming session's steps wait on the device for a chunk fed on a caller's stream (and export synchronises no device); a
+    routed packet call whose k-th launch fails -- every k -- returns an error with the caller's stream joined behind the side stream, and the next call is clean; a
+    failed multi-launch stream_update_dev ends the session (ESTATE until it is begun again)"""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"))
+    out = subprocess.run([sys.executable, os.path.join(d, "order_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert out.returncode == 0 and "FAKE ORDER OK" in out.stdout, out.stdout[-3000:]
+
+
 def test_bench_single_process_queues_its_messages_without_a_host_sync_per_message():
     """bench.py --gpus 4 --single-process (the fallback of the N-rank launch on a box where RCCL comes up inside one process only) over the fake runtime: the line is
     printed, no call leaves its device, and the number of host synchronisations does not grow with the number of timed steps -- the messages of a step are

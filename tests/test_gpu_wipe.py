@@ -1,10 +1,13 @@
 """GPU: the context option "wipe_on_auth_fail" (round 5) -- a decrypt call that verifies a tag leaves zeros, not unauthenticated plaintext, where verification
 fails; with the option off (the default) the bytes stay, as in the reference model (tb/gcm_model.py:29-30,47-51: decrypt returns the plaintext, then raises).
 Also here: aesgcm_ctx_last_launch, and aesgcm_last_tag's refusal of a stream the message was not enqueued on."""
+import hashlib
+import random
 import struct
 
 import pytest
 
+from oracle import oracle as O
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +114,106 @@ def test_wipe_helper_behind_a_batch_call(hip, orc):
     back = bytes(d_buf.download(pkt * n))
     for p in range(n):
         assert back[pkt * p:pkt * (p + 1)] == (bytes(pkt) if p in (7, 39) else pt[pkt * p:pkt * (p + 1)]), p
+
+
+def _guarded(hip, nbytes, seed):
+    """a device buffer of nbytes (a multiple of 64) filled with a seeded pattern, and the SHA-256 of that pattern built on the host"""
+    d = hip.DeviceBuffer(nbytes)
+    d.fill_splitmix64(seed)
+    return d, hashlib.sha256(O.fill_splitmix64(nbytes, seed)).hexdigest()
+
+
+def _round64(x):
+    return (x + 63) // 64 * 64
+
+
+@pytest.mark.parametrize("n", [100, 6000])
+def test_a_refused_decrypt_call_wipes_nothing(hip, orc, n):
+    """A call the device refuses (a 2^29 gap in d_data_off, offsets that fall, a length of 2^28 in d_len: aesgcm_rows.h RowsHdr::bad) runs NOTHING -- with the option
+    wipe_on_auth_fail on as well: k_wipe_failed behind it returns at once instead of trusting verdicts no kernel wrote and ranges the call was refused for.
+    Every buffer stays inside memory this test owns even on a library without that check: pattern A leaves the bad message's verdict nonzero (a wipe that ran would
+    zero the GOOD messages, inside d_out); pattern B zeroes every verdict and gives d_out room for the bad message's whole range (gap and len only -- falling
+    offsets would make that range about 2^64 bytes: the CPU harness, tests/host_emul, covers it).  Then the context works on the true offsets, wipe included."""
+    key = splitmix_bytes(9100, 32)
+    f = orc.Fast(key)
+    rng = random.Random(9101 + n)
+    lens = [rng.choice((0, 100, 1500, 3000, 20000)) for _ in range(n)]
+    at = n // 2 + 3
+    lens[at] = 1500
+    doff = [0]
+    for x in lens:
+        doff.append(doff[-1] + x)
+    ivs, pt = splitmix_bytes(9102, 12 * n), splitmix_bytes(9103, doff[-1])
+    d_ivs, d_in = _up(hip, ivs), _up(hip, pt)
+    gap = list(doff)
+    for k in range(at + 1, n + 1):
+        gap[k] += 1 << 29                                        # message `at` seems to be 2^29 bytes longer
+    fall = list(doff)
+    fall[at + 1] = fall[at] - 1                                  # message `at` ends before it begins
+    big_len = list(lens)
+    big_len[at] = 1 << 28
+    cases = [("gap", "A", dict(d_data_off=gap), doff[-1] + (1 << 29) + 16),
+             ("gap", "B", dict(d_data_off=gap), doff[-1] + (1 << 29) + 16),
+             ("falling", "A", dict(d_data_off=fall), doff[-1] + 16),
+             ("len", "A", dict(lens=big_len), doff[-1] + 16),
+             ("len", "B", dict(lens=big_len), max(doff[-1], doff[at] + (1 << 28)) + 16)]
+    ctx = hip.Context(key).set_option("wipe_on_auth_fail", 1)
+    d_exp = _up(hip, splitmix_bytes(9104, 16 * n))
+    for name, pattern, kw, size in cases:
+        d_out, want_sha = _guarded(hip, _round64(size), 9105 + len(name))
+        d_tags = _up(hip, bytes([0x5A]) * (16 * n))
+        auth = [0] * n
+        if pattern == "A":
+            auth[at] = 0x77777777
+        auth_bytes = struct.pack("<%di" % n, *auth)
+        d_auth = _up(hip, auth_bytes)
+        if "lens" in kw:
+            d_len = _up(hip, struct.pack("<%dI" % n, *kw["lens"]))
+            d_inp, d_outp = _up(hip, struct.pack("<%dQ" % n, *[d_in.ptr + x for x in doff[:-1]])), _up(hip, struct.pack("<%dQ" % n, *[d_out.ptr + x for x in doff[:-1]]))
+            ctx.messages_crypt_dev(True, n, d_ivs.ptr, d_inp.ptr, d_len.ptr, d_outp.ptr, d_tags.ptr, d_expect_tags=d_exp.ptr, d_auth=d_auth.ptr)
+        else:
+            d_off = _up(hip, struct.pack("<%dQ" % (n + 1), *kw["d_data_off"]))
+            ctx.packets_crypt_dev(True, n, d_ivs.ptr, d_in.ptr, d_out.ptr, d_tags.ptr, d_data_off=d_off.ptr, d_expect_tags=d_exp.ptr, d_auth=d_auth.ptr)
+        hip.dev_sync()
+        assert hashlib.sha256(d_out.download()).hexdigest() == want_sha, (n, name, pattern, "output written")
+        assert bytes(d_tags.download()) == bytes([0x5A]) * (16 * n), (n, name, pattern, "tags written")
+        assert bytes(d_auth.download(4 * n)) == auth_bytes, (n, name, pattern, "verdicts written")
+        assert ctx.status() == (hip.STATUS_LENGTH, at), (n, name, pattern)
+        assert ctx.status() == (hip.STATUS_OK, 0)
+        d_out.free()
+    # the same context on the true offsets: ciphertext and tags as the oracle's; then a decrypt with one forged tag wipes exactly that message
+    d_off = _up(hip, struct.pack("<%dQ" % (n + 1), *doff))
+    d_ct, d_tags, d_back, d_auth = hip.DeviceBuffer(doff[-1] + 16), hip.DeviceBuffer(16 * n), hip.DeviceBuffer(doff[-1] + 16), hip.DeviceBuffer(4 * n)
+    ctx.packets_crypt_dev(False, n, d_ivs.ptr, d_in.ptr, d_ct.ptr, d_tags.ptr, d_data_off=d_off.ptr)
+    hip.dev_sync()
+    assert ctx.status() == (hip.STATUS_OK, 0)
+    ct, tags = bytes(d_ct.download(doff[-1])), bytearray(d_tags.download())
+    for p in list(range(0, n, 7)) + [at]:
+        assert (ct[doff[p]:doff[p + 1]], bytes(tags[16 * p:16 * p + 16])) == f.encrypt(ivs[12 * p:12 * p + 12], b"", pt[doff[p]:doff[p + 1]]), (n, p)
+    tags[16 * at] ^= 1
+    d_exp2 = _up(hip, bytes(tags))
+    ctx.packets_crypt_dev(True, n, d_ivs.ptr, d_ct.ptr, d_back.ptr, d_tags.ptr, d_data_off=d_off.ptr, d_expect_tags=d_exp2.ptr, d_auth=d_auth.ptr)
+    hip.dev_sync()
+    assert ctx.status() == (hip.STATUS_OK, 0)
+    auth = struct.unpack("<%di" % n, bytes(d_auth.download()))
+    assert [i for i, a in enumerate(auth) if not a] == [at]
+    back = bytearray(pt)
+    back[doff[at]:doff[at + 1]] = bytes(lens[at])
+    assert bytes(d_back.download(doff[-1])) == bytes(back)
+
+
+def test_wipe_helper_leaves_a_range_no_call_could_have_written(hip):
+    """aesgcm_wipe_failed_dev takes offsets no kernel has checked: a packet of 2^29 bytes (offset array or fixed size) is left untouched although its verdict is 0
+    (include/aesgcm.h: the bound is 2^28 bytes); the 16-byte packet before it is wiped.  The buffer holds the whole 2^29 bytes, so nothing faults either way."""
+    size = (1 << 29) + 64
+    d_buf, _ = _guarded(hip, size, 9120)
+    want = O.fill_splitmix64(size, 9120)
+    want[:16] = bytes(16)
+    d_off, d_auth = _up(hip, struct.pack("<3Q", 0, 16, 16 + (1 << 29))), _up(hip, struct.pack("<2i", 0, 0))
+    hip.wipe_failed_dev(2, d_buf.ptr, d_auth.ptr, d_data_off=d_off.ptr)
+    hip.wipe_failed_dev(1, d_buf.ptr + 16, d_auth.ptr, pkt_len=1 << 29)
+    hip.dev_sync()
+    assert hashlib.sha256(d_buf.download()).digest() == hashlib.sha256(want).digest()
 
 
 def test_last_launch_and_last_tag_on_the_wrong_stream(hip, orc):
