@@ -1,0 +1,208 @@
+// aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_keytab_kernels.hip.
+// A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word; k_kt_setup fills slots from raw keys, a crypt call is one
+// k_kt_batch launch with batch_launch's geometry: the shape by batch_pick_lg, the same dispenser ring, the same order by falling length class.
+#include "aesgcm_keytab.h"
+
+#include <string.h>
+
+struct aesgcm_keytab {
+    int device = 0;
+    int nr = 0;
+    size_t key_len = 0, n_slots = 0;
+    KtSlot *tab = nullptr;
+    u32 *status = nullptr;             // device: the lowest refused packet (or set entry) since the last aesgcm_keytab_status, ~0 = none
+    unsigned char *stage = nullptr;    // device: host keys wait here for k_kt_setup; zeroed behind it on the same stream
+    size_t stage_cap = 0;
+    hipEvent_t stage_done = nullptr;   // behind the last zeroing of `stage`, on whichever stream it ran
+    std::mutex mu;
+};
+
+// 72 KiB and more of dynamic LDS: opt in once per device for this unit's kernels (set_lds_attrs does the same for aesgcm_kernels.hip)
+static std::mutex &kt_attr_mu = *new std::mutex();
+static std::vector<char> &kt_attr_done = *new std::vector<char>();
+static int kt_attrs(int device) {
+    std::lock_guard<std::mutex> lk(kt_attr_mu);
+    if ((int)kt_attr_done.size() <= device) kt_attr_done.resize(device + 1, 0);
+    if (kt_attr_done[device]) return AESGCM_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(klaunch_kt_attributes());
+    kt_attr_done[device] = 1;
+    return AESGCM_OK;
+}
+
+static int kt_setup(aesgcm_keytab *t, const unsigned char *d_keys, const u32 *d_slots, size_t first, size_t n, hipStream_t st) {
+    DeviceState *ds;
+    int rc = device_state(t->device, &ds);
+    if (rc) return rc;
+    if ((rc = kt_attrs(t->device))) return rc;
+    KtSetupParams s;
+    s.keys = d_keys; s.slots = d_slots; s.first = (u32)first; s.n = (u32)n; s.n_slots = (u32)t->n_slots; s.tab = t->tab; s.status = t->status;
+    HIPCHK(klaunch_kt_setup(t->nr, st, ds->tables, s));
+    return AESGCM_OK;
+}
+
+int aesgcm_keytab_create(aesgcm_keytab **out, int device, size_t key_len, size_t n_slots) {
+    if (!out) return AESGCM_EARG;
+    *out = nullptr;
+    if ((key_len != 16 && key_len != 24 && key_len != 32) || !n_slots || n_slots >= ((size_t)1 << 31)) return AESGCM_EARG;
+    DeviceState *ds;
+    int rc = device_state(device, &ds);            // (AESGCM_EHIP without a device)
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    aesgcm_keytab *t = new aesgcm_keytab();
+    t->device = device; t->key_len = key_len; t->n_slots = n_slots; t->nr = (int)(key_len / 4 + 6);
+    hipError_t e = hipMalloc((void **)&t->tab, n_slots * sizeof(KtSlot));
+    if (e == hipSuccess) e = hipMalloc((void **)&t->status, sizeof(u32));
+    if (e == hipSuccess) e = hipMemset(t->tab, 0, n_slots * sizeof(KtSlot));
+    if (e == hipSuccess) e = hipMemset(t->status, 0xFF, sizeof(u32));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (t->tab) (void)hipFree(t->tab);
+        if (t->status) (void)hipFree(t->status);
+        delete t;
+        return e == hipErrorOutOfMemory ? AESGCM_ENOMEM : hip_fail(e, "aesgcm_keytab_create");
+    }
+    *out = t;
+    return AESGCM_OK;
+}
+
+int aesgcm_keytab_set(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *keys, void *stream) {
+    if (!t) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (!keys || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);
+    HIPCHK(hipSetDevice(t->device));
+    const size_t bytes = n * t->key_len;
+    if (bytes > t->stage_cap) {
+        if (t->stage) { HIPCHK(hipFree(t->stage)); t->stage = nullptr; t->stage_cap = 0; }   // hipFree waits for the launches that may still read it
+        const hipError_t e = hipMalloc((void **)&t->stage, bytes);
+        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+        t->stage_cap = bytes;
+    }
+    if (!t->stage_done) HIPCHK(hipEventCreateWithFlags(&t->stage_done, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent(st, t->stage_done, 0));                       // the previous set's kernel and zeroing, on whatever stream they ran
+    HIPCHK(hipMemcpyAsync(t->stage, keys, bytes, hipMemcpyHostToDevice, st));
+    int rc = kt_setup(t, t->stage, nullptr, first_slot, n, st);
+    const hipError_t ez = hipMemsetAsync(t->stage, 0, bytes, st);               // the raw keys do not outlive the expansion
+    if (rc) return rc;
+    HIPCHK(ez);
+    HIPCHK(hipEventRecord(t->stage_done, st));
+    return AESGCM_OK;
+}
+
+int aesgcm_keytab_set_dev(aesgcm_keytab *t, size_t n, const uint32_t *d_slots, const void *d_keys, void *stream) {
+    if (!t) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (!d_slots || !d_keys || n >= ((size_t)1 << 31)) return AESGCM_EARG;
+    HIPCHK(hipSetDevice(t->device));
+    return kt_setup(t, (const unsigned char *)d_keys, d_slots, 0, n, (hipStream_t)stream);
+}
+
+int aesgcm_keytab_clear(aesgcm_keytab *t, size_t first_slot, size_t n, void *stream) {
+    if (!t) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipMemsetAsync(t->tab + first_slot, 0, n * sizeof(KtSlot), (hipStream_t)stream));
+    return AESGCM_OK;
+}
+
+// Batches with a slot per packet: batch_launch's geometry (aesgcm_host.hip) around k_kt_batch
+#define KT_ORDER_MIN(nr) ((nr) == 10 ? 262144u : 98304u)       /* as BATCH_ORDER_MIN */
+int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const void *d_ivs,
+                            const void *d_aad, size_t aad_len, const uint64_t *d_aad_off,
+                            const void *d_in, size_t pkt_len, const uint64_t *d_data_off, void *d_out,
+                            void *d_tags, const void *d_expect_tags, int *d_auth, void *stream) {
+    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
+    if (!n_pkts) return AESGCM_OK;
+    const bool var = d_data_off != nullptr;
+    if (!d_slots || !d_ivs || !d_tags || n_pkts >= ((size_t)1 << 31)) return AESGCM_EARG;
+    if (var ? (!d_in || !d_out) : (pkt_len && (!d_in || !d_out))) return AESGCM_EARG;
+    if (d_aad_off ? !d_aad : (!var && aad_len && !d_aad)) return AESGCM_EARG;
+    if (!var && (pkt_len >= ((size_t)1 << 28) || aad_len >= ((size_t)1 << 28))) return AESGCM_EARG;
+    DeviceState *ds;
+    int rc = device_state(t->device, &ds);
+    if (rc) return rc;
+    if ((rc = kt_attrs(t->device))) return rc;
+    HIPCHK(hipSetDevice(t->device));
+    KtParams kp;
+    memset(&kp, 0, sizeof kp);
+    BatchParams &p = kp.b;
+    p.ivs = (const unsigned char *)d_ivs; p.in = (const unsigned char *)d_in; p.out = (unsigned char *)d_out; p.tags = (unsigned char *)d_tags;
+    p.expect = (const unsigned char *)d_expect_tags; p.auth = d_auth;
+    p.data_off = d_data_off; p.aad_off = d_aad_off;
+    if (d_aad_off) p.aad = (const unsigned char *)d_aad;
+    else if (!var) { p.aad = aad_len ? (const unsigned char *)d_aad : nullptr; p.aad_len = (u32)aad_len; }
+    p.pkt_len = var ? 0u : (u32)pkt_len;
+    p.aligned = (var || pkt_len % 16 == 0) && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;     // offset arrays: and the packet's offset is a multiple of 16
+    p.n_pkts = (u32)n_pkts;
+    kp.slots = d_slots; kp.tab = t->tab; kp.n_slots = (u32)t->n_slots; kp.status = t->status;
+    hipStream_t st = (hipStream_t)stream;
+    {   // a fresh dispenser per launch, as batch_launch
+        std::lock_guard<std::mutex> lk(g_mu);
+        p.counter = ds->batch_counter + (ds->batch_slot++ % BATCH_DISPENSERS);
+        p.counter_base = 0;
+    }
+    HIPCHK(hipMemsetAsync(p.counter, 0, 4, st));
+    const int nr = t->nr;
+    int lg = batch_pick_lg(ds->n_cu, n_pkts, p.pkt_len, var);
+#ifdef AESGCM_DEBUG_KNOBS
+    if (g_force.batch_lanes) lg = g_force.batch_lanes == 8 ? 3 : g_force.batch_lanes == 16 ? 4 : 6;
+#endif
+    OrderSlot *oslot = nullptr;
+    bool ordered = lg < 6 && var && n_pkts >= KT_ORDER_MIN(nr);
+#ifdef AESGCM_DEBUG_KNOBS
+    if (g_force.batch_order) ordered = lg < 6 && var && g_force.batch_order == 1;
+#endif
+    std::unique_lock<std::mutex> order_lock(g_mu, std::defer_lock);
+    if (ordered) {
+        // (a falling range sorts into some class -- pkt_len_class clamps -- and is refused by the kernel all the same)
+        order_lock.lock();
+        oslot = &ds->order[ds->order_next++ & 3u];
+        if ((rc = order_launch(*oslot, p.data_off, n_pkts, st, &p.perm))) return rc;
+    }
+    p.plain = !p.data_off && !p.aad_off && !p.aad_len && p.aligned && p.pkt_len && p.pkt_len % (16u << lg) == 0;
+    const u32 waves_per_wg = (u32)BATCH3_LANES(nr) / 64;
+    const u32 P = 64u >> lg, per_wg = waves_per_wg * P;
+    u32 wgs = (u32)((n_pkts + per_wg - 1) / per_wg);
+    if (wgs > (u32)ds->n_cu) wgs = (u32)ds->n_cu;
+    u32 deal = (u32)(n_pkts / ((size_t)wgs * waves_per_wg * 16));
+    deal = deal < P ? P : deal > 8 * P ? 8 * P : (deal + P - 1) / P * P;
+#ifdef AESGCM_DEBUG_KNOBS
+    if (g_force.batch_deal >= 1 && g_force.batch_deal <= 4096) deal = ((u32)g_force.batch_deal + P - 1) / P * P;
+#endif
+    p.deal = deal;
+    HIPCHK(klaunch_kt_batch(nr, decrypt, lg, wgs, st, ds->tables, kp));
+    if (oslot && p.perm) HIPCHK(hipEventRecord(oslot->done, st));
+    return AESGCM_OK;
+}
+
+int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {
+    if (!t || !code) return AESGCM_EARG;
+    HIPCHK(hipSetDevice(t->device));
+    u32 w = ~0u;
+    HIPCHK(hipMemcpy(&w, t->status, sizeof w, hipMemcpyDeviceToHost));
+    *code = w == ~0u ? AESGCM_OK : AESGCM_EARG;
+    if (detail) *detail = w == ~0u ? 0 : w;
+    if (w != ~0u) HIPCHK(hipMemset(t->status, 0xFF, sizeof(u32)));
+    return AESGCM_OK;
+}
+
+int aesgcm_keytab_destroy(aesgcm_keytab *t) {
+    if (!t) return AESGCM_OK;
+    int rc = AESGCM_OK;
+    hipError_t e = hipSetDevice(t->device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();                       // calls in flight may still read the slots
+    if (e == hipSuccess) e = hipMemset(t->tab, 0, t->n_slots * sizeof(KtSlot));
+    if (e == hipSuccess && t->stage) e = hipMemset(t->stage, 0, t->stage_cap);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) rc = hip_fail(e, "aesgcm_keytab_destroy");
+    (void)hipFree(t->tab);
+    (void)hipFree(t->status);
+    if (t->stage) (void)hipFree(t->stage);
+    if (t->stage_done) (void)hipEventDestroy(t->stage_done);
+    delete t;
+    return rc;
+}

@@ -38,6 +38,7 @@ SYMBOLS = [
     "aesgcm_mgpu_create", "aesgcm_mgpu_ranks", "aesgcm_mgpu_ctx", "aesgcm_mgpu_crypt_dev", "aesgcm_mgpu_destroy",
     "aesgcm_ctx_last_launch", "aesgcm_wipe_failed_dev", "aesgcm_mgpu_last_tags", "aesgcm_mgpu_sync", "aesgcm_batch_ceiling_probe_dev",
     "aesgcm_ctx_status", "aesgcm_stream_update_dev", "aesgcm_stream_export", "aesgcm_stream_import", "aesgcm_frames_ceiling_probe_dev", "aesgcm_ctx_last_route",
+    "aesgcm_keytab_create", "aesgcm_keytab_set", "aesgcm_keytab_set_dev", "aesgcm_keytab_clear", "aesgcm_keytab_crypt_dev", "aesgcm_keytab_status", "aesgcm_keytab_destroy",
 ]
 
 
@@ -695,6 +696,123 @@ class Context:
         h, b = u64(0), u64(0)
         _chk(self._lib.aesgcm_ctx_split(self._c, nbytes, first_block, ctypes.byref(h), ctypes.byref(b)))
         return h.value, b.value
+
+
+# ---------------------------------------------------------------- key tables (aesgcm_keytab_*)
+def _keytab_typed(L):
+    """type the aesgcm_keytab_* symbols on first use, not in _typed: the fake runtime of tests/fake_hip links no key-table unit and still loads"""
+    if not getattr(L, "_keytab_typed", False):
+        L.aesgcm_keytab_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_keytab_set.argtypes = [vp, sz, sz, vp, vp]
+        L.aesgcm_keytab_set_dev.argtypes = [vp, sz, vp, vp, vp]
+        L.aesgcm_keytab_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_keytab_crypt_dev.argtypes = [vp, cint, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_keytab_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_keytab_destroy.argtypes = [vp]
+        L._keytab_typed = True
+    return L
+
+
+class KeyTable:
+    """aesgcm_keytab: n_slots device-resident slots of one key size; the key schedule, H and its powers are computed on the GPU once per `set`, and a crypt call
+    names a slot per packet (include/aesgcm.h "key tables").  Belongs to the library that made it (create it inside a debug_library block to force shapes)."""
+
+    def __init__(self, key_len, n_slots, device=0):
+        self._t = None
+        L = _keytab_typed(load())
+        t = vp()
+        _chk(L.aesgcm_keytab_create(ctypes.byref(t), device, key_len, n_slots))
+        self._t, self._lib = t.value, L
+        self.key_len, self.n_slots, self.device = key_len, n_slots, device
+
+    _lib = None
+
+    def close(self):
+        if self._t:
+            self._lib.aesgcm_keytab_destroy(self._t)
+            self._t = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set(self, first_slot, keys, stream=None):
+        """aesgcm_keytab_set: host keys (one bytes-like of n * key_len bytes, or a list of keys) into slots first_slot, first_slot + 1, ..."""
+        kb = b"".join(bytes(k) for k in keys) if isinstance(keys, (list, tuple)) else bytes(keys)
+        if len(kb) % self.key_len:
+            raise AesGcmError(EARG, "keys must be a multiple of %d bytes" % self.key_len)
+        _chk(self._lib.aesgcm_keytab_set(self._t, first_slot, len(kb) // self.key_len, kb, stream))
+        return self
+
+    def set_dev(self, n, d_slots, d_keys, stream=None):
+        """aesgcm_keytab_set_dev: n keys from device memory (n x key_len bytes) into the slots d_slots (n uint32, device memory)"""
+        _chk(self._lib.aesgcm_keytab_set_dev(self._t, n, d_slots, d_keys, stream))
+        return self
+
+    def clear(self, first_slot, n=1, stream=None):
+        """aesgcm_keytab_clear: retire slots first_slot .. first_slot + n - 1 (zeroed, unset: their packets are refused)"""
+        _chk(self._lib.aesgcm_keytab_clear(self._t, first_slot, n, stream))
+        return self
+
+    def crypt_dev(self, decrypt, n_pkts, d_slots, d_ivs, d_in, d_data_off, d_out, d_tags, d_aad=None, d_aad_off=None,
+                  d_expect_tags=None, d_auth=None, pkt_len=0, aad_len=0, stream=None):
+        """aesgcm_keytab_crypt_dev: packet p under slot d_slots[p] (uint32, device memory); the rest as batch_crypt_var_dev.  d_data_off = None: fixed-size
+        records of pkt_len bytes (and aad_len bytes of AAD each unless d_aad_off is given)."""
+        _chk(self._lib.aesgcm_keytab_crypt_dev(self._t, int(bool(decrypt)), n_pkts, d_slots, d_ivs, d_aad, aad_len, d_aad_off,
+                                               d_in, pkt_len, d_data_off, d_out, d_tags, d_expect_tags, d_auth, stream))
+
+    def status(self):
+        """aesgcm_keytab_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""
+        code, detail = cint(0), u64(0)
+        _chk(self._lib.aesgcm_keytab_status(self._t, ctypes.byref(code), ctypes.byref(detail)))
+        return code.value, detail.value
+
+    def crypt(self, slots, ivs, aads, datas, decrypt=False, tags=None):
+        """Host convenience (tests, examples): packet p = (slots[p], ivs[p], aads[p], datas[p]) through one offset-array call.
+        -> (outputs, tags) on encrypt; (outputs, tags, auth) on decrypt, auth[p] = 1 when tags[p] (the expected tags given) matches."""
+        import struct
+        n = len(slots)
+        if not (len(ivs) == len(aads) == len(datas) == n) or not n:
+            raise AesGcmError(EARG, "slots, ivs, aads and datas must be equally long and not empty")
+        doff, aoff = [0], [0]
+        for d in datas:
+            doff.append(doff[-1] + len(d))
+        for a in aads:
+            aoff.append(aoff[-1] + len(a))
+        blob = b"".join(bytes(d) for d in datas)
+        ablob = b"".join(bytes(a) for a in aads)
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("ivs", 12 * n), ("data", len(blob)), ("aad", len(ablob)),
+                                                                          ("doff", 8 * (n + 1)), ("aoff", 8 * (n + 1)), ("tags", 16 * n), ("exp", 16 * n), ("auth", 4 * n))}
+        try:
+            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
+            bufs["ivs"].upload(b"".join(_fixed(iv, 12, "iv") for iv in ivs))
+            if blob:
+                bufs["data"].upload(blob)
+            if ablob:
+                bufs["aad"].upload(ablob)
+            bufs["doff"].upload(struct.pack("<%dQ" % (n + 1), *doff))
+            bufs["aoff"].upload(struct.pack("<%dQ" % (n + 1), *aoff))
+            if decrypt and tags is not None:
+                bufs["exp"].upload(b"".join(_fixed(t, 16, "tag") for t in tags))
+            self.crypt_dev(decrypt, n, bufs["slots"].ptr, bufs["ivs"].ptr, bufs["data"].ptr, bufs["doff"].ptr, bufs["data"].ptr, bufs["tags"].ptr,
+                           d_aad=bufs["aad"].ptr, d_aad_off=bufs["aoff"].ptr, d_expect_tags=bufs["exp"].ptr if (decrypt and tags is not None) else None,
+                           d_auth=bufs["auth"].ptr if decrypt else None)
+            _chk(load().aesgcm_dev_sync(self.device))
+            out = bytes(bufs["data"].download(len(blob))) if blob else b""
+            tg = bytes(bufs["tags"].download(16 * n))
+            outs = [out[doff[p]:doff[p + 1]] for p in range(n)]
+            tgs = [tg[16 * p:16 * p + 16] for p in range(n)]
+            if not decrypt:
+                return outs, tgs
+            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n))))
+            return outs, tgs, auth
+        finally:
+            for b in bufs.values():
+                b.free()
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

@@ -382,6 +382,48 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
                                const void *d_aad, const uint64_t *d_aad_off, const void *d_in, const uint64_t *d_data_off,
                                void *d_out, void *d_tags, const void *d_expect_tags, int *d_auth, void *stream);
 
+/* ---------------------------------------------------------------- key tables: batches of many keys without per-packet key setup
+ * Between one key per context and one raw key per packet (the batch entry points above): a MACsec SecY with many secure associations, an IPsec gateway, a TLS
+ * terminator -- thousands of keys, each used for many packets and changed rarely; the reference's own pre-expanded-key mode (config/config_aes_kprexp.py) and its
+ * harness, which loads a key and then sends frame after frame under it (tb/gcm_gctr.py:144-175).  A table is device memory of n_slots slots of ONE key size
+ * (16, 24 or 32 bytes); a slot holds the round keys, H and the powers H^(2^j) of the GHASH Horner strides, computed on the GPU once when the key is set -- none of
+ * it is ever copied back to the host, and there is no call to read it.  A crypt call names a slot per packet and runs the batch kernel's loop without the
+ * per-packet key schedule, H = E_K(0) and squaring chain; E_K(J0) stays per packet.
+ *   aesgcm_keytab_create   n_slots zeroed slots, all unset (n_slots < 2^31).  AESGCM_EHIP without a usable device.
+ *   aesgcm_keytab_set      keys[n][key_len] from HOST memory into slots first_slot .. first_slot + n - 1 (AESGCM_EARG past the end).  The keys pass through a
+ *                          device staging buffer of the table that is zeroed on `stream` as soon as the expansion has read it; `keys` may be reused on return.
+ *   aesgcm_keytab_set_dev  d_keys[n][key_len] in DEVICE memory into the slots d_slots[0 .. n-1] (device memory).  An entry whose slot is n_slots or more is skipped and
+ *                          reported through aesgcm_keytab_status (detail = its index in d_slots); a slot named twice in one call takes one of its keys.
+ *   aesgcm_keytab_clear    retire slots first_slot .. first_slot + n - 1: zeroed and unset; packets that name them are refused from then on.
+ *   aesgcm_keytab_crypt_dev  n_pkts packets, packet p under slot d_slots[p]; the other arguments as aesgcm_packets_crypt_dev: fixed-size records (d_aad_off and
+ *                          d_data_off NULL: aad_len / pkt_len bytes each, < 2^28, packets back to back) or offset arrays of n_pkts + 1 uint64 entries (aad_len /
+ *                          pkt_len then ignored; d_aad_off NULL = no AAD).  d_ivs[n][12], d_tags[n][16] (decrypt: the COMPUTED tags), d_auth[p] (decrypt, optional)
+ *                          = 1 if the tag equals d_expect_tags[p] (all 1 when that is NULL).  Shape and order as aesgcm_batch_crypt_var_dev: 8, 16 or 64 lanes per
+ *                          packet by count (aesgcm_batch_shape), by falling length class from 262144 packets (98304 for the longer keys).  A long packet still runs
+ *                          on one lane group: key tables do not route messages of megabytes to the row kernels (use a context for those).
+ *   A packet the device cannot process -- its slot is n_slots or more, unset or cleared; its data or AAD range falls (an offset below the one before) or is 2^28
+ *   bytes or more -- is REFUSED on its own: its output bytes are left untouched (nothing else of it is read), its tag is written as 16 zero bytes, d_auth[p] = 0 on
+ *   decrypt, and the table's status word records it.  Every other packet of the call is processed normally; an out-of-range slot is never read.
+ *   aesgcm_keytab_status   *code = AESGCM_EARG and *detail = the LOWEST refused packet (or skipped set_dev entry) since the last read, or AESGCM_OK and 0.  Reading
+ *                          clears it.  It does not wait for calls in flight: synchronise the streams they ran on first.
+ *   aesgcm_keytab_destroy  waits for the device, zeroes the slots and the staging buffer, frees them.
+ * Decrypt outputs work with aesgcm_wipe_failed_dev (a refused packet has d_auth = 0; a falling or too-long range is left untouched by it as well).
+ * ORDERING: every call is asynchronous and stream-ordered on `stream` (NULL = the null stream).  A set or clear on stream A and a crypt call on stream B that names
+ * the same slot are NOT ordered by the library: the caller orders them (an event, or one stream for both).  Key rotation: set the new key into an unused slot,
+ * switch the packets' slot numbers to it, clear the old slot once no call in flight names it (INTEGRATION.md "Key tables").  The calls of one table are
+ * thread-safe; a table belongs to the device it was created on. */
+typedef struct aesgcm_keytab aesgcm_keytab;
+AESGCM_API int aesgcm_keytab_create(aesgcm_keytab **out, int device, size_t key_len, size_t n_slots);
+AESGCM_API int aesgcm_keytab_set(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *keys, void *stream);
+AESGCM_API int aesgcm_keytab_set_dev(aesgcm_keytab *t, size_t n, const uint32_t *d_slots, const void *d_keys, void *stream);
+AESGCM_API int aesgcm_keytab_clear(aesgcm_keytab *t, size_t first_slot, size_t n, void *stream);
+AESGCM_API int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const void *d_ivs,
+                            const void *d_aad, size_t aad_len, const uint64_t *d_aad_off,
+                            const void *d_in, size_t pkt_len, const uint64_t *d_data_off, void *d_out,
+                            void *d_tags, const void *d_expect_tags, int *d_auth, void *stream);
+AESGCM_API int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_keytab_destroy(aesgcm_keytab *t);
+
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
  * tb/gcm_model.py:21-35): all AAD first, then data; every chunk except the last of its kind must be
