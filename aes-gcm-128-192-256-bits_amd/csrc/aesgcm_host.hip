@@ -832,7 +832,7 @@ int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u6
 // Variable-length batches by length class: mixed frames of 64 .. 1514 bytes, GiB/s in array order / by class (profiles/r04/batch_mixed_*.txt): AES-128 65536 packets
 // 202 / 178, 262144 313 / 307, 393216 332 / 342, 2^20 362 / 493; AES-256 65536 177 / 167, 98304 205 / 213, 262144 266 / 290, 2^20 301 / 437.
 #define BATCH_ORDER_MIN(nr) ((nr) == 10 ? 262144u : 98304u)
-int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchParams &p, void *stream) {
+int batch_plan(int device, int decrypt, size_t n_pkts, size_t key_len, BatchParams &p, void *stream, BatchPlan &b) {
     if (key_len != 16 && key_len != 24 && key_len != 32) return AESGCM_EKEYLEN;
     if (n_pkts >= (((size_t)1) << 31)) return AESGCM_ETOOLONG;
     DeviceState *ds;
@@ -841,7 +841,6 @@ int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchPa
     if ((rc = set_lds_attrs(device, ds))) return rc;
     HIPCHK(hipSetDevice(device));
     p.n_pkts = (u32)n_pkts;
-    u32 wgs = 0;
     {   // a fresh dispenser per launch (zeroed on the launch stream), so launches on different streams may overlap
         std::lock_guard<std::mutex> lk(g_mu);
         p.counter = ds->batch_counter + (ds->batch_slot++ % BATCH_DISPENSERS);
@@ -857,21 +856,19 @@ int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchPa
     if (decrypt == 2 && lg != 3) { snprintf(g_err, sizeof g_err, "the probe of the batch kernel exists in the 8-lanes-per-packet shape; this call takes %d", 1 << lg); return AESGCM_EARG; }
     if (lg <= 6) {
         // packets of mixed length: by falling length class once the batch fills the machine several times over (BATCH_ORDER_MIN; as aesgcm_packets_crypt_dev)
-        OrderSlot *oslot = nullptr;
         bool ordered = lg < 6 && p.data_off && n_pkts >= BATCH_ORDER_MIN(nr);
 #ifdef AESGCM_DEBUG_KNOBS
         if (g_force.batch_order) ordered = lg < 6 && p.data_off && g_force.batch_order == 1;
 #endif
-        std::unique_lock<std::mutex> order_lock(g_mu, std::defer_lock);             // held from the choice of the slot to the event behind its reader: callers on other threads queue up here
         if (ordered) {
-            order_lock.lock();
-            oslot = &ds->order[ds->order_next++ & 3u];
-            if ((rc = order_launch(*oslot, p.data_off, n_pkts, st, &p.perm))) return rc;
+            b.order_lock = std::unique_lock<std::mutex>(g_mu);                        // held from the choice of the slot to the event behind its reader: callers on other threads queue up here
+            b.oslot = &ds->order[ds->order_next++ & 3u];
+            if ((rc = order_launch(*b.oslot, p.data_off, n_pkts, st, &p.perm))) return rc;
         }
         p.plain = !p.data_off && !p.aad_off && !p.aad_len && p.aligned && p.pkt_len && p.pkt_len % (16u << lg) == 0;
         const u32 waves_per_wg = (u32)BATCH3_LANES(nr) / 64;
         const u32 P = 64u >> lg, per_wg = waves_per_wg * P;
-        wgs = (u32)((n_pkts + per_wg - 1) / per_wg);
+        u32 wgs = (u32)((n_pkts + per_wg - 1) / per_wg);
         if (wgs > (u32)ds->n_cu) wgs = (u32)ds->n_cu;
         u32 deal = (u32)(n_pkts / ((size_t)wgs * waves_per_wg * 16));
         deal = deal < P ? P : deal > 8 * P ? 8 * P : (deal + P - 1) / P * P;
@@ -879,11 +876,21 @@ int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchPa
         if (g_force.batch_deal >= 1 && g_force.batch_deal <= 4096) deal = ((u32)g_force.batch_deal + P - 1) / P * P;
 #endif
         p.deal = deal;
-        HIPCHK(klaunch_batch3(nr, decrypt, lg, wgs, st, ds->tables, p));
-        if (oslot && p.perm) HIPCHK(hipEventRecord(oslot->done, st));
+        b.nr = nr; b.lg = lg; b.wgs = wgs; b.st = st; b.tables = ds->tables;
         return AESGCM_OK;
     }
     return AESGCM_EARG;                                         // batch_pick_lg gives 3, 4 or 6
+}
+int batch_done(const BatchPlan &b, const BatchParams &p) {
+    if (b.oslot && p.perm) HIPCHK(hipEventRecord(b.oslot->done, b.st));
+    return AESGCM_OK;
+}
+int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchParams &p, void *stream) {
+    BatchPlan b;
+    const int rc = batch_plan(device, decrypt, n_pkts, key_len, p, stream, b);
+    if (rc) return rc;
+    HIPCHK(klaunch_batch3(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, p));
+    return batch_done(b, p);
 }
 
 

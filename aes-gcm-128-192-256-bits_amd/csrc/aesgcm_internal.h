@@ -233,6 +233,11 @@ int rows_scratch(aesgcm_ctx *c, size_t slots, size_t n, hipStream_t st, RowsScra
 int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktParams *k = nullptr);
 bool packets_by_rows(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len);
 int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr = nullptr, const u32 *d_len = nullptr, const RowsHdr *hdr = nullptr);
+// A batch launch as batch_plan chose it (fills p's dispenser, order, plain and deal): the caller launches k_batch3 (batch_launch) or k_kt_batch
+// (aesgcm_keytab_crypt_dev) with it, then batch_done records the order slot's event behind that launch.  order_lock holds the order slots until then.
+struct BatchPlan { int nr = 0, lg = 0; u32 wgs = 0; hipStream_t st = nullptr; const DevTables *tables = nullptr; OrderSlot *oslot = nullptr; std::unique_lock<std::mutex> order_lock; };
+int batch_plan(int device, int decrypt, size_t n_pkts, size_t key_len, BatchParams &p, void *stream, BatchPlan &b);
+int batch_done(const BatchPlan &b, const BatchParams &p);
 int batch_launch(int device, int decrypt, size_t n_pkts, size_t key_len, BatchParams &p, void *stream);
 void pipeline_release(aesgcm_ctx *c);
 int pipeline_prepare(aesgcm_ctx *c, size_t chunk);

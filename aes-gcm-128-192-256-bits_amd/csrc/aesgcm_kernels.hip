@@ -23,6 +23,7 @@
 // lane-wise (B_L = sum_i item_i[L] * H^(blocks to the end)), k_combine forms P = sum_L B_L * H^(63-L).
 // The tag is (P*H ^ L)*H ^ E_K(J0) = P*H^2 ^ L*H ^ E_K(J0).
 #include "aesgcm_internal.h"
+#include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
 
 #include <stddef.h>
@@ -714,174 +715,12 @@ __device__ __forceinline__ u32 groups_max(u32 v) {
 // at 10.3 cycles instead of 4.  BATCH3_PERM=1 makes the packets unions of service-group quads: at 16 lanes per packet a packet IS a service group (no
 // collision possible), at 8 a service group holds two packets.  With b = the lane's bits: 16 lanes: grp = b5 | b2^b3^b4, l = b4 b3 b1 b0; 8 lanes:
 // grp = b5 b4 | b2^b3, l = b3 b1 b0.  The tree partner l ^ 2^j is then lane ^ {1, 2, 12, 20}[j]: still a ds_swizzle, no index register.
+// The body is aesgcm_batch3_body.inc, which k_kt_batch (key tables, aesgcm_keytab_kernels.hip) runs as well with its key material read from slots.
 template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 decrypt, 2 = encrypt WITHOUT the data's loads and stores (aesgcm_batch_ceiling_probe_dev: what the formulation costs by itself)
 __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_batch3(const DevTables *__restrict__ tb, const BatchParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr u32 G = 1u << LG, P = 64u >> LG;
-    // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
-    // the slot address), then 32 bytes per packet for its H and E_K(J0)
-    constexpr u32 GRP_TAB = BATCH3_GROUP_LDS_LG(LG) - 32u, WAVES = BATCH3_LANES(NR) / 64u, HSLOTS = BATCH3_LDS_TAB_OFF + WAVES * P * GRP_TAB;
-    static_assert(BATCH3_LDS_TAB_OFF % 256u == 0 && GRP_TAB % 256u == 0, "k_batch3: table slots are 256-byte aligned");
-    constexpr bool ONE_TAB = LG < 4;
-    constexpr bool PAIR = BATCH3_PAIR && BATCH3_PERM && BATCH3_DR && LG == 3;
-    const u32 tid = threadIdx.x, lane = tid & 63u;
-    main_fill_lds(smem, nullptr, tb, tid, false, BATCH3_LANES(NR));
-    __syncthreads();
-    const u32 lb = (lane & 31u) << 2;
-    const u32 wave_id = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));                                          // scalar
-    const u32 wave_tab = BATCH3_LDS_TAB_OFF + wave_id * P * GRP_TAB, wave_hs = HSLOTS + wave_id * P * 32u;
-    constexpr u32 KEYLEN = 4 * (NR - 6);
-    const u32 K = p.deal, nb = (p.n_pkts + K - 1) / K;
-    u32 pk0 = 0, pk_end = 0;
-    for (u32 guard = 0; guard <= p.n_pkts; ++guard, pk0 += P) {      // bounded on purpose (as every dispenser loop)
-        if (pk0 >= pk_end) {
-            u32 b = 0;
-            if (lane == 0) b = atomicAdd(p.counter, 1u) - p.counter_base;
-            b = __builtin_amdgcn_readfirstlane(b);
-            if (b >= nb) break;
-            pk0 = b * K;
-            pk_end = pk0 + K < p.n_pkts ? pk0 + K : p.n_pkts;
-        }
-        // the lane's position from a fresh lane id here and again behind the block loop (lane_id_fresh), so that none of it stays in a register across the loop
-        u32 grp, l;
-        batch3_pos<LG>(lane_id_fresh(), grp, l);
-        const u32 tabA = wave_tab + grp * GRP_TAB, hsA = wave_hs + grp * 32u;
-        const u32 tabAp = wave_tab + (grp ^ 3u) * GRP_TAB;             // PAIR: the table slot of the packet on lanes ^ 20
-        const bool pair_first = (grp & 2u) == 0;                       // lane bit 4 clear
-        const bool act = pk0 + grp < pk_end;                 // groups past the end shadow the first packet; their stores are masked
-        const u32 pkt = batch_map(p, act ? pk0 + grp : pk0);
-        const unsigned char *key = p.keys + (size_t)pkt * KEYLEN;
-        const unsigned char *ivp = p.ivs + (size_t)pkt * 12;
-        u32 pkt_len = p.pkt_len, aad_len = p.aad_len;
-        u64 doff = (u64)pkt * p.pkt_len, aoff = (u64)pkt * p.aad_len;
-        if (p.data_off) { doff = p.data_off[pkt]; pkt_len = (u32)(p.data_off[pkt + 1] - doff); }
-        if (p.aad_off) { aoff = p.aad_off[pkt]; aad_len = (u32)(p.aad_off[pkt + 1] - aoff); }
-        const bool aligned = p.aligned && ((doff & 15) == 0);
-        const unsigned char *aad = p.aad ? p.aad + aoff : nullptr;
-        const unsigned char *in = p.in + doff;
-        unsigned char *out = p.out + doff;
-        const u32 n_aad = (aad_len + 15) / 16, n_ct = (pkt_len + 15) / 16, n_seq = n_aad + n_ct;
-        const u32 iters = batch3_groups_max<LG>((n_seq + G - 1) / G);          // the wave runs to its longest packet; shorter ones idle FIRST (front padding)
-        const u32 pad = G * iters - n_seq;
-
-        // ---- aes_kexp for this lane's packet (config/config_aes_kexp.py:128-159); every lane of a group computes the same words
-        u32 rk[4 * (NR + 1)];
-        batch_key_expand<NR>(key, rk, smem, lb);
-        const u32 iv0 = load_le32(ivp), iv1 = load_le32(ivp + 4), iv2 = load_le32(ivp + 8);
-        // ---- H = E_K(0^128) on lane 0 and E_K(IV || 1) on lane 1 of the group (gcm_gctr.vhd:141-145), one pass for both
-        // Both go to the group's LDS slot (32 bytes behind its tables) and are read back where they are needed: H now and at the closing, E_K(J0) at the very
-        // end -- held in registers across the block loop they were part of what the 128-register build spilled.
-        {
-            u32 s0 = (l == 0 ? 0u : iv0) ^ rk[0], s1 = (l == 0 ? 0u : iv1) ^ rk[1], s2 = (l == 0 ? 0u : iv2) ^ rk[2];
-            u32 s3 = (l == 0 ? 0u : 0x01000000u) ^ rk[3];
-            aes_rounds_lds<NR>(s0, s1, s2, s3, rk, smem, lb);
-            const G128 e = mo_to_be(make_uint4(s0, s1, s2, s3));
-            if (l < 2) *reinterpret_cast<uint4 *>(smem + hsA + 16u * l) = make_uint4(e.w[0], e.w[1], e.w[2], e.w[3]);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        {
-            const uint4 hv = *reinterpret_cast<const uint4 *>(smem + hsA);
-            G128 h; h.w[0] = hv.x; h.w[1] = hv.y; h.w[2] = hv.z; h.w[3] = hv.w;
-            G128 hs = gf_sqr(gf_sqr(gf_sqr(h)));                                       // Horner stride H^(lanes per packet): LG squarings (linear: gf_sqr, no table)
-#pragma unroll
-            for (int j = 3; j < LG; j++) hs = gf_sqr(hs);
-            shoup2_build<LG>(smem, tabA, hs, l);
-        }
-
-        // ---- one pass: CTR on the lane's blocks and Horner over its slots
-        G128 acc; acc.w[0] = acc.w[1] = acc.w[2] = acc.w[3] = 0;
-        const CtrConsts cc = ctr_round1_consts(iv0, iv1, iv2, rk, smem, lb);
-        // Records of one size that is a whole number of wave-iterations, no AAD, aligned (cfg5's shape): no padding slot, no AAD slot, no ragged block -- the
-        // same work without the per-iteration tests and masks of the general loop below (launch-uniform: BatchParams::plain)
-        if (p.plain) {
-            const unsigned char *src = in + 16u * l;
-            unsigned char *dst = out + 16u * l;
-            for (u32 k = 0; k < iters; k++) {
-                if (k) acc = PAIR ? batch3_mul_pair(acc, smem, tabA, tabAp, pair_first) : BATCH3_MUL(acc, smem, tabA);
-                const uint4 x = DEC == 2 ? make_uint4(l, k, pkt, 0u) : gload16(src);     // (DEC == 2, the PROBE: the same instruction stream without the data's HBM traffic)
-                u32 s0, s1, s2, s3;
-                ctr_rounds_lds<NR>(bswap32(2u + k * G + l), cc, s0, s1, s2, s3, rk, smem, lb);
-                const uint4 y = make_uint4(x.x ^ s0, x.y ^ s1, x.z ^ s2, x.w ^ s3);
-                if (act && DEC != 2) gstore16(dst, y);
-                const G128 b = mo_to_be(DEC == 1 ? x : y);           // aes_gcm.vhd:207-211
-                acc.w[0] ^= b.w[0]; acc.w[1] ^= b.w[1]; acc.w[2] ^= b.w[2]; acc.w[3] ^= b.w[3];
-                src += 16u * G; dst += 16u * G;
-            }
-        } else
-        for (u32 k = 0; k < iters; k++) {
-            if (k) acc = PAIR ? batch3_mul_pair(acc, smem, tabA, tabAp, pair_first) : BATCH3_MUL(acc, smem, tabA);
-            const u32 v = k * G + l;
-            if (v < pad) continue;
-            const u32 j = v - pad;
-            uint4 gin;
-            if (j < n_aad) {
-                const u32 off = 16 * j, rem = aad_len - off;
-                gin = rem >= 16 ? gload16_any(aad + off) : load_block_bytes(aad + off, rem);
-            } else {
-                const u32 i = j - n_aad, off = 16 * i, rem = pkt_len - off;
-                const bool full = rem >= 16;                    // a whole block is one access at any address
-                uint4 x;
-                if (DEC == 2) x = make_uint4(l, i, pkt, 0u);
-                else if (full) x = aligned ? gload16(in + off) : gload16_any(in + off);
-                else x = load_block_bytes(in + off, rem < 16 ? rem : 16);
-                u32 s0, s1, s2, s3;
-                ctr_rounds_lds<NR>(bswap32(2u + i), cc, s0, s1, s2, s3, rk, smem, lb);
-                uint4 y = make_uint4(x.x ^ s0, x.y ^ s1, x.z ^ s2, x.w ^ s3);
-                if (rem < 16) y = mask_block(y, rem);
-                if (act && DEC != 2) {
-                    if (full) { if (aligned) gstore16(out + off, y); else gstore16_any(out + off, y); }
-                    else store_block_bytes(out + off, y, rem < 16 ? rem : 16);
-                }
-                gin = DEC == 1 ? x : y;                          // aes_gcm.vhd:207-211
-            }
-            const G128 b = mo_to_be(gin);
-            acc.w[0] ^= b.w[0]; acc.w[1] ^= b.w[1]; acc.w[2] ^= b.w[2]; acc.w[3] ^= b.w[3];
-        }
-
-        // ---- closing: P = sum_l B_l H^(15-l);  tag = P H^2 ^ L H ^ E_K(J0)  (gcm_ghash.vhd:257,293), as in k_pktg
-        u32 grp2, l2;
-        batch3_pos<LG>(lane_id_fresh(), grp2, l2);
-        const u32 tabA2 = wave_tab + grp2 * GRP_TAB, tabB2 = ONE_TAB ? tabA2 : tabA2 + 512u, hsA2 = wave_hs + grp2 * 32u;
-        const bool act2 = pk0 + grp2 < pk_end;
-        const u32 pkt2 = batch_map(p, act2 ? pk0 + grp2 : pk0);
-        G128 h;
-        { const uint4 hv = *reinterpret_cast<const uint4 *>(smem + hsA2); h.w[0] = hv.x; h.w[1] = hv.y; h.w[2] = hv.z; h.w[3] = hv.w; }
-        G128 c = gf_sqr(h);                                     // H^2
-        if (ONE_TAB) __builtin_amdgcn_wave_barrier();           // every lane is done with the Horner table
-        shoup2_build<LG>(smem, tabB2, c, l2);
-        const u32 tabAp2 = wave_tab + (grp2 ^ 3u) * GRP_TAB;
-        const bool pair_first2 = (grp2 & 2u) == 0;
-        acc = PAIR ? batch3_mul_pair(acc, smem, tabB2, tabAp2, pair_first2) : BATCH3_MUL(acc, smem, tabB2);
-        if (l2 == G - 2u) { acc.w[1] ^= aad_len * 8u; acc.w[3] ^= pkt_len * 8u; }     // the length block: both < 2^32 bits by the ABI's limits
-        if (ONE_TAB) __builtin_amdgcn_wave_barrier();
-        shoup2_build<LG>(smem, tabA2, h, l2);                   // the Horner table is no longer needed
-#pragma unroll
-        for (int j = 0; j < LG; j++) {
-            // level j: constant H^(2^j); two slots: H in tabA, H^2 in tabB, then H^4 -> tabA, H^8 -> tabB; one slot: each level rebuilds it (c = H^2 is still at hand for level 1)
-            if (ONE_TAB) { if (j >= 1) { if (j >= 2) c = gf_sqr(c); __builtin_amdgcn_wave_barrier(); shoup2_build<LG>(smem, tabA2, c, l2); } }
-            else if (j >= 2) { c = gf_sqr(c); shoup2_build<LG>(smem, (j & 1) ? tabB2 : tabA2, c, l2); }
-            const G128 t = PAIR ? batch3_mul_pair(acc, smem, tabA2, tabAp2, pair_first2) : BATCH3_MUL(acc, smem, (j & 1) ? tabB2 : tabA2);
-            G128 o;
-            o.w[0] = batch3_partner<LG>(t.w[0], j); o.w[1] = batch3_partner<LG>(t.w[1], j);
-            o.w[2] = batch3_partner<LG>(t.w[2], j); o.w[3] = batch3_partner<LG>(t.w[3], j);
-            if (l2 & (1u << j)) { acc.w[0] ^= o.w[0]; acc.w[1] ^= o.w[1]; acc.w[2] ^= o.w[2]; acc.w[3] ^= o.w[3]; }
-        }
-        { const uint4 ev = *reinterpret_cast<const uint4 *>(smem + hsA2 + 16u); acc.w[0] ^= ev.x; acc.w[1] ^= ev.y; acc.w[2] ^= ev.z; acc.w[3] ^= ev.w; }
-        if (l2 == G - 1u && act2) {
-            const uint4 tag = be_to_mo(acc);
-            store_block_bytes(p.tags + (size_t)pkt2 * 16, tag, 16);
-            if (DEC == 1 && p.auth) {
-                int ok = 1;
-                if (p.expect) {
-                    const uint4 e = load_block_bytes(p.expect + (size_t)pkt2 * 16, 16);
-                    ok = ((e.x ^ tag.x) | (e.y ^ tag.y) | (e.z ^ tag.z) | (e.w ^ tag.w)) == 0;
-                }
-                p.auth[pkt2] = ok;
-            }
-        }
-    }
+    constexpr bool SLOTS = false;                        // raw keys
+    constexpr const KtParams *kt = nullptr;
+#include "aesgcm_batch3_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1631,7 +1470,7 @@ hipError_t klaunch_set_attributes() {
     SETATTRB3P(10); SETATTRB3P(12); SETATTRB3P(14);
 #undef SETATTRB3P
 #undef ATTRCHK
-    return hipSuccess;
+    return klaunch_kt_attributes();                                            // the key tables' kernels (aesgcm_keytab_kernels.hip)
 }
 hipError_t klaunch_init_tables(DevTables *t) { hipLaunchKernelGGL(k_init_tables, dim3(1), dim3(256), 0, 0, t); return hipGetLastError(); }
 hipError_t klaunch_setup(hipStream_t st, KeyMaterial *km, const DevTables *tb, const uint8_t *d_key, int key_len, int pre_nr, u32 G) {

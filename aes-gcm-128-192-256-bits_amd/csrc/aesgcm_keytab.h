@@ -1,5 +1,6 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
-// Shared by the kernels' translation unit (aesgcm_keytab_kernels.hip: k_kt_setup, k_kt_batch) and the host's (aesgcm_keytab.hip); nothing else includes it.
+// Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots) and the host
+// (aesgcm_keytab.hip, which launches k_kt_batch as aesgcm_host.hip's batch_plan plans it for k_batch3).
 #pragma once
 #include "aesgcm_internal.h"
 
@@ -32,6 +33,6 @@ struct KtParams {
     u32 *status;
 };
 
-hipError_t klaunch_kt_attributes();        // hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every keytab instance, on the current device
+hipError_t klaunch_kt_attributes();        // hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every keytab instance, on the current device (klaunch_set_attributes)
 hipError_t klaunch_kt_setup(int nr, hipStream_t st, const DevTables *tb, const KtSetupParams &s);
 hipError_t klaunch_kt_batch(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtParams &p);

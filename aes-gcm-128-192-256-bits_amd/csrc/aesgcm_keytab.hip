@@ -1,6 +1,6 @@
 // aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_keytab_kernels.hip.
 // A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word; k_kt_setup fills slots from raw keys, a crypt call is one
-// k_kt_batch launch with batch_launch's geometry: the shape by batch_pick_lg, the same dispenser ring, the same order by falling length class.
+// k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.
 #include "aesgcm_keytab.h"
 
 #include <string.h>
@@ -17,24 +17,11 @@ struct aesgcm_keytab {
     std::mutex mu;
 };
 
-// 72 KiB and more of dynamic LDS: opt in once per device for this unit's kernels (set_lds_attrs does the same for aesgcm_kernels.hip)
-static std::mutex &kt_attr_mu = *new std::mutex();
-static std::vector<char> &kt_attr_done = *new std::vector<char>();
-static int kt_attrs(int device) {
-    std::lock_guard<std::mutex> lk(kt_attr_mu);
-    if ((int)kt_attr_done.size() <= device) kt_attr_done.resize(device + 1, 0);
-    if (kt_attr_done[device]) return AESGCM_OK;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(klaunch_kt_attributes());
-    kt_attr_done[device] = 1;
-    return AESGCM_OK;
-}
-
 static int kt_setup(aesgcm_keytab *t, const unsigned char *d_keys, const u32 *d_slots, size_t first, size_t n, hipStream_t st) {
     DeviceState *ds;
     int rc = device_state(t->device, &ds);
     if (rc) return rc;
-    if ((rc = kt_attrs(t->device))) return rc;
+    if ((rc = set_lds_attrs(t->device, ds))) return rc;
     KtSetupParams s;
     s.keys = d_keys; s.slots = d_slots; s.first = (u32)first; s.n = (u32)n; s.n_slots = (u32)t->n_slots; s.tab = t->tab; s.status = t->status;
     HIPCHK(klaunch_kt_setup(t->nr, st, ds->tables, s));
@@ -109,8 +96,7 @@ int aesgcm_keytab_clear(aesgcm_keytab *t, size_t first_slot, size_t n, void *str
     return AESGCM_OK;
 }
 
-// Batches with a slot per packet: batch_launch's geometry (aesgcm_host.hip) around k_kt_batch
-#define KT_ORDER_MIN(nr) ((nr) == 10 ? 262144u : 98304u)       /* as BATCH_ORDER_MIN */
+// Batches with a slot per packet: the argument checks and KtParams here, the dispenser, shape, order and deal by batch_plan, as batch_launch does for k_batch3
 int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const void *d_ivs,
                             const void *d_aad, size_t aad_len, const uint64_t *d_aad_off,
                             const void *d_in, size_t pkt_len, const uint64_t *d_data_off, void *d_out,
@@ -122,11 +108,6 @@ int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const 
     if (var ? (!d_in || !d_out) : (pkt_len && (!d_in || !d_out))) return AESGCM_EARG;
     if (d_aad_off ? !d_aad : (!var && aad_len && !d_aad)) return AESGCM_EARG;
     if (!var && (pkt_len >= ((size_t)1 << 28) || aad_len >= ((size_t)1 << 28))) return AESGCM_EARG;
-    DeviceState *ds;
-    int rc = device_state(t->device, &ds);
-    if (rc) return rc;
-    if ((rc = kt_attrs(t->device))) return rc;
-    HIPCHK(hipSetDevice(t->device));
     KtParams kp;
     memset(&kp, 0, sizeof kp);
     BatchParams &p = kp.b;
@@ -137,46 +118,12 @@ int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const 
     else if (!var) { p.aad = aad_len ? (const unsigned char *)d_aad : nullptr; p.aad_len = (u32)aad_len; }
     p.pkt_len = var ? 0u : (u32)pkt_len;
     p.aligned = (var || pkt_len % 16 == 0) && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;     // offset arrays: and the packet's offset is a multiple of 16
-    p.n_pkts = (u32)n_pkts;
     kp.slots = d_slots; kp.tab = t->tab; kp.n_slots = (u32)t->n_slots; kp.status = t->status;
-    hipStream_t st = (hipStream_t)stream;
-    {   // a fresh dispenser per launch, as batch_launch
-        std::lock_guard<std::mutex> lk(g_mu);
-        p.counter = ds->batch_counter + (ds->batch_slot++ % BATCH_DISPENSERS);
-        p.counter_base = 0;
-    }
-    HIPCHK(hipMemsetAsync(p.counter, 0, 4, st));
-    const int nr = t->nr;
-    int lg = batch_pick_lg(ds->n_cu, n_pkts, p.pkt_len, var);
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.batch_lanes) lg = g_force.batch_lanes == 8 ? 3 : g_force.batch_lanes == 16 ? 4 : 6;
-#endif
-    OrderSlot *oslot = nullptr;
-    bool ordered = lg < 6 && var && n_pkts >= KT_ORDER_MIN(nr);
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.batch_order) ordered = lg < 6 && var && g_force.batch_order == 1;
-#endif
-    std::unique_lock<std::mutex> order_lock(g_mu, std::defer_lock);
-    if (ordered) {
-        // (a falling range sorts into some class -- pkt_len_class clamps -- and is refused by the kernel all the same)
-        order_lock.lock();
-        oslot = &ds->order[ds->order_next++ & 3u];
-        if ((rc = order_launch(*oslot, p.data_off, n_pkts, st, &p.perm))) return rc;
-    }
-    p.plain = !p.data_off && !p.aad_off && !p.aad_len && p.aligned && p.pkt_len && p.pkt_len % (16u << lg) == 0;
-    const u32 waves_per_wg = (u32)BATCH3_LANES(nr) / 64;
-    const u32 P = 64u >> lg, per_wg = waves_per_wg * P;
-    u32 wgs = (u32)((n_pkts + per_wg - 1) / per_wg);
-    if (wgs > (u32)ds->n_cu) wgs = (u32)ds->n_cu;
-    u32 deal = (u32)(n_pkts / ((size_t)wgs * waves_per_wg * 16));
-    deal = deal < P ? P : deal > 8 * P ? 8 * P : (deal + P - 1) / P * P;
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.batch_deal >= 1 && g_force.batch_deal <= 4096) deal = ((u32)g_force.batch_deal + P - 1) / P * P;
-#endif
-    p.deal = deal;
-    HIPCHK(klaunch_kt_batch(nr, decrypt, lg, wgs, st, ds->tables, kp));
-    if (oslot && p.perm) HIPCHK(hipEventRecord(oslot->done, st));
-    return AESGCM_OK;
+    BatchPlan b;
+    const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
+    if (rc) return rc;
+    HIPCHK(klaunch_kt_batch(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, kp));
+    return batch_done(b, p);
 }
 
 int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {

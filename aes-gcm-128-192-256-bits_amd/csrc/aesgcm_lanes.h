@@ -1,4 +1,4 @@
-// aesgcm_lanes.h -- cross-lane helpers and the lane-group pieces of k_batch3 that the key-table kernels (aesgcm_keytab_kernels.hip) run as well.
+// aesgcm_lanes.h -- cross-lane helpers and the lane-group pieces of the body k_batch3 shares with k_kt_batch (aesgcm_batch3_body.inc).
 // Device code only: included by the two kernel translation units, not by aesgcm_dev.h (the host harness of tests/host_emul never sees it).
 #pragma once
 #include "aesgcm_dev.h"
