@@ -1,9 +1,12 @@
 // the body of k_batch3 (aesgcm_kernels.hip says what it computes and why its lanes are laid out so) and of k_kt_batch (aesgcm_keytab_kernels.hip).  Each kernel
 // includes this file with `p` (BatchParams), `kt` (KtParams *) and the key source SLOTS, a constant: false, the packet's raw key (aes_kexp, H = E_K(0) beside
 // E_K(J0), LG squarings of H; kt is null); true, its slot in the key table kt (round keys, H and H^(2^LG) as k_kt_setup stored them), and the checks that refuse
-// a packet on its own.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
+// a packet on its own.  WIRE (k_kt_wire, aesgcm_wire_kernels.hip; needs SLOTS): the packet is a FRAME in wire format, bytes [data_off[pkt], data_off[pkt + 1]) of
+// p.in = header | payload | ICV as `wf` (aesgcm_wire_fmt) lays it out -- AAD range, payload range, nonce (the slot's salt, then header bytes) and the ICV's place all come
+// from that one offset; p.aad is p.in, p.ivs / p.tags / p.expect / p.aad_off are unused.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
 // what that cost there).  For the same reason the two key sources read a packet's offsets in different orders: each keeps its kernel's instruction stream.
     static_assert(DEC == 0 || DEC == 1 || (DEC == 2 && !SLOTS), "the probe (DEC == 2) takes raw keys");
+    static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
@@ -51,6 +54,20 @@
         const unsigned char *ivp = p.ivs + (size_t)pkt * 12;
         u32 pkt_len = p.pkt_len, aad_len = p.aad_len;
         u64 doff = (u64)pkt * p.pkt_len, aoff = (u64)pkt * p.aad_len;
+        if constexpr (WIRE) {
+            // the frame's one range: AAD from its first byte, payload behind the header, the ICV last; auth-only: everything in front of the ICV is AAD.  A frame too
+            // short for header (nonce bytes included) and ICV is refused like a falling range
+            const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
+            const bool auth_only = (wf->flags & AESGCM_WIRE_AUTH_ONLY) != 0;
+            const u32 nonce_end = wf->iv_off + 12u - wf->salt_len, front = auth_only && nonce_end > wf->hdr_len ? nonce_end : wf->hdr_len;
+            bad |= e < b || e - b >= ((u64)1 << 28) || e - b < (u64)(front + wf->tag_len);
+            const u32 body = bad ? 0u : (u32)(e - b) - wf->tag_len;                  // the bytes in front of the ICV
+            aoff = b;
+            aad_len = auth_only ? body : wf->aad_len;
+            pkt_len = auth_only ? 0u : body - wf->hdr_len;
+            doff = b + (auth_only ? body : wf->hdr_len);
+            ivp = p.in + b + wf->iv_off;
+        } else {
         if (p.data_off) {
             if constexpr (SLOTS) { const u64 e = p.data_off[pkt + 1]; doff = p.data_off[pkt]; bad |= e < doff || e - doff >= ((u64)1 << 28); pkt_len = (u32)(e - doff); }
             else { doff = p.data_off[pkt]; pkt_len = (u32)(p.data_off[pkt + 1] - doff); }
@@ -58,6 +75,7 @@
         if (p.aad_off) {
             if constexpr (SLOTS) { const u64 e = p.aad_off[pkt + 1]; aoff = p.aad_off[pkt]; bad |= e < aoff || e - aoff >= ((u64)1 << 28); aad_len = (u32)(e - aoff); }
             else { aoff = p.aad_off[pkt]; aad_len = (u32)(p.aad_off[pkt + 1] - aoff); }
+        }
         }
         if constexpr (SLOTS) {
             bad |= ks->set != KT_SET;
@@ -83,7 +101,17 @@
                 rk[4 * q] = v.x; rk[4 * q + 1] = v.y; rk[4 * q + 2] = v.z; rk[4 * q + 3] = v.w;
             }
         } else batch_key_expand<NR>(p.keys + (size_t)pkt * KEYLEN, rk, smem, lb);
-        const u32 iv0 = load_le32(ivp), iv1 = load_le32(ivp + 4), iv2 = load_le32(ivp + 8);
+        u32 iv0, iv1, iv2;
+        if constexpr (WIRE) {
+            // the nonce: salt_len (0, 4 or 8) bytes of the slot's salt, then header bytes -- whole words either way; a refused frame's header is not read
+            const u32 sw = wf->salt_len >> 2;
+            const u32 f0 = bad ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
+            iv0 = sw ? ks->salt[0] : f0;
+            iv1 = sw > 1u ? ks->salt[1] : sw ? f0 : f1;
+            iv2 = sw > 1u ? f0 : sw ? f1 : f2;
+            // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through
+            if (p.in != p.out && st_ok) wire_copy_front(p.out + aoff, p.in + aoff, (u32)(doff - aoff), l, G);
+        } else { iv0 = load_le32(ivp); iv1 = load_le32(ivp + 4); iv2 = load_le32(ivp + 8); }
         // ---- H on lane 0 and E_K(IV || 1) on lane 1 of the group: with a raw key H = E_K(0^128) in the same pass (gcm_gctr.vhd:141-145), with a slot its stored H
         // Both go to the group's LDS slot (32 bytes behind its tables) and are read back where they are needed: H now and at the closing, E_K(J0) at the very
         // end -- held in registers across the block loop they were part of what the 128-register build spilled.
@@ -193,6 +221,24 @@
             if (l2 & (1u << j)) { acc.w[0] ^= o.w[0]; acc.w[1] ^= o.w[1]; acc.w[2] ^= o.w[2]; acc.w[3] ^= o.w[3]; }
         }
         { const uint4 ev = *reinterpret_cast<const uint4 *>(smem + hsA2 + 16u); acc.w[0] ^= ev.x; acc.w[1] ^= ev.y; acc.w[2] ^= ev.z; acc.w[3] ^= ev.w; }
+        if constexpr (WIRE) {
+            // the ICV = the tag's first tag_len bytes, the frame's last: written (encrypt) or compared (decrypt; copied when out of place) with stores that end at the
+            // frame's end.  A refused frame: nothing but auth 0.
+            if (l2 == G - 1u && act2) {
+                int ok = 0;
+                if (!bad) {
+                    const u32 tl = wf->tag_len;
+                    const u64 at = p.data_off[pkt2 + 1] - tl;
+                    const uint4 tag = be_to_mo(acc);                       // (tl is 8, 12 or 16: whole words)
+                    if (DEC == 1) {
+                        const uint4 e = wire_load_icv(p.in + at, tl);
+                        ok = ((e.x ^ tag.x) | (e.y ^ tag.y) | (tl > 8u ? e.z ^ tag.z : 0u) | (tl > 12u ? e.w ^ tag.w : 0u)) == 0;
+                        if (p.in != p.out) wire_store_icv(p.out + at, e, tl);
+                    } else wire_store_icv(p.out + at, tag, tl);
+                }
+                if (DEC == 1) p.auth[pkt2] = ok;
+            }
+        } else
         if (l2 == G - 1u && act2) {
             const uint4 tag = bad ? make_uint4(0u, 0u, 0u, 0u) : be_to_mo(acc);
             store_block_bytes(p.tags + (size_t)pkt2 * 16, tag, 16);

@@ -720,6 +720,8 @@ template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 de
 __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_batch3(const DevTables *__restrict__ tb, const BatchParams p) {
     constexpr bool SLOTS = false;                        // raw keys
     constexpr const KtParams *kt = nullptr;
+    constexpr bool WIRE = false;                         // packets as five arrays, not frames in wire format (aesgcm_wire_kernels.hip)
+    constexpr const aesgcm_wire_fmt *wf = nullptr;
 #include "aesgcm_batch3_body.inc"
 }
 
@@ -1470,7 +1472,8 @@ hipError_t klaunch_set_attributes() {
     SETATTRB3P(10); SETATTRB3P(12); SETATTRB3P(14);
 #undef SETATTRB3P
 #undef ATTRCHK
-    return klaunch_kt_attributes();                                            // the key tables' kernels (aesgcm_keytab_kernels.hip)
+    const hipError_t ek = klaunch_kt_attributes();                             // the key tables' kernels (aesgcm_keytab_kernels.hip, aesgcm_wire_kernels.hip)
+    return ek != hipSuccess ? ek : klaunch_wire_attributes();
 }
 hipError_t klaunch_init_tables(DevTables *t) { hipLaunchKernelGGL(k_init_tables, dim3(1), dim3(256), 0, 0, t); return hipGetLastError(); }
 hipError_t klaunch_setup(hipStream_t st, KeyMaterial *km, const DevTables *tb, const uint8_t *d_key, int key_len, int pre_nr, u32 G) {

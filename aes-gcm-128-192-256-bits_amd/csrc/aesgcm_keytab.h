@@ -1,5 +1,6 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
-// Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots) and the host
+// Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots; aesgcm_wire_kernels.hip:
+// k_kt_wire, the same body on frames in wire format) and the host
 // (aesgcm_keytab.hip, which launches k_kt_batch as aesgcm_host.hip's batch_plan plans it for k_batch3).
 #pragma once
 #include "aesgcm_internal.h"
@@ -11,7 +12,7 @@ struct __attribute__((aligned(128))) KtSlot {
     u32 rk[60];                            // round keys in memory-order words (KeyMaterial::rk); AES-128 / 192 use the first 44 / 52
     u32 nr;
     u32 set;                               // KT_SET once the rest is written
-    u32 pad0[2];
+    u32 salt[2];                           // the first bytes of a wire-format frame's nonce (aesgcm_keytab_set_salt), as two memory-order words; k_kt_setup leaves them alone
     uint4 hpow[KT_HPOW];                   // BE words (G128)
     u32 pad1[4];
 };
@@ -33,6 +34,30 @@ struct KtParams {
     u32 *status;
 };
 
+// A call of frames in wire format (k_kt_wire): b.data_off = the frame offsets, b.in = b.aad = the frames, b.ivs / b.tags / b.expect / b.aad_off unused
+struct KtWireParams {
+    KtParams k;
+    aesgcm_wire_fmt f;                     // checked by aesgcm_wire_fmt_check
+};
+
+// The frame-side accesses of k_kt_wire (aesgcm_batch3_body.inc, WIRE), all inside the frame and at any byte address.  The ICV is 8, 12 or 16 bytes: dwords.
+HD uint4 wire_load_icv(const unsigned char *p, u32 tag_len) {          // zero beyond tag_len
+    return make_uint4(gload4_any(p), gload4_any(p + 4), tag_len > 8u ? gload4_any(p + 8) : 0u, tag_len > 12u ? gload4_any(p + 12) : 0u);
+}
+HD void wire_store_icv(unsigned char *p, uint4 v, u32 tag_len) {
+    gstore4_any(p, v.x); gstore4_any(p + 4, v.y);
+    if (tag_len > 8u) gstore4_any(p + 8, v.z);
+    if (tag_len > 12u) gstore4_any(p + 12, v.w);
+}
+// out of place: the `front` bytes in front of the payload pass through, copied by the frame's G lanes (l = the lane's number) in 16-byte pieces; the last piece ends at
+// `front` and may overlap the one before (the same bytes twice).  Fewer than 16 bytes: byte by byte.
+HD void wire_copy_front(unsigned char *dst, const unsigned char *src, u32 front, u32 l, u32 G) {
+    if (front >= 16u) for (u32 o = 16u * l; o < front; o += 16u * G) { const u32 q = o + 16u <= front ? o : front - 16u; gstore16_any(dst + q, gload16_any(src + q)); }
+    else for (u32 o = l; o < front; o += G) dst[o] = src[o];
+}
+
 hipError_t klaunch_kt_attributes();        // hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every keytab instance, on the current device (klaunch_set_attributes)
 hipError_t klaunch_kt_setup(int nr, hipStream_t st, const DevTables *tb, const KtSetupParams &s);
 hipError_t klaunch_kt_batch(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtParams &p);
+hipError_t klaunch_wire_attributes();      // the same for the k_kt_wire instances (aesgcm_wire_kernels.hip)
+hipError_t klaunch_kt_wire(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireParams &p);

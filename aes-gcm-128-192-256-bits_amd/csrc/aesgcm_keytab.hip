@@ -1,8 +1,10 @@
 // aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_keytab_kernels.hip.
 // A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word; k_kt_setup fills slots from raw keys, a crypt call is one
-// k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.
+// k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.  Frames in wire
+// format (aesgcm_keytab_frames_crypt_dev) are one k_kt_wire launch (aesgcm_wire_kernels.hip) planned the same way.
 #include "aesgcm_keytab.h"
 
+#include <stddef.h>
 #include <string.h>
 
 struct aesgcm_keytab {
@@ -123,6 +125,67 @@ int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const 
     const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
     if (rc) return rc;
     HIPCHK(klaunch_kt_batch(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, kp));
+    return batch_done(b, p);
+}
+
+// ---------------------------------------------------------------- frames in wire format
+int aesgcm_wire_fmt_check(const aesgcm_wire_fmt *f) {
+    if (!f) return AESGCM_EARG;
+    if (f->salt_len != 0 && f->salt_len != 4 && f->salt_len != 8) return AESGCM_EARG;
+    if (f->tag_len != 8 && f->tag_len != 12 && f->tag_len != 16) return AESGCM_EARG;
+    if (f->flags & ~AESGCM_WIRE_AUTH_ONLY) return AESGCM_EARG;
+    if (f->hdr_len >= (1u << 16) || (!(f->flags & AESGCM_WIRE_AUTH_ONLY) && f->hdr_len < f->aad_len)) return AESGCM_EARG;      // (auth-only: aad_len is ignored)
+    if (f->iv_off > f->hdr_len || 12u - f->salt_len > f->hdr_len - f->iv_off) return AESGCM_EARG;       // the nonce's frame bytes end at the payload at the latest
+    return AESGCM_OK;
+}
+
+// the salts go the way the keys go: through the table's staging buffer on `stream`, from there into the slots (8 bytes each, 384 apart) by one 2-D copy
+int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, void *stream) {
+    if (!t) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (!salts || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);
+    HIPCHK(hipSetDevice(t->device));
+    const size_t bytes = n * 8;
+    if (bytes > t->stage_cap) {
+        if (t->stage) { HIPCHK(hipFree(t->stage)); t->stage = nullptr; t->stage_cap = 0; }   // hipFree waits for the launches that may still read it
+        const hipError_t e = hipMalloc((void **)&t->stage, bytes);
+        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+        t->stage_cap = bytes;
+    }
+    if (!t->stage_done) HIPCHK(hipEventCreateWithFlags(&t->stage_done, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent(st, t->stage_done, 0));                       // the staging buffer's previous user, on whatever stream it ran
+    HIPCHK(hipMemcpyAsync(t->stage, salts, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpy2DAsync((unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, salt), sizeof(KtSlot), t->stage, 8, 8, n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
+    HIPCHK(hipEventRecord(t->stage_done, st));
+    return AESGCM_OK;
+}
+
+// One k_kt_wire launch: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in and d_out, laid out by *fmt.  Planned as aesgcm_keytab_crypt_dev's offset-array
+// call (the lengths are on the device: shape by count, order by falling frame length class).
+int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, size_t n_frames, const uint32_t *d_slots, const void *d_in,
+                                   const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
+    const int frc = aesgcm_wire_fmt_check(fmt);
+    if (frc) return frc;
+    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
+    if (!n_frames) return AESGCM_OK;
+    if (!d_slots || !d_in || !d_out || !d_frame_off || (decrypt && !d_auth) || n_frames >= ((size_t)1 << 31)) return AESGCM_EARG;
+    KtWireParams wp;
+    memset(&wp, 0, sizeof wp);
+    BatchParams &p = wp.k.b;
+    p.in = p.aad = (const unsigned char *)d_in; p.out = (unsigned char *)d_out;
+    p.auth = decrypt ? d_auth : nullptr;
+    p.data_off = d_frame_off;
+    p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per frame, in the kernel)
+    wp.k.slots = d_slots; wp.k.tab = t->tab; wp.k.n_slots = (u32)t->n_slots; wp.k.status = t->status;
+    wp.f = *fmt;
+    BatchPlan b;
+    const int rc = batch_plan(t->device, decrypt, n_frames, t->key_len, p, stream, b);
+    if (rc) return rc;
+    HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, wp));
     return batch_done(b, p);
 }
 

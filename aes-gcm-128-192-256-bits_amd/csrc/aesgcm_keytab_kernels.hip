@@ -42,6 +42,8 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
     constexpr bool SLOTS = true;                         // key material from the slots of kt
     const KtParams *const kt = &kp;
     const BatchParams &p = kp.b;
+    constexpr bool WIRE = false;                         // packets as five arrays, not frames in wire format (aesgcm_wire_kernels.hip)
+    constexpr const aesgcm_wire_fmt *wf = nullptr;
 #include "aesgcm_batch3_body.inc"
 }
 

@@ -39,6 +39,7 @@ SYMBOLS = [
     "aesgcm_ctx_last_launch", "aesgcm_wipe_failed_dev", "aesgcm_mgpu_last_tags", "aesgcm_mgpu_sync", "aesgcm_batch_ceiling_probe_dev",
     "aesgcm_ctx_status", "aesgcm_stream_update_dev", "aesgcm_stream_export", "aesgcm_stream_import", "aesgcm_frames_ceiling_probe_dev", "aesgcm_ctx_last_route",
     "aesgcm_keytab_create", "aesgcm_keytab_set", "aesgcm_keytab_set_dev", "aesgcm_keytab_clear", "aesgcm_keytab_crypt_dev", "aesgcm_keytab_status", "aesgcm_keytab_destroy",
+    "aesgcm_wire_fmt_check", "aesgcm_keytab_set_salt", "aesgcm_keytab_frames_crypt_dev",
 ]
 
 
@@ -709,8 +710,38 @@ def _keytab_typed(L):
         L.aesgcm_keytab_crypt_dev.argtypes = [vp, cint, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
         L.aesgcm_keytab_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
         L.aesgcm_keytab_destroy.argtypes = [vp]
+        L.aesgcm_wire_fmt_check.argtypes = [ctypes.POINTER(WireFormat)]
+        L.aesgcm_keytab_set_salt.argtypes = [vp, sz, sz, vp, vp]
+        L.aesgcm_keytab_frames_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(WireFormat), sz, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
+
+
+WIRE_AUTH_ONLY = 1      # AESGCM_WIRE_AUTH_ONLY
+
+
+class WireFormat(ctypes.Structure):
+    """aesgcm_wire_fmt: how a frame header | payload | ICV is laid out (include/aesgcm.h "frames in WIRE FORMAT")"""
+    _fields_ = [("aad_len", ctypes.c_uint32), ("hdr_len", ctypes.c_uint32), ("iv_off", ctypes.c_uint32), ("salt_len", ctypes.c_uint32),
+                ("tag_len", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+    @classmethod
+    def macsec(cls, sci=True, auth_only=False):
+        """IEEE 802.1AE: DA SA | SecTAG (with or without the explicit SCI) | user data | 16-byte ICV; the slot's salt = the SCI, the PN is read from the SecTAG"""
+        h = 28 if sci else 20
+        return cls(h, h, 16, 8, 16, WIRE_AUTH_ONLY if auth_only else 0)
+
+    @classmethod
+    def esp(cls, tag_len=16):
+        """RFC 4106: SPI, sequence number | 8-byte IV field | payload | ICV of 16, 12 or 8 bytes; the slot's salt = the SA's 4-byte salt"""
+        return cls(8, 16, 8, 4, tag_len, 0)
+
+    def check(self):
+        """aesgcm_wire_fmt_check -> OK or EARG (no device needed)"""
+        return _keytab_typed(load()).aesgcm_wire_fmt_check(ctypes.byref(self))
+
+    def __repr__(self):
+        return "WireFormat(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
 
 
 class KeyTable:
@@ -764,6 +795,47 @@ class KeyTable:
         records of pkt_len bytes (and aad_len bytes of AAD each unless d_aad_off is given)."""
         _chk(self._lib.aesgcm_keytab_crypt_dev(self._t, int(bool(decrypt)), n_pkts, d_slots, d_ivs, d_aad, aad_len, d_aad_off,
                                                d_in, pkt_len, d_data_off, d_out, d_tags, d_expect_tags, d_auth, stream))
+
+    def set_salt(self, first_slot, salts, stream=None):
+        """aesgcm_keytab_set_salt: 8 bytes per slot (one bytes-like of n * 8 bytes, or a list; shorter entries are zero-padded) into slots first_slot, ..."""
+        items = [bytes(x) for x in salts] if isinstance(salts, (list, tuple)) else None
+        sb = b"".join(x.ljust(8, b"\0") for x in items) if items is not None else bytes(salts)
+        if len(sb) % 8 or (items is not None and any(len(x) > 8 for x in items)):
+            raise AesGcmError(EARG, "a salt is 8 bytes")
+        _chk(self._lib.aesgcm_keytab_set_salt(self._t, first_slot, len(sb) // 8, sb, stream))
+        return self
+
+    def frames_crypt_dev(self, decrypt, fmt, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth=None, stream=None):
+        """aesgcm_keytab_frames_crypt_dev: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in / d_out in the wire format fmt, under slot d_slots[p]"""
+        _chk(self._lib.aesgcm_keytab_frames_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream))
+
+    def crypt_frames(self, fmt, slots, frames, decrypt=False):
+        """Host convenience (tests, examples): whole frames (header | payload | ICV; on encrypt the ICV bytes are placeholders) through one call, in place.
+        -> (frames_out, auth); auth is None on encrypt."""
+        import struct
+        n = len(slots)
+        if len(frames) != n or not n:
+            raise AesGcmError(EARG, "slots and frames must be equally long and not empty")
+        off = [0]
+        for f in frames:
+            off.append(off[-1] + len(f))
+        blob = b"".join(bytes(f) for f in frames)
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("data", len(blob)), ("off", 8 * (n + 1)), ("auth", 4 * n))}
+        try:
+            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
+            if blob:
+                bufs["data"].upload(blob)
+            bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
+            self.frames_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
+                                  d_auth=bufs["auth"].ptr if decrypt else None)
+            _chk(load().aesgcm_dev_sync(self.device))
+            out = bytes(bufs["data"].download(len(blob))) if blob else b""
+            outs = [out[off[p]:off[p + 1]] for p in range(n)]
+            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
+            return outs, auth
+        finally:
+            for b in bufs.values():
+                b.free()
 
     def status(self):
         """aesgcm_keytab_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""

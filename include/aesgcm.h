@@ -424,6 +424,53 @@ AESGCM_API int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_p
 AESGCM_API int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_keytab_destroy(aesgcm_keytab *t);
 
+/* ---------------------------------------------------------------- key tables on frames in WIRE FORMAT (MACsec, ESP): one buffer, one launch
+ * What a SecY or an IPsec gateway holds is not five parallel arrays but FRAMES: one byte-packed buffer in which every frame is header | payload | ICV, the nonce partly
+ * in the header and partly a constant of the secure association, the ICV 8, 12 or 16 bytes.  aesgcm_keytab_frames_crypt_dev takes that buffer as it is: frame p is bytes
+ * [d_frame_off[p], d_frame_off[p + 1]) of d_in and of d_out (the same n_frames + 1 offsets for both; d_in == d_out allowed; any byte alignment), laid out by *fmt, which
+ * is per call:
+ *   bytes [0, aad_len)              authenticated, pass through unchanged
+ *   bytes [aad_len, hdr_len)        pass through, NOT authenticated (ESP's explicit IV field)
+ *   bytes [hdr_len, len - tag_len)  the payload: encrypted / decrypted (length 0 is legal)
+ *   the last tag_len bytes          the ICV = the leading tag_len bytes of the GCM tag
+ *   nonce                           salt[0 .. salt_len) of the frame's slot, then the 12 - salt_len frame bytes at iv_off (which end at hdr_len at the latest)
+ * The SALT is 8 bytes of slot state beside the key material: zero after aesgcm_keytab_create and aesgcm_keytab_clear, left alone by aesgcm_keytab_set / _set_dev,
+ * written by aesgcm_keytab_set_salt (salts[n][8] in HOST memory into slots first_slot .. first_slot + n - 1; stream-ordered like aesgcm_keytab_set; a format with
+ * salt_len 4 uses the first four bytes).
+ * Encrypt: the payload is encrypted and the ICV written.  Decrypt: the payload is decrypted and d_auth[p] = 1 iff the ICV in d_in equals the leading tag_len bytes of
+ * the computed tag (d_auth is required for decrypt and ignored for encrypt).  Out of place every byte of an accepted frame in d_out is defined: the header is copied,
+ * and on decrypt the ICV.  No byte outside an accepted frame's range and no byte at all of a refused frame is written.
+ * AESGCM_WIRE_AUTH_ONLY: nothing is encrypted; every byte in front of the ICV is AAD (MACsec integrity-only, E = 0; GMAC) and passes through.
+ * A frame the device cannot take is REFUSED on its own, as aesgcm_keytab_crypt_dev refuses a packet: its slot is n_slots or more, unset or cleared; its offsets fall;
+ * it is 2^28 bytes or more; it is shorter than hdr_len + tag_len (auth-only: than max(hdr_len, iv_off + 12 - salt_len) + tag_len).  Its output is untouched,
+ * d_auth[p] = 0 on decrypt, and the LOWEST such index goes to aesgcm_keytab_status.
+ * aesgcm_wire_fmt_check: AESGCM_OK, or AESGCM_EARG for a format the call refuses as a whole -- NULL, salt_len not 0 / 4 / 8, tag_len not 8 / 12 / 16, hdr_len < aad_len
+ * (unless auth-only), nonce bytes past hdr_len, an unknown flag, hdr_len >= 2^16.  It touches no device; aesgcm_keytab_frames_crypt_dev runs it first.
+ * FAIL-CLOSED needs nothing new: aesgcm_wipe_failed_dev(device, n_frames, d_out, 0, d_frame_off, d_auth, stream) behind a decrypt zeroes the failed frames whole.
+ * One k_kt_wire launch per call and one pass over the frame bytes; shape and order as aesgcm_keytab_crypt_dev with offset arrays (8, 16 or 64 lanes per frame by count,
+ * by falling frame length class from 262144 frames, 98304 for the longer keys).  Ordering and thread safety as the other key-table calls.
+ * Formats {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}:
+ *   MACsec, explicit SCI    {28, 28, 16, 8, 16, 0}   DA SA | SecTAG with SCI; the slot's salt = the secure channel's SCI, the PN is read at bytes 16 .. 19
+ *   MACsec, no SCI          {20, 20, 16, 8, 16, 0}   the salt as above (the SCI is implicit)
+ *   MACsec integrity-only   the same with AESGCM_WIRE_AUTH_ONLY (the user data is AAD as well)
+ *   ESP, RFC 4106           {8, 16, 8, 4, 16 | 12 | 8, 0}   SPI, sequence number | 8-byte IV field | payload | ICV; the slot's salt = the SA's 4-byte salt
+ * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows, ESN (its high sequence bits are not in the packet), MACsec confidentiality offsets
+ * 30 / 50, XPN, TLS records (their AAD is not a span of the wire bytes), and routing long frames to the row kernels (a frame runs on one lane group). */
+#define AESGCM_WIRE_AUTH_ONLY 1u   /* nothing is encrypted: every byte in front of the ICV is AAD (MACsec integrity-only, E = 0; GMAC) */
+typedef struct aesgcm_wire_fmt {
+    uint32_t aad_len;   /* frame bytes [0, aad_len) are authenticated and pass through unchanged                          */
+    uint32_t hdr_len;   /* payload starts here; hdr_len >= aad_len; bytes [aad_len, hdr_len) pass through, unauthenticated */
+    uint32_t iv_off;    /* the nonce's last 12 - salt_len bytes are frame bytes [iv_off, iv_off + 12 - salt_len) <= hdr_len */
+    uint32_t salt_len;  /* 0, 4 or 8: the nonce's first bytes come from the slot's salt                                   */
+    uint32_t tag_len;   /* 8, 12 or 16: the ICV = the frame's last tag_len bytes = the leading bytes of the GCM tag       */
+    uint32_t flags;     /* 0 or AESGCM_WIRE_AUTH_ONLY (then aad_len is ignored; hdr_len only bounds iv_off)               */
+} aesgcm_wire_fmt;
+AESGCM_API int aesgcm_wire_fmt_check(const aesgcm_wire_fmt *fmt);
+AESGCM_API int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, void *stream);
+AESGCM_API int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, size_t n_frames,
+                                   const uint32_t *d_slots, const void *d_in, const uint64_t *d_frame_off,
+                                   void *d_out, int *d_auth, void *stream);
+
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
  * tb/gcm_model.py:21-35): all AAD first, then data; every chunk except the last of its kind must be
