@@ -3,10 +3,15 @@
 // E_K(J0), LG squarings of H; kt is null); true, its slot in the key table kt (round keys, H and H^(2^LG) as k_kt_setup stored them), and the checks that refuse
 // a packet on its own.  WIRE (k_kt_wire, aesgcm_wire_kernels.hip; needs SLOTS): the packet is a FRAME in wire format, bytes [data_off[pkt], data_off[pkt + 1]) of
 // p.in = header | payload | ICV as `wf` (aesgcm_wire_fmt) lays it out -- AAD range, payload range, nonce (the slot's salt, then header bytes) and the ICV's place all come
-// from that one offset; p.aad is p.in, p.ivs / p.tags / p.expect / p.aad_off are unused.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
+// from that one offset; p.aad is p.in, p.ivs / p.tags / p.expect / p.aad_off are unused.  WIREX (k_kt_wirex, aesgcm_wirex_kernels.hip; needs WIRE): `wx` (KtWireXParams) adds
+// a 32-bit number per frame that is not on the wire, the upper half of its packet or sequence number; WIREX itself says whether it enters the nonce (AESGCM_WIREX_XPN,
+// MACsec XPN) or the AAD (AESGCM_WIREX_ESN, ESP with extended sequence numbers), and is 0 in every other kernel.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
 // what that cost there).  For the same reason the two key sources read a packet's offsets in different orders: each keeps its kernel's instruction stream.
     static_assert(DEC == 0 || DEC == 1 || (DEC == 2 && !SLOTS), "the probe (DEC == 2) takes raw keys");
     static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
+    static_assert(!WIREX || WIRE, "the number that is not on the wire belongs to a frame in wire format");
+    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN, "one extension or none");
+    constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
@@ -58,7 +63,7 @@
             // the frame's one range: AAD from its first byte, payload behind the header, the ICV last; auth-only: everything in front of the ICV is AAD.  A frame too
             // short for header (nonce bytes included) and ICV is refused like a falling range
             const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
-            const bool auth_only = (wf->flags & AESGCM_WIRE_AUTH_ONLY) != 0;
+            const bool auth_only = !x_esn && (wf->flags & AESGCM_WIRE_AUTH_ONLY) != 0;                   // (ESN: never -- aesgcm_wire_xfmt_check)
             const u32 nonce_end = wf->iv_off + 12u - wf->salt_len, front = auth_only && nonce_end > wf->hdr_len ? nonce_end : wf->hdr_len;
             bad |= e < b || e - b >= ((u64)1 << 28) || e - b < (u64)(front + wf->tag_len);
             const u32 body = bad ? 0u : (u32)(e - b) - wf->tag_len;                  // the bytes in front of the ICV
@@ -66,6 +71,7 @@
             aad_len = auth_only ? body : wf->aad_len;
             pkt_len = auth_only ? 0u : body - wf->hdr_len;
             doff = b + (auth_only ? body : wf->hdr_len);
+            if constexpr (x_esn) aad_len = 12u;                                      // SPI | seq-hi | seq-lo (RFC 4303): the frame's first 8 bytes around hi[pkt]
             ivp = p.in + b + wf->iv_off;
         } else {
         if (p.data_off) {
@@ -104,11 +110,16 @@
         u32 iv0, iv1, iv2;
         if constexpr (WIRE) {
             // the nonce: salt_len (0, 4 or 8) bytes of the slot's salt, then header bytes -- whole words either way; a refused frame's header is not read
-            const u32 sw = wf->salt_len >> 2;
+            const u32 sw = x_xpn ? 2u : wf->salt_len >> 2;                                              // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check)
             const u32 f0 = bad ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
             iv0 = sw ? ks->salt[0] : f0;
             iv1 = sw > 1u ? ks->salt[1] : sw ? f0 : f1;
             iv2 = sw > 1u ? f0 : sw ? f1 : f2;
+            if constexpr (x_xpn) {
+                // XPN (802.1AEbw): the slot's 12-byte salt XOR (SSCI | PN), big-endian: hi[pkt], then the four frame bytes at iv_off (f0: salt_len is 8).  The classic salt is
+                // not used; a refused frame's hi is not read
+                iv0 = ks->xpn[0] ^ ks->xpn[3]; iv1 = ks->xpn[1] ^ (bad ? 0u : bswap32(wx->hi[pkt])); iv2 = ks->xpn[2] ^ f0;
+            }
             // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through
             if (p.in != p.out && st_ok) wire_copy_front(p.out + aoff, p.in + aoff, (u32)(doff - aoff), l, G);
         } else { iv0 = load_le32(ivp); iv1 = load_le32(ivp + 4); iv2 = load_le32(ivp + 8); }
@@ -146,8 +157,9 @@
         G128 acc; acc.w[0] = acc.w[1] = acc.w[2] = acc.w[3] = 0;
         const CtrConsts cc = ctr_round1_consts(iv0, iv1, iv2, rk, smem, lb);
         // Records of one size that is a whole number of wave-iterations, no AAD, aligned (cfg5's shape): no padding slot, no AAD slot, no ragged block -- the
-        // same work without the per-iteration tests and masks of the general loop below (launch-uniform: BatchParams::plain)
-        if (p.plain) {
+        // same work without the per-iteration tests and masks of the general loop below (launch-uniform: BatchParams::plain; never frames, whose lengths are on the
+        // device -- k_kt_wirex is built without it)
+        if (!WIREX && p.plain) {
             const unsigned char *src = in + 16u * l;
             unsigned char *dst = out + 16u * l;
             for (u32 k = 0; k < iters; k++) {
@@ -170,6 +182,14 @@
             uint4 gin;
             if (j < n_aad) {
                 const u32 off = 16 * j, rem = aad_len - off;
+                if constexpr (x_esn) {
+                    // the one AAD block, built around the number that is not in the frame.  It is fetched here, once per frame on one lane, from a frame number worked out
+                    // afresh: loaded in front of the loop it would be one more register across it.  (A refused frame has no AAD block.)
+                    u32 xg, xl;
+                    batch3_pos<LG>(lane_id_fresh(), xg, xl);
+                    const u32 xpkt = batch_map(p, pk0 + xg < pk_end ? pk0 + xg : pk0);
+                    gin = make_uint4(gload4_any(aad), bswap32(wx->hi[xpkt]), gload4_any(aad + 4), 0u);
+                } else
                 gin = rem >= 16 ? gload16_any(aad + off) : load_block_bytes(aad + off, rem);
             } else {
                 const u32 i = j - n_aad, off = 16 * i, rem = pkt_len - off;

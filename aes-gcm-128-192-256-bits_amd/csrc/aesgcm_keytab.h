@@ -1,9 +1,10 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
 // Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots; aesgcm_wire_kernels.hip:
-// k_kt_wire, the same body on frames in wire format) and the host
+// k_kt_wire, the same body on frames in wire format; aesgcm_wirex_kernels.hip: k_kt_wirex, that with a 32-bit number per frame that is not on the wire) and the host
 // (aesgcm_keytab.hip, which launches k_kt_batch as aesgcm_host.hip's batch_plan plans it for k_batch3).
 #pragma once
 #include "aesgcm_internal.h"
+#include <stddef.h>
 
 // One slot: everything k_batch3 rebuilds per packet from a raw key, built once by k_kt_setup.  384 bytes = three 128-byte lines; `set` is written last.
 #define KT_SET 0x5345544Bu                 /* "KTES": the slot holds key material (zero = unset or cleared) */
@@ -14,8 +15,9 @@ struct __attribute__((aligned(128))) KtSlot {
     u32 set;                               // KT_SET once the rest is written
     u32 salt[2];                           // the first bytes of a wire-format frame's nonce (aesgcm_keytab_set_salt), as two memory-order words; k_kt_setup leaves them alone
     uint4 hpow[KT_HPOW];                   // BE words (G128)
-    u32 pad1[4];
+    u32 xpn[4];                            // MACsec XPN (aesgcm_keytab_set_xpn): the 12-byte salt as three memory-order words, then the SSCI; apart from `salt`, and k_kt_setup leaves them alone too
 };
+static_assert(offsetof(KtSlot, xpn) == 368, "the XPN state fills what was padding: the slot's other fields stay where they were");
 static_assert(sizeof(KtSlot) == 384, "a slot is three 128-byte lines");
 
 struct KtSetupParams {
@@ -40,6 +42,12 @@ struct KtWireParams {
     aesgcm_wire_fmt f;                     // checked by aesgcm_wire_fmt_check
 };
 
+// ... with an extension (k_kt_wirex): hi[p] = the upper half of frame p's 64-bit packet / sequence number, which is not in the frame
+struct KtWireXParams {
+    KtWireParams w;
+    const u32 *hi;                         // n_pkts numeric values
+};
+
 // The frame-side accesses of k_kt_wire (aesgcm_batch3_body.inc, WIRE), all inside the frame and at any byte address.  The ICV is 8, 12 or 16 bytes: dwords.
 HD uint4 wire_load_icv(const unsigned char *p, u32 tag_len) {          // zero beyond tag_len
     return make_uint4(gload4_any(p), gload4_any(p + 4), tag_len > 8u ? gload4_any(p + 8) : 0u, tag_len > 12u ? gload4_any(p + 12) : 0u);
@@ -61,3 +69,5 @@ hipError_t klaunch_kt_setup(int nr, hipStream_t st, const DevTables *tb, const K
 hipError_t klaunch_kt_batch(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtParams &p);
 hipError_t klaunch_wire_attributes();      // the same for the k_kt_wire instances (aesgcm_wire_kernels.hip)
 hipError_t klaunch_kt_wire(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireParams &p);
+hipError_t klaunch_wirex_attributes();     // ... and for the k_kt_wirex instances (aesgcm_wirex_kernels.hip)
+hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);

@@ -1,7 +1,8 @@
 // aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_keytab_kernels.hip.
 // A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word; k_kt_setup fills slots from raw keys, a crypt call is one
 // k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.  Frames in wire
-// format (aesgcm_keytab_frames_crypt_dev) are one k_kt_wire launch (aesgcm_wire_kernels.hip) planned the same way.
+// format (aesgcm_keytab_frames_crypt_dev) are one k_kt_wire launch (aesgcm_wire_kernels.hip) planned the same way; with a number per frame that is not on the wire
+// (aesgcm_keytab_frames_crypt_x_dev: MACsec XPN, ESP ESN) one k_kt_wirex launch (aesgcm_wirex_kernels.hip).
 #include "aesgcm_keytab.h"
 
 #include <stddef.h>
@@ -18,6 +19,21 @@ struct aesgcm_keytab {
     hipEvent_t stage_done = nullptr;   // behind the last zeroing of `stage`, on whichever stream it ran
     std::mutex mu;
 };
+
+// `bytes` of the table's staging buffer for a host-to-device copy on `st`, behind the buffer's previous user on whatever stream that ran; the caller holds t->mu and
+// records t->stage_done behind its own last use
+static int kt_stage(aesgcm_keytab *t, size_t bytes, hipStream_t st) {
+    if (bytes > t->stage_cap) {
+        if (t->stage) { HIPCHK(hipFree(t->stage)); t->stage = nullptr; t->stage_cap = 0; }   // hipFree waits for the launches that may still read it
+        const hipError_t e = hipMalloc((void **)&t->stage, bytes);
+        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+        t->stage_cap = bytes;
+    }
+    if (!t->stage_done) HIPCHK(hipEventCreateWithFlags(&t->stage_done, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent(st, t->stage_done, 0));
+    return AESGCM_OK;
+}
 
 static int kt_setup(aesgcm_keytab *t, const unsigned char *d_keys, const u32 *d_slots, size_t first, size_t n, hipStream_t st) {
     DeviceState *ds;
@@ -63,17 +79,10 @@ int aesgcm_keytab_set(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8
     std::lock_guard<std::mutex> lk(t->mu);
     HIPCHK(hipSetDevice(t->device));
     const size_t bytes = n * t->key_len;
-    if (bytes > t->stage_cap) {
-        if (t->stage) { HIPCHK(hipFree(t->stage)); t->stage = nullptr; t->stage_cap = 0; }   // hipFree waits for the launches that may still read it
-        const hipError_t e = hipMalloc((void **)&t->stage, bytes);
-        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-        t->stage_cap = bytes;
-    }
-    if (!t->stage_done) HIPCHK(hipEventCreateWithFlags(&t->stage_done, hipEventDisableTiming));
-    else HIPCHK(hipStreamWaitEvent(st, t->stage_done, 0));                       // the previous set's kernel and zeroing, on whatever stream they ran
+    int rc = kt_stage(t, bytes, st);                                            // (behind the previous set's kernel and zeroing)
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(t->stage, keys, bytes, hipMemcpyHostToDevice, st));
-    int rc = kt_setup(t, t->stage, nullptr, first_slot, n, st);
+    rc = kt_setup(t, t->stage, nullptr, first_slot, n, st);
     const hipError_t ez = hipMemsetAsync(t->stage, 0, bytes, st);               // the raw keys do not outlive the expansion
     if (rc) return rc;
     HIPCHK(ez);
@@ -148,15 +157,8 @@ int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const 
     std::lock_guard<std::mutex> lk(t->mu);
     HIPCHK(hipSetDevice(t->device));
     const size_t bytes = n * 8;
-    if (bytes > t->stage_cap) {
-        if (t->stage) { HIPCHK(hipFree(t->stage)); t->stage = nullptr; t->stage_cap = 0; }   // hipFree waits for the launches that may still read it
-        const hipError_t e = hipMalloc((void **)&t->stage, bytes);
-        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-        t->stage_cap = bytes;
-    }
-    if (!t->stage_done) HIPCHK(hipEventCreateWithFlags(&t->stage_done, hipEventDisableTiming));
-    else HIPCHK(hipStreamWaitEvent(st, t->stage_done, 0));                       // the staging buffer's previous user, on whatever stream it ran
+    const int rc = kt_stage(t, bytes, st);
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(t->stage, salts, bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpy2DAsync((unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, salt), sizeof(KtSlot), t->stage, 8, 8, n, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
@@ -164,17 +166,47 @@ int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const 
     return AESGCM_OK;
 }
 
-// One k_kt_wire launch: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in and d_out, laid out by *fmt.  Planned as aesgcm_keytab_crypt_dev's offset-array
-// call (the lengths are on the device: shape by count, order by falling frame length class).
-int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, size_t n_frames, const uint32_t *d_slots, const void *d_in,
-                                   const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
-    const int frc = aesgcm_wire_fmt_check(fmt);
+// MACsec XPN's slot state the same way: salts (12 bytes each) and SSCIs (4 each) side by side in the staging buffer, from there into KtSlot::xpn by two 2-D copies
+int aesgcm_keytab_set_xpn(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, const uint8_t *sscis, void *stream) {
+    if (!t) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (!salts || !sscis || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);
+    HIPCHK(hipSetDevice(t->device));
+    const size_t bytes = n * 16;
+    const int rc = kt_stage(t, bytes, st);
+    if (rc) return rc;
+    unsigned char *const x = (unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, xpn);
+    HIPCHK(hipMemcpyAsync(t->stage, salts, n * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t->stage + n * 12, sscis, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(x, sizeof(KtSlot), t->stage, 12, 12, n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(x + 12, sizeof(KtSlot), t->stage + n * 12, 4, 4, n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
+    HIPCHK(hipEventRecord(t->stage_done, st));
+    return AESGCM_OK;
+}
+
+int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf) {
+    if (!xf) return AESGCM_EARG;
+    const int frc = aesgcm_wire_fmt_check(&xf->f);
     if (frc) return frc;
+    if (xf->reserved || (xf->ext & ~(AESGCM_WIREX_XPN | AESGCM_WIREX_ESN)) || xf->ext == (AESGCM_WIREX_XPN | AESGCM_WIREX_ESN)) return AESGCM_EARG;
+    if ((xf->ext & AESGCM_WIREX_XPN) && xf->f.salt_len != 8) return AESGCM_EARG;                // the PN's lower half is the nonce's only frame bytes
+    if ((xf->ext & AESGCM_WIREX_ESN) && (xf->f.aad_len != 8 || (xf->f.flags & AESGCM_WIRE_AUTH_ONLY))) return AESGCM_EARG;      // SPI | sequence number, and a payload behind the header
+    return AESGCM_OK;
+}
+
+// One launch: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in and d_out, laid out by *fmt (checked by the caller).  Planned as aesgcm_keytab_crypt_dev's
+// offset-array call (the lengths are on the device: shape by count, order by falling frame length class).  ext 0: k_kt_wire; otherwise k_kt_wirex with d_hi.
+static int kt_frames_crypt(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, u32 ext, const uint32_t *d_hi, size_t n_frames, const uint32_t *d_slots,
+                           const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
     if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
     if (!n_frames) return AESGCM_OK;
     if (!d_slots || !d_in || !d_out || !d_frame_off || (decrypt && !d_auth) || n_frames >= ((size_t)1 << 31)) return AESGCM_EARG;
-    KtWireParams wp;
-    memset(&wp, 0, sizeof wp);
+    KtWireXParams xp;
+    memset(&xp, 0, sizeof xp);
+    KtWireParams &wp = xp.w;
     BatchParams &p = wp.k.b;
     p.in = p.aad = (const unsigned char *)d_in; p.out = (unsigned char *)d_out;
     p.auth = decrypt ? d_auth : nullptr;
@@ -182,11 +214,29 @@ int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_w
     p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per frame, in the kernel)
     wp.k.slots = d_slots; wp.k.tab = t->tab; wp.k.n_slots = (u32)t->n_slots; wp.k.status = t->status;
     wp.f = *fmt;
+    xp.hi = d_hi;
     BatchPlan b;
     const int rc = batch_plan(t->device, decrypt, n_frames, t->key_len, p, stream, b);
     if (rc) return rc;
-    HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, wp));
+    if (ext) HIPCHK(klaunch_kt_wirex(ext, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
+    else HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, wp));
     return batch_done(b, p);
+}
+
+int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, size_t n_frames, const uint32_t *d_slots, const void *d_in,
+                                   const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
+    const int frc = aesgcm_wire_fmt_check(fmt);
+    if (frc) return frc;
+    return kt_frames_crypt(t, decrypt, fmt, 0u, nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
+}
+
+// ... with hi[p], the half of frame p's 64-bit number that is not on the wire (MACsec XPN: into the nonce; ESP ESN: into the AAD).  ext 0 is the call above.
+int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_xfmt *xf, size_t n_frames, const uint32_t *d_slots, const uint32_t *d_hi,
+                                     const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
+    const int frc = aesgcm_wire_xfmt_check(xf);
+    if (frc) return frc;
+    if (xf->ext && !d_hi) return AESGCM_EARG;
+    return kt_frames_crypt(t, decrypt, &xf->f, xf->ext, xf->ext ? d_hi : nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
 }
 
 int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {

@@ -44,6 +44,8 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
     const BatchParams &p = kp.b;
     constexpr bool WIRE = false;                         // packets as five arrays, not frames in wire format (aesgcm_wire_kernels.hip)
     constexpr const aesgcm_wire_fmt *wf = nullptr;
+    constexpr u32 WIREX = 0;                            // ... and no number per packet beside them (aesgcm_wirex_kernels.hip)
+    constexpr const KtWireXParams *wx = nullptr;
 #include "aesgcm_batch3_body.inc"
 }
 

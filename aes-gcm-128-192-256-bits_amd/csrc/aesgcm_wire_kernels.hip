@@ -15,6 +15,8 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
     const KtParams *const kt = &wp.k;
     const BatchParams &p = wp.k.b;
     const aesgcm_wire_fmt *const wf = &wp.f;
+    constexpr u32 WIREX = 0;                            // every nonce and AAD byte is a frame byte or the slot's salt (otherwise: aesgcm_wirex_kernels.hip)
+    constexpr const KtWireXParams *wx = nullptr;
 #include "aesgcm_batch3_body.inc"
 }
 

@@ -1,0 +1,55 @@
+// aesgcm_wirex_kernels.hip -- key tables on frames in wire format whose 64-bit packet / sequence number is only half on the wire (gfx950): aesgcm_keytab_frames_crypt_x_dev's
+// kernel and its launcher; the host side is aesgcm_keytab.hip.
+//
+//   k_kt_wirex<NR,DEC,LG,EXT>   k_kt_wire's loop (aesgcm_batch3_body.inc, SLOTS = WIRE = true, WIREX = EXT) with one more 4-byte load per frame: hi[p], the upper half of
+//                           the frame's number, which the caller assigned (transmit) or recovered from its window (receive).  EXT says where it goes:
+//                             AESGCM_WIREX_XPN  the nonce = the slot's 12-byte XPN salt XOR (the slot's SSCI | be32(hi) | the SecTAG's four PN bytes); the rest as k_kt_wire
+//                             AESGCM_WIREX_ESN  the AAD = SPI | be32(hi) | sequence number, one block built in registers (96 bits in the length block); nonce, pass-through
+//                                               header and payload as k_kt_wire
+//                           A frame it cannot take is refused as k_kt_wire refuses it, and its hi is not read.
+// The mode is a template argument: 36 instances.  As a kernel parameter (one scalar branch per frame) it cost the AES-256 decrypt instances of 16 and 64 lanes per frame,
+// which sit at 128 registers in k_kt_wire already, eight bytes of scratch -- a launch-uniform flag that no longer fitted the scalar registers.  For the same reason the
+// body's loop for fixed-size records without AAD (BatchParams::plain), which a call of frames never takes, is not compiled into these kernels (that form was not tried
+// again as a kernel parameter afterwards).  Every instance: no scratch, 92 - 126 registers.
+// A translation unit of its own: its ISA census (`make asm_wirex`) is read apart from k_kt_wire's (`make asm_wire`), whose instruction streams stay what they were.
+#include "aesgcm_keytab.h"
+#include "aesgcm_lanes.h"
+
+template <int NR, int DEC, int LG, u32 EXT>              // DEC: 0 encrypt, 1 decrypt; EXT: AESGCM_WIREX_XPN or AESGCM_WIREX_ESN
+__global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_kt_wirex(const DevTables *__restrict__ tb, const KtWireXParams xp) {
+    static_assert(EXT == AESGCM_WIREX_XPN || EXT == AESGCM_WIREX_ESN, "without an extension the kernel is k_kt_wire");
+    constexpr bool SLOTS = true, WIRE = true;
+    constexpr u32 WIREX = EXT;
+    const KtWireXParams *const wx = &xp;
+    const KtParams *const kt = &xp.w.k;
+    const BatchParams &p = xp.w.k.b;
+    const aesgcm_wire_fmt *const wf = &xp.w.f;
+#include "aesgcm_batch3_body.inc"
+}
+
+// ------------------------------------------------------------------------------------------------ launchers
+hipError_t klaunch_wirex_attributes() {
+#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
+#define SETATTRX1(NR, D, LG, X) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR, D, LG, X>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG)))
+#define SETATTRX(NR, D) SETATTRX1(NR, D, 6, AESGCM_WIREX_XPN); SETATTRX1(NR, D, 4, AESGCM_WIREX_XPN); SETATTRX1(NR, D, 3, AESGCM_WIREX_XPN); \
+                        SETATTRX1(NR, D, 6, AESGCM_WIREX_ESN); SETATTRX1(NR, D, 4, AESGCM_WIREX_ESN); SETATTRX1(NR, D, 3, AESGCM_WIREX_ESN)
+    SETATTRX(10, 0); SETATTRX(12, 0); SETATTRX(14, 0); SETATTRX(10, 1); SETATTRX(12, 1); SETATTRX(14, 1);
+#undef SETATTRX
+#undef SETATTRX1
+#undef ATTRCHK
+    return hipSuccess;
+}
+
+hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
+    if (ext != AESGCM_WIREX_XPN && ext != AESGCM_WIREX_ESN) return hipErrorInvalidValue;
+#define LKX(NR, D, LG, X) hipLaunchKernelGGL((k_kt_wirex<NR, D, LG, X>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
+#define LKXE(NR, D, LG) do { if (ext == AESGCM_WIREX_XPN) LKX(NR, D, LG, AESGCM_WIREX_XPN); else LKX(NR, D, LG, AESGCM_WIREX_ESN); } while (0)
+#define LKXN(D, LG) do { if (nr == 10) LKXE(10, D, LG); else if (nr == 12) LKXE(12, D, LG); else LKXE(14, D, LG); } while (0)
+    if (lg == 3) { if (dec) LKXN(1, 3); else LKXN(0, 3); }
+    else if (lg == 4) { if (dec) LKXN(1, 4); else LKXN(0, 4); }
+    else { if (dec) LKXN(1, 6); else LKXN(0, 6); }
+#undef LKXN
+#undef LKXE
+#undef LKX
+    return hipGetLastError();
+}

@@ -40,6 +40,7 @@ SYMBOLS = [
     "aesgcm_ctx_status", "aesgcm_stream_update_dev", "aesgcm_stream_export", "aesgcm_stream_import", "aesgcm_frames_ceiling_probe_dev", "aesgcm_ctx_last_route",
     "aesgcm_keytab_create", "aesgcm_keytab_set", "aesgcm_keytab_set_dev", "aesgcm_keytab_clear", "aesgcm_keytab_crypt_dev", "aesgcm_keytab_status", "aesgcm_keytab_destroy",
     "aesgcm_wire_fmt_check", "aesgcm_keytab_set_salt", "aesgcm_keytab_frames_crypt_dev",
+    "aesgcm_wire_xfmt_check", "aesgcm_keytab_set_xpn", "aesgcm_keytab_frames_crypt_x_dev",
 ]
 
 
@@ -713,6 +714,9 @@ def _keytab_typed(L):
         L.aesgcm_wire_fmt_check.argtypes = [ctypes.POINTER(WireFormat)]
         L.aesgcm_keytab_set_salt.argtypes = [vp, sz, sz, vp, vp]
         L.aesgcm_keytab_frames_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(WireFormat), sz, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_wire_xfmt_check.argtypes = [ctypes.POINTER(WireFormatX)]
+        L.aesgcm_keytab_set_xpn.argtypes = [vp, sz, sz, vp, vp, vp]
+        L.aesgcm_keytab_frames_crypt_x_dev.argtypes = [vp, cint, ctypes.POINTER(WireFormatX), sz, vp, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
 
@@ -742,6 +746,32 @@ class WireFormat(ctypes.Structure):
 
     def __repr__(self):
         return "WireFormat(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+WIREX_XPN = 1           # AESGCM_WIREX_XPN
+WIREX_ESN = 2           # AESGCM_WIREX_ESN
+
+
+class WireFormatX(ctypes.Structure):
+    """aesgcm_wire_xfmt: a WireFormat and what the 32-bit number per frame that is not on the wire does (include/aesgcm.h "wire frames with 64-BIT NUMBERS")"""
+    _fields_ = [("f", WireFormat), ("ext", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    @classmethod
+    def macsec_xpn(cls, sci=True, auth_only=False):
+        """IEEE 802.1AEbw: a MACsec frame whose nonce is the slot's 12-byte XPN salt XOR (SSCI | 64-bit PN); hi = the PN's upper half, the SecTAG holds the lower"""
+        return cls(WireFormat.macsec(sci=sci, auth_only=auth_only), WIREX_XPN, 0)
+
+    @classmethod
+    def esp_esn(cls, tag_len=16):
+        """RFC 4303 / RFC 4106 section 5: an ESP frame whose AAD is SPI | seq-hi | seq-lo; hi = seq-hi, which is never transmitted"""
+        return cls(WireFormat.esp(tag_len), WIREX_ESN, 0)
+
+    def check(self):
+        """aesgcm_wire_xfmt_check -> OK or EARG (no device needed)"""
+        return _keytab_typed(load()).aesgcm_wire_xfmt_check(ctypes.byref(self))
+
+    def __repr__(self):
+        return "WireFormatX(%r, ext=%d, reserved=%d)" % (self.f, self.ext, self.reserved)
 
 
 class KeyTable:
@@ -809,25 +839,48 @@ class KeyTable:
         """aesgcm_keytab_frames_crypt_dev: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in / d_out in the wire format fmt, under slot d_slots[p]"""
         _chk(self._lib.aesgcm_keytab_frames_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream))
 
-    def crypt_frames(self, fmt, slots, frames, decrypt=False):
+    def set_xpn(self, first_slot, salts, sscis, stream=None):
+        """aesgcm_keytab_set_xpn: MACsec XPN's 12-byte salt and 4-byte SSCI per slot (each one bytes-like of n * 12 / n * 4 bytes, or a list) into slots first_slot, ..."""
+        sb = b"".join(bytes(x) for x in salts) if isinstance(salts, (list, tuple)) else bytes(salts)
+        cb = b"".join(bytes(x) for x in sscis) if isinstance(sscis, (list, tuple)) else bytes(sscis)
+        if len(sb) % 12 or len(cb) % 4 or len(sb) // 12 != len(cb) // 4:
+            raise AesGcmError(EARG, "an XPN salt is 12 bytes, an SSCI 4, one of each per slot")
+        _chk(self._lib.aesgcm_keytab_set_xpn(self._t, first_slot, len(sb) // 12, sb, cb, stream))
+        return self
+
+    def frames_crypt_x_dev(self, decrypt, xfmt, n_frames, d_slots, d_hi, d_in, d_frame_off, d_out, d_auth=None, stream=None):
+        """aesgcm_keytab_frames_crypt_x_dev: frames_crypt_dev in the format xfmt (WireFormatX) with d_hi[p] (uint32, device memory) = the upper half of frame p's
+        64-bit packet / sequence number"""
+        _chk(self._lib.aesgcm_keytab_frames_crypt_x_dev(self._t, int(bool(decrypt)), ctypes.byref(xfmt), n_frames, d_slots, d_hi, d_in, d_frame_off, d_out, d_auth, stream))
+
+    def crypt_frames(self, fmt, slots, frames, decrypt=False, hi=None):
         """Host convenience (tests, examples): whole frames (header | payload | ICV; on encrypt the ICV bytes are placeholders) through one call, in place.
-        -> (frames_out, auth); auth is None on encrypt."""
+        fmt a WireFormatX: through frames_crypt_x_dev with hi (one number per frame).  -> (frames_out, auth); auth is None on encrypt."""
         import struct
         n = len(slots)
         if len(frames) != n or not n:
             raise AesGcmError(EARG, "slots and frames must be equally long and not empty")
+        ext = isinstance(fmt, WireFormatX)
+        if (hi is not None and not ext) or (hi is not None and len(hi) != n):
+            raise AesGcmError(EARG, "hi goes with a WireFormatX, one number per frame")
         off = [0]
         for f in frames:
             off.append(off[-1] + len(f))
         blob = b"".join(bytes(f) for f in frames)
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("data", len(blob)), ("off", 8 * (n + 1)), ("auth", 4 * n))}
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("data", len(blob)), ("off", 8 * (n + 1)), ("auth", 4 * n), ("hi", 4 * n))}
         try:
             bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
             if blob:
                 bufs["data"].upload(blob)
             bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
-            self.frames_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
-                                  d_auth=bufs["auth"].ptr if decrypt else None)
+            if ext:
+                if hi is not None:
+                    bufs["hi"].upload(struct.pack("<%dI" % n, *hi))
+                self.frames_crypt_x_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["hi"].ptr if hi is not None else None, bufs["data"].ptr, bufs["off"].ptr,
+                                        bufs["data"].ptr, d_auth=bufs["auth"].ptr if decrypt else None)
+            else:
+                self.frames_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
+                                      d_auth=bufs["auth"].ptr if decrypt else None)
             _chk(load().aesgcm_dev_sync(self.device))
             out = bytes(bufs["data"].download(len(blob))) if blob else b""
             outs = [out[off[p]:off[p + 1]] for p in range(n)]

@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define AESGCM_ABI_VERSION 5   /* 5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
+#define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev)
+                                  5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
                                   4 (round 5): packets of message size by rows (AESGCM_SHAPE_ROWS), aesgcm_messages_crypt_dev, aesgcm_ctx_last_launch, aesgcm_wipe_failed_dev and the option "wipe_on_auth_fail",
@@ -454,8 +455,10 @@ AESGCM_API int aesgcm_keytab_destroy(aesgcm_keytab *t);
  *   MACsec, no SCI          {20, 20, 16, 8, 16, 0}   the salt as above (the SCI is implicit)
  *   MACsec integrity-only   the same with AESGCM_WIRE_AUTH_ONLY (the user data is AAD as well)
  *   ESP, RFC 4106           {8, 16, 8, 4, 16 | 12 | 8, 0}   SPI, sequence number | 8-byte IV field | payload | ICV; the slot's salt = the SA's 4-byte salt
- * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows, ESN (its high sequence bits are not in the packet), MACsec confidentiality offsets
- * 30 / 50, XPN, TLS records (their AAD is not a span of the wire bytes), and routing long frames to the row kernels (a frame runs on one lane group). */
+ *   MACsec confidentiality offset 30 / 50   {28 + 30, 28 + 30, 16, 8, 16, 0}: the offset's bytes are authenticated header
+ * MACsec XPN and ESP with extended sequence numbers need a number that is not in the frame: aesgcm_keytab_frames_crypt_x_dev, below.
+ * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows, TLS records (their AAD is not a span of the wire bytes), and routing long frames to
+ * the row kernels (a frame runs on one lane group). */
 #define AESGCM_WIRE_AUTH_ONLY 1u   /* nothing is encrypted: every byte in front of the ICV is AAD (MACsec integrity-only, E = 0; GMAC) */
 typedef struct aesgcm_wire_fmt {
     uint32_t aad_len;   /* frame bytes [0, aad_len) are authenticated and pass through unchanged                          */
@@ -470,6 +473,38 @@ AESGCM_API int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_
 AESGCM_API int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, size_t n_frames,
                                    const uint32_t *d_slots, const void *d_in, const uint64_t *d_frame_off,
                                    void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- wire frames with 64-BIT NUMBERS: MACsec XPN (IEEE 802.1AEbw), ESP with ESN (RFC 4303, RFC 4106 section 5)
+ * At this library's frame rates a 32-bit packet number lasts seconds.  Both standards answer with a 64-bit number of which only the LOWER half is in the frame; the upper
+ * half enters the nonce (XPN) or the AAD (ESN).  aesgcm_keytab_frames_crypt_x_dev is aesgcm_keytab_frames_crypt_dev with that half as one more array: d_hi, DEVICE memory,
+ * n_frames numeric 32-bit values indexed by frame like d_slots.  A transmitter's d_hi[p] is pn >> 32 of the number it assigned; a receiver recovers it from its replay
+ * window before the call (802.1AEbw 10.6.2, RFC 4303 Appendix A).  The format is aesgcm_wire_xfmt = a base format f and ext:
+ *   ext 0                 d_hi is ignored (NULL allowed); the call IS aesgcm_keytab_frames_crypt_dev with f
+ *   AESGCM_WIREX_XPN      f a MACsec format {28 | 20, 28 | 20, 16, 8, 16, 0 | AESGCM_WIRE_AUTH_ONLY} (salt_len must be 8).  Everything about the frame is as f says but the
+ *                         nonce = xsalt[0..12) XOR (ssci[0..4) | be32(d_hi[p]) | frame[iv_off, iv_off + 4)): the SSCI XORs the salt's first four bytes, the 64-bit PN, big-endian,
+ *                         its last eight.  xsalt and ssci are 16 bytes of slot state APART from the 8-byte salt of aesgcm_keytab_set_salt: zero after aesgcm_keytab_create and
+ *                         aesgcm_keytab_clear, left alone by aesgcm_keytab_set / _set_dev / _set_salt, written by aesgcm_keytab_set_xpn (salts[n][12] and sscis[n][4] in HOST
+ *                         memory, both required, into slots first_slot .. first_slot + n - 1; stream-ordered like aesgcm_keytab_set_salt).  XPN calls ignore the 8-byte
+ *                         salt; calls without XPN ignore this state.
+ *   AESGCM_WIREX_ESN      f an ESP format {8, 16, 8, 4, 16 | 12 | 8, 0} (aad_len must be 8, AESGCM_WIRE_AUTH_ONLY clear).  AAD = frame[0, 4) | be32(d_hi[p]) | frame[4, 8): SPI,
+ *                         seq-hi, seq-lo, 12 bytes.  The nonce (the slot's 4-byte salt, the IV field), the pass-through header and the payload are as f says.
+ * aesgcm_wire_xfmt_check: aesgcm_wire_fmt_check on f, then AESGCM_EARG for NULL, reserved != 0, an unknown bit in ext or both bits, XPN unless f.salt_len == 8, ESN unless
+ * f.aad_len == 8 without AESGCM_WIRE_AUTH_ONLY.  It touches no device; the crypt call runs it first, and with ext != 0 it returns AESGCM_EARG for d_hi == NULL.
+ * Refusals, aesgcm_keytab_status, out-of-place copies, d_auth, aesgcm_wipe_failed_dev, shape, order and thread safety are aesgcm_keytab_frames_crypt_dev's; a refused
+ * frame's d_hi is not read.  One k_kt_wirex launch per call (ext 0: one k_kt_wire launch).
+ * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself, generating packet numbers, writing the PN into the SecTAG, TLS 1.3 records (their nonce takes a
+ * 64-bit number with no wire part: a later mode on the same array), ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
+#define AESGCM_WIREX_XPN 1u   /* nonce = the slot's 12-byte XPN salt XOR (the slot's SSCI | be32(d_hi[p]) | the 4 frame bytes at iv_off) */
+#define AESGCM_WIREX_ESN 2u   /* AAD = frame[0,4) | be32(d_hi[p]) | frame[4,8): 12 bytes; nonce as the base format says */
+typedef struct aesgcm_wire_xfmt {
+    aesgcm_wire_fmt f;  /* the frame's layout, as aesgcm_keytab_frames_crypt_dev takes it */
+    uint32_t ext;       /* 0, AESGCM_WIREX_XPN or AESGCM_WIREX_ESN                         */
+    uint32_t reserved;  /* 0                                                              */
+} aesgcm_wire_xfmt;     /* 32 bytes */
+AESGCM_API int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf);
+AESGCM_API int aesgcm_keytab_set_xpn(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, const uint8_t *sscis, void *stream);
+AESGCM_API int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_xfmt *xf, size_t n_frames, const uint32_t *d_slots,
+                                     const uint32_t *d_hi, const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
