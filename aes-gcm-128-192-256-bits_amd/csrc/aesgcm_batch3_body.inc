@@ -5,13 +5,15 @@
 // p.in = header | payload | ICV as `wf` (aesgcm_wire_fmt) lays it out -- AAD range, payload range, nonce (the slot's salt, then header bytes) and the ICV's place all come
 // from that one offset; p.aad is p.in, p.ivs / p.tags / p.expect / p.aad_off are unused.  WIREX (k_kt_wirex, aesgcm_wirex_kernels.hip; needs WIRE): `wx` (KtWireXParams) adds
 // a 32-bit number per frame that is not on the wire, the upper half of its packet or sequence number; WIREX itself says whether it enters the nonce (AESGCM_WIREX_XPN,
-// MACsec XPN) or the AAD (AESGCM_WIREX_ESN, ESP with extended sequence numbers), and is 0 in every other kernel.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
+// MACsec XPN) or the AAD (AESGCM_WIREX_ESN, ESP with extended sequence numbers), and is 0 in every other kernel.  KT_WIREX_TLS13 / KT_WIREX_TLS12 (k_kt_tls,
+// aesgcm_tls_kernels.hip; internal values, aesgcm_keytab.h): the frame is a TLS record hdr[5] | (1.2: explicit nonce[8]) | payload | tag[16] and the number is its whole 64-bit
+// sequence number, wx->seq[pkt]: 1.3 XORs it into the slot's 12-byte IV (KtSlot::xpn) and reads no nonce byte from the record, 1.2 puts it in front of the one AAD block.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
 // what that cost there).  For the same reason the two key sources read a packet's offsets in different orders: each keeps its kernel's instruction stream.
     static_assert(DEC == 0 || DEC == 1 || (DEC == 2 && !SLOTS), "the probe (DEC == 2) takes raw keys");
     static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
     static_assert(!WIREX || WIRE, "the number that is not on the wire belongs to a frame in wire format");
-    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN, "one extension or none");
-    constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN;
+    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12, "one extension or none");
+    constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN, x_t13 = WIREX == KT_WIREX_TLS13, x_t12 = WIREX == KT_WIREX_TLS12;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
@@ -66,12 +68,14 @@
             const bool auth_only = !x_esn && (wf->flags & AESGCM_WIRE_AUTH_ONLY) != 0;                   // (ESN: never -- aesgcm_wire_xfmt_check)
             const u32 nonce_end = wf->iv_off + 12u - wf->salt_len, front = auth_only && nonce_end > wf->hdr_len ? nonce_end : wf->hdr_len;
             bad |= e < b || e - b >= ((u64)1 << 28) || e - b < (u64)(front + wf->tag_len);
+            if constexpr (x_t13 || x_t12) bad |= e - b > 5u + 65535u;                // a TLS record's length field says what follows its five header bytes
             const u32 body = bad ? 0u : (u32)(e - b) - wf->tag_len;                  // the bytes in front of the ICV
             aoff = b;
             aad_len = auth_only ? body : wf->aad_len;
             pkt_len = auth_only ? 0u : body - wf->hdr_len;
             doff = b + (auth_only ? body : wf->hdr_len);
             if constexpr (x_esn) aad_len = 12u;                                      // SPI | seq-hi | seq-lo (RFC 4303): the frame's first 8 bytes around hi[pkt]
+            if constexpr (x_t12) aad_len = 13u;                                      // seq | type, version | payload length (RFC 5246 6.2.3.3): seq[pkt], three header bytes, pkt_len
             ivp = p.in + b + wf->iv_off;
         } else {
         if (p.data_off) {
@@ -110,8 +114,8 @@
         u32 iv0, iv1, iv2;
         if constexpr (WIRE) {
             // the nonce: salt_len (0, 4 or 8) bytes of the slot's salt, then header bytes -- whole words either way; a refused frame's header is not read
-            const u32 sw = x_xpn ? 2u : wf->salt_len >> 2;                                              // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check)
-            const u32 f0 = bad ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
+            const u32 sw = x_xpn ? 2u : x_t13 ? 3u : x_t12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
+            const u32 f0 = bad || x_t13 ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
             iv0 = sw ? ks->salt[0] : f0;
             iv1 = sw > 1u ? ks->salt[1] : sw ? f0 : f1;
             iv2 = sw > 1u ? f0 : sw ? f1 : f2;
@@ -119,6 +123,12 @@
                 // XPN (802.1AEbw): the slot's 12-byte salt XOR (SSCI | PN), big-endian: hi[pkt], then the four frame bytes at iv_off (f0: salt_len is 8).  The classic salt is
                 // not used; a refused frame's hi is not read
                 iv0 = ks->xpn[0] ^ ks->xpn[3]; iv1 = ks->xpn[1] ^ (bad ? 0u : bswap32(wx->hi[pkt])); iv2 = ks->xpn[2] ^ f0;
+            }
+            if constexpr (x_t12) iv0 = ks->xpn[0];                    // TLS 1.2 (RFC 5288): the slot IV's first four bytes (aesgcm_keytab_set_tls_iv), then the record's explicit eight (f0, f1)
+            if constexpr (x_t13) {
+                // TLS 1.3 (RFC 8446 5.3): the slot's 12-byte IV XOR the sequence number, big-endian, right-aligned.  A refused record's number is not read
+                const u64 sq = bad ? (u64)0 : wx->seq[pkt];
+                iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(sq >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)sq);
             }
             // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through
             if (p.in != p.out && st_ok) wire_copy_front(p.out + aoff, p.in + aoff, (u32)(doff - aoff), l, G);
@@ -189,6 +199,14 @@
                     batch3_pos<LG>(lane_id_fresh(), xg, xl);
                     const u32 xpkt = batch_map(p, pk0 + xg < pk_end ? pk0 + xg : pk0);
                     gin = make_uint4(gload4_any(aad), bswap32(wx->hi[xpkt]), gload4_any(aad + 4), 0u);
+                } else if constexpr (x_t12) {
+                    // TLS 1.2's one AAD block, built the same way: be64(seq) | type, version (the record's first three bytes) | be16(payload length), the length from the
+                    // offsets (pkt_len < 2^16: the check above), not from the header's own two bytes
+                    u32 xg, xl;
+                    batch3_pos<LG>(lane_id_fresh(), xg, xl);
+                    const u32 xpkt = batch_map(p, pk0 + xg < pk_end ? pk0 + xg : pk0);
+                    const u64 sq = wx->seq[xpkt];
+                    gin = make_uint4(bswap32((u32)(sq >> 32)), bswap32((u32)sq), (gload4_any(aad) & 0x00FFFFFFu) | ((pkt_len >> 8) << 24), pkt_len & 0xFFu);
                 } else
                 gin = rem >= 16 ? gload16_any(aad + off) : load_block_bytes(aad + off, rem);
             } else {

@@ -1,6 +1,6 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
 // Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots; aesgcm_wire_kernels.hip:
-// k_kt_wire, the same body on frames in wire format; aesgcm_wirex_kernels.hip: k_kt_wirex, that with a 32-bit number per frame that is not on the wire) and the host
+// k_kt_wire, the same body on frames in wire format; aesgcm_wirex_kernels.hip: k_kt_wirex, that with a 32-bit number per frame that is not on the wire; aesgcm_tls_kernels.hip: k_kt_tls, TLS records with their 64-bit sequence numbers) and the host
 // (aesgcm_keytab.hip, which launches k_kt_batch as aesgcm_host.hip's batch_plan plans it for k_batch3).
 #pragma once
 #include "aesgcm_internal.h"
@@ -15,7 +15,8 @@ struct __attribute__((aligned(128))) KtSlot {
     u32 set;                               // KT_SET once the rest is written
     u32 salt[2];                           // the first bytes of a wire-format frame's nonce (aesgcm_keytab_set_salt), as two memory-order words; k_kt_setup leaves them alone
     uint4 hpow[KT_HPOW];                   // BE words (G128)
-    u32 xpn[4];                            // MACsec XPN (aesgcm_keytab_set_xpn): the 12-byte salt as three memory-order words, then the SSCI; apart from `salt`, and k_kt_setup leaves them alone too
+    u32 xpn[4];                            // MACsec XPN (aesgcm_keytab_set_xpn): the 12-byte salt as three memory-order words, then the SSCI; apart from `salt`, and k_kt_setup leaves them alone too.
+                                           // A TLS connection direction instead (aesgcm_keytab_set_tls_iv): its 12-byte write IV as three memory-order words, then 0 -- either setter overwrites the other
 };
 static_assert(offsetof(KtSlot, xpn) == 368, "the XPN state fills what was padding: the slot's other fields stay where they were");
 static_assert(sizeof(KtSlot) == 384, "a slot is three 128-byte lines");
@@ -43,9 +44,15 @@ struct KtWireParams {
 };
 
 // ... with an extension (k_kt_wirex): hi[p] = the upper half of frame p's 64-bit packet / sequence number, which is not in the frame
+// The body's WIREX modes that the ABI does not name (aesgcm_wire_xfmt_check refuses them as it refuses every unknown bit): TLS records, aesgcm_keytab_records_crypt_dev
+#define KT_WIREX_TLS13 0x10u
+#define KT_WIREX_TLS12 0x20u
 struct KtWireXParams {
     KtWireParams w;
-    const u32 *hi;                         // n_pkts numeric values
+    union {
+        const u32 *hi;                     // n_pkts numeric values
+        const u64 *seq;                    // k_kt_tls: n_pkts whole 64-bit record sequence numbers; w.f = {5, 5, 5, 0, 16, 0} (1.3) or {13, 13, 5, 4, 16, 0} (1.2)
+    };
 };
 
 // The frame-side accesses of k_kt_wire (aesgcm_batch3_body.inc, WIRE), all inside the frame and at any byte address.  The ICV is 8, 12 or 16 bytes: dwords.
@@ -71,3 +78,5 @@ hipError_t klaunch_wire_attributes();      // the same for the k_kt_wire instanc
 hipError_t klaunch_kt_wire(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireParams &p);
 hipError_t klaunch_wirex_attributes();     // ... and for the k_kt_wirex instances (aesgcm_wirex_kernels.hip)
 hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
+hipError_t klaunch_tls_attributes();       // ... and for the k_kt_tls instances (aesgcm_tls_kernels.hip)
+hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);

@@ -2,7 +2,8 @@
 // A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word; k_kt_setup fills slots from raw keys, a crypt call is one
 // k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.  Frames in wire
 // format (aesgcm_keytab_frames_crypt_dev) are one k_kt_wire launch (aesgcm_wire_kernels.hip) planned the same way; with a number per frame that is not on the wire
-// (aesgcm_keytab_frames_crypt_x_dev: MACsec XPN, ESP ESN) one k_kt_wirex launch (aesgcm_wirex_kernels.hip).
+// (aesgcm_keytab_frames_crypt_x_dev: MACsec XPN, ESP ESN) one k_kt_wirex launch (aesgcm_wirex_kernels.hip); TLS records with their 64-bit sequence numbers
+// (aesgcm_keytab_records_crypt_dev) one k_kt_tls launch (aesgcm_tls_kernels.hip).
 #include "aesgcm_keytab.h"
 
 #include <stddef.h>
@@ -198,9 +199,10 @@ int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf) {
 }
 
 // One launch: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in and d_out, laid out by *fmt (checked by the caller).  Planned as aesgcm_keytab_crypt_dev's
-// offset-array call (the lengths are on the device: shape by count, order by falling frame length class).  ext 0: k_kt_wire; otherwise k_kt_wirex with d_hi.
+// offset-array call (the lengths are on the device: shape by count, order by falling frame length class).  ext 0: k_kt_wire; otherwise k_kt_wirex with d_hi.  tls
+// (AESGCM_TLS_13 / AESGCM_TLS_12; ext 0): k_kt_tls with d_seq, the records laid out by *fmt as aesgcm_tls_kernels.hip says.
 static int kt_frames_crypt(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, u32 ext, const uint32_t *d_hi, size_t n_frames, const uint32_t *d_slots,
-                           const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
+                           const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream, u32 tls = 0u, const uint64_t *d_seq = nullptr) {
     if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
     if (!n_frames) return AESGCM_OK;
     if (!d_slots || !d_in || !d_out || !d_frame_off || (decrypt && !d_auth) || n_frames >= ((size_t)1 << 31)) return AESGCM_EARG;
@@ -214,11 +216,12 @@ static int kt_frames_crypt(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt 
     p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per frame, in the kernel)
     wp.k.slots = d_slots; wp.k.tab = t->tab; wp.k.n_slots = (u32)t->n_slots; wp.k.status = t->status;
     wp.f = *fmt;
-    xp.hi = d_hi;
+    if (tls) xp.seq = d_seq; else xp.hi = d_hi;
     BatchPlan b;
     const int rc = batch_plan(t->device, decrypt, n_frames, t->key_len, p, stream, b);
     if (rc) return rc;
-    if (ext) HIPCHK(klaunch_kt_wirex(ext, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
+    if (tls) HIPCHK(klaunch_kt_tls(tls, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
+    else if (ext) HIPCHK(klaunch_kt_wirex(ext, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
     else HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, wp));
     return batch_done(b, p);
 }
@@ -237,6 +240,43 @@ int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, const aesgcm
     if (frc) return frc;
     if (xf->ext && !d_hi) return AESGCM_EARG;
     return kt_frames_crypt(t, decrypt, &xf->f, xf->ext, xf->ext ? d_hi : nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
+}
+
+// ---------------------------------------------------------------- TLS records
+int aesgcm_tls_fmt_check(const aesgcm_tls_fmt *f) {
+    if (!f || (f->version != AESGCM_TLS_13 && f->version != AESGCM_TLS_12) || f->reserved) return AESGCM_EARG;
+    return AESGCM_OK;
+}
+
+// a connection direction's 12-byte write IV into KtSlot::xpn, the way aesgcm_keytab_set_xpn's salts go; the word behind it (there: the SSCI) becomes zero
+int aesgcm_keytab_set_tls_iv(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *ivs, void *stream) {
+    if (!t) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (!ivs || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);
+    HIPCHK(hipSetDevice(t->device));
+    const size_t bytes = n * 12;
+    const int rc = kt_stage(t, bytes, st);
+    if (rc) return rc;
+    unsigned char *const x = (unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, xpn);
+    HIPCHK(hipMemcpyAsync(t->stage, ivs, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpy2DAsync(x, sizeof(KtSlot), t->stage, 12, 12, n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemset2DAsync(x + 12, sizeof(KtSlot), 0, 4, n, st));
+    HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
+    HIPCHK(hipEventRecord(t->stage_done, st));
+    return AESGCM_OK;
+}
+
+// One k_kt_tls launch: record p = bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in and d_out.  The kernel runs k_kt_wire's loop; what it takes from a wire format
+// (header length, where the explicit nonce lies, the tag's length) is the version's constant format here
+int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_tls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint64_t *d_seq,
+                                    const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth, void *stream) {
+    const int frc = aesgcm_tls_fmt_check(fmt);
+    if (frc) return frc;
+    if (!d_seq) return AESGCM_EARG;
+    static const aesgcm_wire_fmt f13 = {5, 5, 5, 0, 16, 0}, f12 = {13, 13, 5, 4, 16, 0};          // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
+    return kt_frames_crypt(t, decrypt, fmt->version == AESGCM_TLS_13 ? &f13 : &f12, 0u, nullptr, n_recs, d_slots, d_in, d_rec_off, d_out, d_auth, stream, fmt->version, d_seq);
 }
 
 int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {

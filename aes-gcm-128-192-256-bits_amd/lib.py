@@ -41,6 +41,7 @@ SYMBOLS = [
     "aesgcm_keytab_create", "aesgcm_keytab_set", "aesgcm_keytab_set_dev", "aesgcm_keytab_clear", "aesgcm_keytab_crypt_dev", "aesgcm_keytab_status", "aesgcm_keytab_destroy",
     "aesgcm_wire_fmt_check", "aesgcm_keytab_set_salt", "aesgcm_keytab_frames_crypt_dev",
     "aesgcm_wire_xfmt_check", "aesgcm_keytab_set_xpn", "aesgcm_keytab_frames_crypt_x_dev",
+    "aesgcm_tls_fmt_check", "aesgcm_keytab_set_tls_iv", "aesgcm_keytab_records_crypt_dev",
 ]
 
 
@@ -717,6 +718,9 @@ def _keytab_typed(L):
         L.aesgcm_wire_xfmt_check.argtypes = [ctypes.POINTER(WireFormatX)]
         L.aesgcm_keytab_set_xpn.argtypes = [vp, sz, sz, vp, vp, vp]
         L.aesgcm_keytab_frames_crypt_x_dev.argtypes = [vp, cint, ctypes.POINTER(WireFormatX), sz, vp, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_tls_fmt_check.argtypes = [ctypes.POINTER(TlsFormat)]
+        L.aesgcm_keytab_set_tls_iv.argtypes = [vp, sz, sz, vp, vp]
+        L.aesgcm_keytab_records_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(TlsFormat), sz, vp, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
 
@@ -772,6 +776,32 @@ class WireFormatX(ctypes.Structure):
 
     def __repr__(self):
         return "WireFormatX(%r, ext=%d, reserved=%d)" % (self.f, self.ext, self.reserved)
+
+
+TLS_13 = 1              # AESGCM_TLS_13
+TLS_12 = 2              # AESGCM_TLS_12
+
+
+class TlsFormat(ctypes.Structure):
+    """aesgcm_tls_fmt: which TLS record header | ciphertext | tag a records call takes (include/aesgcm.h "TLS RECORDS")"""
+    _fields_ = [("version", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    @classmethod
+    def tls13(cls):
+        """RFC 8446: hdr[5] | payload | tag[16]; nonce = the slot's IV XOR the 64-bit sequence number, AAD = the header"""
+        return cls(TLS_13, 0)
+
+    @classmethod
+    def tls12(cls):
+        """RFC 5288: hdr[5] | explicit nonce[8] | payload | tag[16]; nonce = the slot IV's four bytes | explicit nonce, AAD = seq | type, version | payload length"""
+        return cls(TLS_12, 0)
+
+    def check(self):
+        """aesgcm_tls_fmt_check -> OK or EARG (no device needed)"""
+        return _keytab_typed(load()).aesgcm_tls_fmt_check(ctypes.byref(self))
+
+    def __repr__(self):
+        return "TlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
 
 
 class KeyTable:
@@ -881,6 +911,49 @@ class KeyTable:
             else:
                 self.frames_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
                                       d_auth=bufs["auth"].ptr if decrypt else None)
+            _chk(load().aesgcm_dev_sync(self.device))
+            out = bytes(bufs["data"].download(len(blob))) if blob else b""
+            outs = [out[off[p]:off[p + 1]] for p in range(n)]
+            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
+            return outs, auth
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    def set_tls_iv(self, first_slot, ivs, stream=None):
+        """aesgcm_keytab_set_tls_iv: a TLS connection direction's 12-byte write IV per slot (one bytes-like of n * 12 bytes, or a list) into slots first_slot, ...;
+        it takes the place of the slot's XPN state"""
+        ib = b"".join(bytes(x) for x in ivs) if isinstance(ivs, (list, tuple)) else bytes(ivs)
+        if len(ib) % 12:
+            raise AesGcmError(EARG, "a TLS write IV is 12 bytes")
+        _chk(self._lib.aesgcm_keytab_set_tls_iv(self._t, first_slot, len(ib) // 12, ib, stream))
+        return self
+
+    def records_crypt_dev(self, decrypt, fmt, n_recs, d_slots, d_seq, d_in, d_rec_off, d_out, d_auth=None, stream=None):
+        """aesgcm_keytab_records_crypt_dev: TLS record p = bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in / d_out, of the version fmt (TlsFormat) says, under slot
+        d_slots[p] with the 64-bit sequence number d_seq[p] (uint64, device memory)"""
+        _chk(self._lib.aesgcm_keytab_records_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_recs, d_slots, d_seq, d_in, d_rec_off, d_out, d_auth, stream))
+
+    def crypt_records(self, fmt, slots, seqs, records, decrypt=False):
+        """Host convenience (tests, examples), crypt_frames' counterpart: whole TLS records (header | (1.2: explicit nonce |) payload | tag; on encrypt the tag's bytes are
+        placeholders) with a sequence number each through one call, in place.  -> (records_out, auth); auth is None on encrypt."""
+        import struct
+        n = len(slots)
+        if len(records) != n or len(seqs) != n or not n:
+            raise AesGcmError(EARG, "slots, seqs and records must be equally long and not empty")
+        off = [0]
+        for r in records:
+            off.append(off[-1] + len(r))
+        blob = b"".join(bytes(r) for r in records)
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("seq", 8 * n), ("data", len(blob)), ("off", 8 * (n + 1)), ("auth", 4 * n))}
+        try:
+            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
+            bufs["seq"].upload(struct.pack("<%dQ" % n, *seqs))
+            if blob:
+                bufs["data"].upload(blob)
+            bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
+            self.records_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["seq"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
+                                   d_auth=bufs["auth"].ptr if decrypt else None)
             _chk(load().aesgcm_dev_sync(self.device))
             out = bytes(bufs["data"].download(len(blob))) if blob else b""
             outs = [out[off[p]:off[p + 1]] for p in range(n)]

@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev)
+#define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
+                                  aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -457,8 +458,8 @@ AESGCM_API int aesgcm_keytab_destroy(aesgcm_keytab *t);
  *   ESP, RFC 4106           {8, 16, 8, 4, 16 | 12 | 8, 0}   SPI, sequence number | 8-byte IV field | payload | ICV; the slot's salt = the SA's 4-byte salt
  *   MACsec confidentiality offset 30 / 50   {28 + 30, 28 + 30, 16, 8, 16, 0}: the offset's bytes are authenticated header
  * MACsec XPN and ESP with extended sequence numbers need a number that is not in the frame: aesgcm_keytab_frames_crypt_x_dev, below.
- * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows, TLS records (their AAD is not a span of the wire bytes), and routing long frames to
- * the row kernels (a frame runs on one lane group). */
+ * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows, and routing long frames to the row kernels (a frame runs on one lane
+ * group).  TLS records (their AAD is not a span of the wire bytes) are not a format of this call: aesgcm_keytab_records_crypt_dev, further below. */
 #define AESGCM_WIRE_AUTH_ONLY 1u   /* nothing is encrypted: every byte in front of the ICV is AAD (MACsec integrity-only, E = 0; GMAC) */
 typedef struct aesgcm_wire_fmt {
     uint32_t aad_len;   /* frame bytes [0, aad_len) are authenticated and pass through unchanged                          */
@@ -492,8 +493,9 @@ AESGCM_API int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, con
  * f.aad_len == 8 without AESGCM_WIRE_AUTH_ONLY.  It touches no device; the crypt call runs it first, and with ext != 0 it returns AESGCM_EARG for d_hi == NULL.
  * Refusals, aesgcm_keytab_status, out-of-place copies, d_auth, aesgcm_wipe_failed_dev, shape, order and thread safety are aesgcm_keytab_frames_crypt_dev's; a refused
  * frame's d_hi is not read.  One k_kt_wirex launch per call (ext 0: one k_kt_wire launch).
- * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself, generating packet numbers, writing the PN into the SecTAG, TLS 1.3 records (their nonce takes a
- * 64-bit number with no wire part: a later mode on the same array), ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
+ * TLS 1.3 records (their nonce takes a 64-bit number with no wire part) are not a mode of this call either: d_hi holds 32-bit values.  They have a call of their own,
+ * aesgcm_keytab_records_crypt_dev, below.
+ * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself, generating packet numbers, writing the PN into the SecTAG, ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
 #define AESGCM_WIREX_XPN 1u   /* nonce = the slot's 12-byte XPN salt XOR (the slot's SSCI | be32(d_hi[p]) | the 4 frame bytes at iv_off) */
 #define AESGCM_WIREX_ESN 2u   /* AAD = frame[0,4) | be32(d_hi[p]) | frame[4,8): 12 bytes; nonce as the base format says */
 typedef struct aesgcm_wire_xfmt {
@@ -505,6 +507,44 @@ AESGCM_API int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf);
 AESGCM_API int aesgcm_keytab_set_xpn(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, const uint8_t *sscis, void *stream);
 AESGCM_API int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_xfmt *xf, size_t n_frames, const uint32_t *d_slots,
                                      const uint32_t *d_hi, const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- key tables on TLS RECORDS in wire format: TLS 1.3 (RFC 8446) and TLS 1.2 AES-GCM (RFC 5288)
+ * What a TLS terminator holds is one buffer of records header | ciphertext | tag.  Neither call above can express one: a TLS 1.3 nonce takes the record's 64-bit sequence
+ * number, of which no byte is on the wire, and a TLS 1.2 AAD is not a span of the record's bytes.  aesgcm_keytab_records_crypt_dev takes the buffer as it is: record p is
+ * bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in and of d_out (the same n_recs + 1 offsets for both; d_in == d_out allowed; any byte alignment), L bytes long, under slot
+ * d_slots[p], with the sequence number d_seq[p]: DEVICE memory, n_recs numeric 64-bit values (the kernel forms their big-endian bytes).  fmt->version says which record:
+ *   AESGCM_TLS_13   hdr[5] | payload | tag[16]  (RFC 8446 5.2, 5.3).  AAD = the five header bytes as they lie in the buffer.  Nonce = the slot's 12-byte IV XOR
+ *                   (00 00 00 00 | be64(d_seq[p])).  The payload (TLSInnerPlaintext: content, content type, padding) is not interpreted; length 0 is taken.  L >= 21.
+ *   AESGCM_TLS_12   hdr[5] | explicit_nonce[8] | payload | tag[16]  (RFC 5288 3, RFC 5246 6.2.3.3).  Nonce = the slot IV's first four bytes, then the record's eight
+ *                   explicit bytes.  AAD = be64(d_seq[p]) | hdr[0..3) | be16(L - 29), 13 bytes: type and version from the record, the LENGTH FROM THE OFFSETS -- the
+ *                   header's own two length bytes are not read for it.  Header and explicit nonce pass through.  L >= 29.
+ * The slot's IV is 12 bytes of slot state: the client_write_iv / server_write_iv of the connection direction the slot stands for (TLS 1.2: its four bytes, the rest
+ * ignored), written by aesgcm_keytab_set_tls_iv (ivs[n][12] in HOST memory into slots first_slot .. first_slot + n - 1; stream-ordered like aesgcm_keytab_set_xpn, through the
+ * zeroed staging buffer).  It lies in the 16 bytes that hold MACsec XPN's salt and SSCI: a slot is a MACsec association or a TLS connection direction, never both, and
+ * aesgcm_keytab_set_xpn and aesgcm_keytab_set_tls_iv OVERWRITE one another (set_tls_iv leaves the SSCI's place zero).  Zero after aesgcm_keytab_create and
+ * aesgcm_keytab_clear, left alone by aesgcm_keytab_set / _set_dev / _set_salt.
+ * Encrypt writes the payload and the tag; the caller wrote the header and, for 1.2, the explicit nonce, as a SecY writes its SecTAG.  Decrypt writes the payload and
+ * d_auth[p] = 1 iff the record's tag equals the computed one (d_auth is required for decrypt and ignored for encrypt).  Out of place every byte of an accepted record in
+ * d_out is defined: the header (1.2: and the explicit nonce) is copied, and on decrypt the tag.  No byte outside an accepted record is written.
+ * A record the device cannot take is REFUSED on its own, exactly as aesgcm_keytab_frames_crypt_dev refuses a frame: its slot is n_slots or more, unset or cleared; its
+ * offsets fall; L is below the shortest record; L - 5 > 65535 (the wire's length field cannot say it).  Nothing of it is written, d_seq[p] is not read, d_auth[p] = 0 on
+ * decrypt, and the LOWEST such index goes to aesgcm_keytab_status.  FAIL-CLOSED: aesgcm_wipe_failed_dev(device, n_recs, d_out, 0, d_rec_off, d_auth, stream) behind a decrypt.
+ * aesgcm_tls_fmt_check: AESGCM_EARG for NULL, a version other than AESGCM_TLS_13 / AESGCM_TLS_12, reserved != 0.  It touches no device; the crypt call runs it first,
+ * then returns AESGCM_EARG for d_seq == NULL, both before it looks at the table.
+ * One k_kt_tls launch per call; shape and order as aesgcm_keytab_frames_crypt_dev (8, 16 or 64 lanes per record by count, by falling length class from 262144 records, 98304
+ * for the longer keys).  Ordering and thread safety as the other key-table calls.
+ * OUT OF SCOPE: checking the header's version, type or length bytes against the offsets; padding and content type (the payload's last bytes in 1.3); generating sequence
+ * numbers or explicit nonces; key derivation (INTEGRATION.md "TLS records" says which secret becomes what); DTLS and QUIC; routing long records to the row kernels. */
+#define AESGCM_TLS_13 1u   /* hdr[5] | payload | tag[16]; nonce = slot IV XOR (0^32 | be64(d_seq[p])); AAD = hdr */
+#define AESGCM_TLS_12 2u   /* hdr[5] | explicit nonce[8] | payload | tag[16]; nonce = slot IV[0..4) | explicit nonce; AAD = be64(d_seq[p]) | hdr[0..3) | be16(L - 29) */
+typedef struct aesgcm_tls_fmt {
+    uint32_t version;   /* AESGCM_TLS_13 or AESGCM_TLS_12 */
+    uint32_t reserved;  /* 0                              */
+} aesgcm_tls_fmt;       /* 8 bytes */
+AESGCM_API int aesgcm_tls_fmt_check(const aesgcm_tls_fmt *fmt);
+AESGCM_API int aesgcm_keytab_set_tls_iv(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *ivs, void *stream);
+AESGCM_API int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_tls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint64_t *d_seq,
+                                    const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth, void *stream);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
