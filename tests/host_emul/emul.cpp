@@ -9,6 +9,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <stdint.h>
+#include <algorithm>
 #include <vector>
 
 extern "C" {
@@ -514,10 +516,10 @@ static void test_batch_pieces() {
 
 // packets under one key, 2^LG lanes per packet (k_pktg): per-packet IV/AAD/length; lane accumulators, the H^2 step with the
 // length block in lane G-2, the cross-lane tree with wave-uniform constants, E_K(J0) from the one-lane-per-packet pass
-template <int NR, int DEC, int LG>
+template <int NR, int DEC, int LG, bool SC = false>
 static uint4 emu_pktg_packet(const KeyMaterial *km, const PktParams &p, const unsigned char *smem, u32 pkt, u32 extra_iters, u32 grp) {
     constexpr u32 G = 1u << LG;
-    const PktInfo q = pkt_info(p, pkt);
+    const PktInfo q = pkt_info<SC>(p, pkt);                       // SC: the body of k_pktgs (places from the arrays of addresses behind p.route)
     const u32 iters = pktg_iters(q, G) + extra_iters;             // a wave runs to the longest packet of its groups
     uint4 acc[G];
     for (u32 l = 0; l < G; l++) acc[l] = pktg_close_lane<LG>(pktg_lane<NR, DEC, LG>(km, p, q, smem, l, grp * G + l, iters, true), q, smem, l);
@@ -528,11 +530,11 @@ static uint4 emu_pktg_packet(const KeyMaterial *km, const PktParams &p, const un
     }
     return xor4(acc[G - 1], pktg_ej0_lane<NR>(km, p, smem, pkt, (pkt * 5 + 3) % 64));
 }
-template <int LG>
+template <int LG, bool SC = false>
 static uint4 emu_pktg(const KeyMaterial *km, int dec, const PktParams &p, const unsigned char *smem, u32 pkt, u32 extra, u32 grp) {
-    if (km->nr == 10) return dec ? emu_pktg_packet<10, 1, LG>(km, p, smem, pkt, extra, grp) : emu_pktg_packet<10, 0, LG>(km, p, smem, pkt, extra, grp);
-    if (km->nr == 12) return dec ? emu_pktg_packet<12, 1, LG>(km, p, smem, pkt, extra, grp) : emu_pktg_packet<12, 0, LG>(km, p, smem, pkt, extra, grp);
-    return dec ? emu_pktg_packet<14, 1, LG>(km, p, smem, pkt, extra, grp) : emu_pktg_packet<14, 0, LG>(km, p, smem, pkt, extra, grp);
+    if (km->nr == 10) return dec ? emu_pktg_packet<10, 1, LG, SC>(km, p, smem, pkt, extra, grp) : emu_pktg_packet<10, 0, LG, SC>(km, p, smem, pkt, extra, grp);
+    if (km->nr == 12) return dec ? emu_pktg_packet<12, 1, LG, SC>(km, p, smem, pkt, extra, grp) : emu_pktg_packet<12, 0, LG, SC>(km, p, smem, pkt, extra, grp);
+    return dec ? emu_pktg_packet<14, 1, LG, SC>(km, p, smem, pkt, extra, grp) : emu_pktg_packet<14, 0, LG, SC>(km, p, smem, pkt, extra, grp);
 }
 static void test_packets(int key_len, u64 seed) {
     auto key = rnd(key_len, seed);
@@ -1060,9 +1062,262 @@ static void test_wipe() {
     }
 }
 
+// ================================================================================================
+// The alignment grid of the packet kernels (tests/pkt_grid.py states the same rules for the GPU tests, tests/test_gpu_pkt_grid.py): every (start residue, length)
+// cell through every form of the lane code the kernels instantiate -- pktl_lane with four T-tables as k_pktl launches it (768-lane form, ILP form, with the launch's
+// PktDesc records), the scattered form of k_pktls, and the lane groups of k_pktg / k_pktgs -- in arenas with canary guards, input and output at differing residues.
+// After EVERY packet the bytes around it (GRID_GUARD on either side) are compared with what they should be, so a store outside the packet names its cell; the whole
+// arenas are compared at the end.  Reads may be anywhere inside the arena; what lies outside it is the sanitizer build's.
+// ================================================================================================
+static const u32 GRID_GUARD = 256;
+static const uint8_t GRID_CANARY_IN = 0xC3, GRID_CANARY_OUT = 0x5E;
+static const u32 GRID_AADS[13] = {0, 1, 12, 15, 16, 17, 20, 28, 31, 32, 33, 40, 20};       // period 13: coprime to the residues' 16 and 128 and to the forged tags' 7
+static void grid_group_edges(std::vector<u32> &v, u32 G) { for (u32 m : {G - 1, G, G + 1, 2 * G - 1, 2 * G, 2 * G + 1}) for (int d = -1; d <= 1; d++) v.push_back((u32)(16 * (int)m + d)); }
+// all: every length 0 .. 272 and the group edges of every lane group; else L_c -- the edges of the lane's loops -- and the group edges of G lanes (0: none)
+static std::vector<u32> grid_lengths(bool all, u32 G) {
+    std::vector<u32> v;
+    if (all) { for (u32 l = 0; l <= 272; l++) v.push_back(l); for (u32 g : {4u, 8u, 16u, 64u}) grid_group_edges(v, g); }
+    else {
+        v = {0, 1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 79, 80, 81, 111, 112, 113, 127, 128, 129, 143, 144, 145, 191, 192, 193, 255, 256, 257, 271, 272};
+        if (G) grid_group_edges(v, G);
+    }
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return v;
+}
+// byte-packed packets such that every length of L starts at every residue mod M: fillers of 1 .. M - 1 bytes (ordinary packets) steer the starts
+static void grid_walk(std::vector<u32> &lens, u64 &pos, u32 M, const std::vector<u32> &L) {
+    for (u32 l : L) {
+        std::vector<char> seen(M, 0);
+        for (u32 k = 0; k < M; k++) {
+            u32 f = 0;
+            while (seen[(pos + f) % M]) f++;
+            if (f) { lens.push_back(f); pos += f; }
+            seen[pos % M] = 1;
+            lens.push_back(l); pos += l;
+        }
+    }
+}
+struct GridArena {
+    uint8_t *p; size_t n;
+    GridArena(size_t n_, uint8_t fill) : n(n_) { p = (uint8_t *)aligned_alloc(128, (n + 127) / 128 * 128); memset(p, fill, n); }       // on a 128-byte line: offsets are residues
+    GridArena(const GridArena &o) : n(o.n) { p = (uint8_t *)aligned_alloc(128, (n + 127) / 128 * 128); memcpy(p, o.p, n); }
+    ~GridArena() { free(p); }
+};
+// the bytes [lo - GRID_GUARD, hi + GRID_GUARD) of two arenas: the first that differs, relative to lo, or INT64_MIN
+static long long grid_window_diff(const GridArena &got, const GridArena &want, u64 lo, u64 hi) {
+    const u64 a = lo > GRID_GUARD ? lo - GRID_GUARD : 0, b = hi + GRID_GUARD < got.n ? hi + GRID_GUARD : got.n;
+    if (!memcmp(got.p + a, want.p + a, b - a)) return INT64_MIN;
+    for (u64 i = a; i < b; i++) if (got.p[i] != want.p[i]) return (long long)i - (long long)lo;
+    return INT64_MIN;
+}
+enum GridForm { GF_LANE, GF_LANE_ILP, GF_LANE_DESC, GF_G4, GF_G8, GF_G16, GF_WAVE };
+static const char *const GRID_FORM_NAME[] = {"lane", "lane_ilp", "lane_desc", "g4", "g8", "group16", "wave"};
+static u32 grid_form_G(int form) { return form == GF_G4 ? 4u : form == GF_G8 ? 8u : form == GF_G16 ? 16u : form == GF_WAVE ? 64u : 0u; }
+// one packet through one form of the lane code: pktl_lane as k_pktl / k_pktls instantiate it (AESGCM_PKTL_T4 tables; ILP only without SC), or a lane group
+static uint4 grid_packet(const KeyMaterial *km, int form, bool sc, int dec, const PktParams &p, const unsigned char *smem, u32 pkt, const PktDesc *desc) {
+    constexpr bool T4 = AESGCM_PKTL_T4 != 0;
+    const u32 lane = (pkt * 7u + 3u) % 64u;
+    if (form <= GF_LANE_DESC) {
+        const PktDesc *d = form == GF_LANE_DESC ? desc + pkt : nullptr;
+        const u32 k = d ? 0u : pkt;                              // (as pktl_body passes them)
+#define GL(NR) do { if (sc) { if (dec) pktl_lane<NR, 1, T4, false, true>(km, p, smem, k, lane, d); else pktl_lane<NR, 0, T4, false, true>(km, p, smem, k, lane, d); } \
+                    else if (form == GF_LANE_ILP) { if (dec) pktl_lane<NR, 1, T4, true, false>(km, p, smem, k, lane, d); else pktl_lane<NR, 0, T4, true, false>(km, p, smem, k, lane, d); } \
+                    else { if (dec) pktl_lane<NR, 1, T4, false, false>(km, p, smem, k, lane, d); else pktl_lane<NR, 0, T4, false, false>(km, p, smem, k, lane, d); } } while (0)
+        if (km->nr == 10) GL(10); else if (km->nr == 12) GL(12); else GL(14);
+#undef GL
+        uint4 t; memcpy(&t, p.tags + (size_t)pkt * 16, 16);
+        return t;
+    }
+    const u32 lg = form == GF_G4 ? 2u : form == GF_G8 ? 3u : form == GF_G16 ? 4u : 6u, extra = (pkt % 3 == 1) ? 2 : 0, grp = pkt & ((64u >> lg) - 1u);
+    if (sc) return lg == 2 ? emu_pktg<2, true>(km, dec, p, smem, pkt, extra, grp) : lg == 3 ? emu_pktg<3, true>(km, dec, p, smem, pkt, extra, grp) : emu_pktg<4, true>(km, dec, p, smem, pkt, extra, grp);
+    return lg == 2 ? emu_pktg<2>(km, dec, p, smem, pkt, extra, grp) : lg == 3 ? emu_pktg<3>(km, dec, p, smem, pkt, extra, grp) : lg == 4 ? emu_pktg<4>(km, dec, p, smem, pkt, extra, grp)
+                                                                                                                              : emu_pktg<6>(km, dec, p, smem, pkt, extra, grp);
+}
+static const unsigned char *grid_lds(const KeyMaterial *km, int form) {
+    if (form <= GF_LANE_DESC) {
+        static unsigned char smem[AESGCM_LDS_BYTES_T4] __attribute__((aligned(16)));
+        const u32 WG = form == GF_LANE_ILP ? 512u : (u32)AESGCM_PKTL_WG;            // (AESGCM_PKTL_WG_ILP)
+        memset(smem, 0xEE, sizeof smem);
+        for (u32 tid = 0; tid < WG; tid++) { main_fill_lds(smem, km, &g_tb, tid, true, WG, GH_TAB_H); fill_lds_t4(smem, &g_tb, tid, WG); }
+        return smem;
+    }
+    static unsigned char smem[PKTG_LDS_BYTES(6)] __attribute__((aligned(16)));
+    const int lg = form == GF_G4 ? 2 : form == GF_G8 ? 3 : form == GF_G16 ? 4 : 6;
+    memset(smem, 0xEE, sizeof smem);
+    for (u32 tid = 0; tid < AESGCM_PKT_WG; tid++) pktg_fill_lds(smem, km, &g_tb, tid, AESGCM_PKT_WG, lg);
+    return smem;
+}
+// One grid through one form.  in_at / out_at / aad_at: where message k lies in its arena (packed form: in_at == out_at, consecutive; the output arena is then used
+// from byte out_shift on, so that the two residues differ).  Encrypt out of place, then decrypt the ORACLE's ciphertext with one tag in seven forged: in place
+// (packed) or to a third arena at the input's places (scattered).  Returns the packets run.
+struct GridLayout { std::vector<u32> lens, aads; std::vector<u64> in_at, out_at, aad_at; u64 size_in, size_out, size_aad; bool packed; };
+static u32 grid_run(Emu &E, const uint8_t *key, int key_len, int form, bool sc, const GridLayout &g, u64 seed) {
+    const u32 n = (u32)g.lens.size(), out_shift = g.packed ? 5u : 0u;
+    const char *fname = GRID_FORM_NAME[form];
+    const int fails_before = g_fail;
+    GridArena in(g.size_in, GRID_CANARY_IN), aad(g.size_aad, GRID_CANARY_IN), out(g.size_out + 16, GRID_CANARY_OUT);
+    auto ivs = rnd(12 * (size_t)n, seed + 2);
+    {
+        auto r = rnd(g.size_in, seed + 3), ra = rnd(g.size_aad, seed + 1);
+        for (u32 k = 0; k < n; k++) { memcpy(in.p + g.in_at[k], r.data() + g.in_at[k], g.lens[k]); memcpy(aad.p + g.aad_at[k], ra.data() + g.aad_at[k], g.aads[k]); }
+    }
+    const GridArena in0(in), aad0(aad);
+    GridArena want(out), ct_in(g.packed ? in : out);                      // ct_in: the decrypt's input, the oracle's ciphertext at the output's places (packed: at the input's, guards as the input's)
+    std::vector<uint8_t> rtags(16 * (size_t)n), tags(16 * (size_t)n + 16), bad(16 * (size_t)n);
+    for (u32 k = 0; k < n; k++) {
+        std::vector<uint8_t> ref(g.lens[k] + 16);
+        orc_gcm_crypt(0, key, key_len, ivs.data() + 12 * k, aad.p + g.aad_at[k], g.aads[k], in.p + g.in_at[k], g.lens[k], ref.data(), rtags.data() + 16 * k);
+        memcpy(ct_in.p + (g.packed ? g.in_at[k] : g.out_at[k]), ref.data(), g.lens[k]);
+    }
+    // the call's arrays as the kernels read them
+    std::vector<u64> doff(n + 1), aoff(n + 1), in_ptr(n), out_ptr(n), aad_ptr(n);
+    std::vector<int> auth(n);
+    std::vector<PktDesc> desc(n);
+    RowsHdr hdr;
+    PktParams p;
+    auto setup = [&](const uint8_t *src, uint8_t *dst, const std::vector<u64> &src_at, const std::vector<u64> &dst_at) {
+        memset(&p, 0, sizeof p); memset(&hdr, 0, sizeof hdr);
+        p.ivs = ivs.data(); p.tags = tags.data(); p.n_pkts = n;
+        LenSrc ls; memset(&ls, 0, sizeof ls);
+        DescSrc ds = {desc.data(), ivs.data(), nullptr, nullptr, nullptr};
+        if (g.packed) {
+            for (u32 k = 0; k < n; k++) { doff[k] = src_at[k]; aoff[k] = g.aad_at[k]; }
+            doff[n] = src_at[n - 1] + g.lens[n - 1]; aoff[n] = g.aad_at[n - 1] + g.aads[n - 1];
+            p.in = src; p.out = dst; p.aad = aad.p; p.data_off = doff.data(); p.aad_off = aoff.data();
+            p.aligned = ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) ? 1u : 0u;
+            ls.off = doff.data(); ls.aoff = aoff.data();
+        } else {
+            for (u32 k = 0; k < n; k++) { in_ptr[k] = (u64)(uintptr_t)(src + src_at[k]); out_ptr[k] = (u64)(uintptr_t)(dst + dst_at[k]); aad_ptr[k] = (u64)(uintptr_t)(aad.p + g.aad_at[k]); }
+            hdr.sc_in = (u64)(uintptr_t)in_ptr.data(); hdr.sc_out = (u64)(uintptr_t)out_ptr.data(); hdr.sc_aad = (u64)(uintptr_t)aad_ptr.data();
+            hdr.sc_len = (u64)(uintptr_t)g.lens.data(); hdr.sc_alen = (u64)(uintptr_t)g.aads.data();
+            p.route = &hdr; p.scattered = 1; p.aligned = 1;
+            ls.len_arr = g.lens.data(); ls.alen_arr = g.aads.data();
+            ds.in_ptr = in_ptr.data(); ds.out_ptr = out_ptr.data(); ds.aad_ptr = aad_ptr.data();
+        }
+        for (u32 k = 0; k < n; k++) desc[k] = len_src_desc(ls, ds, k, g.lens[k], g.aads[k]);       // what k_len_scatter writes for a lane per packet
+        if (form == GF_LANE_DESC) p.desc = desc.data();
+    };
+    const unsigned char *smem = grid_lds(&E.km, form);
+    // encrypt, out of place
+    setup(in.p, out.p + out_shift, g.in_at, g.out_at);
+    for (u32 k = 0; k < n; k++) {
+        const uint4 t = grid_packet(&E.km, form, sc, 0, p, smem, k, desc.data());
+        const u64 at = out_shift + g.out_at[k];
+        memcpy(want.p + at, ct_in.p + (g.packed ? g.in_at[k] : g.out_at[k]), g.lens[k]);
+        const long long d = grid_window_diff(out, want, at, at + g.lens[k]);
+        CHECK(d == INT64_MIN && !memcmp(&t, rtags.data() + 16 * k, 16), "packet grid %s%s AES-%d enc: in %% 16 = %u (%% 128 = %u), out %% 16 = %u, len %u, aad %u at %% 16 = %u (packet %u): %s, first wrong byte %lld",
+              fname, sc ? " scattered" : "", 8 * key_len, (u32)(g.in_at[k] % 16), (u32)(g.in_at[k] % 128), (u32)(at % 16), g.lens[k], g.aads[k], (u32)(g.aad_at[k] % 16), k,
+              d == INT64_MIN ? "tag" : "bytes", d == INT64_MIN ? 0ll : d);
+        if (g_fail != fails_before) return k;                       // the first cell is the finding
+    }
+    CHECK(!memcmp(out.p, want.p, out.n) && !memcmp(in.p, in0.p, in.n) && !memcmp(aad.p, aad0.p, aad.n), "packet grid %s%s AES-%d enc: arenas", fname, sc ? " scattered" : "", 8 * key_len);
+    // decrypt the oracle's ciphertext: packed in place, scattered to a third arena at the input's places; one tag in seven forged, the first and the last among them
+    memcpy(bad.data(), rtags.data(), bad.size());
+    for (u32 k = 0; k < n; k++) if (k % 7 == 0 || k == n - 1) bad[16 * k + k % 16] ^= (uint8_t)(1u << (k % 8));
+    GridArena back(g.packed ? ct_in : GridArena(g.size_in, GRID_CANARY_OUT));
+    GridArena wantb(back);
+    const GridArena ct0(ct_in);
+    if (g.packed) setup(back.p, back.p, g.in_at, g.in_at); else setup(ct_in.p, back.p, g.out_at, g.in_at);
+    p.expect = bad.data(); p.auth = auth.data();
+    memset(tags.data(), 0, tags.size());
+    for (u32 k = 0; k < n; k++) auth[k] = -1;
+    for (u32 k = 0; k < n; k++) {
+        const uint4 t = grid_packet(&E.km, form, sc, 1, p, smem, k, desc.data());
+        const u64 at = g.in_at[k];
+        memcpy(wantb.p + at, in0.p + at, g.lens[k]);
+        const long long d = grid_window_diff(back, wantb, at, at + g.lens[k]);
+        const bool forged = k % 7 == 0 || k == n - 1, auth_ok = form > GF_LANE_DESC || auth[k] == (forged ? 0 : 1);     // (a lane group's verdict is the kernel's, not the lane code's)
+        CHECK(d == INT64_MIN && !memcmp(&t, rtags.data() + 16 * k, 16) && auth_ok, "packet grid %s%s AES-%d dec: in %% 16 = %u, out %% 16 = %u (%% 128 = %u), len %u, aad %u (packet %u): %s, first wrong byte %lld",
+              fname, sc ? " scattered" : "", 8 * key_len, (u32)((g.packed ? g.in_at[k] : g.out_at[k]) % 16), (u32)(at % 16), (u32)(at % 128), g.lens[k], g.aads[k], k,
+              d != INT64_MIN ? "bytes" : auth_ok ? "tag" : "verdict", d == INT64_MIN ? 0ll : d);
+        if (g_fail != fails_before) return n + k;
+    }
+    CHECK(!memcmp(back.p, wantb.p, back.n) && (g.packed || !memcmp(ct_in.p, ct0.p, ct_in.n)) && !memcmp(aad.p, aad0.p, aad.n), "packet grid %s%s AES-%d dec: arenas", fname, sc ? " scattered" : "", 8 * key_len);
+    return 2 * n;
+}
+// packed: every length of `l16` at every start mod 16, every length of `l128` at every start mod 128
+static GridLayout grid_packed(const std::vector<u32> &l16, const std::vector<u32> &l128) {
+    GridLayout g;
+    g.packed = true;
+    u64 pos = 0;
+    grid_walk(g.lens, pos, 16, l16);
+    grid_walk(g.lens, pos, 128, l128);
+    const u32 n = (u32)g.lens.size();
+    u64 a = GRID_GUARD, c = GRID_GUARD;
+    for (u32 k = 0; k < n; k++) { g.aads.push_back(GRID_AADS[k % 13]); g.in_at.push_back(a); g.aad_at.push_back(c); a += g.lens[k]; c += g.aads[k]; }
+    g.out_at = g.in_at;
+    g.size_in = g.size_out = a + GRID_GUARD; g.size_aad = c + GRID_GUARD;
+    // completeness
+    std::vector<char> s16(16 * 4096, 0), s128(128 * 4096, 0);
+    for (u32 k = 0; k < n; k++) { s16[(g.in_at[k] % 16) * 4096 + g.lens[k]] = 1; s128[(g.in_at[k] % 128) * 4096 + g.lens[k]] = 1; }
+    u32 miss = 0;
+    for (u32 l : l16) for (u32 r = 0; r < 16; r++) miss += !s16[r * 4096 + l];
+    for (u32 l : l128) for (u32 r = 0; r < 128; r++) miss += !s128[r * 4096 + l];
+    CHECK(!miss && n, "packed grid: %u cells missing", miss);
+    return g;
+}
+// scattered: every length of L at (input residue a, output residue b) for all 16 a and `nb` values of b (16: every pair; fewer: b walks with the length), 1 .. 19
+// guard bytes between neighbours in every arena
+static GridLayout grid_scattered(const std::vector<u32> &L, u32 nb) {
+    GridLayout g;
+    g.packed = false;
+    std::vector<u32> cells;                                                  // a | b << 4 | length index << 8
+    for (u32 li = 0; li < L.size(); li++) for (u32 a = 0; a < 16; a++) for (u32 j = 0; j < nb; j++) cells.push_back(a | (((nb == 16 ? j : a + 1 + 5 * j + li) % 16) << 4) | (li << 8));
+    const u32 n = (u32)cells.size();
+    u32 step = n / 3 | 1;
+    auto gcd = [](u32 x, u32 y) { while (y) { const u32 t = x % y; x = y; y = t; } return x; };
+    while (gcd(step, n) != 1) step += 2;                                     // neighbours of unlike length and residue
+    auto place = [](u64 pos, u32 res, u32 i) { u64 gap = (res + 16 - (pos + 1) % 16) % 16 + 1; if (gap <= 3 && i % 2) gap += 16; return pos + gap; };
+    u64 a = GRID_GUARD - 1, b = GRID_GUARD - 1, c = GRID_GUARD - 1;
+    std::vector<char> seen(256 * L.size(), 0);
+    for (u32 i = 0; i < n; i++) {
+        const u32 cell = cells[(u64)i * step % n], len = L[cell >> 8];
+        g.lens.push_back(len); g.aads.push_back(GRID_AADS[i % 13]);
+        a = place(a, cell & 15, i); g.in_at.push_back(a); a += len;
+        b = place(b, (cell >> 4) & 15, i + 1); g.out_at.push_back(b); b += len;
+        c = place(c, (5 * i + 3) % 16, i); g.aad_at.push_back(c); c += g.aads[i];
+        seen[(cell >> 8) * 256 + (g.in_at[i] % 16) * 16 + g.out_at[i] % 16] = 1;
+    }
+    u32 hit = 0;
+    for (char s : seen) hit += s;
+    CHECK(hit == n && n == 16 * nb * L.size(), "scattered grid: %u of %u cells", hit, n);
+    g.size_in = a + 1 + GRID_GUARD; g.size_out = b + 1 + GRID_GUARD; g.size_aad = c + 1 + GRID_GUARD;
+    return g;
+}
+// Level 1 (the sanitizer build): L_c at every start mod 16, every form, direction and key size.  Level 2: the full grid -- every length at every start mod 16, L_c at
+// every start mod 128, every residue pair of the scattered form -- for every form, the key sizes taking turns so that every form meets each of them at least at level 1's size.
+static void test_packet_grid(int level) {
+    const int klens[3] = {16, 24, 32};
+    std::vector<uint8_t> keys[3];
+    Emu *E[3];
+    for (int i = 0; i < 3; i++) { keys[i] = rnd(klens[i], 7100 + i); E[i] = new Emu(keys[i].data(), klens[i], 0); }
+    u32 ran = 0, turn = 0;
+    for (int form = GF_LANE; form <= GF_WAVE; form++) {
+        const u32 G = grid_form_G(form);
+        const GridLayout small = grid_packed(grid_lengths(false, G), {}), small_sc = grid_scattered(grid_lengths(false, G), 1);
+        for (int i = 0; i < 3; i++) {
+            ran += grid_run(*E[i], keys[i].data(), klens[i], form, false, small, 7200 + 10 * form + i);
+            if (form != GF_LANE_ILP && form != GF_WAVE) ran += grid_run(*E[i], keys[i].data(), klens[i], form, true, small_sc, 7300 + 10 * form + i);      // (no scattered instance of the ILP form or of a wave per packet)
+        }
+        if (level < 2) continue;
+        const int i = turn++ % 3;
+        ran += grid_run(*E[i], keys[i].data(), klens[i], form, false, grid_packed(grid_lengths(true, 0), grid_lengths(false, G)), 7400 + form);
+        if (form != GF_LANE_ILP && form != GF_WAVE) ran += grid_run(*E[(i + 1) % 3], keys[(i + 1) % 3].data(), klens[(i + 1) % 3], form, true, grid_scattered(grid_lengths(false, G), 16), 7500 + form);
+    }
+    CHECK(ran > 0, "packet grid ran nothing");
+    printf("packet grid: %u packets through the lane code (level %d)\n", ran, level);
+    for (int i = 0; i < 3; i++) delete E[i];
+}
+
 int main(int argc, char **argv) {
     int level = argc > 1 ? atoi(argv[1]) : 1;
     init_tables();
+    if (argc > 2 && !strcmp(argv[2], "grid")) {                 // the packet grid alone (what a change to the frame lane runs first)
+        test_packet_grid(level);
+        printf(g_fail ? "EMUL FAILED (%d)\n" : "EMUL OK\n", g_fail);
+        return g_fail ? 1 : 0;
+    }
     test_units();
     test_bitslice();
     const u64 W = AESGCM_WG;     // blocks per chunk at the production Tw = 16
@@ -1101,6 +1356,7 @@ int main(int argc, char **argv) {
     test_batch_pieces();
     test_wipe();
     test_packets(16, 61); test_packets(24, 62); test_packets(32, 63);
+    test_packet_grid(level);
     // many messages by rows: offset arrays with every kind of length (empty, shorter than a block, tails of 63 blocks + 15 bytes = two tail rows, whole super-rows,
     // 1 .. 3 rows behind them), AAD of none / a ragged block / more than a row; fixed-size records; one block per wave for few and for many waves (cuts in the
     // middle of strands), dealt blocks of 1 / 2 / 3 / 7 units
