@@ -7,13 +7,16 @@
 // a 32-bit number per frame that is not on the wire, the upper half of its packet or sequence number; WIREX itself says whether it enters the nonce (AESGCM_WIREX_XPN,
 // MACsec XPN) or the AAD (AESGCM_WIREX_ESN, ESP with extended sequence numbers), and is 0 in every other kernel.  KT_WIREX_TLS13 / KT_WIREX_TLS12 (k_kt_tls,
 // aesgcm_tls_kernels.hip; internal values, aesgcm_keytab.h): the frame is a TLS record hdr[5] | (1.2: explicit nonce[8]) | payload | tag[16] and the number is its whole 64-bit
-// sequence number, wx->seq[pkt]: 1.3 XORs it into the slot's 12-byte IV (KtSlot::xpn) and reads no nonce byte from the record, 1.2 puts it in front of the one AAD block.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
+// sequence number, wx->seq[pkt]: 1.3 XORs it into the slot's 12-byte IV (KtSlot::xpn) and reads no nonce byte from the record, 1.2 puts it in front of the one AAD block.
+// KT_WIREX_QUIC (k_kt_quic, aesgcm_quic_kernels.hip): the frame is a QUIC packet header | payload | tag[16] whose header ends behind its packet-number field, at
+// wx->pn_off[pkt] + (first byte & 3) + 1 -- per packet, the first byte read through p.aad, where the header lies unprotected; nonce as TLS 1.3's from wx->seq[pkt], the full
+// packet number.  The header itself is k_kt_quic_hp's business: it is not copied here.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
 // what that cost there).  For the same reason the two key sources read a packet's offsets in different orders: each keeps its kernel's instruction stream.
     static_assert(DEC == 0 || DEC == 1 || (DEC == 2 && !SLOTS), "the probe (DEC == 2) takes raw keys");
     static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
     static_assert(!WIREX || WIRE, "the number that is not on the wire belongs to a frame in wire format");
-    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12, "one extension or none");
-    constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN, x_t13 = WIREX == KT_WIREX_TLS13, x_t12 = WIREX == KT_WIREX_TLS12;
+    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_QUIC, "one extension or none");
+    constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN, x_t13 = WIREX == KT_WIREX_TLS13, x_t12 = WIREX == KT_WIREX_TLS12, x_quic = WIREX == KT_WIREX_QUIC;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
@@ -61,6 +64,24 @@
         const unsigned char *ivp = p.ivs + (size_t)pkt * 12;
         u32 pkt_len = p.pkt_len, aad_len = p.aad_len;
         u64 doff = (u64)pkt * p.pkt_len, aoff = (u64)pkt * p.aad_len;
+        [[maybe_unused]] u64 qpn = 0;                    // QUIC: the packet's full number
+        if constexpr (x_quic) {
+            // a QUIC packet (RFC 9001 5.3): AAD = the header up to and including the packet-number field, whose length is in the unprotected first byte; payload behind
+            // it; the tag last.  Refused: what k_kt_quic_hp refuses (aesgcm_quic_kernels.hip: quic_refused) -- either slot, the offsets, more than 65535 bytes, pn_off 0,
+            // the sample's 16 bytes at pn_off + 4 not inside the packet (so header and tag fit for every pn_len), and on encrypt a number of 2^62 or more.  A refused
+            // packet's number and first byte are not read
+            const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
+            const u32 hslot = wx->hp_slots[pkt], po = wx->pn_off[pkt];
+            bad |= hslot >= kt->n_slots || e < b || e - b > 65535u || po == 0u || (u64)po + 20u > e - b;
+            bad |= ks->set != KT_SET || kt->tab[bad ? 0u : hslot].set != KT_SET;
+            qpn = bad ? (u64)0 : wx->seq[pkt];
+            if (DEC == 0) bad |= (qpn >> 62) != 0;
+            const u32 hdr = bad ? 0u : po + (p.aad[b] & 3u) + 1u;
+            aoff = b;
+            aad_len = hdr;
+            pkt_len = bad ? 0u : (u32)(e - b) - 16u - hdr;
+            doff = b + hdr;
+        } else
         if constexpr (WIRE) {
             // the frame's one range: AAD from its first byte, payload behind the header, the ICV last; auth-only: everything in front of the ICV is AAD.  A frame too
             // short for header (nonce bytes included) and ICV is refused like a falling range
@@ -114,8 +135,8 @@
         u32 iv0, iv1, iv2;
         if constexpr (WIRE) {
             // the nonce: salt_len (0, 4 or 8) bytes of the slot's salt, then header bytes -- whole words either way; a refused frame's header is not read
-            const u32 sw = x_xpn ? 2u : x_t13 ? 3u : x_t12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
-            const u32 f0 = bad || x_t13 ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
+            const u32 sw = x_xpn ? 2u : x_t13 || x_quic ? 3u : x_t12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
+            const u32 f0 = bad || x_t13 || x_quic ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
             iv0 = sw ? ks->salt[0] : f0;
             iv1 = sw > 1u ? ks->salt[1] : sw ? f0 : f1;
             iv2 = sw > 1u ? f0 : sw ? f1 : f2;
@@ -130,7 +151,12 @@
                 const u64 sq = bad ? (u64)0 : wx->seq[pkt];
                 iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(sq >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)sq);
             }
-            // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through
+            if constexpr (x_quic) {
+                // QUIC (RFC 9001 5.3): TLS 1.3's formula with the packet number
+                iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(qpn >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)qpn);
+            }
+            // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through (QUIC: k_kt_quic_hp writes the header)
+            if constexpr (!x_quic)
             if (p.in != p.out && st_ok) wire_copy_front(p.out + aoff, p.in + aoff, (u32)(doff - aoff), l, G);
         } else { iv0 = load_le32(ivp); iv1 = load_le32(ivp + 4); iv2 = load_le32(ivp + 8); }
         // ---- H on lane 0 and E_K(IV || 1) on lane 1 of the group: with a raw key H = E_K(0^128) in the same pass (gcm_gctr.vhd:141-145), with a slot its stored H

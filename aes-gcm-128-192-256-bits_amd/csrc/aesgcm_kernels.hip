@@ -1474,10 +1474,11 @@ hipError_t klaunch_set_attributes() {
     SETATTRB3P(10); SETATTRB3P(12); SETATTRB3P(14);
 #undef SETATTRB3P
 #undef ATTRCHK
-    const hipError_t ek = klaunch_kt_attributes();                             // the key tables' kernels (aesgcm_keytab_kernels.hip, aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip)
+    const hipError_t ek = klaunch_kt_attributes();                             // the key tables' kernels (aesgcm_keytab_kernels.hip, aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip, aesgcm_quic_kernels.hip)
     const hipError_t ew = ek != hipSuccess ? ek : klaunch_wire_attributes();
     const hipError_t ex = ew != hipSuccess ? ew : klaunch_wirex_attributes();
-    return ex != hipSuccess ? ex : klaunch_tls_attributes();
+    const hipError_t et = ex != hipSuccess ? ex : klaunch_tls_attributes();
+    return et != hipSuccess ? et : klaunch_quic_attributes();
 }
 hipError_t klaunch_init_tables(DevTables *t) { hipLaunchKernelGGL(k_init_tables, dim3(1), dim3(256), 0, 0, t); return hipGetLastError(); }
 hipError_t klaunch_setup(hipStream_t st, KeyMaterial *km, const DevTables *tb, const uint8_t *d_key, int key_len, int pre_nr, u32 G) {

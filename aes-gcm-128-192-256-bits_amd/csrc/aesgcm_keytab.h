@@ -1,6 +1,6 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
 // Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots; aesgcm_wire_kernels.hip:
-// k_kt_wire, the same body on frames in wire format; aesgcm_wirex_kernels.hip: k_kt_wirex, that with a 32-bit number per frame that is not on the wire; aesgcm_tls_kernels.hip: k_kt_tls, TLS records with their 64-bit sequence numbers) and the host
+// k_kt_wire, the same body on frames in wire format; aesgcm_wirex_kernels.hip: k_kt_wirex, that with a 32-bit number per frame that is not on the wire; aesgcm_tls_kernels.hip: k_kt_tls, TLS records with their 64-bit sequence numbers; aesgcm_quic_kernels.hip: k_kt_quic and k_kt_quic_hp, QUIC packets and their header protection) and the host
 // (aesgcm_keytab.hip, which launches k_kt_batch as aesgcm_host.hip's batch_plan plans it for k_batch3).
 #pragma once
 #include "aesgcm_internal.h"
@@ -44,15 +44,32 @@ struct KtWireParams {
 };
 
 // ... with an extension (k_kt_wirex): hi[p] = the upper half of frame p's 64-bit packet / sequence number, which is not in the frame
-// The body's WIREX modes that the ABI does not name (aesgcm_wire_xfmt_check refuses them as it refuses every unknown bit): TLS records, aesgcm_keytab_records_crypt_dev
+// The body's WIREX modes that the ABI does not name (aesgcm_wire_xfmt_check refuses them as it refuses every unknown bit): TLS records, aesgcm_keytab_records_crypt_dev;
+// QUIC packets, aesgcm_keytab_quic_crypt_dev
 #define KT_WIREX_TLS13 0x10u
 #define KT_WIREX_TLS12 0x20u
+#define KT_WIREX_QUIC  0x40u
 struct KtWireXParams {
     KtWireParams w;
     union {
         const u32 *hi;                     // n_pkts numeric values
         const u64 *seq;                    // k_kt_tls: n_pkts whole 64-bit record sequence numbers; w.f = {5, 5, 5, 0, 16, 0} (1.3) or {13, 13, 5, 4, 16, 0} (1.2)
+                                           // k_kt_quic: n_pkts full packet numbers (decrypt: as k_kt_quic_hp decoded them); w.f = {0, 0, 0, 0, 16, 0}, the header's length is per packet
     };
+    const u32 *pn_off;                     // k_kt_quic only (behind everything the other kernels read): where packet p's packet-number field starts, n_pkts values
+    const u32 *hp_slots;                   // ... and its header-protection slot, which the AEAD checks as k_kt_quic_hp does: a packet is refused by both kernels or by neither
+};
+
+// A QUIC call's header-protection pass (k_kt_quic_hp, a lane per packet): packet p = bytes [pkt_off[p], pkt_off[p + 1]) of in / out
+struct KtQuicHpParams {
+    const unsigned char *in;
+    unsigned char *out;
+    const u64 *pkt_off;
+    const u32 *slots, *hp_slots, *pn_off;
+    const u64 *pn;                         // encrypt: the full numbers (only their range is checked here); decrypt: the expected ones
+    u64 *pn_out;                           // decrypt: the decoded numbers (may be pn)
+    const KtSlot *tab;
+    u32 n_pkts, n_slots;
 };
 
 // The frame-side accesses of k_kt_wire (aesgcm_batch3_body.inc, WIRE), all inside the frame and at any byte address.  The ICV is 8, 12 or 16 bytes: dwords.
@@ -80,3 +97,6 @@ hipError_t klaunch_wirex_attributes();     // ... and for the k_kt_wirex instanc
 hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
 hipError_t klaunch_tls_attributes();       // ... and for the k_kt_tls instances (aesgcm_tls_kernels.hip)
 hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
+hipError_t klaunch_quic_attributes();      // ... and for the k_kt_quic and k_kt_quic_hp instances (aesgcm_quic_kernels.hip)
+hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
+hipError_t klaunch_kt_quic_hp(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p);

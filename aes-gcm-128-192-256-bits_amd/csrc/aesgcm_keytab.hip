@@ -3,7 +3,8 @@
 // k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.  Frames in wire
 // format (aesgcm_keytab_frames_crypt_dev) are one k_kt_wire launch (aesgcm_wire_kernels.hip) planned the same way; with a number per frame that is not on the wire
 // (aesgcm_keytab_frames_crypt_x_dev: MACsec XPN, ESP ESN) one k_kt_wirex launch (aesgcm_wirex_kernels.hip); TLS records with their 64-bit sequence numbers
-// (aesgcm_keytab_records_crypt_dev) one k_kt_tls launch (aesgcm_tls_kernels.hip).
+// (aesgcm_keytab_records_crypt_dev) one k_kt_tls launch (aesgcm_tls_kernels.hip); QUIC packets (aesgcm_keytab_quic_crypt_dev) two launches, k_kt_quic planned the same way and
+// k_kt_quic_hp, a lane per packet (aesgcm_quic_kernels.hip).
 #include "aesgcm_keytab.h"
 
 #include <stddef.h>
@@ -277,6 +278,39 @@ int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_
     if (!d_seq) return AESGCM_EARG;
     static const aesgcm_wire_fmt f13 = {5, 5, 5, 0, 16, 0}, f12 = {13, 13, 5, 4, 16, 0};          // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
     return kt_frames_crypt(t, decrypt, fmt->version == AESGCM_TLS_13 ? &f13 : &f12, 0u, nullptr, n_recs, d_slots, d_in, d_rec_off, d_out, d_auth, stream, fmt->version, d_seq);
+}
+
+// ---------------------------------------------------------------- QUIC packets
+// Two launches on the caller's stream: the AEAD (k_kt_quic, planned as kt_frames_crypt plans k_kt_wire) and header protection (k_kt_quic_hp, a lane per packet).  Encrypt:
+// AEAD first, then the mask from the fresh ciphertext.  Decrypt: the mask off first -- that kernel leaves the unprotected header in d_out and the decoded numbers in
+// d_pn_out, which is where the AEAD reads both.  No scratch memory, no host synchronisation: capture-safe.
+int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_hp_slots, const uint64_t *d_pn, uint64_t *d_pn_out,
+                                 const uint32_t *d_pn_off, const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream) {
+    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
+    if (!n_pkts) return AESGCM_OK;
+    if (!d_slots || !d_hp_slots || !d_pn || !d_pn_off || !d_in || !d_out || !d_pkt_off || (decrypt && (!d_auth || !d_pn_out)) || n_pkts >= ((size_t)1 << 31)) return AESGCM_EARG;
+    KtWireXParams xp;
+    memset(&xp, 0, sizeof xp);
+    BatchParams &p = xp.w.k.b;
+    p.in = (const unsigned char *)d_in; p.out = (unsigned char *)d_out;
+    p.aad = decrypt ? (const unsigned char *)d_out : (const unsigned char *)d_in;     // where the header lies unprotected
+    p.auth = decrypt ? d_auth : nullptr;
+    p.data_off = d_pkt_off;
+    p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
+    xp.w.k.slots = d_slots; xp.w.k.tab = t->tab; xp.w.k.n_slots = (u32)t->n_slots; xp.w.k.status = t->status;
+    xp.w.f.tag_len = 16;                                                              // the rest of a wire format is per packet here
+    xp.seq = decrypt ? d_pn_out : d_pn;
+    xp.pn_off = d_pn_off; xp.hp_slots = d_hp_slots;
+    KtQuicHpParams hp;
+    hp.in = p.in; hp.out = p.out; hp.pkt_off = d_pkt_off; hp.slots = d_slots; hp.hp_slots = d_hp_slots; hp.pn_off = d_pn_off;
+    hp.pn = d_pn; hp.pn_out = decrypt ? d_pn_out : nullptr; hp.tab = t->tab; hp.n_pkts = (u32)n_pkts; hp.n_slots = (u32)t->n_slots;
+    BatchPlan b;
+    const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
+    if (rc) return rc;
+    if (decrypt) HIPCHK(klaunch_kt_quic_hp(b.nr, 1, b.st, b.tables, hp));
+    HIPCHK(klaunch_kt_quic(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
+    if (!decrypt) HIPCHK(klaunch_kt_quic_hp(b.nr, 0, b.st, b.tables, hp));
+    return batch_done(b, p);
 }
 
 int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {

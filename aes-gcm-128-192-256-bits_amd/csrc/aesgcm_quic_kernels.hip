@@ -1,0 +1,115 @@
+// aesgcm_quic_kernels.hip -- key tables on QUIC packets in wire format (gfx950, RFC 9001 section 5): aesgcm_keytab_quic_crypt_dev's two kernels and their launchers; the
+// host side is aesgcm_keytab.hip.
+//
+//   k_kt_quic<NR,DEC,LG>    the AEAD: k_kt_tls's TLS 1.3 path (aesgcm_batch3_body.inc, SLOTS = WIRE = true, WIREX = KT_WIREX_QUIC) with a header whose length differs from
+//                           packet to packet: AAD = bytes [0, pn_off[p] + pn_len), pn_len = (first byte & 3) + 1, the first byte read through p.aad where the header lies
+//                           UNPROTECTED (encrypt: d_in; decrypt: d_out, where k_kt_quic_hp left it).  Nonce = the slot's 12-byte IV (KtSlot::xpn) XOR seq[p], the full packet
+//                           number (decrypt: as k_kt_quic_hp decoded it into d_pn_out).  It copies no header: that is the other kernel's.
+//   k_kt_quic_hp<NR,DEC>    header protection (RFC 9001 5.4), a lane per packet: mask = AES-ECB of the 16 ciphertext bytes at pn_off + 4 under the round keys of the packet's
+//                           hp slot; the first byte's low bits and the pn_len packet-number bytes are XORed with it, byte by byte, inside the packet.  Decrypt: it also
+//                           decodes the full number from the truncated one and the expected one (RFC 9000 A.3) into pn_out[p].  Out of place it writes the whole header.
+// Encrypt runs k_kt_quic, then k_kt_quic_hp (the sample is fresh ciphertext); decrypt the other way round (the AEAD needs the unmasked header and the number).  Both refuse
+// the same packets by the same test (quic_refused below and the body's copy of it), so a refused packet is touched by neither; k_kt_quic alone reports it (status word,
+// auth 0).  18 + 6 instances; every k_kt_quic one: no scratch, at most 128 registers.
+// A translation unit of its own: its ISA census (`make asm_quic`) is read apart from the others', whose instruction streams stay what they were.
+#include "aesgcm_keytab.h"
+#include "aesgcm_lanes.h"
+
+template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 decrypt
+__global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_kt_quic(const DevTables *__restrict__ tb, const KtWireXParams xp) {
+    constexpr bool SLOTS = true, WIRE = true;
+    constexpr u32 WIREX = KT_WIREX_QUIC;
+    const KtWireXParams *const wx = &xp;
+    const KtParams *const kt = &xp.w.k;
+    const BatchParams &p = xp.w.k.b;
+    const aesgcm_wire_fmt *const wf = &xp.w.f;
+#include "aesgcm_batch3_body.inc"
+}
+
+// RFC 9000 A.3 (DecodePacketNumber) on unsigned 64-bit values: the RFC's integers are unbounded, so each comparison is written so that it cannot wrap
+HD u64 quic_decode_pn(u64 expected, u32 truncated, u32 pn_nbits) {
+    const u64 win = (u64)1 << pn_nbits, hwin = win >> 1, mask = win - 1;
+    const u64 cand = (expected & ~mask) | truncated;
+    if (expected >= hwin && cand <= expected - hwin && cand < ((u64)1 << 62) - win) return cand + win;
+    if (expected <= ~(u64)0 - hwin && cand > expected + hwin && cand >= win) return cand - win;
+    return cand;
+}
+
+template <int NR, int DEC>
+__global__ __launch_bounds__(256) void k_kt_quic_hp(const DevTables *__restrict__ tb, const KtQuicHpParams q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const u32 tid = threadIdx.x;
+    main_fill_lds(smem, nullptr, tb, tid, false, 256u);          // T0 | T2
+    __syncthreads();
+    const u32 i = blockIdx.x * 256u + tid;
+    if (i >= q.n_pkts) return;
+    // the refusals, as k_kt_quic makes them (aesgcm_batch3_body.inc, x_quic): a refused packet's number is not read and nothing of it is written
+    const u32 slot = q.slots[i], hslot = q.hp_slots[i], po = q.pn_off[i];
+    const u64 b = q.pkt_off[i], e = q.pkt_off[i + 1];
+    if (slot >= q.n_slots || hslot >= q.n_slots || e < b || e - b > 65535u || po == 0u || (u64)po + 20u > e - b) return;
+    const KtSlot *const hs = q.tab + hslot;
+    if (q.tab[slot].set != KT_SET || hs->set != KT_SET) return;
+    const u64 pn = q.pn[i];
+    if (DEC == 0 && (pn >> 62) != 0) return;
+    const unsigned char *const src = q.in + b;
+    unsigned char *const dst = q.out + b;
+    // mask = AES-ECB(hp key, sample): the sample is ciphertext -- encrypt: what k_kt_quic has just written to `out`; decrypt: the protected packet's
+    const u32 lb = (tid & 31u) << 2;
+    u32 rk[4 * (NR + 1)];
+#pragma unroll
+    for (int r = 0; r < NR + 1; r++) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(hs->rk + 4 * r);
+        rk[4 * r] = v.x; rk[4 * r + 1] = v.y; rk[4 * r + 2] = v.z; rk[4 * r + 3] = v.w;
+    }
+    const uint4 sample = gload16_any((DEC ? src : (const unsigned char *)dst) + po + 4u);
+    u32 s0 = sample.x ^ rk[0], s1 = sample.y ^ rk[1], s2 = sample.z ^ rk[2], s3 = sample.w ^ rk[3];
+    aes_rounds_lds<NR>(s0, s1, s2, s3, rk, smem, lb);            // memory-order words: mask[0 .. 3] = the bytes of s0 from the lowest, mask[4] = the lowest of s1
+    const u32 f_in = src[0];
+    const u32 first = f_in ^ (s0 & (f_in & 0x80u ? 0x0Fu : 0x1Fu));      // (the form bit itself is never masked)
+    const u32 pn_len = ((DEC ? first : f_in) & 3u) + 1u;
+    if (q.in != q.out) wire_copy_front(dst, src, po, 0u, 1u);    // out of place: the header in front of the packet number, by this one lane
+    dst[0] = (unsigned char)first;
+    const u32 m = (s0 >> 8) | (s1 << 24);                         // mask[1 .. 4]
+    u32 trunc = 0;
+    for (u32 k = 0; k < pn_len; k++) {
+        const u32 x = src[po + k] ^ ((m >> (8u * k)) & 0xFFu);
+        dst[po + k] = (unsigned char)x;
+        trunc = (trunc << 8) | x;
+    }
+    if (DEC) q.pn_out[i] = quic_decode_pn(pn, trunc, 8u * pn_len);
+}
+
+// ------------------------------------------------------------------------------------------------ launchers
+#define KT_QUIC_HP_LDS (AESGCM_LDS_AES_OFF + AESGCM_LDS_AES)
+hipError_t klaunch_quic_attributes() {
+#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
+#define SETATTRQ1(NR, D, LG) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic<NR, D, LG>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG)))
+#define SETATTRQ(NR, D) SETATTRQ1(NR, D, 6); SETATTRQ1(NR, D, 4); SETATTRQ1(NR, D, 3); \
+                        ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR, D>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS))
+    SETATTRQ(10, 0); SETATTRQ(12, 0); SETATTRQ(14, 0); SETATTRQ(10, 1); SETATTRQ(12, 1); SETATTRQ(14, 1);
+#undef SETATTRQ
+#undef SETATTRQ1
+#undef ATTRCHK
+    return hipSuccess;
+}
+
+hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
+#define LKQ(NR, D, LG) hipLaunchKernelGGL((k_kt_quic<NR, D, LG>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
+#define LKQN(D, LG) do { if (nr == 10) LKQ(10, D, LG); else if (nr == 12) LKQ(12, D, LG); else LKQ(14, D, LG); } while (0)
+    if (lg == 3) { if (dec) LKQN(1, 3); else LKQN(0, 3); }
+    else if (lg == 4) { if (dec) LKQN(1, 4); else LKQN(0, 4); }
+    else { if (dec) LKQN(1, 6); else LKQN(0, 6); }
+#undef LKQN
+#undef LKQ
+    return hipGetLastError();
+}
+
+hipError_t klaunch_kt_quic_hp(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) {
+    const unsigned wgs = (p.n_pkts + 255u) / 256u;
+#define LKH(NR, D) hipLaunchKernelGGL((k_kt_quic_hp<NR, D>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p)
+#define LKHN(D) do { if (nr == 10) LKH(10, D); else if (nr == 12) LKH(12, D); else LKH(14, D); } while (0)
+    if (dec) LKHN(1); else LKHN(0);
+#undef LKHN
+#undef LKH
+    return hipGetLastError();
+}

@@ -42,6 +42,7 @@ SYMBOLS = [
     "aesgcm_wire_fmt_check", "aesgcm_keytab_set_salt", "aesgcm_keytab_frames_crypt_dev",
     "aesgcm_wire_xfmt_check", "aesgcm_keytab_set_xpn", "aesgcm_keytab_frames_crypt_x_dev",
     "aesgcm_tls_fmt_check", "aesgcm_keytab_set_tls_iv", "aesgcm_keytab_records_crypt_dev",
+    "aesgcm_keytab_quic_crypt_dev",
 ]
 
 
@@ -721,6 +722,7 @@ def _keytab_typed(L):
         L.aesgcm_tls_fmt_check.argtypes = [ctypes.POINTER(TlsFormat)]
         L.aesgcm_keytab_set_tls_iv.argtypes = [vp, sz, sz, vp, vp]
         L.aesgcm_keytab_records_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(TlsFormat), sz, vp, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_keytab_quic_crypt_dev.argtypes = [vp, cint, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
 
@@ -959,6 +961,49 @@ class KeyTable:
             outs = [out[off[p]:off[p + 1]] for p in range(n)]
             auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
             return outs, auth
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    def quic_crypt_dev(self, decrypt, n_pkts, d_slots, d_hp_slots, d_pn, d_pn_off, d_in, d_pkt_off, d_out, d_pn_out=None, d_auth=None, stream=None):
+        """aesgcm_keytab_quic_crypt_dev: QUIC packet p = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in / d_out, its packet-number field at byte d_pn_off[p] (uint32), under
+        the AEAD slot d_slots[p] (key by set, IV by set_tls_iv) and the header-protection slot d_hp_slots[p] (key by set).  d_pn[p] (uint64): the full packet number on
+        encrypt, the expected one on decrypt, where the decoded number goes to d_pn_out[p] (may be d_pn) and the verdict to d_auth[p]"""
+        _chk(self._lib.aesgcm_keytab_quic_crypt_dev(self._t, int(bool(decrypt)), n_pkts, d_slots, d_hp_slots, d_pn, d_pn_out, d_pn_off, d_in, d_pkt_off, d_out, d_auth, stream))
+
+    def crypt_quic(self, slots, hp_slots, pns, pn_offs, packets, decrypt=False):
+        """Host convenience (tests, examples), crypt_records' counterpart: whole QUIC packets (header | payload | tag; on encrypt the header is unprotected with the truncated
+        packet number written and the tag's bytes are placeholders) through one call, in place.  pns: the full packet numbers (encrypt) or the expected ones (decrypt).
+        -> (packets_out, auth, pns_out); auth and pns_out are None on encrypt."""
+        import struct
+        n = len(slots)
+        if len(packets) != n or len(hp_slots) != n or len(pns) != n or len(pn_offs) != n or not n:
+            raise AesGcmError(EARG, "slots, hp_slots, pns, pn_offs and packets must be equally long and not empty")
+        off = [0]
+        for r in packets:
+            off.append(off[-1] + len(r))
+        blob = b"".join(bytes(r) for r in packets)
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("hp", 4 * n), ("pn", 8 * n), ("pn_off", 4 * n), ("data", len(blob)),
+                                                                        ("off", 8 * (n + 1)), ("auth", 4 * n), ("pn_out", 8 * n))}
+        try:
+            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
+            bufs["hp"].upload(struct.pack("<%dI" % n, *hp_slots))
+            bufs["pn"].upload(struct.pack("<%dQ" % n, *pns))
+            bufs["pn_off"].upload(struct.pack("<%dI" % n, *pn_offs))
+            if blob:
+                bufs["data"].upload(blob)
+            bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
+            if decrypt:
+                bufs["auth"].upload(bytes(4 * n))
+                bufs["pn_out"].upload(bytes(8 * n))
+            self.quic_crypt_dev(decrypt, n, bufs["slots"].ptr, bufs["hp"].ptr, bufs["pn"].ptr, bufs["pn_off"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
+                                d_pn_out=bufs["pn_out"].ptr if decrypt else None, d_auth=bufs["auth"].ptr if decrypt else None)
+            _chk(load().aesgcm_dev_sync(self.device))
+            out = bytes(bufs["data"].download(len(blob))) if blob else b""
+            outs = [out[off[p]:off[p + 1]] for p in range(n)]
+            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
+            pns_out = list(struct.unpack("<%dQ" % n, bytes(bufs["pn_out"].download(8 * n)))) if decrypt else None
+            return outs, auth, pns_out
         finally:
             for b in bufs.values():
                 b.free()

@@ -38,7 +38,7 @@ extern "C" {
 #endif
 
 #define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
-                                  aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev)
+                                  aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -534,7 +534,7 @@ AESGCM_API int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, c
  * One k_kt_tls launch per call; shape and order as aesgcm_keytab_frames_crypt_dev (8, 16 or 64 lanes per record by count, by falling length class from 262144 records, 98304
  * for the longer keys).  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: checking the header's version, type or length bytes against the offsets; padding and content type (the payload's last bytes in 1.3); generating sequence
- * numbers or explicit nonces; key derivation (INTEGRATION.md "TLS records" says which secret becomes what); DTLS and QUIC; routing long records to the row kernels. */
+ * numbers or explicit nonces; key derivation (INTEGRATION.md "TLS records" says which secret becomes what); DTLS; routing long records to the row kernels. */
 #define AESGCM_TLS_13 1u   /* hdr[5] | payload | tag[16]; nonce = slot IV XOR (0^32 | be64(d_seq[p])); AAD = hdr */
 #define AESGCM_TLS_12 2u   /* hdr[5] | explicit nonce[8] | payload | tag[16]; nonce = slot IV[0..4) | explicit nonce; AAD = be64(d_seq[p]) | hdr[0..3) | be16(L - 29) */
 typedef struct aesgcm_tls_fmt {
@@ -545,6 +545,42 @@ AESGCM_API int aesgcm_tls_fmt_check(const aesgcm_tls_fmt *fmt);
 AESGCM_API int aesgcm_keytab_set_tls_iv(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *ivs, void *stream);
 AESGCM_API int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_tls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint64_t *d_seq,
                                     const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- key tables on QUIC PACKETS in wire format, with header protection (RFC 9001 section 5, AES-GCM suites)
+ * What an HTTP/3 terminator holds is one buffer of QUIC packets header | ciphertext | tag.  No call above can express one: its AAD is the packet header, whose length differs
+ * from packet to packet; its nonce takes a 62-bit packet number of which only 1 to 4 truncated bytes are on the wire; and those bytes and the low bits of the first byte are
+ * masked by header protection, AES-ECB of a 16-byte ciphertext sample under a second key.  aesgcm_keytab_quic_crypt_dev takes the buffer as it is: packet p is bytes
+ * [d_pkt_off[p], d_pkt_off[p + 1]) of d_in and of d_out (the same n_pkts + 1 offsets for both; d_in == d_out allowed; any byte alignment), L bytes long: ONE QUIC packet, long
+ * or short header, laid out header | payload | tag[16].  Its packet-number field starts at byte d_pn_off[p] (DEVICE memory, n_pkts uint32): the caller parses the unprotected
+ * parts of the header (connection-ID lengths, token, Length) to find it.  pn_len = (first byte & 3) + 1, read from the UNPROTECTED first byte; AAD = bytes
+ * [0, d_pn_off[p] + pn_len); payload = [d_pn_off[p] + pn_len, L - 16), length 0 is taken.
+ * Two slots of the same table per packet.  d_slots[p]: the AEAD -- its key by aesgcm_keytab_set from the `quic key`, its 12-byte IV by aesgcm_keytab_set_tls_iv from the
+ * `quic iv` (the same slot state and the same formula as TLS 1.3): nonce = IV XOR (00 00 00 00 | be64(pn)).  d_hp_slots[p]: an ordinary slot set by aesgcm_keytab_set from the
+ * `quic hp` key, of which only the round keys are used: mask = AES-ECB of the sample, the 16 bytes at d_pn_off[p] + 4 of the PROTECTED packet (RFC 9001 5.4.2); first byte
+ * ^= mask[0] & (first byte & 0x80 ? 0x0f : 0x1f); pn byte i ^= mask[1 + i] for i < pn_len.
+ *   ENCRYPT (protect)    d_in holds the unprotected header with the truncated packet number already written by the caller (as a SecY writes its SecTAG), the plaintext, and
+ *                        16 bytes of room for the tag.  d_pn[p] (DEVICE memory, n_pkts uint64) is the FULL packet number.  The AEAD runs first, then the mask is taken from
+ *                        the fresh ciphertext.  d_pn_out and d_auth are ignored.
+ *   DECRYPT (unprotect)  d_in holds the protected packet.  d_pn[p] is the EXPECTED packet number: the largest one received in that packet-number space, plus 1.  The device
+ *                        removes header protection, decodes the full number from the truncated one exactly as RFC 9000 Appendix A.3 does (the (1 << 62) guard included),
+ *                        writes it to d_pn_out[p] (required; may be d_pn), decrypts, and sets d_auth[p] (required) = 1 iff the tag equals the computed one.  The unmasked
+ *                        first byte in d_out shows the caller the Key Phase bit.
+ * Out of place every byte of an accepted packet in d_out is defined: the header (encrypt: protected, decrypt: unprotected), the payload, and on decrypt the tag copied.  No
+ * byte outside an accepted packet is written.
+ * A packet the device cannot take is REFUSED on its own, as a TLS record is: either slot is n_slots or more, unset or cleared; its offsets fall; L > 65535;
+ * d_pn_off[p] == 0; d_pn_off[p] + 20 > L (the sample must lie inside the packet, which also guarantees that header and tag fit for every pn_len); on encrypt
+ * d_pn[p] >= 2^62.  Nothing of it is written, d_pn_out[p] included; d_pn[p] is not read unless every other test passed; d_auth[p] = 0 on decrypt; and the LOWEST such index
+ * goes to aesgcm_keytab_status.  FAIL-CLOSED: aesgcm_wipe_failed_dev(device, n_pkts, d_out, 0, d_pkt_off, d_auth, stream) behind a decrypt.
+ * AESGCM_EARG, before the table or a device is touched: t NULL; decrypt not 0 / 1; (n_pkts == 0 is AESGCM_OK;) any of d_slots, d_hp_slots, d_pn, d_pn_off, d_in, d_out,
+ * d_pkt_off NULL; decrypt without d_auth or d_pn_out; n_pkts >= 2^31.
+ * Two launches per call on `stream`, no scratch memory, capture-safe and asynchronous: encrypt k_kt_quic (the AEAD; shape and order as aesgcm_keytab_records_crypt_dev) then
+ * k_kt_quic_hp (a lane per packet); decrypt the other way round.  Ordering and thread safety as the other key-table calls.
+ * OUT OF SCOPE: Retry and Version Negotiation packets; coalesced datagrams (split them: one entry of d_pkt_off per packet); ChaCha20; key derivation (INTEGRATION.md "QUIC
+ * packets" says which secret becomes what); choosing the slot from the Key Phase bit (the caller who needs it decrypts out of place and retries the failed packets under the
+ * next-phase slot); DTLS; anti-replay; routing long packets to the row kernels. */
+AESGCM_API int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_hp_slots,
+                                 const uint64_t *d_pn, uint64_t *d_pn_out, const uint32_t *d_pn_off,
+                                 const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
