@@ -1,5 +1,6 @@
 // aesgcm_device.hip -- the library's ONE device translation unit: libaesgcm_hip.so carries a single gfx950 code object (tests/test_abi_cpu.py lists the offload
-// bundle's entries), so every kernel source is compiled here together.  Each source still compiles on its own for its ISA census (`make asm`, `make asm_keytab`, `make asm_wire`, `make asm_wirex`, `make asm_tls`, `make asm_quic`).
+// bundle's entries), so every kernel source is compiled here together.  Each source still compiles on its own for its ISA census
+// (`make asm` for aesgcm_kernels.hip, `make asm_<family>` for aesgcm_<family>_kernels.hip).
 #include "aesgcm_kernels.hip"
 #include "aesgcm_keytab_kernels.hip"
 #include "aesgcm_wire_kernels.hip"

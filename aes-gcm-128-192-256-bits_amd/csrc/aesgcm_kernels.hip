@@ -25,6 +25,7 @@
 #include "aesgcm_internal.h"
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_dispatch.h"
 
 #include <stddef.h>
 #include <stdint.h>
@@ -1465,16 +1466,12 @@ hipError_t klaunch_set_attributes() {
 #undef SETATTRP
     ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_combine), hipFuncAttributeMaxDynamicSharedMemorySize, CMB_LDS_BYTES));
     ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_combine_batch), hipFuncAttributeMaxDynamicSharedMemorySize, CMB_LDS_BYTES));
-#define SETATTRB3(NR, D) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR, D, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(6))); \
-                         ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR, D, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(4))); \
-                         ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR, D, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(3)))
-    SETATTRB3(10, 0); SETATTRB3(12, 0); SETATTRB3(14, 0); SETATTRB3(10, 1); SETATTRB3(12, 1); SETATTRB3(14, 1);
-#undef SETATTRB3
-#define SETATTRB3P(NR) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR, 2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(3)))
-    SETATTRB3P(10); SETATTRB3P(12); SETATTRB3P(14);
-#undef SETATTRB3P
 #undef ATTRCHK
-    const hipError_t ek = klaunch_kt_attributes();                             // the key tables' kernels (aesgcm_keytab_kernels.hip, aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip, aesgcm_quic_kernels.hip)
+    const hipError_t eb = batch3_each([](auto NR, auto D, auto LG) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR(), D(), LG()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG())); });
+    if (eb != hipSuccess) return eb;
+    const hipError_t ep = nr_each([](auto NR) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR(), 2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(3)); });      // the probe
+    if (ep != hipSuccess) return ep;
+    const hipError_t ek = klaunch_kt_attributes();                             // the key tables' kernels, family by family (aesgcm_keytab.h)
     const hipError_t ew = ek != hipSuccess ? ek : klaunch_wire_attributes();
     const hipError_t ex = ew != hipSuccess ? ew : klaunch_wirex_attributes();
     const hipError_t et = ex != hipSuccess ? ex : klaunch_tls_attributes();
@@ -1562,14 +1559,11 @@ hipError_t klaunch_pktg(int nr, int dec, int lg, unsigned wgs, hipStream_t st, c
     return hipGetLastError();
 }
 hipError_t klaunch_batch3(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const BatchParams &p) {
-#define LB3(NR, D, LG) hipLaunchKernelGGL((k_batch3<NR, D, LG>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
-#define LB3N(D, LG) do { if (nr == 10) LB3(10, D, LG); else if (nr == 12) LB3(12, D, LG); else LB3(14, D, LG); } while (0)
-    if (dec == 2) { if (lg != 3) return hipErrorInvalidValue; LB3N(2, 3); }   // the probe exists in the shape of BASELINE config 5
-    else if (lg == 3) { if (dec) LB3N(1, 3); else LB3N(0, 3); }
-    else if (lg == 4) { if (dec) LB3N(1, 4); else LB3N(0, 4); }
-    else { if (dec) LB3N(1, 6); else LB3N(0, 6); }
-#undef LB3N
-#undef LB3
+    if (dec == 2) {                                                           // the probe exists in the shape of BASELINE config 5
+        if (lg != 3) return hipErrorInvalidValue;
+        nr_dispatch(nr, [&](auto NR) { hipLaunchKernelGGL((k_batch3<NR(), 2, 3>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(3), st, tb, p); });
+    }
+    else batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) { hipLaunchKernelGGL((k_batch3<NR(), D(), LG()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p); });
     return hipGetLastError();
 }
 hipError_t klaunch_len_sort(hipStream_t st, const LenSrc &src, u32 n, u32 *bins, u32 *perm, const RouteCfg &rc, u64 *bad_part, u32 *host_status, const DescSrc &ds) {

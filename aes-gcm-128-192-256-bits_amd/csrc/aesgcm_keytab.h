@@ -1,7 +1,8 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
-// Shared by the kernels (aesgcm_keytab_kernels.hip: k_kt_setup; k_kt_batch runs k_batch3's body, aesgcm_batch3_body.inc, which names the slots; aesgcm_wire_kernels.hip:
-// k_kt_wire, the same body on frames in wire format; aesgcm_wirex_kernels.hip: k_kt_wirex, that with a 32-bit number per frame that is not on the wire; aesgcm_tls_kernels.hip: k_kt_tls, TLS records with their 64-bit sequence numbers; aesgcm_quic_kernels.hip: k_kt_quic and k_kt_quic_hp, QUIC packets and their header protection) and the host
-// (aesgcm_keytab.hip, which launches k_kt_batch as aesgcm_host.hip's batch_plan plans it for k_batch3).
+// Shared by the kernels -- aesgcm_keytab_kernels.hip: k_kt_setup, and k_kt_batch, which runs k_batch3's body (aesgcm_batch3_body.inc) with the key material read from
+// slots; aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip, aesgcm_quic_kernels.hip: the same body on packets in wire format, one source per
+// family (aesgcm_keytab.hip lists them) -- and the host (aesgcm_keytab.hip, which launches each as aesgcm_host.hip's batch_plan plans k_batch3).  Every launcher below
+// picks its instance by aesgcm_dispatch.h.
 #pragma once
 #include "aesgcm_internal.h"
 #include <stddef.h>
@@ -88,15 +89,16 @@ HD void wire_copy_front(unsigned char *dst, const unsigned char *src, u32 front,
     else for (u32 o = l; o < front; o += G) dst[o] = src[o];
 }
 
-hipError_t klaunch_kt_attributes();        // hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every keytab instance, on the current device (klaunch_set_attributes)
+// per family: klaunch_*_attributes = hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every instance, on the current device (klaunch_set_attributes calls them all)
+hipError_t klaunch_kt_attributes();
 hipError_t klaunch_kt_setup(int nr, hipStream_t st, const DevTables *tb, const KtSetupParams &s);
 hipError_t klaunch_kt_batch(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtParams &p);
-hipError_t klaunch_wire_attributes();      // the same for the k_kt_wire instances (aesgcm_wire_kernels.hip)
+hipError_t klaunch_wire_attributes();
 hipError_t klaunch_kt_wire(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireParams &p);
-hipError_t klaunch_wirex_attributes();     // ... and for the k_kt_wirex instances (aesgcm_wirex_kernels.hip)
-hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
-hipError_t klaunch_tls_attributes();       // ... and for the k_kt_tls instances (aesgcm_tls_kernels.hip)
-hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
-hipError_t klaunch_quic_attributes();      // ... and for the k_kt_quic and k_kt_quic_hp instances (aesgcm_quic_kernels.hip)
+hipError_t klaunch_wirex_attributes();
+hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);     // ext: AESGCM_WIREX_XPN or _ESN
+hipError_t klaunch_tls_attributes();
+hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);   // version: AESGCM_TLS_13 or _12
+hipError_t klaunch_quic_attributes();      // k_kt_quic and k_kt_quic_hp
 hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);
 hipError_t klaunch_kt_quic_hp(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p);

@@ -1,10 +1,14 @@
-// aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_keytab_kernels.hip.
-// A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word; k_kt_setup fills slots from raw keys, a crypt call is one
-// k_kt_batch launch planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.  Frames in wire
-// format (aesgcm_keytab_frames_crypt_dev) are one k_kt_wire launch (aesgcm_wire_kernels.hip) planned the same way; with a number per frame that is not on the wire
-// (aesgcm_keytab_frames_crypt_x_dev: MACsec XPN, ESP ESN) one k_kt_wirex launch (aesgcm_wirex_kernels.hip); TLS records with their 64-bit sequence numbers
-// (aesgcm_keytab_records_crypt_dev) one k_kt_tls launch (aesgcm_tls_kernels.hip); QUIC packets (aesgcm_keytab_quic_crypt_dev) two launches, k_kt_quic planned the same way and
-// k_kt_quic_hp, a lane per packet (aesgcm_quic_kernels.hip).
+// aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_<family>_kernels.hip, one source per family.
+// A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word.  Host data reaches the slots through the table's staging buffer
+// (kt_stage_set): keys by k_kt_setup, the other fields (salt, XPN state, TLS IV) by strided copies.  A crypt call is one launch of a kernel that runs k_batch3's body,
+// planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.
+//   family   entry point                          kernel
+//   keytab   aesgcm_keytab_crypt_dev              k_kt_batch   packets as five arrays
+//   wire     aesgcm_keytab_frames_crypt_dev       k_kt_wire    frames in wire format
+//   wirex    aesgcm_keytab_frames_crypt_x_dev     k_kt_wirex   ... with a number per frame that is not on the wire (MACsec XPN, ESP ESN)
+//   tls      aesgcm_keytab_records_crypt_dev      k_kt_tls     TLS records with their 64-bit sequence numbers
+//   quic     aesgcm_keytab_quic_crypt_dev         k_kt_quic    QUIC packets, and a second launch, k_kt_quic_hp (header protection, a lane per packet)
+// The calls in wire format fill their kernel parameters by kt_wire_params.
 #include "aesgcm_keytab.h"
 
 #include <stddef.h>
@@ -73,23 +77,52 @@ int aesgcm_keytab_create(aesgcm_keytab **out, int device, size_t key_len, size_t
     return AESGCM_OK;
 }
 
+// What every host-to-slot setter does, under t->mu: `parts` side by side through the table's staging buffer on `st` -- the host copies into the stage, `into_slots` (the
+// expansion kernel, or a strided copy per part) from there into the slots, the stage zeroed behind it whatever into_slots returned (raw key material does not outlive
+// the call), t->stage_done recorded.  The caller has checked its arguments.
+struct KtPart {
+    const uint8_t *src;                // host: n * width bytes; NULL = the field becomes zero (nothing staged)
+    size_t width, field;               // bytes per slot; offset inside KtSlot
+};
+template <size_t N, class F>
+static int kt_stage_set(aesgcm_keytab *t, size_t n, const KtPart (&parts)[N], hipStream_t st, F into_slots) {
+    std::lock_guard<std::mutex> lk(t->mu);
+    HIPCHK(hipSetDevice(t->device));
+    size_t bytes = 0;
+    for (const KtPart &p : parts) if (p.src) bytes += n * p.width;
+    int rc = kt_stage(t, bytes, st);                                            // (behind the previous set's kernel and zeroing)
+    if (rc) return rc;
+    size_t at = 0;
+    for (const KtPart &p : parts) if (p.src) { HIPCHK(hipMemcpyAsync(t->stage + at, p.src, n * p.width, hipMemcpyHostToDevice, st)); at += n * p.width; }
+    rc = into_slots();
+    const hipError_t ez = hipMemsetAsync(t->stage, 0, bytes, st);
+    if (rc) return rc;
+    HIPCHK(ez);
+    HIPCHK(hipEventRecord(t->stage_done, st));
+    return AESGCM_OK;
+}
+
+// the fields that k_kt_setup leaves alone (salt, xpn): each part from the stage into its field of slots first_slot, ... by one 2-D copy (the slots are 384 bytes apart)
+template <size_t N>
+static int kt_set_fields(aesgcm_keytab *t, size_t first_slot, size_t n, const KtPart (&parts)[N], hipStream_t st) {
+    return kt_stage_set(t, n, parts, st, [&]() -> int {
+        size_t at = 0;
+        for (const KtPart &p : parts) {
+            unsigned char *const dst = (unsigned char *)(t->tab + first_slot) + p.field;
+            if (p.src) { HIPCHK(hipMemcpy2DAsync(dst, sizeof(KtSlot), t->stage + at, p.width, p.width, n, hipMemcpyDeviceToDevice, st)); at += n * p.width; }
+            else HIPCHK(hipMemset2DAsync(dst, sizeof(KtSlot), 0, p.width, n, st));
+        }
+        return AESGCM_OK;
+    });
+}
+
 int aesgcm_keytab_set(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *keys, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!keys || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
     hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(t->mu);
-    HIPCHK(hipSetDevice(t->device));
-    const size_t bytes = n * t->key_len;
-    int rc = kt_stage(t, bytes, st);                                            // (behind the previous set's kernel and zeroing)
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(t->stage, keys, bytes, hipMemcpyHostToDevice, st));
-    rc = kt_setup(t, t->stage, nullptr, first_slot, n, st);
-    const hipError_t ez = hipMemsetAsync(t->stage, 0, bytes, st);               // the raw keys do not outlive the expansion
-    if (rc) return rc;
-    HIPCHK(ez);
-    HIPCHK(hipEventRecord(t->stage_done, st));
-    return AESGCM_OK;
+    const KtPart parts[] = {{keys, t->key_len, 0}};
+    return kt_stage_set(t, n, parts, st, [&] { return kt_setup(t, t->stage, nullptr, first_slot, n, st); });
 }
 
 int aesgcm_keytab_set_dev(aesgcm_keytab *t, size_t n, const uint32_t *d_slots, const void *d_keys, void *stream) {
@@ -150,43 +183,22 @@ int aesgcm_wire_fmt_check(const aesgcm_wire_fmt *f) {
     return AESGCM_OK;
 }
 
-// the salts go the way the keys go: through the table's staging buffer on `stream`, from there into the slots (8 bytes each, 384 apart) by one 2-D copy
+// the salts go the way the keys go: through the table's staging buffer on `stream`, from there into the slots (8 bytes each)
 int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!salts || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(t->mu);
-    HIPCHK(hipSetDevice(t->device));
-    const size_t bytes = n * 8;
-    const int rc = kt_stage(t, bytes, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(t->stage, salts, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpy2DAsync((unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, salt), sizeof(KtSlot), t->stage, 8, 8, n, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
-    HIPCHK(hipEventRecord(t->stage_done, st));
-    return AESGCM_OK;
+    const KtPart parts[] = {{salts, 8, offsetof(KtSlot, salt)}};
+    return kt_set_fields(t, first_slot, n, parts, (hipStream_t)stream);
 }
 
-// MACsec XPN's slot state the same way: salts (12 bytes each) and SSCIs (4 each) side by side in the staging buffer, from there into KtSlot::xpn by two 2-D copies
+// MACsec XPN's slot state the same way: salts (12 bytes each) and SSCIs (4 each) side by side in the staging buffer, from there into KtSlot::xpn
 int aesgcm_keytab_set_xpn(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, const uint8_t *sscis, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!salts || !sscis || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(t->mu);
-    HIPCHK(hipSetDevice(t->device));
-    const size_t bytes = n * 16;
-    const int rc = kt_stage(t, bytes, st);
-    if (rc) return rc;
-    unsigned char *const x = (unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, xpn);
-    HIPCHK(hipMemcpyAsync(t->stage, salts, n * 12, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(t->stage + n * 12, sscis, n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(x, sizeof(KtSlot), t->stage, 12, 12, n, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(x + 12, sizeof(KtSlot), t->stage + n * 12, 4, 4, n, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
-    HIPCHK(hipEventRecord(t->stage_done, st));
-    return AESGCM_OK;
+    const KtPart parts[] = {{salts, 12, offsetof(KtSlot, xpn)}, {sscis, 4, offsetof(KtSlot, xpn) + 12}};
+    return kt_set_fields(t, first_slot, n, parts, (hipStream_t)stream);
 }
 
 int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf) {
@@ -199,31 +211,38 @@ int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf) {
     return AESGCM_OK;
 }
 
+// What every call of packets in wire format passes to its kernel the same way (the arguments checked by the caller): packet p = bytes [d_off[p], d_off[p + 1]) of d_in and
+// d_out under slot d_slots[p], its AAD read from d_aad at the same offsets.  The format (w.f) and the per-packet numbers are the caller's.
+static void kt_wire_params(KtWireXParams &xp, const aesgcm_keytab *t, int decrypt, const void *d_in, const void *d_aad, void *d_out, const uint64_t *d_off,
+                           const uint32_t *d_slots, int *d_auth) {
+    memset(&xp, 0, sizeof xp);
+    BatchParams &p = xp.w.k.b;
+    p.in = (const unsigned char *)d_in; p.aad = (const unsigned char *)d_aad; p.out = (unsigned char *)d_out;
+    p.auth = decrypt ? d_auth : nullptr;
+    p.data_off = d_off;
+    p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per packet, in the kernel)
+    xp.w.k.slots = d_slots; xp.w.k.tab = t->tab; xp.w.k.n_slots = (u32)t->n_slots; xp.w.k.status = t->status;
+}
+
 // One launch: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in and d_out, laid out by *fmt (checked by the caller).  Planned as aesgcm_keytab_crypt_dev's
-// offset-array call (the lengths are on the device: shape by count, order by falling frame length class).  ext 0: k_kt_wire; otherwise k_kt_wirex with d_hi.  tls
-// (AESGCM_TLS_13 / AESGCM_TLS_12; ext 0): k_kt_tls with d_seq, the records laid out by *fmt as aesgcm_tls_kernels.hip says.
-static int kt_frames_crypt(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, u32 ext, const uint32_t *d_hi, size_t n_frames, const uint32_t *d_slots,
-                           const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream, u32 tls = 0u, const uint64_t *d_seq = nullptr) {
+// offset-array call (the lengths are on the device: shape by count, order by falling frame length class).  tls (AESGCM_TLS_13 / AESGCM_TLS_12, or 0): k_kt_tls with
+// d_seq, the records laid out by *fmt as aesgcm_tls_kernels.hip says; otherwise ext (or 0): k_kt_wirex with d_hi; neither: k_kt_wire.
+static int kt_frames_crypt(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, u32 ext, const uint32_t *d_hi, u32 tls, const uint64_t *d_seq, size_t n_frames,
+                           const uint32_t *d_slots, const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
     if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
     if (!n_frames) return AESGCM_OK;
     if (!d_slots || !d_in || !d_out || !d_frame_off || (decrypt && !d_auth) || n_frames >= ((size_t)1 << 31)) return AESGCM_EARG;
     KtWireXParams xp;
-    memset(&xp, 0, sizeof xp);
-    KtWireParams &wp = xp.w;
-    BatchParams &p = wp.k.b;
-    p.in = p.aad = (const unsigned char *)d_in; p.out = (unsigned char *)d_out;
-    p.auth = decrypt ? d_auth : nullptr;
-    p.data_off = d_frame_off;
-    p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per frame, in the kernel)
-    wp.k.slots = d_slots; wp.k.tab = t->tab; wp.k.n_slots = (u32)t->n_slots; wp.k.status = t->status;
-    wp.f = *fmt;
+    kt_wire_params(xp, t, decrypt, d_in, d_in, d_out, d_frame_off, d_slots, d_auth);
+    xp.w.f = *fmt;
     if (tls) xp.seq = d_seq; else xp.hi = d_hi;
+    BatchParams &p = xp.w.k.b;
     BatchPlan b;
     const int rc = batch_plan(t->device, decrypt, n_frames, t->key_len, p, stream, b);
     if (rc) return rc;
     if (tls) HIPCHK(klaunch_kt_tls(tls, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
     else if (ext) HIPCHK(klaunch_kt_wirex(ext, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
-    else HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, wp));
+    else HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp.w));
     return batch_done(b, p);
 }
 
@@ -231,7 +250,7 @@ int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_w
                                    const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
     const int frc = aesgcm_wire_fmt_check(fmt);
     if (frc) return frc;
-    return kt_frames_crypt(t, decrypt, fmt, 0u, nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
+    return kt_frames_crypt(t, decrypt, fmt, 0u, nullptr, 0u, nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
 }
 
 // ... with hi[p], the half of frame p's 64-bit number that is not on the wire (MACsec XPN: into the nonce; ESP ESN: into the AAD).  ext 0 is the call above.
@@ -240,7 +259,7 @@ int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, const aesgcm
     const int frc = aesgcm_wire_xfmt_check(xf);
     if (frc) return frc;
     if (xf->ext && !d_hi) return AESGCM_EARG;
-    return kt_frames_crypt(t, decrypt, &xf->f, xf->ext, xf->ext ? d_hi : nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
+    return kt_frames_crypt(t, decrypt, &xf->f, xf->ext, xf->ext ? d_hi : nullptr, 0u, nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
 }
 
 // ---------------------------------------------------------------- TLS records
@@ -254,19 +273,8 @@ int aesgcm_keytab_set_tls_iv(aesgcm_keytab *t, size_t first_slot, size_t n, cons
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!ivs || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(t->mu);
-    HIPCHK(hipSetDevice(t->device));
-    const size_t bytes = n * 12;
-    const int rc = kt_stage(t, bytes, st);
-    if (rc) return rc;
-    unsigned char *const x = (unsigned char *)(t->tab + first_slot) + offsetof(KtSlot, xpn);
-    HIPCHK(hipMemcpyAsync(t->stage, ivs, bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpy2DAsync(x, sizeof(KtSlot), t->stage, 12, 12, n, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemset2DAsync(x + 12, sizeof(KtSlot), 0, 4, n, st));
-    HIPCHK(hipMemsetAsync(t->stage, 0, bytes, st));
-    HIPCHK(hipEventRecord(t->stage_done, st));
-    return AESGCM_OK;
+    const KtPart parts[] = {{ivs, 12, offsetof(KtSlot, xpn)}, {nullptr, 4, offsetof(KtSlot, xpn) + 12}};
+    return kt_set_fields(t, first_slot, n, parts, (hipStream_t)stream);
 }
 
 // One k_kt_tls launch: record p = bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in and d_out.  The kernel runs k_kt_wire's loop; what it takes from a wire format
@@ -277,7 +285,7 @@ int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_
     if (frc) return frc;
     if (!d_seq) return AESGCM_EARG;
     static const aesgcm_wire_fmt f13 = {5, 5, 5, 0, 16, 0}, f12 = {13, 13, 5, 4, 16, 0};          // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
-    return kt_frames_crypt(t, decrypt, fmt->version == AESGCM_TLS_13 ? &f13 : &f12, 0u, nullptr, n_recs, d_slots, d_in, d_rec_off, d_out, d_auth, stream, fmt->version, d_seq);
+    return kt_frames_crypt(t, decrypt, fmt->version == AESGCM_TLS_13 ? &f13 : &f12, 0u, nullptr, fmt->version, d_seq, n_recs, d_slots, d_in, d_rec_off, d_out, d_auth, stream);
 }
 
 // ---------------------------------------------------------------- QUIC packets
@@ -290,14 +298,8 @@ int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, c
     if (!n_pkts) return AESGCM_OK;
     if (!d_slots || !d_hp_slots || !d_pn || !d_pn_off || !d_in || !d_out || !d_pkt_off || (decrypt && (!d_auth || !d_pn_out)) || n_pkts >= ((size_t)1 << 31)) return AESGCM_EARG;
     KtWireXParams xp;
-    memset(&xp, 0, sizeof xp);
+    kt_wire_params(xp, t, decrypt, d_in, decrypt ? d_out : d_in, d_out, d_pkt_off, d_slots, d_auth);      // the AAD: where the header lies unprotected
     BatchParams &p = xp.w.k.b;
-    p.in = (const unsigned char *)d_in; p.out = (unsigned char *)d_out;
-    p.aad = decrypt ? (const unsigned char *)d_out : (const unsigned char *)d_in;     // where the header lies unprotected
-    p.auth = decrypt ? d_auth : nullptr;
-    p.data_off = d_pkt_off;
-    p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
-    xp.w.k.slots = d_slots; xp.w.k.tab = t->tab; xp.w.k.n_slots = (u32)t->n_slots; xp.w.k.status = t->status;
     xp.w.f.tag_len = 16;                                                              // the rest of a wire format is per packet here
     xp.seq = decrypt ? d_pn_out : d_pn;
     xp.pn_off = d_pn_off; xp.hp_slots = d_hp_slots;

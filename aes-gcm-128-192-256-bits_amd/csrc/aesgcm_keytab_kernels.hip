@@ -7,6 +7,7 @@
 //                           slot number and offsets: output untouched, tag zero, auth 0, its index into the table's status word (atomicMin).
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_dispatch.h"
 
 template <int NR>
 __global__ __launch_bounds__(256) void k_kt_setup(const DevTables *__restrict__ tb, const KtSetupParams s) {
@@ -51,35 +52,18 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 #define KT_SETUP_LDS (AESGCM_LDS_AES_OFF + AESGCM_LDS_AES)
-#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
 hipError_t klaunch_kt_attributes() {
-#define SETATTRKT(NR, D) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_batch<NR, D, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(6))); \
-                         ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_batch<NR, D, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(4))); \
-                         ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_batch<NR, D, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(3)))
-    SETATTRKT(10, 0); SETATTRKT(12, 0); SETATTRKT(14, 0); SETATTRKT(10, 1); SETATTRKT(12, 1); SETATTRKT(14, 1);
-#undef SETATTRKT
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_setup<10>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_SETUP_LDS));
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_setup<12>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_SETUP_LDS));
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_setup<14>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_SETUP_LDS));
-    return hipSuccess;
+    const hipError_t e = batch3_each([](auto NR, auto D, auto LG) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_batch<NR(), D(), LG()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG())); });
+    return e != hipSuccess ? e : nr_each([](auto NR) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_setup<NR()>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_SETUP_LDS); });
 }
-#undef ATTRCHK
 
 hipError_t klaunch_kt_setup(int nr, hipStream_t st, const DevTables *tb, const KtSetupParams &s) {
     const unsigned wgs = (s.n + 255u) / 256u;
-    if (nr == 10) hipLaunchKernelGGL(k_kt_setup<10>, dim3(wgs), dim3(256), KT_SETUP_LDS, st, tb, s);
-    else if (nr == 12) hipLaunchKernelGGL(k_kt_setup<12>, dim3(wgs), dim3(256), KT_SETUP_LDS, st, tb, s);
-    else hipLaunchKernelGGL(k_kt_setup<14>, dim3(wgs), dim3(256), KT_SETUP_LDS, st, tb, s);
+    nr_dispatch(nr, [&](auto NR) { hipLaunchKernelGGL(k_kt_setup<NR()>, dim3(wgs), dim3(256), KT_SETUP_LDS, st, tb, s); });
     return hipGetLastError();
 }
 
 hipError_t klaunch_kt_batch(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtParams &p) {
-#define LKT(NR, D, LG) hipLaunchKernelGGL((k_kt_batch<NR, D, LG>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
-#define LKTN(D, LG) do { if (nr == 10) LKT(10, D, LG); else if (nr == 12) LKT(12, D, LG); else LKT(14, D, LG); } while (0)
-    if (lg == 3) { if (dec) LKTN(1, 3); else LKTN(0, 3); }
-    else if (lg == 4) { if (dec) LKTN(1, 4); else LKTN(0, 4); }
-    else { if (dec) LKTN(1, 6); else LKTN(0, 6); }
-#undef LKTN
-#undef LKT
+    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) { hipLaunchKernelGGL((k_kt_batch<NR(), D(), LG()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p); });
     return hipGetLastError();
 }

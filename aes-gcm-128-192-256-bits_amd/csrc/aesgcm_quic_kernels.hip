@@ -14,6 +14,7 @@
 // A translation unit of its own: its ISA census (`make asm_quic`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 decrypt
 __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_kt_quic(const DevTables *__restrict__ tb, const KtWireXParams xp) {
@@ -82,34 +83,23 @@ __global__ __launch_bounds__(256) void k_kt_quic_hp(const DevTables *__restrict_
 // ------------------------------------------------------------------------------------------------ launchers
 #define KT_QUIC_HP_LDS (AESGCM_LDS_AES_OFF + AESGCM_LDS_AES)
 hipError_t klaunch_quic_attributes() {
-#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
-#define SETATTRQ1(NR, D, LG) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic<NR, D, LG>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG)))
-#define SETATTRQ(NR, D) SETATTRQ1(NR, D, 6); SETATTRQ1(NR, D, 4); SETATTRQ1(NR, D, 3); \
-                        ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR, D>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS))
-    SETATTRQ(10, 0); SETATTRQ(12, 0); SETATTRQ(14, 0); SETATTRQ(10, 1); SETATTRQ(12, 1); SETATTRQ(14, 1);
-#undef SETATTRQ
-#undef SETATTRQ1
-#undef ATTRCHK
-    return hipSuccess;
+    const hipError_t e = batch3_each([](auto NR, auto D, auto LG) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic<NR(), D(), LG()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG())); });
+    return e != hipSuccess ? e : nr_each([](auto NR) {
+        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR(), 0>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS);
+        return e0 != hipSuccess ? e0 : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR(), 1>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS);
+    });
 }
 
 hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
-#define LKQ(NR, D, LG) hipLaunchKernelGGL((k_kt_quic<NR, D, LG>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
-#define LKQN(D, LG) do { if (nr == 10) LKQ(10, D, LG); else if (nr == 12) LKQ(12, D, LG); else LKQ(14, D, LG); } while (0)
-    if (lg == 3) { if (dec) LKQN(1, 3); else LKQN(0, 3); }
-    else if (lg == 4) { if (dec) LKQN(1, 4); else LKQN(0, 4); }
-    else { if (dec) LKQN(1, 6); else LKQN(0, 6); }
-#undef LKQN
-#undef LKQ
+    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) { hipLaunchKernelGGL((k_kt_quic<NR(), D(), LG()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p); });
     return hipGetLastError();
 }
 
 hipError_t klaunch_kt_quic_hp(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) {
     const unsigned wgs = (p.n_pkts + 255u) / 256u;
-#define LKH(NR, D) hipLaunchKernelGGL((k_kt_quic_hp<NR, D>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p)
-#define LKHN(D) do { if (nr == 10) LKH(10, D); else if (nr == 12) LKH(12, D); else LKH(14, D); } while (0)
-    if (dec) LKHN(1); else LKHN(0);
-#undef LKHN
-#undef LKH
+    nr_dispatch(nr, [&](auto NR) {
+        if (dec) hipLaunchKernelGGL((k_kt_quic_hp<NR(), 1>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p);
+        else hipLaunchKernelGGL((k_kt_quic_hp<NR(), 0>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p);
+    });
     return hipGetLastError();
 }

@@ -14,6 +14,7 @@
 // A translation unit of its own: its ISA census (`make asm_tls`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG, u32 VER>              // DEC: 0 encrypt, 1 decrypt; VER: AESGCM_TLS_13 or AESGCM_TLS_12
 __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_kt_tls(const DevTables *__restrict__ tb, const KtWireXParams xp) {
@@ -29,27 +30,17 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t klaunch_tls_attributes() {
-#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
-#define SETATTRT1(NR, D, LG, V) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_tls<NR, D, LG, V>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG)))
-#define SETATTRT(NR, D) SETATTRT1(NR, D, 6, AESGCM_TLS_13); SETATTRT1(NR, D, 4, AESGCM_TLS_13); SETATTRT1(NR, D, 3, AESGCM_TLS_13); \
-                        SETATTRT1(NR, D, 6, AESGCM_TLS_12); SETATTRT1(NR, D, 4, AESGCM_TLS_12); SETATTRT1(NR, D, 3, AESGCM_TLS_12)
-    SETATTRT(10, 0); SETATTRT(12, 0); SETATTRT(14, 0); SETATTRT(10, 1); SETATTRT(12, 1); SETATTRT(14, 1);
-#undef SETATTRT
-#undef SETATTRT1
-#undef ATTRCHK
-    return hipSuccess;
+    return batch3_each([](auto NR, auto D, auto LG) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_tls<NR(), D(), LG(), AESGCM_TLS_13>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_tls<NR(), D(), LG(), AESGCM_TLS_12>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+    });
 }
 
 hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
     if (version != AESGCM_TLS_13 && version != AESGCM_TLS_12) return hipErrorInvalidValue;
-#define LKT(NR, D, LG, V) hipLaunchKernelGGL((k_kt_tls<NR, D, LG, V>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
-#define LKTV(NR, D, LG) do { if (version == AESGCM_TLS_13) LKT(NR, D, LG, AESGCM_TLS_13); else LKT(NR, D, LG, AESGCM_TLS_12); } while (0)
-#define LKTN(D, LG) do { if (nr == 10) LKTV(10, D, LG); else if (nr == 12) LKTV(12, D, LG); else LKTV(14, D, LG); } while (0)
-    if (lg == 3) { if (dec) LKTN(1, 3); else LKTN(0, 3); }
-    else if (lg == 4) { if (dec) LKTN(1, 4); else LKTN(0, 4); }
-    else { if (dec) LKTN(1, 6); else LKTN(0, 6); }
-#undef LKTN
-#undef LKTV
-#undef LKT
+    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) {
+        if (version == AESGCM_TLS_13) hipLaunchKernelGGL((k_kt_tls<NR(), D(), LG(), AESGCM_TLS_13>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+        else hipLaunchKernelGGL((k_kt_tls<NR(), D(), LG(), AESGCM_TLS_12>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+    });
     return hipGetLastError();
 }

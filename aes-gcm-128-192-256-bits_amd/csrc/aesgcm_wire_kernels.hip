@@ -8,6 +8,7 @@
 // A translation unit of its own: its ISA census (`make asm_wire`) is read apart from the key tables' (`make asm_keytab`).
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 decrypt
 __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_kt_wire(const DevTables *__restrict__ tb, const KtWireParams wp) {
@@ -22,23 +23,10 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t klaunch_wire_attributes() {
-#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
-#define SETATTRW(NR, D) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wire<NR, D, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(6))); \
-                        ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wire<NR, D, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(4))); \
-                        ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wire<NR, D, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(3)))
-    SETATTRW(10, 0); SETATTRW(12, 0); SETATTRW(14, 0); SETATTRW(10, 1); SETATTRW(12, 1); SETATTRW(14, 1);
-#undef SETATTRW
-#undef ATTRCHK
-    return hipSuccess;
+    return batch3_each([](auto NR, auto D, auto LG) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wire<NR(), D(), LG()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG())); });
 }
 
 hipError_t klaunch_kt_wire(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireParams &p) {
-#define LKW(NR, D, LG) hipLaunchKernelGGL((k_kt_wire<NR, D, LG>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
-#define LKWN(D, LG) do { if (nr == 10) LKW(10, D, LG); else if (nr == 12) LKW(12, D, LG); else LKW(14, D, LG); } while (0)
-    if (lg == 3) { if (dec) LKWN(1, 3); else LKWN(0, 3); }
-    else if (lg == 4) { if (dec) LKWN(1, 4); else LKWN(0, 4); }
-    else { if (dec) LKWN(1, 6); else LKWN(0, 6); }
-#undef LKWN
-#undef LKW
+    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) { hipLaunchKernelGGL((k_kt_wire<NR(), D(), LG()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p); });
     return hipGetLastError();
 }

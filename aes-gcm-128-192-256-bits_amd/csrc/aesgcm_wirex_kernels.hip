@@ -14,6 +14,7 @@
 // A translation unit of its own: its ISA census (`make asm_wirex`) is read apart from k_kt_wire's (`make asm_wire`), whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG, u32 EXT>              // DEC: 0 encrypt, 1 decrypt; EXT: AESGCM_WIREX_XPN or AESGCM_WIREX_ESN
 __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) void k_kt_wirex(const DevTables *__restrict__ tb, const KtWireXParams xp) {
@@ -29,27 +30,17 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t klaunch_wirex_attributes() {
-#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
-#define SETATTRX1(NR, D, LG, X) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR, D, LG, X>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG)))
-#define SETATTRX(NR, D) SETATTRX1(NR, D, 6, AESGCM_WIREX_XPN); SETATTRX1(NR, D, 4, AESGCM_WIREX_XPN); SETATTRX1(NR, D, 3, AESGCM_WIREX_XPN); \
-                        SETATTRX1(NR, D, 6, AESGCM_WIREX_ESN); SETATTRX1(NR, D, 4, AESGCM_WIREX_ESN); SETATTRX1(NR, D, 3, AESGCM_WIREX_ESN)
-    SETATTRX(10, 0); SETATTRX(12, 0); SETATTRX(14, 0); SETATTRX(10, 1); SETATTRX(12, 1); SETATTRX(14, 1);
-#undef SETATTRX
-#undef SETATTRX1
-#undef ATTRCHK
-    return hipSuccess;
+    return batch3_each([](auto NR, auto D, auto LG) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_XPN>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_ESN>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+    });
 }
 
 hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
     if (ext != AESGCM_WIREX_XPN && ext != AESGCM_WIREX_ESN) return hipErrorInvalidValue;
-#define LKX(NR, D, LG, X) hipLaunchKernelGGL((k_kt_wirex<NR, D, LG, X>), dim3(wgs), dim3(BATCH3_LANES(NR)), BATCH3_LDS_BYTES_LG(LG), st, tb, p)
-#define LKXE(NR, D, LG) do { if (ext == AESGCM_WIREX_XPN) LKX(NR, D, LG, AESGCM_WIREX_XPN); else LKX(NR, D, LG, AESGCM_WIREX_ESN); } while (0)
-#define LKXN(D, LG) do { if (nr == 10) LKXE(10, D, LG); else if (nr == 12) LKXE(12, D, LG); else LKXE(14, D, LG); } while (0)
-    if (lg == 3) { if (dec) LKXN(1, 3); else LKXN(0, 3); }
-    else if (lg == 4) { if (dec) LKXN(1, 4); else LKXN(0, 4); }
-    else { if (dec) LKXN(1, 6); else LKXN(0, 6); }
-#undef LKXN
-#undef LKXE
-#undef LKX
+    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) {
+        if (ext == AESGCM_WIREX_XPN) hipLaunchKernelGGL((k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_XPN>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+        else hipLaunchKernelGGL((k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_ESN>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+    });
     return hipGetLastError();
 }

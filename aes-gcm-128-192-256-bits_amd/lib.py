@@ -7,6 +7,7 @@ buffers).  Loading fails loudly when the library is missing; compute calls fail 
 """
 import ctypes
 import os
+import struct
 
 from .build import SO, SO_DEBUG, build
 
@@ -806,6 +807,15 @@ class TlsFormat(ctypes.Structure):
         return "TlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
 
 
+def _per_slot(x, width, what, pad=False):
+    """a setter's host data: one bytes-like of n * width bytes, or a list of n items (pad: shorter ones zero-padded to width) -> (bytes, n)"""
+    items = [bytes(i) for i in x] if isinstance(x, (list, tuple)) else None
+    b = bytes(x) if items is None else b"".join(i.ljust(width, b"\0") if pad else i for i in items)
+    if len(b) % width or (pad and items is not None and any(len(i) > width for i in items)):
+        raise AesGcmError(EARG, what)
+    return b, len(b) // width
+
+
 class KeyTable:
     """aesgcm_keytab: n_slots device-resident slots of one key size; the key schedule, H and its powers are computed on the GPU once per `set`, and a crypt call
     names a slot per packet (include/aesgcm.h "key tables").  Belongs to the library that made it (create it inside a debug_library block to force shapes)."""
@@ -835,10 +845,8 @@ class KeyTable:
 
     def set(self, first_slot, keys, stream=None):
         """aesgcm_keytab_set: host keys (one bytes-like of n * key_len bytes, or a list of keys) into slots first_slot, first_slot + 1, ..."""
-        kb = b"".join(bytes(k) for k in keys) if isinstance(keys, (list, tuple)) else bytes(keys)
-        if len(kb) % self.key_len:
-            raise AesGcmError(EARG, "keys must be a multiple of %d bytes" % self.key_len)
-        _chk(self._lib.aesgcm_keytab_set(self._t, first_slot, len(kb) // self.key_len, kb, stream))
+        kb, n = _per_slot(keys, self.key_len, "keys must be a multiple of %d bytes" % self.key_len)
+        _chk(self._lib.aesgcm_keytab_set(self._t, first_slot, n, kb, stream))
         return self
 
     def set_dev(self, n, d_slots, d_keys, stream=None):
@@ -860,11 +868,8 @@ class KeyTable:
 
     def set_salt(self, first_slot, salts, stream=None):
         """aesgcm_keytab_set_salt: 8 bytes per slot (one bytes-like of n * 8 bytes, or a list; shorter entries are zero-padded) into slots first_slot, ..."""
-        items = [bytes(x) for x in salts] if isinstance(salts, (list, tuple)) else None
-        sb = b"".join(x.ljust(8, b"\0") for x in items) if items is not None else bytes(salts)
-        if len(sb) % 8 or (items is not None and any(len(x) > 8 for x in items)):
-            raise AesGcmError(EARG, "a salt is 8 bytes")
-        _chk(self._lib.aesgcm_keytab_set_salt(self._t, first_slot, len(sb) // 8, sb, stream))
+        sb, n = _per_slot(salts, 8, "a salt is 8 bytes", pad=True)
+        _chk(self._lib.aesgcm_keytab_set_salt(self._t, first_slot, n, sb, stream))
         return self
 
     def frames_crypt_dev(self, decrypt, fmt, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth=None, stream=None):
@@ -873,11 +878,11 @@ class KeyTable:
 
     def set_xpn(self, first_slot, salts, sscis, stream=None):
         """aesgcm_keytab_set_xpn: MACsec XPN's 12-byte salt and 4-byte SSCI per slot (each one bytes-like of n * 12 / n * 4 bytes, or a list) into slots first_slot, ..."""
-        sb = b"".join(bytes(x) for x in salts) if isinstance(salts, (list, tuple)) else bytes(salts)
-        cb = b"".join(bytes(x) for x in sscis) if isinstance(sscis, (list, tuple)) else bytes(sscis)
-        if len(sb) % 12 or len(cb) % 4 or len(sb) // 12 != len(cb) // 4:
-            raise AesGcmError(EARG, "an XPN salt is 12 bytes, an SSCI 4, one of each per slot")
-        _chk(self._lib.aesgcm_keytab_set_xpn(self._t, first_slot, len(sb) // 12, sb, cb, stream))
+        what = "an XPN salt is 12 bytes, an SSCI 4, one of each per slot"
+        (sb, n), (cb, nc) = _per_slot(salts, 12, what), _per_slot(sscis, 4, what)
+        if n != nc:
+            raise AesGcmError(EARG, what)
+        _chk(self._lib.aesgcm_keytab_set_xpn(self._t, first_slot, n, sb, cb, stream))
         return self
 
     def frames_crypt_x_dev(self, decrypt, xfmt, n_frames, d_slots, d_hi, d_in, d_frame_off, d_out, d_auth=None, stream=None):
@@ -888,47 +893,27 @@ class KeyTable:
     def crypt_frames(self, fmt, slots, frames, decrypt=False, hi=None):
         """Host convenience (tests, examples): whole frames (header | payload | ICV; on encrypt the ICV bytes are placeholders) through one call, in place.
         fmt a WireFormatX: through frames_crypt_x_dev with hi (one number per frame).  -> (frames_out, auth); auth is None on encrypt."""
-        import struct
         n = len(slots)
         if len(frames) != n or not n:
             raise AesGcmError(EARG, "slots and frames must be equally long and not empty")
         ext = isinstance(fmt, WireFormatX)
         if (hi is not None and not ext) or (hi is not None and len(hi) != n):
             raise AesGcmError(EARG, "hi goes with a WireFormatX, one number per frame")
-        off = [0]
-        for f in frames:
-            off.append(off[-1] + len(f))
-        blob = b"".join(bytes(f) for f in frames)
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("data", len(blob)), ("off", 8 * (n + 1)), ("auth", 4 * n), ("hi", 4 * n))}
-        try:
-            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
-            if blob:
-                bufs["data"].upload(blob)
-            bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
+
+        def call(b):
+            auth = b["auth"].ptr if decrypt else None
             if ext:
-                if hi is not None:
-                    bufs["hi"].upload(struct.pack("<%dI" % n, *hi))
-                self.frames_crypt_x_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["hi"].ptr if hi is not None else None, bufs["data"].ptr, bufs["off"].ptr,
-                                        bufs["data"].ptr, d_auth=bufs["auth"].ptr if decrypt else None)
+                self.frames_crypt_x_dev(decrypt, fmt, n, b["slots"].ptr, b["hi"].ptr if hi is not None else None, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_auth=auth)
             else:
-                self.frames_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
-                                      d_auth=bufs["auth"].ptr if decrypt else None)
-            _chk(load().aesgcm_dev_sync(self.device))
-            out = bytes(bufs["data"].download(len(blob))) if blob else b""
-            outs = [out[off[p]:off[p + 1]] for p in range(n)]
-            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
-            return outs, auth
-        finally:
-            for b in bufs.values():
-                b.free()
+                self.frames_crypt_dev(decrypt, fmt, n, b["slots"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_auth=auth)
+        outs, got = self._packed_call(frames, {"slots": ("I", slots), "hi": ("I", hi if hi is not None else ())}, {"auth": "i"} if decrypt else {}, call)
+        return outs, got.get("auth")
 
     def set_tls_iv(self, first_slot, ivs, stream=None):
         """aesgcm_keytab_set_tls_iv: a TLS connection direction's 12-byte write IV per slot (one bytes-like of n * 12 bytes, or a list) into slots first_slot, ...;
         it takes the place of the slot's XPN state"""
-        ib = b"".join(bytes(x) for x in ivs) if isinstance(ivs, (list, tuple)) else bytes(ivs)
-        if len(ib) % 12:
-            raise AesGcmError(EARG, "a TLS write IV is 12 bytes")
-        _chk(self._lib.aesgcm_keytab_set_tls_iv(self._t, first_slot, len(ib) // 12, ib, stream))
+        ib, n = _per_slot(ivs, 12, "a TLS write IV is 12 bytes")
+        _chk(self._lib.aesgcm_keytab_set_tls_iv(self._t, first_slot, n, ib, stream))
         return self
 
     def records_crypt_dev(self, decrypt, fmt, n_recs, d_slots, d_seq, d_in, d_rec_off, d_out, d_auth=None, stream=None):
@@ -939,31 +924,14 @@ class KeyTable:
     def crypt_records(self, fmt, slots, seqs, records, decrypt=False):
         """Host convenience (tests, examples), crypt_frames' counterpart: whole TLS records (header | (1.2: explicit nonce |) payload | tag; on encrypt the tag's bytes are
         placeholders) with a sequence number each through one call, in place.  -> (records_out, auth); auth is None on encrypt."""
-        import struct
         n = len(slots)
         if len(records) != n or len(seqs) != n or not n:
             raise AesGcmError(EARG, "slots, seqs and records must be equally long and not empty")
-        off = [0]
-        for r in records:
-            off.append(off[-1] + len(r))
-        blob = b"".join(bytes(r) for r in records)
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("seq", 8 * n), ("data", len(blob)), ("off", 8 * (n + 1)), ("auth", 4 * n))}
-        try:
-            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
-            bufs["seq"].upload(struct.pack("<%dQ" % n, *seqs))
-            if blob:
-                bufs["data"].upload(blob)
-            bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
-            self.records_crypt_dev(decrypt, fmt, n, bufs["slots"].ptr, bufs["seq"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
-                                   d_auth=bufs["auth"].ptr if decrypt else None)
-            _chk(load().aesgcm_dev_sync(self.device))
-            out = bytes(bufs["data"].download(len(blob))) if blob else b""
-            outs = [out[off[p]:off[p + 1]] for p in range(n)]
-            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
-            return outs, auth
-        finally:
-            for b in bufs.values():
-                b.free()
+
+        def call(b):
+            self.records_crypt_dev(decrypt, fmt, n, b["slots"].ptr, b["seq"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_auth=b["auth"].ptr if decrypt else None)
+        outs, got = self._packed_call(records, {"slots": ("I", slots), "seq": ("Q", seqs)}, {"auth": "i"} if decrypt else {}, call)
+        return outs, got.get("auth")
 
     def quic_crypt_dev(self, decrypt, n_pkts, d_slots, d_hp_slots, d_pn, d_pn_off, d_in, d_pkt_off, d_out, d_pn_out=None, d_auth=None, stream=None):
         """aesgcm_keytab_quic_crypt_dev: QUIC packet p = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in / d_out, its packet-number field at byte d_pn_off[p] (uint32), under
@@ -975,38 +943,18 @@ class KeyTable:
         """Host convenience (tests, examples), crypt_records' counterpart: whole QUIC packets (header | payload | tag; on encrypt the header is unprotected with the truncated
         packet number written and the tag's bytes are placeholders) through one call, in place.  pns: the full packet numbers (encrypt) or the expected ones (decrypt).
         -> (packets_out, auth, pns_out); auth and pns_out are None on encrypt."""
-        import struct
         n = len(slots)
         if len(packets) != n or len(hp_slots) != n or len(pns) != n or len(pn_offs) != n or not n:
             raise AesGcmError(EARG, "slots, hp_slots, pns, pn_offs and packets must be equally long and not empty")
-        off = [0]
-        for r in packets:
-            off.append(off[-1] + len(r))
-        blob = b"".join(bytes(r) for r in packets)
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("hp", 4 * n), ("pn", 8 * n), ("pn_off", 4 * n), ("data", len(blob)),
-                                                                        ("off", 8 * (n + 1)), ("auth", 4 * n), ("pn_out", 8 * n))}
-        try:
-            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
-            bufs["hp"].upload(struct.pack("<%dI" % n, *hp_slots))
-            bufs["pn"].upload(struct.pack("<%dQ" % n, *pns))
-            bufs["pn_off"].upload(struct.pack("<%dI" % n, *pn_offs))
-            if blob:
-                bufs["data"].upload(blob)
-            bufs["off"].upload(struct.pack("<%dQ" % (n + 1), *off))
-            if decrypt:
-                bufs["auth"].upload(bytes(4 * n))
-                bufs["pn_out"].upload(bytes(8 * n))
-            self.quic_crypt_dev(decrypt, n, bufs["slots"].ptr, bufs["hp"].ptr, bufs["pn"].ptr, bufs["pn_off"].ptr, bufs["data"].ptr, bufs["off"].ptr, bufs["data"].ptr,
-                                d_pn_out=bufs["pn_out"].ptr if decrypt else None, d_auth=bufs["auth"].ptr if decrypt else None)
-            _chk(load().aesgcm_dev_sync(self.device))
-            out = bytes(bufs["data"].download(len(blob))) if blob else b""
-            outs = [out[off[p]:off[p + 1]] for p in range(n)]
-            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n)))) if decrypt else None
-            pns_out = list(struct.unpack("<%dQ" % n, bytes(bufs["pn_out"].download(8 * n)))) if decrypt else None
-            return outs, auth, pns_out
-        finally:
-            for b in bufs.values():
-                b.free()
+        up = {"slots": ("I", slots), "hp": ("I", hp_slots), "pn": ("Q", pns), "pn_off": ("I", pn_offs)}
+        if decrypt:
+            up.update(auth=bytes(4 * n), pn_out=bytes(8 * n))                      # zero where a refused packet leaves them alone
+
+        def call(b):
+            self.quic_crypt_dev(decrypt, n, b["slots"].ptr, b["hp"].ptr, b["pn"].ptr, b["pn_off"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr,
+                                d_pn_out=b["pn_out"].ptr if decrypt else None, d_auth=b["auth"].ptr if decrypt else None)
+        outs, got = self._packed_call(packets, up, {"auth": "i", "pn_out": "Q"} if decrypt else {}, call)
+        return outs, got.get("auth"), got.get("pn_out")
 
     def status(self):
         """aesgcm_keytab_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""
@@ -1017,42 +965,46 @@ class KeyTable:
     def crypt(self, slots, ivs, aads, datas, decrypt=False, tags=None):
         """Host convenience (tests, examples): packet p = (slots[p], ivs[p], aads[p], datas[p]) through one offset-array call.
         -> (outputs, tags) on encrypt; (outputs, tags, auth) on decrypt, auth[p] = 1 when tags[p] (the expected tags given) matches."""
-        import struct
         n = len(slots)
         if not (len(ivs) == len(aads) == len(datas) == n) or not n:
             raise AesGcmError(EARG, "slots, ivs, aads and datas must be equally long and not empty")
-        doff, aoff = [0], [0]
-        for d in datas:
-            doff.append(doff[-1] + len(d))
+        aoff = [0]
         for a in aads:
             aoff.append(aoff[-1] + len(a))
-        blob = b"".join(bytes(d) for d in datas)
-        ablob = b"".join(bytes(a) for a in aads)
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in (("slots", 4 * n), ("ivs", 12 * n), ("data", len(blob)), ("aad", len(ablob)),
-                                                                          ("doff", 8 * (n + 1)), ("aoff", 8 * (n + 1)), ("tags", 16 * n), ("exp", 16 * n), ("auth", 4 * n))}
+        expect = decrypt and tags is not None
+        up = {"slots": ("I", slots), "ivs": b"".join(_fixed(iv, 12, "iv") for iv in ivs), "aad": b"".join(bytes(a) for a in aads), "aoff": ("Q", aoff)}
+        if expect:
+            up["exp"] = b"".join(_fixed(t, 16, "tag") for t in tags)
+
+        def call(b):
+            self.crypt_dev(decrypt, n, b["slots"].ptr, b["ivs"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, b["tags"].ptr, d_aad=b["aad"].ptr, d_aad_off=b["aoff"].ptr,
+                           d_expect_tags=b["exp"].ptr if expect else None, d_auth=b["auth"].ptr if decrypt else None)
+        outs, got = self._packed_call(datas, up, {"tags": "16s", "auth": "i"} if decrypt else {"tags": "16s"}, call)
+        return (outs, got["tags"], got["auth"]) if decrypt else (outs, got["tags"])
+
+    def _packed_call(self, items, up, down, call):
+        """What the host conveniences share.  `items`, a byte string per packet, joined in the buffer "data" with their n + 1 offsets in "off"; every entry of `up` --
+        name: bytes, or (struct code, values) -- uploaded; every entry of `down` -- name: struct code of the n values that come back -- allocated; then call(bufs) over
+        the DeviceBuffers by name (in place on "data") and a device sync.  -> (items_out, {name: list of n values})"""
+        n = len(items)
+        off = [0]
+        for x in items:
+            off.append(off[-1] + len(x))
+        up = dict(up, data=b"".join(bytes(x) for x in items), off=("Q", off))
+        up = {k: v if isinstance(v, bytes) else struct.pack("<%d%s" % (len(v[1]), v[0]), *v[1]) for k, v in up.items()}
+        size = {k: len(v) for k, v in up.items()}
+        for k, code in down.items():
+            size[k] = max(size.get(k, 0), n * struct.calcsize("<" + code))
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in size.items()}
         try:
-            bufs["slots"].upload(struct.pack("<%dI" % n, *slots))
-            bufs["ivs"].upload(b"".join(_fixed(iv, 12, "iv") for iv in ivs))
-            if blob:
-                bufs["data"].upload(blob)
-            if ablob:
-                bufs["aad"].upload(ablob)
-            bufs["doff"].upload(struct.pack("<%dQ" % (n + 1), *doff))
-            bufs["aoff"].upload(struct.pack("<%dQ" % (n + 1), *aoff))
-            if decrypt and tags is not None:
-                bufs["exp"].upload(b"".join(_fixed(t, 16, "tag") for t in tags))
-            self.crypt_dev(decrypt, n, bufs["slots"].ptr, bufs["ivs"].ptr, bufs["data"].ptr, bufs["doff"].ptr, bufs["data"].ptr, bufs["tags"].ptr,
-                           d_aad=bufs["aad"].ptr, d_aad_off=bufs["aoff"].ptr, d_expect_tags=bufs["exp"].ptr if (decrypt and tags is not None) else None,
-                           d_auth=bufs["auth"].ptr if decrypt else None)
+            for k, v in up.items():
+                if v:
+                    bufs[k].upload(v)
+            call(bufs)
             _chk(load().aesgcm_dev_sync(self.device))
-            out = bytes(bufs["data"].download(len(blob))) if blob else b""
-            tg = bytes(bufs["tags"].download(16 * n))
-            outs = [out[doff[p]:doff[p + 1]] for p in range(n)]
-            tgs = [tg[16 * p:16 * p + 16] for p in range(n)]
-            if not decrypt:
-                return outs, tgs
-            auth = list(struct.unpack("<%di" % n, bytes(bufs["auth"].download(4 * n))))
-            return outs, tgs, auth
+            out = bytes(bufs["data"].download(off[n])) if off[n] else b""
+            got = {k: list(struct.unpack("<" + code * n, bytes(bufs[k].download(n * struct.calcsize("<" + code))))) for k, code in down.items()}
+            return [out[off[p]:off[p + 1]] for p in range(n)], got
         finally:
             for b in bufs.values():
                 b.free()

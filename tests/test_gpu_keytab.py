@@ -6,24 +6,10 @@ import struct
 
 import pytest
 
+from kt_common import _u32, _u64, _up
 from util import golden, splitmix_bytes
 
 pytestmark = pytest.mark.gpu
-
-
-def _up(hip, data):
-    b = hip.DeviceBuffer(max(len(data), 16))
-    if data:
-        b.upload(data)
-    return b
-
-
-def _u32(v):
-    return struct.pack("<%dI" % len(v), *v)
-
-
-def _u64(v):
-    return struct.pack("<%dQ" % len(v), *v)
 
 
 def _var_call(hip, kt, decrypt, slots, ivs, aad_blob, aoff, blob, doff, out_fill=None, expect=None, inplace=False, sync=True):

@@ -10,30 +10,14 @@ import struct
 import pytest
 
 import quic_fixture as Q
+from kt_common import CANARY, TRAIL, _layout, _u32, _u64, _up
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC5
-TRAIL = 37
 SPECIAL = (0, 1, 3, 15, 16, 17, 31, 32, 33, 255, 1200, 1452)
 PNS = (0, 2 ** 32 - 1, 2 ** 32, 2 ** 62 - 1)
 PN_SENTINEL = 0x7777777777777777
-
-
-def _up(hip, data):
-    b = hip.DeviceBuffer(max(len(data), 16))
-    if data:
-        b.upload(data)
-    return b
-
-
-def _u32(v):
-    return struct.pack("<%dI" % len(v), *v)
-
-
-def _u64(v):
-    return struct.pack("<%dQ" % len(v), *v)
 
 
 class Table:
@@ -99,13 +83,6 @@ class Pop:
     def expected_pns(self, rng):
         """an expected number per packet from which A.3 decodes the packet's own: at most min(half a window - 1, 100) below it"""
         return [max(0, pn - rng.randrange(0, min((1 << (8 * pl - 1)) - 1, 100) + 1)) for pn, pl in zip(self.pns, self.pn_lens)]
-
-
-def _layout(pkts, lead, trail=TRAIL):
-    off = [lead]
-    for r in pkts:
-        off.append(off[-1] + len(r))
-    return off, bytes([CANARY]) * lead + b"".join(pkts) + bytes([CANARY]) * trail
 
 
 def _run(hip, kt, decrypt, slots, hps, pns, pn_offs, off, buf, inplace, out_fill=CANARY, alias_pn=False, stream=None, sync=True):

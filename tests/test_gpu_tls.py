@@ -11,34 +11,13 @@ import struct
 import pytest
 
 import tls_fixture as T
+from kt_common import CANARY, _collect, _layout, _u32, _u64, _up, evp  # noqa: F401
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC5
 SPECIAL = (16385, 0, 17, 1, 15, 16, 31, 32, 33, 255, 1400)
 SEQS = (0, 2 ** 32 - 1, 2 ** 32, 2 ** 64 - 1)
-
-
-def _up(hip, data):
-    b = hip.DeviceBuffer(max(len(data), 16))
-    if data:
-        b.upload(data)
-    return b
-
-
-def _u32(v):
-    return struct.pack("<%dI" % len(v), *v)
-
-
-def _u64(v):
-    return struct.pack("<%dQ" % len(v), *v)
-
-
-@pytest.fixture(scope="module")
-def evp():
-    from oracle import cpu_baseline
-    return cpu_baseline.evp_batch_lib()
 
 
 def _fmt(hip, ver):
@@ -100,13 +79,6 @@ def _make_seqs(rng, n):
     return seqs
 
 
-def _layout(recs, lead, trail=37):
-    off = [lead]
-    for r in recs:
-        off.append(off[-1] + len(r))
-    return off, bytes([CANARY]) * lead + b"".join(recs) + bytes([CANARY]) * trail
-
-
 def _run(hip, kt, decrypt, ver, slots, seqs, off, buf, inplace, out_fill=CANARY, sync=True):
     n = len(slots)
     d = {"slots": _up(hip, _u32(slots)), "in": _up(hip, buf), "off": _up(hip, _u64(off)), "seq": _up(hip, _u64(seqs))}
@@ -115,13 +87,6 @@ def _run(hip, kt, decrypt, ver, slots, seqs, off, buf, inplace, out_fill=CANARY,
     kt.records_crypt_dev(decrypt, _fmt(hip, ver), n, d["slots"].ptr, d["seq"].ptr, d["in"].ptr, d["off"].ptr, d["out"].ptr, d_auth=d["auth"].ptr if decrypt else None)
     d["nbytes"], d["n"] = len(buf), n
     return _collect(hip, d) if sync else d
-
-
-def _collect(hip, d):
-    hip.dev_sync()
-    out = bytes(d["out"].download(d["nbytes"]))
-    auth = list(struct.unpack("<%di" % d["n"], bytes(d["auth"].download(4 * d["n"])))) if d["auth"] is not None else None
-    return out, auth, d
 
 
 def _table(hip, key_len, n_slots, seed):

@@ -4,36 +4,13 @@ slot's salt and header bytes.  The published MACsec vectors as wire frames in ev
 comparison against the library itself, labelled); containment, tampering and aesgcm_wipe_failed_dev, refusals, the salt's life cycle and stream ordering."""
 import ctypes
 import random
-import struct
 
 import pytest
 
+from kt_common import CANARY, _collect, _layout, _u32, _u64, _up, evp  # noqa: F401
 from util import golden, splitmix_bytes
 
 pytestmark = pytest.mark.gpu
-
-CANARY = 0xC5
-
-
-def _up(hip, data):
-    b = hip.DeviceBuffer(max(len(data), 16))
-    if data:
-        b.upload(data)
-    return b
-
-
-def _u32(v):
-    return struct.pack("<%dI" % len(v), *v)
-
-
-def _u64(v):
-    return struct.pack("<%dQ" % len(v), *v)
-
-
-@pytest.fixture(scope="module")
-def evp():
-    from oracle import cpu_baseline
-    return cpu_baseline.evp_batch_lib()
 
 
 def _fields(fmt):
@@ -94,13 +71,6 @@ def _make_frames(rng, fmt, n, seed, max_payload=1514, aligned=False):
     return frames
 
 
-def _layout(frames, lead, trail=37):
-    off = [lead]
-    for f in frames:
-        off.append(off[-1] + len(f))
-    return off, bytes([CANARY]) * lead + b"".join(frames) + bytes([CANARY]) * trail
-
-
 def _run(hip, kt, decrypt, fmt, slots, off, buf, inplace, out_fill=CANARY, sync=True):
     n = len(slots)
     d = {"slots": _up(hip, _u32(slots)), "in": _up(hip, buf), "off": _up(hip, _u64(off))}
@@ -109,13 +79,6 @@ def _run(hip, kt, decrypt, fmt, slots, off, buf, inplace, out_fill=CANARY, sync=
     kt.frames_crypt_dev(decrypt, fmt, n, d["slots"].ptr, d["in"].ptr, d["off"].ptr, d["out"].ptr, d_auth=d["auth"].ptr if decrypt else None)
     d["nbytes"], d["n"] = len(buf), n
     return _collect(hip, d) if sync else d
-
-
-def _collect(hip, d):
-    hip.dev_sync()
-    out = bytes(d["out"].download(d["nbytes"]))
-    auth = list(struct.unpack("<%di" % d["n"], bytes(d["auth"].download(4 * d["n"])))) if d["auth"] is not None else None
-    return out, auth, d
 
 
 def _table(hip, key_len, n_slots, seed):

@@ -10,36 +10,14 @@ import struct
 
 import pytest
 
+from kt_common import CANARY, _collect, _layout, _u32, _u64, _up, evp  # noqa: F401
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xC5
-
-
-def _up(hip, data):
-    b = hip.DeviceBuffer(max(len(data), 16))
-    if data:
-        b.upload(data)
-    return b
-
-
-def _u32(v):
-    return struct.pack("<%dI" % len(v), *v)
-
-
-def _u64(v):
-    return struct.pack("<%dQ" % len(v), *v)
-
 
 def _xor(a, b):
     return bytes(x ^ y for x, y in zip(a, b))
-
-
-@pytest.fixture(scope="module")
-def evp():
-    from oracle import cpu_baseline
-    return cpu_baseline.evp_batch_lib()
 
 
 class Sa:
@@ -127,13 +105,6 @@ def _make_his(rng, n):
     return his
 
 
-def _layout(frames, lead, trail=37):
-    off = [lead]
-    for f in frames:
-        off.append(off[-1] + len(f))
-    return off, bytes([CANARY]) * lead + b"".join(frames) + bytes([CANARY]) * trail
-
-
 def _run(hip, kt, decrypt, xf, slots, his, off, buf, inplace, out_fill=CANARY, sync=True):
     n = len(slots)
     d = {"slots": _up(hip, _u32(slots)), "in": _up(hip, buf), "off": _up(hip, _u64(off)), "hi": _up(hip, _u32(his)) if his is not None else None}
@@ -143,13 +114,6 @@ def _run(hip, kt, decrypt, xf, slots, his, off, buf, inplace, out_fill=CANARY, s
                           d_auth=d["auth"].ptr if decrypt else None)
     d["nbytes"], d["n"] = len(buf), n
     return _collect(hip, d) if sync else d
-
-
-def _collect(hip, d):
-    hip.dev_sync()
-    out = bytes(d["out"].download(d["nbytes"]))
-    auth = list(struct.unpack("<%di" % d["n"], bytes(d["auth"].download(4 * d["n"])))) if d["auth"] is not None else None
-    return out, auth, d
 
 
 def _table(hip, key_len, n_slots, seed):

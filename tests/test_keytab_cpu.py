@@ -2,26 +2,18 @@
 tools/isa_census.py -- 18 k_kt_batch instances (3 key sizes x encrypt / decrypt x 8, 16, 64 lanes per packet), none with scratch, none above the 128 registers
 of their 1024-lane workgroups -- and checks that the entry points refuse to run (no CPU fallback) where there is no device."""
 import os
-import subprocess
-import sys
 
 import pytest
 
 import aesgcm_amd  # noqa: F401
 from aesgcm_amd import lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CSRC = os.path.join(ROOT, "aes-gcm-128-192-256-bits_amd", "csrc")
+from kt_common import asm_census, assert_in_budget
 
 
 @pytest.fixture(scope="module")
 def census():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    subprocess.run(["make", "-C", CSRC, "-s", "asm_keytab"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    import isa_census
-    return isa_census.census(os.path.join(CSRC, "aesgcm_keytab.gfx950.s"))
+    return asm_census("keytab")
 
 
 def test_keytab_kernel_set(census):
@@ -35,13 +27,7 @@ def test_keytab_kernel_set(census):
 
 
 def test_keytab_kernels_scratch_free_and_in_budget(census):
-    for name, k in census.items():
-        assert k["scratch"] == 0, (name, k["scratch"])
-        assert k["vgpr"] <= 128, (name, k["vgpr"])
-        if name.startswith("k_kt_batch<"):
-            depths = [d for d, ops in k["depth"].items() if ops.get("ds_read", 0) >= 16]
-            assert depths, name
-            assert all(k["depth"][d].get("scratch", 0) == 0 for d in depths), (name, k["depth"])
+    assert_in_budget(census, body="k_kt_batch<")
 
 
 def test_keytab_symbols_in_the_binding():

@@ -5,18 +5,17 @@ A.3 (packet-number decoding, at wrap-around and beside 2^62); the gfx950 assembl
 the 18 k_kt_quic and 6 k_kt_quic_hp instances, none with scratch, none above 128 registers."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import pytest
 
 import aesgcm_amd  # noqa: F401
 from aesgcm_amd import lib
 
+from kt_common import asm_census, assert_in_budget
+
 import quic_fixture as Q
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "aes-gcm-128-192-256-bits_amd", "csrc")
 
 DCID = bytes.fromhex("8394c8f03e515708")
@@ -123,11 +122,7 @@ def test_decode_pn():
 # ---------------------------------------------------------------- the kernels' assembly
 @pytest.fixture(scope="module")
 def census():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    subprocess.run(["make", "-C", CSRC, "-s", "asm_quic"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    import isa_census
-    return isa_census.census(os.path.join(CSRC, "aesgcm_quic.gfx950.s"))
+    return asm_census("quic")
 
 
 def test_quic_kernel_set(census):
@@ -138,13 +133,7 @@ def test_quic_kernel_set(census):
 
 
 def test_quic_kernels_scratch_free_and_in_budget(census):
-    for name, k in census.items():
-        assert k["scratch"] == 0, (name, k["scratch"])
-        assert k["vgpr"] <= 128, (name, k["vgpr"])
-        if name.startswith("k_kt_quic<"):
-            depths = [d for d, ops in k["depth"].items() if ops.get("ds_read", 0) >= 16]       # the block loop: where the AES rounds read their tables
-            assert depths, name
-            assert all(k["depth"][d].get("scratch", 0) == 0 for d in depths), (name, k["depth"])
+    assert_in_budget(census, body="k_kt_quic<")
 
 
 def test_quic_source_is_a_unit_of_its_own():

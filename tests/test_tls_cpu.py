@@ -6,19 +6,18 @@ k_kt_tls instances (3 key sizes x encrypt / decrypt x 8, 16, 64 lanes per record
 (that pins derivation and fixture; what the GPU makes of them is tests/test_gpu_tls.py's business)."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import pytest
 
 import aesgcm_amd  # noqa: F401
 from aesgcm_amd import lib
 
+from kt_common import asm_census, assert_in_budget
+
 import tls_fixture as T
 from util import GOLDEN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "aes-gcm-128-192-256-bits_amd", "csrc")
 
 
@@ -59,11 +58,7 @@ def test_refused_before_any_table_or_device():
 
 @pytest.fixture(scope="module")
 def census():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    subprocess.run(["make", "-C", CSRC, "-s", "asm_tls"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    import isa_census
-    return isa_census.census(os.path.join(CSRC, "aesgcm_tls.gfx950.s"))
+    return asm_census("tls")
 
 
 def test_tls_kernel_set(census):
@@ -73,12 +68,7 @@ def test_tls_kernel_set(census):
 
 
 def test_tls_kernels_scratch_free_and_in_budget(census):
-    for name, k in census.items():
-        assert k["scratch"] == 0, (name, k["scratch"])
-        assert k["vgpr"] <= 128, (name, k["vgpr"])
-        depths = [d for d, ops in k["depth"].items() if ops.get("ds_read", 0) >= 16]           # the block loop: where the AES rounds read their tables
-        assert depths, name
-        assert all(k["depth"][d].get("scratch", 0) == 0 for d in depths), (name, k["depth"])
+    assert_in_budget(census)
 
 
 def test_tls_source_is_a_unit_of_its_own():

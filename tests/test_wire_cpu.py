@@ -3,18 +3,13 @@ needs no device -- accepts every documented format and refuses every malformed o
 with tools/isa_census.py) holds exactly the 18 k_kt_wire instances (3 key sizes x encrypt / decrypt x 8, 16, 64 lanes per frame), none with scratch, none above the
 128 registers of their 1024-lane workgroups."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import pytest
 
 import aesgcm_amd  # noqa: F401
 from aesgcm_amd import lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-CSRC = os.path.join(ROOT, "aes-gcm-128-192-256-bits_amd", "csrc")
+from kt_common import asm_census, assert_in_budget
 
 
 def test_wire_symbols_in_the_binding():
@@ -78,11 +73,7 @@ def test_null_format_is_refused():
 
 @pytest.fixture(scope="module")
 def census():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    subprocess.run(["make", "-C", CSRC, "-s", "asm_wire"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    import isa_census
-    return isa_census.census(os.path.join(CSRC, "aesgcm_wire.gfx950.s"))
+    return asm_census("wire")
 
 
 def test_wire_kernel_set(census):
@@ -91,9 +82,4 @@ def test_wire_kernel_set(census):
 
 
 def test_wire_kernels_scratch_free_and_in_budget(census):
-    for name, k in census.items():
-        assert k["scratch"] == 0, (name, k["scratch"])
-        assert k["vgpr"] <= 128, (name, k["vgpr"])
-        depths = [d for d, ops in k["depth"].items() if ops.get("ds_read", 0) >= 16]
-        assert depths, name
-        assert all(k["depth"][d].get("scratch", 0) == 0 for d in depths), (name, k["depth"])
+    assert_in_budget(census)

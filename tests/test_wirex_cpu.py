@@ -5,16 +5,15 @@ kernels (`make -C csrc asm_wirex`, read with tools/isa_census.py) holds exactly 
 frame x XPN / ESN: the mode is a template argument), none with scratch, none above the 128 registers of their 1024-lane workgroups."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import pytest
 
 import aesgcm_amd  # noqa: F401
 from aesgcm_amd import lib
 
+from kt_common import asm_census, assert_in_budget
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "aes-gcm-128-192-256-bits_amd", "csrc")
 
 
@@ -100,11 +99,7 @@ def test_refused_before_any_table_or_device():
 
 @pytest.fixture(scope="module")
 def census():
-    if not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc")
-    subprocess.run(["make", "-C", CSRC, "-s", "asm_wirex"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    import isa_census
-    return isa_census.census(os.path.join(CSRC, "aesgcm_wirex.gfx950.s"))
+    return asm_census("wirex")
 
 
 def test_wirex_kernel_set(census):
@@ -114,12 +109,7 @@ def test_wirex_kernel_set(census):
 
 
 def test_wirex_kernels_scratch_free_and_in_budget(census):
-    for name, k in census.items():
-        assert k["scratch"] == 0, (name, k["scratch"])
-        assert k["vgpr"] <= 128, (name, k["vgpr"])
-        depths = [d for d, ops in k["depth"].items() if ops.get("ds_read", 0) >= 16]
-        assert depths, name
-        assert all(k["depth"][d].get("scratch", 0) == 0 for d in depths), (name, k["depth"])
+    assert_in_budget(census)
 
 
 def test_wirex_source_is_a_unit_of_its_own():
