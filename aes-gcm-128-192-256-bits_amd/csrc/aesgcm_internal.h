@@ -1,7 +1,7 @@
 // aesgcm_internal.h -- what the three translation units of libaesgcm_hip.so share (round 5: the library was one 2 900-line file until then).
 //
-//   aesgcm_kernels.hip   the kernels and, at its end, the LAUNCHERS: one plain function per kernel family (klaunch_*) that picks the template instance and launches
-//                        it.  Nothing outside that file names a kernel, so the other two units hold no device code at all -- the host side builds and runs against
+//   aesgcm_kernels.hip   the kernels and, at its end, the LAUNCHERS: one plain function per kernel family (klaunch_*) that picks the template instance by the rules of
+//                        aesgcm_dispatch.h (which a host compiler alone can check) and launches it.  Nothing outside that file names a kernel, so the other two units hold no device code at all -- the host side builds and runs against
 //                        a fake HIP runtime on a machine without a GPU (tests/fake_hip: which device is current at every allocation, stream, event and launch).
 //   aesgcm_host.hip      the host runtime: contexts and per-device state, the launch planners (which launches a message takes), the shape rules of the packet
 //                        paths, the scratch of the row path, the pipelined host-buffer path.

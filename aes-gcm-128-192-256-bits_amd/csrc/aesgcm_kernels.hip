@@ -136,13 +136,58 @@ __device__ __forceinline__ u32 next_chunk(u32 *counter, unsigned char *smem, u32
 // (lane body: main_chunk_lane()).  No barrier after the staging one, so the age-ordered issue arbitration
 // of the CU (older waves first) only changes WHO does the work, never how long the kernel's tail is.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ G128 wave_xor_fold(G128 z) {
+// XOR of a value over the lanes of the wave (all lanes get the sum)
+__device__ __forceinline__ G128 wave_xor(G128 z) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         z.w[0] ^= __shfl_xor(z.w[0], off); z.w[1] ^= __shfl_xor(z.w[1], off);
         z.w[2] ^= __shfl_xor(z.w[2], off); z.w[3] ^= __shfl_xor(z.w[3], off);
     }
     return z;
+}
+// Timing mode (p.trace: four words per workgroup).  Word 0: the workgroup's start; word 1: its last wave's end; word 2: where it ran (XCC_ID, HW_ID), and from bit 40 two
+// 12-bit stamps in 10 ns units; word 3: the work done (count) and, from bit 32, the waves' cycles >> 10.
+__device__ __forceinline__ void trace_begin(u64 *trace, u32 tid) {
+    if (trace && tid == 0) {
+        u64 *tr = trace + 4 * (u64)blockIdx.x;
+        tr[0] = wall_clock64();
+        tr[2] = (u64)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((u64)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 32);
+    }
+}
+__device__ __forceinline__ void trace_staged(u64 *trace, u32 tid) {            // when the tables were staged, 10 ns units behind the workgroup's start: bits 40 .. 51 of word 2
+    if (trace && tid == 0) {
+        unsigned long long *tr = reinterpret_cast<unsigned long long *>(trace + 4 * (u64)blockIdx.x);
+        const u64 dt = wall_clock64() - tr[0];
+        atomicOr(tr + 2, (unsigned long long)(dt > 0xFFFu ? 0xFFFu : dt) << 40);
+    }
+}
+__device__ __forceinline__ void trace_end(u64 *trace, u32 lane, u64 cyc0, u64 count) {
+    if (trace && lane == 0) {
+        u64 *tr = trace + 4 * (u64)blockIdx.x;
+        atomicMax((unsigned long long *)&tr[1], (unsigned long long)wall_clock64());
+        atomicAdd((unsigned long long *)&tr[3], (unsigned long long)count | ((unsigned long long)((clock64() - cyc0) >> 10) << 32));
+    }
+}
+__device__ __forceinline__ void trace_closed(u64 *trace) {                     // how long the closing took behind the workgroup's last row, 10 ns units: bits 52 .. 63 of word 2 (one lane calls this)
+    if (trace) {
+        unsigned long long *tr = reinterpret_cast<unsigned long long *>(trace + 4 * (u64)blockIdx.x);
+        const u64 rows_end = __hip_atomic_load(tr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const u64 dt = wall_clock64() - rows_end;
+        atomicOr(tr + 2, (unsigned long long)(dt > 0xFFFu ? 0xFFFu : dt) << 52);
+    }
+}
+// round-1 constants depend on key and IV only (the lane merely picks which table replica it reads), so they are wave-uniform: into scalar registers
+__device__ __forceinline__ CtrConsts wave_uniform(CtrConsts cc) {
+    cc.c0 = __builtin_amdgcn_readfirstlane(cc.c0); cc.c1 = __builtin_amdgcn_readfirstlane(cc.c1);
+    cc.c2 = __builtin_amdgcn_readfirstlane(cc.c2); cc.c3 = __builtin_amdgcn_readfirstlane(cc.c3);
+    return cc;
+}
+// E_K(IV || 1) for the tag (gcm_ghash.vhd:158-169)
+template <int NR>
+__device__ __forceinline__ uint4 ek_j0(const CtrConsts &cc, const u32 *rk, const unsigned char *smem, u32 lane) {
+    u32 s0, s1, s2, s3;
+    ctr_rounds_lds<NR>(bswap32(1u), cc, s0, s1, s2, s3, rk, smem, (lane & 31u) << 2);
+    return make_uint4(s0, s1, s2, s3);
 }
 // result -> pinned host slot, then (behind a system-scope fence) the generation number the host is polling for
 __device__ __forceinline__ void publish_host(uint4 *slot, uint4 v, u64 gen) {
@@ -155,20 +200,12 @@ __global__ __launch_bounds__(AESGCM_MAIN_WG, AESGCM_WAVES_PER_SIMD) void k_main(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool GH = (MODE == MODE_ENC || MODE == MODE_DEC);
     const u32 tid = threadIdx.x, lane = tid & 63u;
-    if (p.trace && tid == 0) {
-        u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-        tr[0] = wall_clock64();
-        tr[2] = (u64)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((u64)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 32);
-    }
+    trace_begin(p.trace, tid);
     const u64 cyc0 = p.trace ? clock64() : 0;
     main_fill_lds(smem, km, tb, tid, GH);
     if (tid == 0) *reinterpret_cast<u32 *>(smem + AESGCM_LDS_DRY_OFF) = 0;                      // dry-queue mask of the workgroup (next_chunk)
     __syncthreads();
-    // round-1 constants depend on key and IV only (the lane merely picks which table replica it reads), so they
-    // are wave-uniform: keep them in scalar registers, the vector file is full at 8 waves per SIMD
-    CtrConsts cc = main_lane_consts<MODE>(km, p, smem, lane);
-    cc.c0 = __builtin_amdgcn_readfirstlane(cc.c0); cc.c1 = __builtin_amdgcn_readfirstlane(cc.c1);
-    cc.c2 = __builtin_amdgcn_readfirstlane(cc.c2); cc.c3 = __builtin_amdgcn_readfirstlane(cc.c3);
+    const CtrConsts cc = wave_uniform(main_lane_consts<MODE>(km, p, smem, lane));                  // in scalar registers: the vector file is full at 8 waves per SIMD
     u32 done = 0;
     // bounded on purpose: no wave can own more than C chunks (plus one dry fetch per queue), so a dispenser problem can
     // never turn into a hang
@@ -185,9 +222,8 @@ __global__ __launch_bounds__(AESGCM_MAIN_WG, AESGCM_WAVES_PER_SIMD) void k_main(
             if (wave_id >= p.C) {
                 // a spare wave (the launch has at least C + 1 of them) computes E_K(IV || 1) off the critical path of chunk 0
                 if (GH && wave_id == p.C && p.ej0 && !p.tail) {
-                    u32 s0, s1, s2, s3;
-                    ctr_rounds_lds<NR>(bswap32(1u), cc, s0, s1, s2, s3, km->rk, smem, (lane & 31u) << 2);
-                    if (lane == 0) *p.ej0 = make_uint4(s0, s1, s2, s3);
+                    const uint4 ej0 = ek_j0<NR>(cc, km->rk, smem, lane);
+                    if (lane == 0) *p.ej0 = ej0;
                 }
                 break;
             }
@@ -199,28 +235,23 @@ __global__ __launch_bounds__(AESGCM_MAIN_WG, AESGCM_WAVES_PER_SIMD) void k_main(
         const uint4 acc = main_chunk_lane<NR, MODE>(km, p, smem, cc, c, lane);
         if (GH) p.parts[(size_t)c * 64 + lane] = acc;          // the chunk's item: 64 raw lane accumulators (k_fold / k_combine take over)
         if (GH && c == 0 && (p.ej0 || p.tail) && (p.nq != 0 || p.tail)) {   // E_K(IV || 1) for the tag (gcm_ghash.vhd:158-169), once per launch (static launches: a spare wave does it)
-            u32 s0, s1, s2, s3;
-            ctr_rounds_lds<NR>(bswap32(1u), cc, s0, s1, s2, s3, km->rk, smem, (lane & 31u) << 2);
-            if (lane == 0 && p.ej0) *p.ej0 = make_uint4(s0, s1, s2, s3);
+            const uint4 ej0 = ek_j0<NR>(cc, km->rk, smem, lane);
+            if (lane == 0 && p.ej0) *p.ej0 = ej0;
             if (p.tail) {
                 // single-chunk message: this wave holds the whole polynomial (lane L: B_L); finish the tag here instead of
                 // launching k_combine: tag = sum_L B_L*H^(65-L) ^ L*H ^ E_K(IV || 1), every term one table multiply deep
                 G128 term = tag_lane_term(km, acc, lane);
                 if (lane == 0) {
                     const G128 lt = tag_len_term(km, p.aad_len, p.len);
-                    term.w[0] ^= lt.w[0] ^ bswap32(s0); term.w[1] ^= lt.w[1] ^ bswap32(s1); term.w[2] ^= lt.w[2] ^ bswap32(s2); term.w[3] ^= lt.w[3] ^ bswap32(s3);
+                    term.w[0] ^= lt.w[0] ^ bswap32(ej0.x); term.w[1] ^= lt.w[1] ^ bswap32(ej0.y); term.w[2] ^= lt.w[2] ^ bswap32(ej0.z); term.w[3] ^= lt.w[3] ^ bswap32(ej0.w);
                 }
-                const G128 t = wave_xor_fold(term);
+                const G128 t = wave_xor(term);
                 if (lane == 0) { *p.tag_out = be_to_mo(t); if (p.tag_host) publish_host(p.tag_host, be_to_mo(t), p.gen); }
             }
         }
         ++done;
     }
-    if (p.trace && lane == 0) {
-        u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-        atomicMax((unsigned long long *)&tr[1], (unsigned long long)wall_clock64());
-        atomicAdd((unsigned long long *)&tr[3], (unsigned long long)done | ((unsigned long long)((clock64() - cyc0) >> 10) << 32));
-    }
+    trace_end(p.trace, lane, cyc0, done);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -245,15 +276,6 @@ __device__ __forceinline__ void publish_host_lean(uint4 *slot, uint4 v, u64 gen)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_store(q + 2, (unsigned long long)gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// XOR of a value over the lanes of the wave (all lanes get the sum)
-__device__ __forceinline__ G128 wave_xor(G128 z) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        z.w[0] ^= __shfl_xor(z.w[0], off); z.w[1] ^= __shfl_xor(z.w[1], off);
-        z.w[2] ^= __shfl_xor(z.w[2], off); z.w[3] ^= __shfl_xor(z.w[3], off);
-    }
-    return z;
-}
 // One workgroup's 16 bytes of a tag into the accumulator slots, and the tag out of them when this was the launch's last arrival (one lane calls this).
 // Memory-side atomics only: the XORs return before the arrival is counted (the increment depends on their results), so the workgroup that counts the
 // last arrival finds every contribution in the slots; it zeroes slots and counter for the next launch.
@@ -272,6 +294,25 @@ __device__ __forceinline__ void acc_arrive(unsigned long long *acc, u32 g, G128 
     G128 t; t.w[0] = (u32)(hi >> 32); t.w[1] = (u32)hi; t.w[2] = (u32)(lo >> 32); t.w[3] = (u32)lo;
     *tag_out = be_to_mo(t);
     if (tag_host) publish_host_lean(tag_host, be_to_mo(t), gen);
+}
+// two pieces the closings of the full and the half shape share, each with its own place in LDS
+// z times the weight wc, through a two-table Shoup form at smem + wtab (one wave calls this)
+__device__ __forceinline__ G128 cyc_weigh(G128 z, uint4 wc, unsigned char *smem, u32 wtab, u32 lane) {
+    if (lane < 32) *reinterpret_cast<uint4 *>(smem + wtab + 16u * lane) = shoup2_entry(mo_to_be(wc), lane);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return shoup2_gmul_lds(z, reinterpret_cast<const uint4 *>(smem + wtab));
+}
+// the sum of the two terms that occur once: the length block times H (tag_len_term with the batched multiply: no registers to spare here) and E_K(J0), parked at smem + park + 1024 (lane 0 calls this)
+__device__ __forceinline__ G128 cyc_len_ej0_term(const KeyMaterial *__restrict__ km, const BodyParams &p, const unsigned char *smem, u32 park) {
+    const uint4 ej0 = *reinterpret_cast<const uint4 *>(smem + park + 1024u);
+    G128 L; const u64 la = p.aad_len * 8, lc = p.ct_len * 8;
+    L.w[0] = (u32)(la >> 32); L.w[1] = (u32)la; L.w[2] = (u32)(lc >> 32); L.w[3] = (u32)lc;
+    L = shoup2_gmul_lds(L, km->ltab[1]);
+    const G128 e = mo_to_be(ej0);
+    L.w[0] ^= e.w[0]; L.w[1] ^= e.w[1]; L.w[2] ^= e.w[2]; L.w[3] ^= e.w[3];
+    return L;
 }
 // the fused closing of a cyclic launch (lane pieces and the algebra: aesgcm_dev.h, "Fused closing"); acc = the wave's item; wave 0 of workgroup 0 has left its
 // partial last row and E_K(IV || 1) at CYC_LDS_PARK
@@ -311,46 +352,27 @@ __device__ __forceinline__ void cyc_close(const KeyMaterial *__restrict__ km, co
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 #endif
     G128 z = wave_xor(cyc_lane_term_lds(smem, y, lane));
-    if (g + 1u != gridDim.x) {                                                // weight H^(1024 (255 - g)) through a two-table Shoup form in LDS
-        if (lane < 32) *reinterpret_cast<uint4 *>(smem + CYC_LDS_WTAB + 16u * lane) = shoup2_entry(mo_to_be(wc), lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        z = shoup2_gmul_lds(z, reinterpret_cast<const uint4 *>(smem + CYC_LDS_WTAB));
-    }
+    if (g + 1u != gridDim.x) z = cyc_weigh(z, wc, smem, CYC_LDS_WTAB, lane);   // weight H^(1024 (255 - g))
     if (g == 0) {                                                             // the terms that occur once
         G128 x; x.w[0] = x.w[1] = x.w[2] = x.w[3] = 0;
         if (p.tb) x = cyc_lane_term_lds(smem, *reinterpret_cast<const uint4 *>(smem + CYC_LDS_PARK + lane * 16u), lane, CYC_LDS_LTAB0);
         if (lane == 0) {
-            const uint4 ej0 = *reinterpret_cast<const uint4 *>(smem + CYC_LDS_PARK + 1024u);
-            G128 L; const u64 la = p.aad_len * 8, lc = p.ct_len * 8;       // the length block times H (tag_len_term with the batched multiply: no registers to spare here)
-            L.w[0] = (u32)(la >> 32); L.w[1] = (u32)la; L.w[2] = (u32)(lc >> 32); L.w[3] = (u32)lc;
-            L = shoup2_gmul_lds(L, km->ltab[1]);
-            const G128 e = mo_to_be(ej0);
-            x.w[0] ^= L.w[0] ^ e.w[0]; x.w[1] ^= L.w[1] ^ e.w[1]; x.w[2] ^= L.w[2] ^ e.w[2]; x.w[3] ^= L.w[3] ^ e.w[3];
+            const G128 t = cyc_len_ej0_term(km, p, smem, CYC_LDS_PARK);
+            x.w[0] ^= t.w[0]; x.w[1] ^= t.w[1]; x.w[2] ^= t.w[2]; x.w[3] ^= t.w[3];
         }
         x = wave_xor(x);
         z.w[0] ^= x.w[0]; z.w[1] ^= x.w[1]; z.w[2] ^= x.w[2]; z.w[3] ^= x.w[3];
     }
     if (lane != 0) return;
     acc_arrive(p.acc, g, z, p.tag_out, p.tag_host, p.gen);
-    if (p.trace) {                                                             // timing mode: how long the closing took behind the workgroup's last row, in 10 ns units, bits 52 .. 63 of word 2
-        unsigned long long *tr = reinterpret_cast<unsigned long long *>(p.trace + 4 * (u64)g);
-        const u64 rows_end = __hip_atomic_load(tr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const u64 dt = wall_clock64() - rows_end;
-        atomicOr(tr + 2, (unsigned long long)(dt > 0xFFFu ? 0xFFFu : dt) << 52);
-    }
+    trace_closed(p.trace);
 }
 
 template <int NR, int MODE, bool CYC>
 __global__ __launch_bounds__(AESGCM_BODY_WG, AESGCM_BODY_WPS) void k_body(const KeyMaterial *__restrict__ km, const DevTables *__restrict__ tb, const BodyParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 tid = threadIdx.x, lane = tid & 63u;
-    if (p.trace && tid == 0) {
-        u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-        tr[0] = wall_clock64();
-        tr[2] = (u64)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((u64)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 32);
-    }
+    trace_begin(p.trace, tid);
     const u64 cyc0 = p.trace ? clock64() : 0;
     main_fill_lds(smem, km, tb, tid, true, AESGCM_BODY_WG, CYC ? GH_TAB_K2P18 : GH_TAB_K256);
 #if AESGCM_T4
@@ -358,14 +380,8 @@ __global__ __launch_bounds__(AESGCM_BODY_WG, AESGCM_BODY_WPS) void k_body(const 
 #endif
     if (tid == 0) *reinterpret_cast<u32 *>(smem + AESGCM_LDS_DRY_OFF) = 0;   // dry-queue mask of the workgroup (next_chunk)
     __syncthreads();
-    if (p.trace && tid == 0) {                                                // timing mode: when the tables were staged, 10 ns units behind the workgroup's start, bits 40 .. 51 of word 2
-        unsigned long long *tr = reinterpret_cast<unsigned long long *>(p.trace + 4 * (u64)blockIdx.x);
-        const u64 dt = wall_clock64() - tr[0];
-        atomicOr(tr + 2, (unsigned long long)(dt > 0xFFFu ? 0xFFFu : dt) << 40);
-    }
-    CtrConsts cc = ctr_round1_consts(p.iv0, p.iv1, p.iv2, km->rk, smem, (lane & 31u) << 2);   // key and IV only: wave-uniform
-    cc.c0 = __builtin_amdgcn_readfirstlane(cc.c0); cc.c1 = __builtin_amdgcn_readfirstlane(cc.c1);
-    cc.c2 = __builtin_amdgcn_readfirstlane(cc.c2); cc.c3 = __builtin_amdgcn_readfirstlane(cc.c3);
+    trace_staged(p.trace, tid);
+    const CtrConsts cc = wave_uniform(ctr_round1_consts(p.iv0, p.iv1, p.iv2, km->rk, smem, (lane & 31u) << 2));
     u32 done = 0;
     if (CYC) {                                                                // cyclic rows: one strand and one item per wave, no dispenser
         const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * (AESGCM_BODY_WG / 64) + (tid >> 6));
@@ -373,17 +389,9 @@ __global__ __launch_bounds__(AESGCM_BODY_WG, AESGCM_BODY_WPS) void k_body(const 
         uint4 last = make_uint4(0, 0, 0, 0), ej0 = make_uint4(0, 0, 0, 0);
         if (w == 0) {                                                         // a strand of the shorter kind: the partial last row and E_K(IV || 1)
             if (p.tb) last = body_cyc_last_lane<NR, MODE>(km, p, smem, cc, lane);
-            if (p.ej0 || p.fuse) {
-                u32 s0, s1, s2, s3;
-                ctr_rounds_lds<NR>(bswap32(1u), cc, s0, s1, s2, s3, km->rk, smem, (lane & 31u) << 2);
-                ej0 = make_uint4(s0, s1, s2, s3);
-            }
+            if (p.ej0 || p.fuse) ej0 = ek_j0<NR>(cc, km->rk, smem, lane);
         }
-        if (p.trace && lane == 0) {
-            u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-            atomicMax((unsigned long long *)&tr[1], (unsigned long long)wall_clock64());
-            atomicAdd((unsigned long long *)&tr[3], (unsigned long long)((p.F + p.R) / BODY_CYC_WAVES) | ((unsigned long long)((clock64() - cyc0) >> 10) << 32));
-        }
+        trace_end(p.trace, lane, cyc0, (p.F + p.R) / BODY_CYC_WAVES);
         if (!p.fuse) {                                                        // items for k_fold / k_combine
             p.parts[(size_t)w * 64 + lane] = acc;
             if (w == 0) {
@@ -408,17 +416,12 @@ __global__ __launch_bounds__(AESGCM_BODY_WG, AESGCM_BODY_WPS) void k_body(const 
         const uint4 acc = body_chunk_lane<NR, MODE>(km, tb, p, smem, cc, c, lane);
         p.parts[(size_t)c * 64 + lane] = acc;
         if (c == 0 && p.ej0) {                                  // E_K(IV || 1) for the tag, once per launch (as in k_main)
-            u32 s0, s1, s2, s3;
-            ctr_rounds_lds<NR>(bswap32(1u), cc, s0, s1, s2, s3, km->rk, smem, (lane & 31u) << 2);
-            if (lane == 0) *p.ej0 = make_uint4(s0, s1, s2, s3);
+            const uint4 ej0 = ek_j0<NR>(cc, km->rk, smem, lane);
+            if (lane == 0) *p.ej0 = ej0;
         }
         ++done;
     }
-    if (p.trace && lane == 0) {
-        u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-        atomicMax((unsigned long long *)&tr[1], (unsigned long long)wall_clock64());
-        atomicAdd((unsigned long long *)&tr[3], (unsigned long long)done | ((unsigned long long)((clock64() - cyc0) >> 10) << 32));
-    }
+    trace_end(p.trace, lane, cyc0, done);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -460,13 +463,7 @@ __device__ __forceinline__ void cyc_close_half(const KeyMaterial *__restrict__ k
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 #endif
     G128 z = wave_xor(cyc_lane_term_lds(smem, y, lane, CYCH_LDS_LTAB));
-    if (g + 1u != gridDim.x) {                                                // the weight through a two-table Shoup form in LDS
-        if (lane < 32) *reinterpret_cast<uint4 *>(smem + CYCH_LDS_WTAB + 16u * lane) = shoup2_entry(mo_to_be(wc), lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        z = shoup2_gmul_lds(z, reinterpret_cast<const uint4 *>(smem + CYCH_LDS_WTAB));
-    }
+    if (g + 1u != gridDim.x) z = cyc_weigh(z, wc, smem, CYCH_LDS_WTAB, lane);
     if (g == 0) {                                                             // the terms that occur once
         G128 x; x.w[0] = x.w[1] = x.w[2] = x.w[3] = 0;
         if (p.tb) {
@@ -480,61 +477,37 @@ __device__ __forceinline__ void cyc_close_half(const KeyMaterial *__restrict__ k
             x = cyc_lane_term_lds(smem, *reinterpret_cast<const uint4 *>(smem + CYCH_LDS_PARK + lane * 16u), lane, CYCH_LDS_LTAB);
         }
         if (lane == 0) {
-            const uint4 ej0 = *reinterpret_cast<const uint4 *>(smem + CYCH_LDS_PARK + 1024u);
-            G128 L; const u64 la = p.aad_len * 8, lc = p.ct_len * 8;
-            L.w[0] = (u32)(la >> 32); L.w[1] = (u32)la; L.w[2] = (u32)(lc >> 32); L.w[3] = (u32)lc;
-            L = shoup2_gmul_lds(L, km->ltab[1]);
-            const G128 e = mo_to_be(ej0);
-            x.w[0] ^= L.w[0] ^ e.w[0]; x.w[1] ^= L.w[1] ^ e.w[1]; x.w[2] ^= L.w[2] ^ e.w[2]; x.w[3] ^= L.w[3] ^ e.w[3];
+            const G128 t = cyc_len_ej0_term(km, p, smem, CYCH_LDS_PARK);
+            x.w[0] ^= t.w[0]; x.w[1] ^= t.w[1]; x.w[2] ^= t.w[2]; x.w[3] ^= t.w[3];
         }
         x = wave_xor(x);
         z.w[0] ^= x.w[0]; z.w[1] ^= x.w[1]; z.w[2] ^= x.w[2]; z.w[3] ^= x.w[3];
     }
     if (lane != 0) return;
     acc_arrive(p.acc, g, z, p.tag_out, p.tag_host, p.gen);
-    if (p.trace) {
-        unsigned long long *tr = reinterpret_cast<unsigned long long *>(p.trace + 4 * (u64)g);
-        const u64 rows_end = __hip_atomic_load(tr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const u64 dt = wall_clock64() - rows_end;
-        atomicOr(tr + 2, (unsigned long long)(dt > 0xFFFu ? 0xFFFu : dt) << 52);
-    }
+    trace_closed(p.trace);
 }
 
 template <int NR, int MODE>
 __global__ __launch_bounds__(AESGCM_BODYH_WG, 4) void k_bodyh(const KeyMaterial *__restrict__ km, const DevTables *__restrict__ tb, const BodyParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 tid = threadIdx.x, lane = tid & 63u;
-    if (p.trace && tid == 0) {
-        u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-        tr[0] = wall_clock64();
-        tr[2] = (u64)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((u64)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 32);
-    }
+    trace_begin(p.trace, tid);
     const u64 cyc0 = p.trace ? clock64() : 0;
     main_fill_lds(smem, km, tb, tid, true, AESGCM_BODYH_WG, GH_TAB_K2P17);    // T0 | T2 and the five-bit tables of the stride H^(2^17)
     __syncthreads();
-    if (p.trace && tid == 0) {
-        unsigned long long *tr = reinterpret_cast<unsigned long long *>(p.trace + 4 * (u64)blockIdx.x);
-        const u64 dt = wall_clock64() - tr[0];
-        atomicOr(tr + 2, (unsigned long long)(dt > 0xFFFu ? 0xFFFu : dt) << 40);
-    }
-    CtrConsts cc = ctr_round1_consts(p.iv0, p.iv1, p.iv2, km->rk, smem, (lane & 31u) << 2);
-    cc.c0 = __builtin_amdgcn_readfirstlane(cc.c0); cc.c1 = __builtin_amdgcn_readfirstlane(cc.c1);
-    cc.c2 = __builtin_amdgcn_readfirstlane(cc.c2); cc.c3 = __builtin_amdgcn_readfirstlane(cc.c3);
+    trace_staged(p.trace, tid);
+    const CtrConsts cc = wave_uniform(ctr_round1_consts(p.iv0, p.iv1, p.iv2, km->rk, smem, (lane & 31u) << 2));
     const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * (AESGCM_BODYH_WG / 64) + (tid >> 6));
     const uint4 acc = body_cyc_lane<NR, MODE, false, BODY_CYC_WAVES_HALF>(km, tb, p, smem, cc, w, lane);
     if (w == 0) {                                                             // a strand of the shorter kind: the partial last row and E_K(IV || 1), parked in LDS for the closing
         uint4 last = make_uint4(0, 0, 0, 0);
         if (p.tb) last = body_cyc_last_lane<NR, MODE>(km, p, smem, cc, lane);
-        u32 s0, s1, s2, s3;
-        ctr_rounds_lds<NR>(bswap32(1u), cc, s0, s1, s2, s3, km->rk, smem, (lane & 31u) << 2);
+        const uint4 ej0 = ek_j0<NR>(cc, km->rk, smem, lane);
         *reinterpret_cast<uint4 *>(smem + CYCH_LDS_PARK + lane * 16u) = last;
-        if (lane == 0) *reinterpret_cast<uint4 *>(smem + CYCH_LDS_PARK + 1024u) = make_uint4(s0, s1, s2, s3);
+        if (lane == 0) *reinterpret_cast<uint4 *>(smem + CYCH_LDS_PARK + 1024u) = ej0;
     }
-    if (p.trace && lane == 0) {
-        u64 *tr = p.trace + 4 * (u64)blockIdx.x;
-        atomicMax((unsigned long long *)&tr[1], (unsigned long long)wall_clock64());
-        atomicAdd((unsigned long long *)&tr[3], (unsigned long long)((p.F + p.R) / BODY_CYC_WAVES_HALF) | ((unsigned long long)((clock64() - cyc0) >> 10) << 32));
-    }
+    trace_end(p.trace, lane, cyc0, (p.F + p.R) / BODY_CYC_WAVES_HALF);
     cyc_close_half(km, p, smem, acc);
 }
 
@@ -1100,9 +1073,7 @@ __global__ __launch_bounds__(AESGCM_BODY_WG, AESGCM_BODY_WPS) void k_rows(const 
                 z = wave_xor(rows_aad_lane(km, p, mq, smem, lane_id_fresh()));
             } else {
                 const unsigned char *ivp = p.ivs + (size_t)m * 12;
-                CtrConsts cc = ctr_round1_consts(uniform32(load_le32(ivp)), uniform32(load_le32(ivp + 4)), uniform32(load_le32(ivp + 8)), km->rk, smem, (lane_id_fresh() & 31u) << 2);   // key and IV only: wave-uniform
-                cc.c0 = __builtin_amdgcn_readfirstlane(cc.c0); cc.c1 = __builtin_amdgcn_readfirstlane(cc.c1);
-                cc.c2 = __builtin_amdgcn_readfirstlane(cc.c2); cc.c3 = __builtin_amdgcn_readfirstlane(cc.c3);
+                const CtrConsts cc = wave_uniform(ctr_round1_consts(uniform32(load_le32(ivp)), uniform32(load_le32(ivp + 4)), uniform32(load_le32(ivp + 8)), km->rk, smem, (lane_id_fresh() & 31u) << 2));
                 if (pc.kind == ROWS_RUN) {
                     const uint4 acc = rows_run_lane<NR, MODE>(km, tb, p, mq, pc, smem, cc, lane_id_fresh(), dyn ? 0u : p.prio_rows, (tid >> 8) & 3u);
                     z = wave_xor(rows_run_term(km, acc, lane_id_fresh()));
@@ -1403,79 +1374,53 @@ __global__ __launch_bounds__(256) void k_wipe_failed(unsigned char *out, const i
 }
 
 // ================================================================================================
-// launchers: the only code that names a kernel (aesgcm_internal.h).  Each picks the template instance by round count / mode / shape and returns hipGetLastError().
+// launchers: the only code that names a kernel (aesgcm_internal.h).  Each picks the template instance by round count / mode / shape (aesgcm_dispatch.h holds the
+// rules and the instance sets) and returns hipGetLastError().  A family of instances is one generic lambda, <family>_instance, that answers the kernel, its workgroup
+// size and its LDS bytes for the constants it is handed: the launcher picks one through it, klaunch_set_attributes walks the same set through it.
 // ================================================================================================
-template <int MODE>
-static hipError_t launch_main_nr(int nr, dim3 grid, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const MainParams &p) {
-    const unsigned lds = AESGCM_LDS_BYTES;
-    switch (nr) {
-    case 10: hipLaunchKernelGGL((k_main<10, MODE>), grid, dim3(AESGCM_MAIN_WG), lds, st, km, tb, p); break;
-    case 12: hipLaunchKernelGGL((k_main<12, MODE>), grid, dim3(AESGCM_MAIN_WG), lds, st, km, tb, p); break;
-    default: hipLaunchKernelGGL((k_main<14, MODE>), grid, dim3(AESGCM_MAIN_WG), lds, st, km, tb, p); break;
-    }
+template <class P> struct KInstance { void (*kernel)(const KeyMaterial *, const DevTables *, const P); unsigned wg, lds; };
+template <class P> static hipError_t launch(KInstance<P> k, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const P &p) {
+    hipLaunchKernelGGL(k.kernel, dim3(wgs), dim3(k.wg), k.lds, st, km, tb, p);
     return hipGetLastError();
 }
-hipError_t klaunch_main(int mode, int nr, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const MainParams &p) {
-    switch (mode) {
-    case MODE_ENC: return launch_main_nr<MODE_ENC>(nr, dim3(wgs), st, km, tb, p);
-    case MODE_DEC: return launch_main_nr<MODE_DEC>(nr, dim3(wgs), st, km, tb, p);
-    case MODE_KS:  return launch_main_nr<MODE_KS>(nr, dim3(wgs), st, km, tb, p);
-    default:       return launch_main_nr<MODE_ECB>(nr, dim3(wgs), st, km, tb, p);
-    }
-}
+template <class K> static hipError_t max_lds(K *kernel, unsigned bytes) { return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+template <class P> static hipError_t max_lds(KInstance<P> k) { return max_lds(k.kernel, k.lds); }
+
+using MainSet = main_set<MODE_ENC, MODE_DEC, MODE_KS, MODE_ECB>;
+static const auto main_instance = [](auto NR, auto M) { return KInstance<MainParams>{&k_main<NR(), M()>, AESGCM_MAIN_WG, AESGCM_LDS_BYTES}; };
+static const auto body_instance = [](auto NR, auto M, auto FORM) {
+    if constexpr (FORM() == BODY_HALF) return KInstance<BodyParams>{&k_bodyh<NR(), M()>, AESGCM_BODYH_WG, AESGCM_LDS_BYTES + CYC_LDS_PARK_BYTES};
+    else return KInstance<BodyParams>{&k_body<NR(), M(), FORM() == BODY_CYC>, AESGCM_BODY_WG, AESGCM_BODY_LDS + (FORM() == BODY_CYC ? CYC_LDS_PARK_BYTES : 0u)};
+};
+static const auto rows_instance = [](auto NR, auto M) { return KInstance<RowsParams>{&k_rows<NR(), M()>, AESGCM_BODY_WG, AESGCM_BODY_LDS}; };
+static const auto pktl_instance = [](auto NR, auto D, auto ILP, auto SCATTERED) {      // the workgroup size follows ILP
+    if constexpr (SCATTERED()) return KInstance<PktParams>{&k_pktls<NR(), D()>, AESGCM_PKTL_WG, AESGCM_PKTL_LDS};
+    else return KInstance<PktParams>{&k_pktl<NR(), D(), ILP()>, ILP() ? AESGCM_PKTL_WG_ILP : AESGCM_PKTL_WG, AESGCM_PKTL_LDS};
+};
+static const auto pktg_instance = [](auto NR, auto D, auto LG, auto SCATTERED) {
+    if constexpr (SCATTERED()) return KInstance<PktParams>{&k_pktgs<NR(), D(), LG()>, PKTG_WG(LG()), PKTG_LDS_TOTAL(LG())};
+    else return KInstance<PktParams>{&k_pktg<NR(), D(), LG()>, PKTG_WG(LG()), PKTG_LDS_TOTAL(LG())};
+};
 
 hipError_t klaunch_set_attributes() {
-#define ATTRCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
-#define SETATTR(NR, MODE) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_main<NR, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_LDS_BYTES))
-    SETATTR(10, MODE_ENC); SETATTR(12, MODE_ENC); SETATTR(14, MODE_ENC);
-    SETATTR(10, MODE_DEC); SETATTR(12, MODE_DEC); SETATTR(14, MODE_DEC);
-    SETATTR(10, MODE_KS);  SETATTR(12, MODE_KS);  SETATTR(14, MODE_KS);
-    SETATTR(10, MODE_ECB); SETATTR(12, MODE_ECB); SETATTR(14, MODE_ECB);
-#undef SETATTR
-#define SETATTRY(NR, MODE, CYC) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_body<NR, MODE, CYC>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_BODY_LDS + (CYC ? CYC_LDS_PARK_BYTES : 0u)))
-    SETATTRY(10, MODE_ENC, false); SETATTRY(12, MODE_ENC, false); SETATTRY(14, MODE_ENC, false); SETATTRY(10, MODE_DEC, false); SETATTRY(12, MODE_DEC, false); SETATTRY(14, MODE_DEC, false);
-    SETATTRY(10, MODE_ENC, true); SETATTRY(12, MODE_ENC, true); SETATTRY(14, MODE_ENC, true); SETATTRY(10, MODE_DEC, true); SETATTRY(12, MODE_DEC, true); SETATTRY(14, MODE_DEC, true);
-    SETATTRY(10, MODE_PROBE, false); SETATTRY(12, MODE_PROBE, false); SETATTRY(14, MODE_PROBE, false);
-#undef SETATTRY
-#define SETATTRH(NR, MODE) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bodyh<NR, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_LDS_BYTES + CYC_LDS_PARK_BYTES))
-    SETATTRH(10, MODE_ENC); SETATTRH(12, MODE_ENC); SETATTRH(14, MODE_ENC); SETATTRH(10, MODE_DEC); SETATTRH(12, MODE_DEC); SETATTRH(14, MODE_DEC);
-#undef SETATTRH
-#define SETATTRR(NR, MODE) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows<NR, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_BODY_LDS))
-    SETATTRR(10, MODE_ENC); SETATTRR(12, MODE_ENC); SETATTRR(14, MODE_ENC); SETATTRR(10, MODE_DEC); SETATTRR(12, MODE_DEC); SETATTRR(14, MODE_DEC);
-#undef SETATTRR
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fold), hipFuncAttributeMaxDynamicSharedMemorySize, FOLD_LDS_CLOSE_BYTES));
-#define SETATTRB(NR, D) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, D, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(2))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, D, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(3))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, D, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(4))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, D, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(6))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktl<NR, D, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_PKTL_LDS)); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktl<NR, D, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_PKTL_LDS))
-    SETATTRB(10, 0); SETATTRB(12, 0); SETATTRB(14, 0); SETATTRB(10, 1); SETATTRB(12, 1); SETATTRB(14, 1);
-#undef SETATTRB
-#define SETATTRS(NR, D) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktgs<NR, D, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(2))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktgs<NR, D, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(3))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktgs<NR, D, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(4))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktls<NR, D>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_PKTL_LDS))
-    SETATTRS(10, 0); SETATTRS(12, 0); SETATTRS(14, 0); SETATTRS(10, 1); SETATTRS(12, 1); SETATTRS(14, 1);
-#undef SETATTRS
-#define SETATTRP(NR) ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(2))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, 2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(3))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktg<NR, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, PKTG_LDS_TOTAL(4))); \
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pktl<NR, 2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, AESGCM_PKTL_LDS))
-    SETATTRP(10); SETATTRP(12); SETATTRP(14);                     // the probes of the packet kernels (aesgcm_frames_ceiling_probe_dev)
-#undef SETATTRP
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_combine), hipFuncAttributeMaxDynamicSharedMemorySize, CMB_LDS_BYTES));
-    ATTRCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_combine_batch), hipFuncAttributeMaxDynamicSharedMemorySize, CMB_LDS_BYTES));
-#undef ATTRCHK
-    const hipError_t eb = batch3_each([](auto NR, auto D, auto LG) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR(), D(), LG()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG())); });
-    if (eb != hipSuccess) return eb;
-    const hipError_t ep = nr_each([](auto NR) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch3<NR(), 2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(3)); });      // the probe
-    if (ep != hipSuccess) return ep;
-    const hipError_t ek = klaunch_kt_attributes();                             // the key tables' kernels, family by family (aesgcm_keytab.h)
-    const hipError_t ew = ek != hipSuccess ? ek : klaunch_wire_attributes();
-    const hipError_t ex = ew != hipSuccess ? ew : klaunch_wirex_attributes();
-    const hipError_t et = ex != hipSuccess ? ex : klaunch_tls_attributes();
-    return et != hipSuccess ? et : klaunch_quic_attributes();
+    hipError_t e = set_each(MainSet{}, [](auto... c) { return max_lds(main_instance(c...)); });
+    if (!e) e = body_each<MODE_ENC, MODE_DEC, MODE_PROBE>([](auto... c) { return max_lds(body_instance(c...)); });
+    if (!e) e = set_each(rows_set<MODE_ENC, MODE_DEC>{}, [](auto... c) { return max_lds(rows_instance(c...)); });
+    if (!e) e = max_lds(&k_fold, FOLD_LDS_CLOSE_BYTES);
+    if (!e) e = pktg_each([](auto... c) { return max_lds(pktg_instance(c...)); });                // with the probes of the packet kernels (aesgcm_frames_ceiling_probe_dev)
+    if (!e) e = pktl_each([](auto... c) { return max_lds(pktl_instance(c...)); });
+    if (!e) e = max_lds(&k_combine, CMB_LDS_BYTES);
+    if (!e) e = max_lds(&k_combine_batch, CMB_LDS_BYTES);
+    if (!e) e = batch3_each([](auto NR, auto D, auto LG) { return max_lds(&k_batch3<NR(), D(), LG()>, BATCH3_LDS_BYTES_LG(LG())); });
+    if (!e) e = nr_each([](auto NR) { return max_lds(&k_batch3<NR(), 2, 3>, BATCH3_LDS_BYTES_LG(3)); });      // the probe
+    if (!e) e = klaunch_kt_attributes();                                       // the key tables' kernels, family by family (aesgcm_keytab.h)
+    if (!e) e = klaunch_wire_attributes();
+    if (!e) e = klaunch_wirex_attributes();
+    if (!e) e = klaunch_tls_attributes();
+    return e ? e : klaunch_quic_attributes();
+}
+hipError_t klaunch_main(int mode, int nr, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const MainParams &p) {
+    return launch(set_pick(MainSet{}, main_instance, nr, mode), wgs, st, km, tb, p);
 }
 hipError_t klaunch_init_tables(DevTables *t) { hipLaunchKernelGGL(k_init_tables, dim3(1), dim3(256), 0, 0, t); return hipGetLastError(); }
 hipError_t klaunch_setup(hipStream_t st, KeyMaterial *km, const DevTables *tb, const uint8_t *d_key, int key_len, int pre_nr, u32 G) {
@@ -1490,22 +1435,9 @@ hipError_t klaunch_fill_splitmix64(hipStream_t st, unsigned blocks, u64 *buf, si
     return hipGetLastError();
 }
 hipError_t klaunch_body(int mode, int nr, bool cyc, bool half, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const BodyParams &p) {
-#define LY(NR, M, CYC) hipLaunchKernelGGL((k_body<NR, M, CYC>), dim3(wgs), dim3(AESGCM_BODY_WG), AESGCM_BODY_LDS + (CYC ? CYC_LDS_PARK_BYTES : 0u), st, km, tb, p)
-#define LH(NR, M) hipLaunchKernelGGL((k_bodyh<NR, M>), dim3(wgs), dim3(AESGCM_BODYH_WG), AESGCM_LDS_BYTES + CYC_LDS_PARK_BYTES, st, km, tb, p)
-    if (half) {
-        if (mode == MODE_DEC)    { if (nr == 10) LH(10, MODE_DEC); else if (nr == 12) LH(12, MODE_DEC); else LH(14, MODE_DEC); }
-        else                     { if (nr == 10) LH(10, MODE_ENC); else if (nr == 12) LH(12, MODE_ENC); else LH(14, MODE_ENC); }
-    }
-    else if (cyc) {
-        if (mode == MODE_DEC)    { if (nr == 10) LY(10, MODE_DEC, true); else if (nr == 12) LY(12, MODE_DEC, true); else LY(14, MODE_DEC, true); }
-        else                     { if (nr == 10) LY(10, MODE_ENC, true); else if (nr == 12) LY(12, MODE_ENC, true); else LY(14, MODE_ENC, true); }
-    }
-    else if (mode == MODE_DEC)   { if (nr == 10) LY(10, MODE_DEC, false); else if (nr == 12) LY(12, MODE_DEC, false); else LY(14, MODE_DEC, false); }
-    else if (mode == MODE_PROBE) { if (nr == 10) LY(10, MODE_PROBE, false); else if (nr == 12) LY(12, MODE_PROBE, false); else LY(14, MODE_PROBE, false); }
-    else                         { if (nr == 10) LY(10, MODE_ENC, false); else if (nr == 12) LY(12, MODE_ENC, false); else LY(14, MODE_ENC, false); }
-#undef LY
-#undef LH
-    return hipGetLastError();
+    KInstance<BodyParams> k{};
+    body_dispatch<MODE_ENC, MODE_DEC, MODE_PROBE>(nr, mode, cyc, half, [&](auto... c) { k = body_instance(c...); });
+    return launch(k, wgs, st, km, tb, p);
 }
 hipError_t klaunch_fold(unsigned wgs, bool closing, hipStream_t st, const KeyMaterial *km, const FoldParams &p) {
     hipLaunchKernelGGL(k_fold, dim3(wgs), dim3(FOLD_WG), closing ? FOLD_LDS_CLOSE_BYTES : FOLD_LDS_BYTES, st, km, p);
@@ -1520,43 +1452,14 @@ hipError_t klaunch_combine_batch(unsigned n, hipStream_t st, const KeyMaterial *
     return hipGetLastError();
 }
 hipError_t klaunch_pktl(int nr, int dec, bool ilp, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const PktParams &p) {
-    if (p.scattered) {                                          // messages wherever they live: k_pktls (no ILP form: a routed call takes a lane per packet only when the packets fill the chip)
-#define LS(NR, D) hipLaunchKernelGGL((k_pktls<NR, D>), dim3(wgs), dim3(AESGCM_PKTL_WG), AESGCM_PKTL_LDS, st, km, tb, p)
-        if (dec) { if (nr == 10) LS(10, 1); else if (nr == 12) LS(12, 1); else LS(14, 1); }
-        else     { if (nr == 10) LS(10, 0); else if (nr == 12) LS(12, 0); else LS(14, 0); }
-#undef LS
-        return hipGetLastError();
-    }
-#define LPI(NR, D, I) hipLaunchKernelGGL((k_pktl<NR, D, I>), dim3(wgs), dim3(I ? AESGCM_PKTL_WG_ILP : AESGCM_PKTL_WG), AESGCM_PKTL_LDS, st, km, tb, p)
-#define LP(NR, D) do { if (ilp) LPI(NR, D, 1); else LPI(NR, D, 0); } while (0)
-    if (dec == 2) { if (ilp) return hipErrorInvalidValue; if (nr == 10) LPI(10, 2, 0); else if (nr == 12) LPI(12, 2, 0); else LPI(14, 2, 0); }      // the probe: the 768-lane form
-    else if (dec) { if (nr == 10) LP(10, 1); else if (nr == 12) LP(12, 1); else LP(14, 1); }
-    else     { if (nr == 10) LP(10, 0); else if (nr == 12) LP(12, 0); else LP(14, 0); }
-#undef LPI
-#undef LP
-    return hipGetLastError();
+    KInstance<PktParams> k{};                                   // scattered: messages wherever they live, k_pktls (no ILP form: a routed call takes a lane per packet only when the packets fill the chip); the probe: the 768-lane form
+    if (!pktl_dispatch(nr, dec, ilp, p.scattered, [&](auto... c) { k = pktl_instance(c...); })) return hipErrorInvalidValue;
+    return launch(k, wgs, st, km, tb, p);
 }
 hipError_t klaunch_pktg(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const PktParams &p) {
-    if (p.scattered) {                                          // messages wherever they live: k_pktgs, lane groups of 4 / 8 / 16
-        if (lg != 2 && lg != 3 && lg != 4) return hipErrorInvalidValue;
-#define LSG(NR, D, LG) hipLaunchKernelGGL((k_pktgs<NR, D, LG>), dim3(wgs), dim3(PKTG_WG(LG)), PKTG_LDS_TOTAL(LG), st, km, tb, p)
-#define LS(NR, D) do { if (lg == 2) LSG(NR, D, 2); else if (lg == 3) LSG(NR, D, 3); else LSG(NR, D, 4); } while (0)
-        if (dec) { if (nr == 10) LS(10, 1); else if (nr == 12) LS(12, 1); else LS(14, 1); }
-        else     { if (nr == 10) LS(10, 0); else if (nr == 12) LS(12, 0); else LS(14, 0); }
-#undef LS
-#undef LSG
-        return hipGetLastError();
-    }
-#define LPG(NR, D, LG) hipLaunchKernelGGL((k_pktg<NR, D, LG>), dim3(wgs), dim3(PKTG_WG(LG)), PKTG_LDS_TOTAL(LG), st, km, tb, p)
-#define LP(NR, D) do { if (lg == 2) LPG(NR, D, 2); else if (lg == 3) LPG(NR, D, 3); else if (lg == 4) LPG(NR, D, 4); else LPG(NR, D, 6); } while (0)
-#define LPP(NR) do { if (lg == 2) LPG(NR, 2, 2); else if (lg == 3) LPG(NR, 2, 3); else LPG(NR, 2, 4); } while (0)
-    if (dec == 2) { if (lg != 2 && lg != 3 && lg != 4) return hipErrorInvalidValue; if (nr == 10) LPP(10); else if (nr == 12) LPP(12); else LPP(14); }      // the probe: lane groups of 4 / 8 / 16
-    else if (dec) { if (nr == 10) LP(10, 1); else if (nr == 12) LP(12, 1); else LP(14, 1); }
-    else     { if (nr == 10) LP(10, 0); else if (nr == 12) LP(12, 0); else LP(14, 0); }
-#undef LP
-#undef LPP
-#undef LPG
-    return hipGetLastError();
+    KInstance<PktParams> k{};                                   // scattered (k_pktgs) and the probe: lane groups of 4 / 8 / 16
+    if (!pktg_dispatch(nr, dec, lg, p.scattered, [&](auto... c) { k = pktg_instance(c...); })) return hipErrorInvalidValue;
+    return launch(k, wgs, st, km, tb, p);
 }
 hipError_t klaunch_batch3(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const BatchParams &p) {
     if (dec == 2) {                                                           // the probe exists in the shape of BASELINE config 5
@@ -1594,15 +1497,10 @@ hipError_t klaunch_rows_plan(hipStream_t st, const RowsParams &p, bool routed, u
     return hipGetLastError();
 }
 hipError_t klaunch_rows(int nr, int dec, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) {
-#define LR(NR, M) hipLaunchKernelGGL((k_rows<NR, M>), dim3(wgs), dim3(AESGCM_BODY_WG), AESGCM_BODY_LDS, st, km, tb, p)
-    if (dec) { if (nr == 10) LR(10, MODE_DEC); else if (nr == 12) LR(12, MODE_DEC); else LR(14, MODE_DEC); }
-    else     { if (nr == 10) LR(10, MODE_ENC); else if (nr == 12) LR(12, MODE_ENC); else LR(14, MODE_ENC); }
-#undef LR
-    return hipGetLastError();
+    return launch(rows_dispatch<MODE_ENC, MODE_DEC>(nr, dec, rows_instance), wgs, st, km, tb, p);
 }
 hipError_t klaunch_rows_close(int dec, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) {
-    if (dec) hipLaunchKernelGGL(k_rows_close<1>, dim3(wgs), dim3(ROWS_CLOSE_WG), 0, st, km, tb, p);
-    else hipLaunchKernelGGL(k_rows_close<0>, dim3(wgs), dim3(ROWS_CLOSE_WG), 0, st, km, tb, p);
+    pick(dec_list{}, dec, [&](auto D) { hipLaunchKernelGGL(k_rows_close<D()>, dim3(wgs), dim3(ROWS_CLOSE_WG), 0, st, km, tb, p); });
     return hipGetLastError();
 }
 hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr) {
