@@ -46,46 +46,65 @@ def forged(n):
     return sorted(set(range(0, n, FORGE_EVERY)) | {n - 1})
 
 
+def pack(full, lc, front=None, span=None, allowed=None, prefer=None):
+    """The placement loop: byte-packed packets such that every (start mod 16, L) for L in `full` and every (start mod 128, L) for L in `lc` occurs -> the lengths
+    in order.  Packet i of length L at `pos` occupies span(i, L) bytes and the start that counts is pos + front(i) (defaults: the packet is its L bytes and starts
+    at pos -- the packet kernels' grid; tests/kt_grid.py places frames header | payload | ICV by their payload).  allowed(i, L): whether packet i may have length L;
+    prefer(i): a length that packet i takes in front of every other choice, or None."""
+    front = front or (lambda i: 0)
+    span = span or (lambda i, L: L)
+    allowed = allowed or (lambda i, L: True)
+    need16 = {r: set(full) for r in range(16)}
+    need128 = {r: set(lc) for r in range(128)}
+    left = 16 * len(full) + 128 * len(lc)
+    lens, pos = [], 0
+    order16 = {r: sorted(need16[r], reverse=True) for r in range(16)}          # deterministic: longest first, so that the fillers (short) find their own cells taken late
+    order128 = {r: sorted(need128[r], reverse=True) for r in range(128)}
+
+    def put(L):
+        nonlocal pos, left
+        r = (pos + front(len(lens))) % 128
+        if L in need128[r]:
+            need128[r].discard(L); left -= 1
+        if L in need16[r % 16]:
+            need16[r % 16].discard(L); left -= 1
+        pos += span(len(lens), L)
+        lens.append(L)
+
+    def pick(r, i):
+        while order128[r] and order128[r][0] not in need128[r]:
+            order128[r].pop(0)
+        for L in order128[r]:
+            if L in need128[r] and allowed(i, L):
+                return L
+        q = order16[r % 16]
+        while q and q[0] not in need16[r % 16]:
+            q.pop(0)
+        for L in q:
+            if L in need16[r % 16] and allowed(i, L):
+                return L
+        return None
+
+    while left:
+        i = len(lens)
+        L = prefer(i) if prefer else None
+        if L is None:
+            L = pick((pos + front(i)) % 128, i)
+        if L is None:                                                          # nothing left at this start: a filler to the nearest start that still needs a packet
+            f = next((f for f in range(1, 128) if allowed(i, f) and pick((pos + span(i, f) + front(i + 1)) % 128, i + 1) is not None), None)
+            put(f if f is not None else next(f for f in range(1, 128) if allowed(i, f)))       # (no start that the next packet may take: any filler, the one after it steers)
+            continue
+        put(L)
+    return lens
+
+
 class Packed:
     """n byte-packed packets: doff / aoff have n + 1 entries, offsets from the arena's first byte (doff[0] = aoff[0] = GUARD); the arenas are doff[n] + GUARD
     and aoff[n] + GUARD bytes.  With the arena on a 128-byte boundary a packet's residues are doff[i] % 16 and % 128."""
 
     def __init__(self, G=0):
         full, lc = all_lengths(), compact_lengths(G)
-        need16 = {r: set(full) for r in range(16)}
-        need128 = {r: set(lc) for r in range(128)}
-        left = 16 * len(full) + 128 * len(lc)
-        lens, pos = [], 0
-        order16 = {r: sorted(need16[r], reverse=True) for r in range(16)}          # deterministic: longest first, so that the fillers (short) find their own cells taken late
-        order128 = {r: sorted(need128[r], reverse=True) for r in range(128)}
-
-        def put(L):
-            nonlocal pos, left
-            r = pos % 128
-            if L in need128[r]:
-                need128[r].discard(L); left -= 1
-            if L in need16[r % 16]:
-                need16[r % 16].discard(L); left -= 1
-            lens.append(L)
-            pos += L
-
-        def pick(r):
-            while order128[r] and order128[r][0] not in need128[r]:
-                order128[r].pop(0)
-            if order128[r]:
-                return order128[r][0]
-            q = order16[r % 16]
-            while q and q[0] not in need16[r % 16]:
-                q.pop(0)
-            return q[0] if q else None
-
-        while left:
-            L = pick(pos % 128)
-            if L is None:                                                          # nothing left at this start: a filler to the nearest start that still needs a packet
-                f = next(f for f in range(1, 128) if pick((pos + f) % 128) is not None)
-                put(f)
-                continue
-            put(L)
+        lens = pack(full, lc)
         self.G, self.n, self.lens = G, len(lens), lens
         self.aads = [AAD_CYCLE[i % len(AAD_CYCLE)] for i in range(self.n)]
         self.doff = np.concatenate(([GUARD], GUARD + np.cumsum(lens))).astype(np.uint64)

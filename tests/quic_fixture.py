@@ -51,7 +51,7 @@ def _load():
         vp = ctypes.c_void_p
         L.EVP_CIPHER_CTX_new.restype = vp
         L.EVP_CIPHER_CTX_free.argtypes = [vp]
-        for nm in ("EVP_aes_128_ecb", "EVP_aes_256_ecb"):
+        for nm in ("EVP_aes_128_ecb", "EVP_aes_192_ecb", "EVP_aes_256_ecb"):
             getattr(L, nm).restype = vp
         L.EVP_EncryptInit_ex.argtypes = [vp, vp, vp, ctypes.c_char_p, ctypes.c_char_p]
         L.EVP_CIPHER_CTX_set_padding.argtypes = [vp, ctypes.c_int]
@@ -61,12 +61,12 @@ def _load():
 
 
 def aes_ecb(key, block):
-    """one block of AES-128 / AES-256 under libcrypto"""
-    assert len(block) == 16 and len(key) in (16, 32)
+    """one block of AES-128 / AES-192 / AES-256 under libcrypto"""
+    assert len(block) == 16 and len(key) in (16, 24, 32)
     L = _load()
     ctx = L.EVP_CIPHER_CTX_new()
     try:
-        assert L.EVP_EncryptInit_ex(ctx, (L.EVP_aes_128_ecb if len(key) == 16 else L.EVP_aes_256_ecb)(), None, key, None) == 1
+        assert L.EVP_EncryptInit_ex(ctx, {16: L.EVP_aes_128_ecb, 24: L.EVP_aes_192_ecb, 32: L.EVP_aes_256_ecb}[len(key)](), None, key, None) == 1
         assert L.EVP_CIPHER_CTX_set_padding(ctx, 0) == 1
         out = ctypes.create_string_buffer(32)
         n = ctypes.c_int(0)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import pkt_grid as PG
+from kt_common import Guarded, up_arena as _up
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
@@ -102,30 +103,8 @@ def _assemble(R, base, at, what, shift=0, wiped=False):
 
 
 # ---------------------------------------------------------------------------------------------- device side helpers
-def _up(hip, data):
-    b = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
-    d = hip.DeviceBuffer(max(len(b), 16))
-    assert d.ptr % 128 == 0, "device allocations are expected on a cache line: the grid's residues are offsets"
-    d.upload(b)
-    d.size = len(b)
-    return d
-
-
 def _canary(size, shift=0):
     return np.full(size + shift, PG.CANARY_OUT, dtype=np.uint8)
-
-
-class Guarded:
-    """a small device array (tags, verdicts) between two guards"""
-
-    def __init__(self, hip, n):
-        self.n, self.buf = n, _up(hip, bytes([0xA7]) * (n + 2 * G_))
-        self.ptr = self.buf.ptr + G_
-
-    def read(self, label):
-        b = bytes(self.buf.download())
-        assert b[:G_] == bytes([0xA7]) * G_ and b[G_ + self.n:] == bytes([0xA7]) * G_, ("guard bytes around tags / verdicts overwritten", label)
-        return b[G_:G_ + self.n]
 
 
 def _same(R, d_buf, want, at, shift, label):

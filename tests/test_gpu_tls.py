@@ -4,7 +4,6 @@ number, AAD = the record header) and TLS 1.2 AES-GCM (RFC 5288 3 / RFC 5246 6.2.
 2. random populations against libcrypto (oracle/evp_batch.c, evp_frames_crypt: nonce and AAD of every record built in tls_fixture.py from the RFCs' formulas), every
 byte of the buffer compared, guard bytes included; 3. every kernel shape on lengths either side of its lane count; 4. where the sequence number goes; 5. the slot's
 IV: its life cycle, the place it shares with the XPN state, stream ordering; 6. refusals, containment, tampering and aesgcm_wipe_failed_dev."""
-import ctypes
 import random
 import struct
 
@@ -12,6 +11,7 @@ import pytest
 
 import tls_fixture as T
 from kt_common import CANARY, _collect, _layout, _u32, _u64, _up, evp  # noqa: F401
+from kt_common import tls_ref_encrypt as _ref_encrypt
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
@@ -22,32 +22,6 @@ SEQS = (0, 2 ** 32 - 1, 2 ** 32, 2 ** 64 - 1)
 
 def _fmt(hip, ver):
     return hip.TlsFormat.tls13() if ver == T.TLS13 else hip.TlsFormat.tls12()
-
-
-def _ref_encrypt(evp, key_len, keys, ivs, ver, slots, seqs, recs):
-    """the expected wire records from libcrypto: per slot one evp_frames_crypt call over that slot's records"""
-    h = T.HDR[ver]
-    by = {}
-    for p, s in enumerate(slots):
-        by.setdefault(s, []).append(p)
-    out = [None] * len(recs)
-    for s, ps in by.items():
-        nonces = [T.nonce_of(ver, ivs[s], seqs[p], recs[p]) for p in ps]
-        aads = [T.aad_of(ver, seqs[p], recs[p]) for p in ps]
-        datas = [recs[p][h:-16] for p in ps]
-        aoff, doff = [0], [0]
-        for a, d in zip(aads, datas):
-            aoff.append(aoff[-1] + len(a)); doff.append(doff[-1] + len(d))
-        data = b"".join(datas)
-        ct = ctypes.create_string_buffer(max(len(data), 1))
-        tags = ctypes.create_string_buffer(16 * len(ps))
-        rc = evp.evp_frames_crypt(len(ps), key_len, keys[key_len * s:key_len * (s + 1)], b"".join(nonces), b"".join(aads), _u64(aoff), 0, data or b"\0", _u64(doff), 0,
-                                  ctypes.addressof(ct), ctypes.addressof(tags))
-        assert rc == 0
-        ctb, tgb = ct.raw, tags.raw
-        for i, p in enumerate(ps):
-            out[p] = recs[p][:h] + ctb[doff[i]:doff[i + 1]] + tgb[16 * i:16 * i + 16]
-    return out
 
 
 def _make_records(rng, ver, n, seed, lens=None, max_payload=2048, aligned=False):

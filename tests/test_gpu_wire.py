@@ -2,56 +2,15 @@
 slot's salt and header bytes.  The published MACsec vectors as wire frames in every kernel shape; random populations of MACsec and ESP frames against libcrypto
 (oracle/evp_batch.c), every frame and every byte around the frames compared; bit-identity with aesgcm_keytab_crypt_dev on the split form of the same frames (the one
 comparison against the library itself, labelled); containment, tampering and aesgcm_wipe_failed_dev, refusals, the salt's life cycle and stream ordering."""
-import ctypes
 import random
 
 import pytest
 
 from kt_common import CANARY, _collect, _layout, _u32, _u64, _up, evp  # noqa: F401
+from kt_common import wire_fields as _fields, wire_ref_encrypt as _ref_encrypt, wire_split as _split
 from util import golden, splitmix_bytes
 
 pytestmark = pytest.mark.gpu
-
-
-def _fields(fmt):
-    return fmt.aad_len, fmt.hdr_len, fmt.iv_off, fmt.salt_len, fmt.tag_len, bool(fmt.flags & 1)
-
-
-def _split(fmt, salt, f):
-    """one wire frame -> (nonce, aad, payload) as the format defines them"""
-    aad_len, hdr_len, iv_off, salt_len, tag_len, auth_only = _fields(fmt)
-    body = len(f) - tag_len
-    nonce = salt[:salt_len] + f[iv_off:iv_off + 12 - salt_len]
-    return nonce, (f[:body] if auth_only else f[:aad_len]), (b"" if auth_only else f[hdr_len:body])
-
-
-def _ref_encrypt(evp, key_len, keys, salts, fmt, slots, frames):
-    """the expected wire frames from libcrypto: per slot one evp_frames_crypt call over that slot's frames"""
-    tag_len = fmt.tag_len
-    by = {}
-    for p, s in enumerate(slots):
-        by.setdefault(s, []).append(p)
-    out = [None] * len(frames)
-    for s, ps in by.items():
-        ivs, aads, datas = [], [], []
-        for p in ps:
-            nonce, a, d = _split(fmt, salts[s], frames[p])
-            ivs.append(nonce); aads.append(a); datas.append(d)
-        aoff, doff = [0], [0]
-        for a, d in zip(aads, datas):
-            aoff.append(aoff[-1] + len(a)); doff.append(doff[-1] + len(d))
-        aad, data = b"".join(aads), b"".join(datas)
-        ct = ctypes.create_string_buffer(max(len(data), 1))
-        tags = ctypes.create_string_buffer(16 * len(ps))
-        rc = evp.evp_frames_crypt(len(ps), key_len, keys[key_len * s:key_len * (s + 1)], b"".join(ivs), aad or b"\0", _u64(aoff), 0, data or b"\0", _u64(doff), 0,
-                                  ctypes.addressof(ct), ctypes.addressof(tags))
-        assert rc == 0
-        ctb, tgb = ct.raw, tags.raw
-        for i, p in enumerate(ps):
-            f = frames[p]
-            front = len(f) - tag_len - (doff[i + 1] - doff[i])
-            out[p] = f[:front] + ctb[doff[i]:doff[i + 1]] + tgb[16 * i:16 * i + tag_len]
-    return out
 
 
 def _make_frames(rng, fmt, n, seed, max_payload=1514, aligned=False):

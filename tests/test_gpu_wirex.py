@@ -4,77 +4,16 @@ in the frame) and ESP with extended sequence numbers (RFC 4303 / RFC 4106 sectio
 Random populations, every byte of the buffer compared, canaries included; where the number goes; the XPN state's life cycle and stream ordering; refusals; and, labelled
 as such, two comparisons of the library with itself (ext 0 against the base call, XPN with a zero salt against the classic MACsec nonce).
 No published XPN vector is among the fixtures, so none is used."""
-import ctypes
 import random
 import struct
 
 import pytest
 
 from kt_common import CANARY, _collect, _layout, _u32, _u64, _up, evp  # noqa: F401
+from kt_common import Sa, x_ref_encrypt as _ref_encrypt
 from util import splitmix_bytes
 
 pytestmark = pytest.mark.gpu
-
-
-def _xor(a, b):
-    return bytes(x ^ y for x, y in zip(a, b))
-
-
-class Sa:
-    """what the slots hold besides their keys: the classic 8-byte salt, the 12-byte XPN salt and the SSCI"""
-
-    def __init__(self, n_slots, seed):
-        sb, xb, cb = splitmix_bytes(seed, 8 * n_slots), splitmix_bytes(seed + 1, 12 * n_slots), splitmix_bytes(seed + 2, 4 * n_slots)
-        self.salt = [sb[8 * s:8 * s + 8] for s in range(n_slots)]
-        self.xsalt = [xb[12 * s:12 * s + 12] for s in range(n_slots)]
-        self.ssci = [cb[4 * s:4 * s + 4] for s in range(n_slots)]
-
-
-def _split(xf, sa, slot, hi, f):
-    """one wire frame -> (nonce, aad, payload) by the standards' formulas"""
-    b = xf.f
-    body = len(f) - b.tag_len
-    auth_only = bool(b.flags & 1)
-    if xf.ext == 1:          # 802.1AEbw: salt XOR (SSCI | PN), the PN big-endian = hi, then the SecTAG's PN field
-        nonce = _xor(sa.xsalt[slot], sa.ssci[slot] + struct.pack(">I", hi) + f[b.iv_off:b.iv_off + 4])
-        aad = f[:body] if auth_only else f[:b.aad_len]
-    elif xf.ext == 2:        # RFC 4106: salt | IV field; RFC 4303: SPI | seq-hi | seq-lo
-        nonce = sa.salt[slot][:4] + f[b.iv_off:b.iv_off + 8]
-        aad = f[0:4] + struct.pack(">I", hi) + f[4:8]
-    else:
-        nonce = sa.salt[slot][:b.salt_len] + f[b.iv_off:b.iv_off + 12 - b.salt_len]
-        aad = f[:body] if auth_only else f[:b.aad_len]
-    return nonce, aad, (b"" if auth_only else f[b.hdr_len:body])
-
-
-def _ref_encrypt(evp, key_len, keys, sa, xf, slots, his, frames):
-    """the expected wire frames from libcrypto: per slot one evp_frames_crypt call over that slot's frames"""
-    tag_len = xf.f.tag_len
-    by = {}
-    for p, s in enumerate(slots):
-        by.setdefault(s, []).append(p)
-    out = [None] * len(frames)
-    for s, ps in by.items():
-        ivs, aads, datas = [], [], []
-        for p in ps:
-            nonce, a, d = _split(xf, sa, s, his[p], frames[p])
-            assert len(nonce) == 12
-            ivs.append(nonce); aads.append(a); datas.append(d)
-        aoff, doff = [0], [0]
-        for a, d in zip(aads, datas):
-            aoff.append(aoff[-1] + len(a)); doff.append(doff[-1] + len(d))
-        aad, data = b"".join(aads), b"".join(datas)
-        ct = ctypes.create_string_buffer(max(len(data), 1))
-        tags = ctypes.create_string_buffer(16 * len(ps))
-        rc = evp.evp_frames_crypt(len(ps), key_len, keys[key_len * s:key_len * (s + 1)], b"".join(ivs), aad or b"\0", _u64(aoff), 0, data or b"\0", _u64(doff), 0,
-                                  ctypes.addressof(ct), ctypes.addressof(tags))
-        assert rc == 0
-        ctb, tgb = ct.raw, tags.raw
-        for i, p in enumerate(ps):
-            f = frames[p]
-            front = len(f) - tag_len - (doff[i + 1] - doff[i])
-            out[p] = f[:front] + ctb[doff[i]:doff[i + 1]] + tgb[16 * i:16 * i + tag_len]
-    return out
 
 
 def _make_frames(rng, xf, n, seed, max_payload=1514, aligned=False):
