@@ -1,13 +1,28 @@
-// aesgcm_abi.hip -- the C ABI of include/aesgcm.h: every exported entry point of libaesgcm_hip.so except the inter-GPU exchange (aesgcm_comm.hip).  Argument checks,
-// the order of calls into the host runtime (aesgcm_host.hip) and the launch of the packet kernels' shapes; no device code (aesgcm_internal.h).
+// aesgcm_abi.hip -- the C ABI of include/aesgcm.h: every exported entry point of libaesgcm_hip.so except the inter-GPU exchange (aesgcm_comm.hip).  Argument checks
+// and the order of calls into the host runtime (aesgcm_host.hip), which plans and makes every launch; no device code (aesgcm_internal.h).
 #include "aesgcm_internal.h"
 
-#include <algorithm>
 #include <new>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
+
+// The caller's arrays and counts as a parameter struct, everything else zero: what PktParams, RowsParams and BatchParams name alike.
+template <class P> static P pkt_args(const void *ivs, const void *aad, const void *in, void *out, void *tags, const void *expect, int *auth, const uint64_t *data_off, const uint64_t *aad_off, size_t n_pkts, size_t pkt_len, size_t aad_len) {
+    P p;
+    memset(&p, 0, sizeof p);
+    p.ivs = (const unsigned char *)ivs; p.aad = (const unsigned char *)aad; p.in = (const unsigned char *)in;
+    p.out = (unsigned char *)out; p.tags = (unsigned char *)tags; p.expect = (const unsigned char *)expect; p.auth = auth;
+    p.data_off = (const u64 *)data_off; p.aad_off = (const u64 *)aad_off;
+    p.n_pkts = (u32)n_pkts; p.pkt_len = (u32)pkt_len; p.aad_len = (u32)aad_len;
+    return p;
+}
+// ... with the packets' keys (the count is batch_plan's to fill in)
+static BatchParams batch_args(const void *keys, const void *ivs, const void *aad, const void *in, void *out, void *tags, const void *expect, int *auth, const uint64_t *data_off, const uint64_t *aad_off, size_t pkt_len, size_t aad_len, bool aligned) {
+    BatchParams p = pkt_args<BatchParams>(ivs, aad, in, out, tags, expect, auth, data_off, aad_off, 0, pkt_len, aad_len);
+    p.keys = (const unsigned char *)keys; p.aligned = aligned;
+    return p;
+}
 
 extern "C" {
 
@@ -72,44 +87,7 @@ int aesgcm_ctx_rekey(aesgcm_ctx *c, const uint8_t *key, size_t key_len) {
     return ctx_load_key(c, key, key_len, 0);
 }
 
-int aesgcm_ctx_destroy(aesgcm_ctx *c) {
-    if (!c) return AESGCM_OK;
-    { std::lock_guard<std::mutex> lk(g_mu); g_ctxs.erase(std::remove(g_ctxs.begin(), g_ctxs.end(), c), g_ctxs.end()); }
-    hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->ev_session) { hipEventSynchronize(c->ev_session); hipEventDestroy(c->ev_session); }      // (a session's last chunk may be on a caller's stream)
-    for (auto &e : c->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    for (auto &e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    if (c->km) { hipMemset(c->km, 0, sizeof(KeyMaterial)); hipFree(c->km); }
-    if (c->d_keystage) hipFree(c->d_keystage);
-    if (c->parts) hipFree(c->parts);
-    if (c->fold_a) hipFree(c->fold_a);
-    if (c->fold_b) hipFree(c->fold_b);
-    if (c->d_counter) hipFree(c->d_counter);
-    if (c->d_cyc) hipFree(c->d_cyc);
-    if (c->d_tag) hipFree(c->d_tag);
-    if (c->h_tag) hipHostFree(c->h_tag);
-    if (c->h_mtag) hipHostFree(c->h_mtag);
-    if (c->d_mtag) hipFree(c->d_mtag);
-    if (c->d_trace) hipFree(c->d_trace);
-    if (c->rows_buf) hipFree(c->rows_buf);
-    if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); }
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
-    pipeline_release(c);
-    if (c->st_in) hipFree(c->st_in);
-    if (c->st_out) hipFree(c->st_out);
-    if (c->st_aad) hipFree(c->st_aad);
-    if (c->ev_sync) hipEventDestroy(c->ev_sync);
-    if (c->ev_fused) hipEventDestroy(c->ev_fused);
-    if (c->stream) {                                            // idle by now (synchronised above): kept for the device's next context, up to 64 of them
-        std::lock_guard<std::mutex> lk(g_mu);
-        if (c->device >= 0 && c->device < (int)g_dev.size() && g_dev[c->device].streams.size() < 64) { g_dev[c->device].streams.push_back(c->stream); c->stream = nullptr; }
-    }
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
-    return AESGCM_OK;
-}
+int aesgcm_ctx_destroy(aesgcm_ctx *c) { return ctx_destroy(c); }
 
 int aesgcm_ctx_device(const aesgcm_ctx *c) { return c ? c->device : AESGCM_EARG; }
 
@@ -155,10 +133,6 @@ int aesgcm_ctx_stream(const aesgcm_ctx *c, void **stream) {
     return AESGCM_OK;
 }
 
-// Everything enqueued from now on on `c`'s own stream starts only after everything enqueued so far on `other`'s own stream
-// has completed (one event record + one stream wait; no host synchronisation).  Two contexts of one key on one device
-// have separate scratch sets and streams, so consecutive messages can alternate between them and message m+1's fused
-// kernel starts while message m's k_fold / k_combine drain; this call orders the step that needs both (the all-gather).
 // the context's status word (pinned host memory, h_tag[2]: {code, 0, detail lo, detail hi}; written by k_rows_plan* when it refuses a call): as an error code, without clearing it
 static int status_pending(const aesgcm_ctx *c) {
     const u32 code = __atomic_load_n(reinterpret_cast<const u32 *>(c->h_tag + 2), __ATOMIC_ACQUIRE);
@@ -176,6 +150,10 @@ int aesgcm_ctx_status(aesgcm_ctx *c, int *code, uint64_t *detail) {
     return AESGCM_OK;
 }
 
+// Everything enqueued from now on on `c`'s own stream starts only after everything enqueued so far on `other`'s own stream
+// has completed (one event record + one stream wait; no host synchronisation).  Two contexts of one key on one device
+// have separate scratch sets and streams, so consecutive messages can alternate between them and message m+1's fused
+// kernel starts while message m's k_fold / k_combine drain; this call orders the step that needs both (the all-gather).
 int aesgcm_ctx_wait(aesgcm_ctx *c, aesgcm_ctx *other) {
     if (!c || !other) return AESGCM_EARG;
     { const int rc = status_pending(other); if (rc) return rc; }            // what `other` was asked to do and refused (aesgcm_ctx_status)
@@ -501,23 +479,7 @@ int aesgcm_shard_finalize_batch_dev(aesgcm_ctx *c, size_t n_msgs, const uint8_t 
     }
     { const hipError_t le = klaunch_combine_batch((unsigned)n_msgs, st, c->km, c->tables, b); if (le != hipSuccess) { gen_give_back(c); return hip_fail(le, "k_combine_batch launch"); } }
     // every workgroup publishes its own generation word behind its tag: poll them all (short), then fall back to the stream
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    bool seen = false;
-    for (u32 spin = 0; !seen; ++spin) {
-        seen = true;
-        for (size_t m = 0; m < n_msgs; m++)
-            if (__atomic_load_n(reinterpret_cast<volatile u64 *>(c->h_mtag + 2 * m + 1), __ATOMIC_ACQUIRE) != gen) { seen = false; break; }
-        if (seen) break;
-        if ((spin & 63u) == 63u) {
-            clock_gettime(CLOCK_MONOTONIC, &t1);
-            if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > c->poll_ns) break;
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!seen) HIPCHK(hipStreamSynchronize(st));
+    if (!poll_gens(reinterpret_cast<const volatile u64 *>(c->h_mtag + 1), n_msgs, 4, gen, c->poll_ns)) HIPCHK(hipStreamSynchronize(st));      // (a slot is two uint4: the word is 4 u64 from the next)
     for (size_t m = 0; m < n_msgs; m++) memcpy(tags + 16 * m, c->h_mtag + 2 * m, 16);
     return AESGCM_OK;
 }
@@ -706,15 +668,10 @@ int aesgcm_messages_crypt_dev(aesgcm_ctx *c, int decrypt, size_t n_msgs, const v
     if (decrypt && c->wipe_on_auth_fail && d_expect_tags && !d_auth) return AESGCM_EARG;      // "no unauthenticated plaintext" needs the per-message verdicts: without d_auth nothing would be compared, nothing wiped
     if (n_msgs >= (((size_t)1) << 31)) return AESGCM_ETOOLONG;
     HIPCHK(hipSetDevice(c->device));
-    RowsParams r;
-    memset(&r, 0, sizeof r);
-    r.ivs = (const unsigned char *)d_ivs; r.tags = (unsigned char *)d_tags; r.expect = (const unsigned char *)d_expect_tags; r.auth = d_auth;
+    RowsParams r = pkt_args<RowsParams>(d_ivs, nullptr, nullptr, nullptr, d_tags, d_expect_tags, d_auth, nullptr, nullptr, n_msgs, 0, 0);
     r.in_ptr = (const u64 *)d_in_ptr; r.out_ptr = (const u64 *)d_out_ptr; r.aad_ptr = (const u64 *)d_aad_ptr; r.len_arr = d_len; r.alen_arr = d_aad_len;
-    r.n_pkts = (u32)n_msgs;
     // routed per message (round 6): the short ones are the packet kernels', which read the same arrays
-    PktParams k;
-    memset(&k, 0, sizeof k);
-    k.ivs = r.ivs; k.tags = r.tags; k.expect = r.expect; k.auth = d_auth;
+    PktParams k = pkt_args<PktParams>(d_ivs, nullptr, nullptr, nullptr, d_tags, d_expect_tags, d_auth, nullptr, nullptr, 0, 0, 0);      // (the count: packets_rows)
     k.aligned = 1;                                                                      // per message: its two addresses decide (pkt_info)
     const int rc = packets_rows(c, decrypt, r, pick_stream(c, stream), &k);
     if (!rc && decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_msgs, nullptr, 0, nullptr, d_auth, pick_stream(c, stream), (const u64 *)d_out_ptr, d_len, r.hdr);      // (r.hdr: nothing behind a refused call)
@@ -732,75 +689,21 @@ int aesgcm_packets_crypt_dev(aesgcm_ctx *c, int decrypt, size_t n_pkts, const vo
     if (decrypt && c->wipe_on_auth_fail && d_expect_tags && !d_auth) return AESGCM_EARG;      // "no unauthenticated plaintext" needs the per-packet verdicts: without d_auth nothing would be compared, nothing wiped
     if (n_pkts >= (((size_t)1) << 31) || pkt_len >= (((size_t)1) << 28) || aad_len >= (((size_t)1) << 28)) return AESGCM_ETOOLONG;
     HIPCHK(hipSetDevice(c->device));
-    PktParams p;
-    memset(&p, 0, sizeof p);
-    p.ivs = (const unsigned char *)d_ivs; p.aad = (const unsigned char *)d_aad; p.in = (const unsigned char *)d_in;
-    p.out = (unsigned char *)d_out; p.tags = (unsigned char *)d_tags; p.expect = (const unsigned char *)d_expect_tags; p.auth = d_auth;
-    p.data_off = (const u64 *)d_data_off; p.aad_off = (const u64 *)d_aad_off;
-    p.n_pkts = (u32)n_pkts; p.pkt_len = (u32)pkt_len; p.aad_len = (u32)aad_len;
+    PktParams p = pkt_args<PktParams>(d_ivs, d_aad, d_in, d_out, d_tags, d_expect_tags, d_auth, d_data_off, d_aad_off, n_pkts, pkt_len, aad_len);
     p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0 && (d_data_off || pkt_len % 16 == 0);
     // Offset arrays: the lengths are on the device, and so is the choice (round 6) -- every message is ROUTED by its own size, the long ones by rows, the short ones
     // through the packet kernels, in one call (the reference's own traffic is both at once: tb/gcm_gctr.py:279-281 draws lengths from a U-shaped distribution).
     // pkt_len is ignored in this form.  Fixed-size records: the host knows the one size and routes the whole call (packets_by_rows).
     const bool routed = d_data_off != nullptr;
     if (routed || packets_by_rows(c, n_pkts, pkt_len)) {                          // message-sized packets: the rows of all of them through k_body's row loop
-        RowsParams r;
-        memset(&r, 0, sizeof r);
-        r.ivs = (const unsigned char *)d_ivs; r.aad = (const unsigned char *)d_aad; r.in = (const unsigned char *)d_in;
-        r.out = (unsigned char *)d_out; r.tags = (unsigned char *)d_tags; r.expect = (const unsigned char *)d_expect_tags; r.auth = d_auth;
-        r.data_off = (const u64 *)d_data_off; r.aad_off = (const u64 *)d_aad_off;
-        r.n_pkts = (u32)n_pkts; r.pkt_len = routed ? 0u : (u32)pkt_len; r.aad_len = (u32)aad_len;
+        RowsParams r = pkt_args<RowsParams>(d_ivs, d_aad, d_in, d_out, d_tags, d_expect_tags, d_auth, d_data_off, d_aad_off, n_pkts, routed ? 0 : pkt_len, aad_len);
         const int rc = packets_rows(c, decrypt, r, pick_stream(c, stream), routed ? &p : nullptr);
         if (!rc && decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_pkts, d_out, pkt_len, (const u64 *)d_data_off, d_auth, pick_stream(c, stream), nullptr, nullptr, r.hdr);
         return rc;
     }
-    const u32 n_cu = (u32)c->G / 2;                                                 // c->G = two workgroups per CU
-    int lg = packets_pick_lg(n_cu, n_pkts, pkt_len);                       // (fixed-size records from here on: offset arrays took the routed path above)
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.pkt_lanes) lg = g_force.pkt_lanes == 1 ? 0 : g_force.pkt_lanes == 64 ? 6 : g_force.pkt_lanes == 16 ? 4 : g_force.pkt_lanes == 8 ? 3 : 2;
-#endif
-    const int shape = lg == 0 ? 'l' : lg == 6 ? 'w' : 'g';
-    hipError_t launch_err = hipSuccess;
-    hipStream_t st = pick_stream(c, stream);
-    p.counter = c->d_counter; p.counter_base = c->counter_base;
-    if (shape == 'l') {
-        const u32 nb = (u32)((n_pkts + 63) / 64);
-        // the ILP form (512-lane workgroups, eight independent keystream chains per line) while the packets fit one round of it; its workgroups are spread over
-        // all CUs, a wave of 64 packets each first
-        // Measured, AES-256, GiB/s 768-lane form / ILP form (profiles/r04/packets_sweep_ilp_aes256.txt): 1 KiB packets 16384 66 / 78, 65536 255 / 306, 131072 481 / 592;
-        // 256 B 32768 99 / 95, 98304 245 / 266, 131072 295 / 330; 64 B (no whole line to work on) 16384 27 / 19.
-        // Packets shorter than two lines gain from it only once they fill the chip (fewer, fatter waves): 196608 x 256 B 380 / 414, 262144 442 / 460 (2^20: 682 / 642);
-        // 64 B 196608 127 / 146, 393216 183 / 201, 2^20 254 / 266.
-        bool ilp = n_pkts <= (size_t)n_cu * AESGCM_PKTL_WG_ILP ? (pkt_len >= 512 || (pkt_len >= 256 && n_pkts >= 49152))
-                                                                : (n_pkts >= (size_t)n_cu * AESGCM_PKTL_WG && (pkt_len <= 64 || (pkt_len <= 256 && n_pkts <= 300000)));
-#ifdef AESGCM_DEBUG_KNOBS
-        if (g_force.pkt_ilp) ilp = g_force.pkt_ilp == 1;
-#endif
-        const u32 waves_per_wg = (ilp ? AESGCM_PKTL_WG_ILP : AESGCM_PKTL_WG) / 64;
-        u32 wgs = ilp ? nb : (nb + waves_per_wg - 1) / waves_per_wg;
-        if (wgs > n_cu) wgs = n_cu;                                                  // one workgroup per CU (registers, and with four T-tables the LDS)
-        c->counter_base += nb + wgs * waves_per_wg;                                 // every wave ends on one failing fetch
-        launch_err = klaunch_pktl(c->nr, decrypt, ilp, wgs, st, c->km, c->tables, p);
-    } else {
-        const u32 P = 64u >> lg;                                                    // packets per wave-iteration
-        p.plain = (lg == 6 || lg == 2) && !d_aad_off && !aad_len && p.aligned && pkt_len && pkt_len % ((size_t)16 << lg) == 0;
-        const u32 waves_per_wg = (u32)PKTG_WG(lg) / 64;
-        // deal: about 4 dispenser fetches per resident wave, a multiple of P, at most 64 packets (one E_K(J0) pass per fetch)
-        u32 deal = (u32)(n_pkts / ((size_t)n_cu * waves_per_wg * 4));
-        deal = deal / P * P;
-        deal = deal < P ? P : deal > PKTG_MAX_DEAL ? PKTG_MAX_DEAL : deal;
-#ifdef AESGCM_DEBUG_KNOBS
-        if (g_force.pkt_deal >= 1 && g_force.pkt_deal <= (int)PKTG_MAX_DEAL) deal = ((u32)g_force.pkt_deal + P - 1) / P * P;
-#endif
-        p.deal = deal;
-        const u32 nb = (u32)((n_pkts + deal - 1) / deal);
-        u32 wgs = (nb + waves_per_wg - 1) / waves_per_wg;
-        if (wgs > n_cu) wgs = n_cu;                                                  // one workgroup per CU (LDS)
-        c->counter_base += nb + wgs * waves_per_wg;                                 // every wave ends on one failing fetch
-        launch_err = klaunch_pktg(c->nr, decrypt, lg, wgs, st, c->km, c->tables, p);
-    }
-    const hipError_t le = launch_err;
-    if (le != hipSuccess) { c->counter_base = p.counter_base; return hip_fail(le, "k_pkt launch"); }
+    hipStream_t st = pick_stream(c, stream);                                       // (fixed-size records from here on: offset arrays took the routed path above)
+    const int rc = packets_launch(c, decrypt, p, st);
+    if (rc) return rc;
     if (decrypt && c->wipe_on_auth_fail && d_expect_tags) return wipe_failed(c->device, n_pkts, d_out, pkt_len, nullptr, d_auth, st);
     return AESGCM_OK;
 }
@@ -828,14 +731,9 @@ int aesgcm_frames_ceiling_probe_dev(aesgcm_ctx *c, size_t n_pkts, const void *d_
     if (!c || !n_pkts || !d_ivs || !d_tags || !d_data_off || (d_aad_off && !d_aad)) return AESGCM_EARG;
     if (n_pkts >= (((size_t)1) << 31)) return AESGCM_ETOOLONG;
     HIPCHK(hipSetDevice(c->device));
-    PktParams p;
-    memset(&p, 0, sizeof p);
-    p.ivs = (const unsigned char *)d_ivs; p.aad = (const unsigned char *)d_aad; p.tags = (unsigned char *)d_tags;
-    p.data_off = (const u64 *)d_data_off; p.aad_off = (const u64 *)d_aad_off;
-    p.n_pkts = (u32)n_pkts; p.aligned = 1;
-    RowsParams r;
-    memset(&r, 0, sizeof r);
-    r.ivs = p.ivs; r.aad = p.aad; r.tags = p.tags; r.data_off = p.data_off; r.aad_off = p.aad_off; r.n_pkts = (u32)n_pkts;
+    PktParams p = pkt_args<PktParams>(d_ivs, d_aad, nullptr, nullptr, d_tags, nullptr, nullptr, d_data_off, d_aad_off, n_pkts, 0, 0);
+    p.aligned = 1;
+    RowsParams r = pkt_args<RowsParams>(d_ivs, d_aad, nullptr, nullptr, d_tags, nullptr, nullptr, d_data_off, d_aad_off, n_pkts, 0, 0);
     return packets_rows(c, 2, r, pick_stream(c, stream), &p);
 }
 
@@ -845,13 +743,7 @@ int aesgcm_batch_crypt_dev(int device, int decrypt, size_t n_pkts, size_t key_le
     if (!n_pkts) return AESGCM_OK;
     if (!d_keys || !d_ivs || !d_tags || (aad_len && !d_aad) || (pkt_len && (!d_in || !d_out))) return AESGCM_EARG;
     if (pkt_len >= (((size_t)1) << 28) || aad_len >= (((size_t)1) << 28)) return AESGCM_ETOOLONG;
-    BatchParams p;
-    memset(&p, 0, sizeof p);
-    p.keys = (const unsigned char *)d_keys; p.ivs = (const unsigned char *)d_ivs; p.aad = (const unsigned char *)d_aad;
-    p.in = (const unsigned char *)d_in; p.out = (unsigned char *)d_out; p.tags = (unsigned char *)d_tags;
-    p.expect = (const unsigned char *)d_expect_tags; p.auth = d_auth;
-    p.pkt_len = (u32)pkt_len; p.aad_len = (u32)aad_len;
-    p.aligned = (pkt_len % 16 == 0) && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
+    BatchParams p = batch_args(d_keys, d_ivs, d_aad, d_in, d_out, d_tags, d_expect_tags, d_auth, nullptr, nullptr, pkt_len, aad_len, (pkt_len % 16 == 0) && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0);
     return batch_launch(device, decrypt, n_pkts, key_len, p, stream);
 }
 
@@ -862,11 +754,7 @@ int aesgcm_batch_crypt_dev(int device, int decrypt, size_t n_pkts, size_t key_le
 int aesgcm_batch_ceiling_probe_dev(int device, size_t n_pkts, size_t key_len, const void *d_keys, const void *d_ivs, size_t pkt_len, void *d_tags, void *stream) {
     if (!n_pkts || !d_keys || !d_ivs || !d_tags || !pkt_len) return AESGCM_EARG;
     if (pkt_len >= (((size_t)1) << 28)) return AESGCM_ETOOLONG;
-    BatchParams p;
-    memset(&p, 0, sizeof p);
-    p.keys = (const unsigned char *)d_keys; p.ivs = (const unsigned char *)d_ivs; p.tags = (unsigned char *)d_tags;
-    p.pkt_len = (u32)pkt_len;
-    p.aligned = pkt_len % 16 == 0;
+    BatchParams p = batch_args(d_keys, d_ivs, nullptr, nullptr, nullptr, d_tags, nullptr, nullptr, nullptr, nullptr, pkt_len, 0, pkt_len % 16 == 0);
     return batch_launch(device, 2, n_pkts, key_len, p, stream);
 }
 
@@ -875,13 +763,7 @@ int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts, size_t ke
                                void *d_out, void *d_tags, const void *d_expect_tags, int *d_auth, void *stream) {
     if (!n_pkts) return AESGCM_OK;
     if (!d_keys || !d_ivs || !d_tags || !d_data_off || !d_in || !d_out || (d_aad_off && !d_aad)) return AESGCM_EARG;
-    BatchParams p;
-    memset(&p, 0, sizeof p);
-    p.keys = (const unsigned char *)d_keys; p.ivs = (const unsigned char *)d_ivs; p.aad = d_aad_off ? (const unsigned char *)d_aad : nullptr;
-    p.in = (const unsigned char *)d_in; p.out = (unsigned char *)d_out; p.tags = (unsigned char *)d_tags;
-    p.expect = (const unsigned char *)d_expect_tags; p.auth = d_auth;
-    p.data_off = (const u64 *)d_data_off; p.aad_off = (const u64 *)d_aad_off;
-    p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;      // per packet: and its offset is a multiple of 16
+    BatchParams p = batch_args(d_keys, d_ivs, d_aad_off ? d_aad : nullptr, d_in, d_out, d_tags, d_expect_tags, d_auth, d_data_off, d_aad_off, 0, 0, (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0);      // per packet: and its offset is a multiple of 16
     return batch_launch(device, decrypt, n_pkts, key_len, p, stream);
 }
 
@@ -893,11 +775,7 @@ int aesgcm_batch_shape(int device, size_t n_pkts, size_t pkt_len, int var_len, i
     DeviceState *ds;
     int rc = device_state(device, &ds);
     if (rc) return rc;
-    int lg = batch_pick_lg(ds->n_cu, n_pkts, pkt_len, var_len != 0);
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.batch_lanes) lg = g_force.batch_lanes == 8 ? 3 : g_force.batch_lanes == 16 ? 4 : 6;
-#endif
-    *lanes_per_packet = 1 << lg;
+    *lanes_per_packet = 1 << batch_lg(ds, n_pkts, pkt_len, var_len != 0);
     return AESGCM_OK;
 }
 
@@ -905,11 +783,7 @@ int aesgcm_packets_shape(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len, int
     if (!c || !lanes_per_packet || !n_pkts) return AESGCM_EARG;
     if (var_len) { *lanes_per_packet = AESGCM_SHAPE_MIXED; return AESGCM_OK; }         // the lengths are on the device: every message is routed there, by rows or to the packet kernels
     if (packets_by_rows(c, n_pkts, pkt_len)) { *lanes_per_packet = AESGCM_SHAPE_ROWS; return AESGCM_OK; }
-    int lg = packets_pick_lg((u32)c->G / 2, n_pkts, pkt_len);
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.pkt_lanes) lg = g_force.pkt_lanes == 1 ? 0 : g_force.pkt_lanes == 64 ? 6 : g_force.pkt_lanes == 16 ? 4 : g_force.pkt_lanes == 8 ? 3 : 2;
-#endif
-    *lanes_per_packet = 1 << lg;
+    *lanes_per_packet = 1 << packets_lg(c, n_pkts, pkt_len);
     return AESGCM_OK;
 }
 

@@ -227,7 +227,7 @@ bool cyc_capable(const aesgcm_ctx *c) {
 }
 // Is a message of ANOTHER context of this device under way right now?  Every result goes to its context's pinned host slot with the generation number of its
 // launch behind it, so "under way" is: the slot does not show the generation last launched.  What the half shape of the cyclic rows is for (two messages
-// share every CU); asked once per whole-message launch, a mutex and a few loads.  Contexts register in ctx_create_common and leave in aesgcm_ctx_destroy.
+// share every CU); asked once per whole-message launch, a mutex and a few loads.  Contexts register in ctx_create_common and leave in ctx_destroy.
 std::vector<aesgcm_ctx *> &g_ctxs = *new std::vector<aesgcm_ctx *>();          // never destroyed: contexts may be destroyed after this library's static destructors have run
 bool others_in_flight(const aesgcm_ctx *c) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -407,21 +407,8 @@ int crypt_dev(aesgcm_ctx *c, int dec, const uint8_t iv[12], const void *d_aad, u
 // result the moment the tag is there.  Tags that come from k_combine or k_main's tail are published by the last kernel of the call.
 int fetch_tag(aesgcm_ctx *c, hipStream_t st, uint8_t tag[16]) {
     const u64 want = gen_now(c);
-    volatile u64 *gen = reinterpret_cast<volatile u64 *>(c->h_tag + 1);
-    bool seen = false;
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (u32 spin = 0;; ++spin) {                                 // poll for at most ~200 us, then block in the runtime
-        if (__atomic_load_n(gen, __ATOMIC_ACQUIRE) == want) { seen = true; break; }
-        if ((spin & 63u) == 63u) {
-            clock_gettime(CLOCK_MONOTONIC, &t1);
-            if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > c->poll_ns) break;
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!seen) {
+    const volatile u64 *gen = reinterpret_cast<const volatile u64 *>(c->h_tag + 1);
+    if (!poll_gens(gen, 1, 0, want, c->poll_ns)) {                  // poll for at most ~200 us, then block in the runtime
         HIPCHK(hipStreamSynchronize(st));
         // the stream the message was enqueued on has drained: its tag is there -- unless `st` is not that stream, or the launch failed after the number was taken
         if (__atomic_load_n(gen, __ATOMIC_ACQUIRE) != want) {
@@ -431,6 +418,23 @@ int fetch_tag(aesgcm_ctx *c, hipStream_t st, uint8_t tag[16]) {
     }
     memcpy(tag, c->h_tag, 16);
     return AESGCM_OK;
+}
+// The poll of a host slot: up to poll_ns, wait for the n generation words at w, `stride` words apart, to show `gen`; whether all did.  The clock is read every 64th turn.
+bool poll_gens(const volatile u64 *w, size_t n, size_t stride, u64 gen, long poll_ns) {
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (u32 spin = 0;; ++spin) {
+        size_t m = 0;
+        while (m < n && __atomic_load_n(w + m * stride, __ATOMIC_ACQUIRE) == gen) m++;
+        if (m == n) return true;
+        if ((spin & 63u) == 63u) {
+            clock_gettime(CLOCK_MONOTONIC, &t1);
+            if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > poll_ns) return false;
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
 }
 
 int ct_compare16(const uint8_t *a, const uint8_t *b) {
@@ -504,10 +508,50 @@ int ctx_create_common(aesgcm_ctx **out, int device, const uint8_t *key, size_t k
         (e = hipHostMalloc((void **)&c->h_tag, 64, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
         (e = hipHostGetDevicePointer((void **)&c->h_tag_dev, c->h_tag, 0)) != hipSuccess ||
         (memset(c->h_tag, 0, 64), false) ||
-        (e = hipMalloc(&c->d_trace, sizeof(u64) * 4 * AESGCM_GMAX)) != hipSuccess) { aesgcm_ctx_destroy(c); return hip_fail(e, "hipMalloc"); }
-    if ((rc = ctx_load_key(c, key, key_len, pre_nr))) { aesgcm_ctx_destroy(c); return rc; }
+        (e = hipMalloc(&c->d_trace, sizeof(u64) * 4 * AESGCM_GMAX)) != hipSuccess) { ctx_destroy(c); return hip_fail(e, "hipMalloc"); }
+    if ((rc = ctx_load_key(c, key, key_len, pre_nr))) { ctx_destroy(c); return rc; }
     { std::lock_guard<std::mutex> lk(g_mu); g_ctxs.push_back(c); }
     *out = c;
+    return AESGCM_OK;
+}
+
+// ... and everything a context owns given back (also a half-built one: ctx_create_common's failures come through here); its stream stays with the device
+int ctx_destroy(aesgcm_ctx *c) {
+    if (!c) return AESGCM_OK;
+    { std::lock_guard<std::mutex> lk(g_mu); g_ctxs.erase(std::remove(g_ctxs.begin(), g_ctxs.end(), c), g_ctxs.end()); }
+    hipSetDevice(c->device);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->ev_session) { hipEventSynchronize(c->ev_session); hipEventDestroy(c->ev_session); }      // (a session's last chunk may be on a caller's stream)
+    for (auto &e : c->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
+    for (auto &e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
+    if (c->km) { hipMemset(c->km, 0, sizeof(KeyMaterial)); hipFree(c->km); }
+    if (c->d_keystage) hipFree(c->d_keystage);
+    if (c->parts) hipFree(c->parts);
+    if (c->fold_a) hipFree(c->fold_a);
+    if (c->fold_b) hipFree(c->fold_b);
+    if (c->d_counter) hipFree(c->d_counter);
+    if (c->d_cyc) hipFree(c->d_cyc);
+    if (c->d_tag) hipFree(c->d_tag);
+    if (c->h_tag) hipHostFree(c->h_tag);
+    if (c->h_mtag) hipHostFree(c->h_mtag);
+    if (c->d_mtag) hipFree(c->d_mtag);
+    if (c->d_trace) hipFree(c->d_trace);
+    if (c->rows_buf) hipFree(c->rows_buf);
+    if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); }
+    if (c->ev_fork) hipEventDestroy(c->ev_fork);
+    if (c->ev_join) hipEventDestroy(c->ev_join);
+    pipeline_release(c);
+    if (c->st_in) hipFree(c->st_in);
+    if (c->st_out) hipFree(c->st_out);
+    if (c->st_aad) hipFree(c->st_aad);
+    if (c->ev_sync) hipEventDestroy(c->ev_sync);
+    if (c->ev_fused) hipEventDestroy(c->ev_fused);
+    if (c->stream) {                                            // idle by now (synchronised above): kept for the device's next context, up to 64 of them
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (c->device >= 0 && c->device < (int)g_dev.size() && g_dev[c->device].streams.size() < 64) { g_dev[c->device].streams.push_back(c->stream); c->stream = nullptr; }
+    }
+    if (c->stream) hipStreamDestroy(c->stream);
+    delete c;
     return AESGCM_OK;
 }
 
@@ -569,46 +613,24 @@ extern "C" __attribute__((visibility("default"))) int aesgcm_debug_force_shape(c
 }
 #endif
 
-// Packets under ONE key: how many lanes work on one packet, as log2 (0 = one LANE per packet, k_pktl; 2, 3, 4 = a lane GROUP of 4, 8, 16, k_pktg; 6 = a whole
-// wave, k_pktg<.., 6>).  Measured (profiles/archive/r03/packets_sweep_aes256.txt, GiB/s wave / g16 / g8 / g4 / lane): the best shape is the one that just fills the
-// resident lanes (256 CUs x 16 waves x 64) -- 65536 x 1 KiB 203 / 232 / 340 / 384 / 194, 16384 x 4 KiB 235 / 367 / 290 / 177 / 53, 4096 x 16 KiB
-// 362 / 172 / 95 / 49 / 13 (the one regime where a whole wave per packet is right: at most 4096 packets of at least 4 KiB) -- but never more lanes than an
-// eighth of the packet's blocks once the machine is full (closing cost per byte: 16384 x 1 KiB 62 / 128 / 176 / 138 / 50, 16384 x 256 B 16 / 35 / 58 / 72 / 41),
-// a quarter when it is not (4096 x 1 KiB 34 / 69 / 57 / 38 / 13).  Lanes win from 131072 packets (2^20 x 1 KiB 303 / 592 / 657 / 742 / 767; 262144 x 4 KiB
-// 496 / 656 / 704 / 722 / 724), short packets from 32768 (65536 x 256 B 51 / 61 / 95 / 129 / 148).
-int packets_pick_lg(u32 n_cu, size_t n_pkts, size_t pkt_len) {
-    const size_t lanes_total = (size_t)n_cu * (AESGCM_PKT_WG / 64) * 64, lanes_l = (size_t)n_cu * AESGCM_PKTL_WG;
-    const size_t blocks = (pkt_len + 15) / 16;
-    // One lane per packet once the packets fill k_pktl's resident lanes (256 x 768); frames of up to 1 KiB from three quarters of that, short ones much earlier.
-    // Round 4 (profiles/r04/packets_sweep_aes256.txt, after k_pktl's rebuild): 131072 x 4 KiB 553 by lanes against 722 by groups of 4 (196608: 795 / 713),
-    // 131072 x 16 KiB 573 / 789, 131072 x 1 KiB 488 / 509 (196608: 677 / 577), 49152 x 256 B 142 / 124, 16384 x 64 B 28 / 23.
-    // (Offset arrays -- the host does not know the lengths -- are routed on the device since round 6: route_pick_lg, aesgcm_pkt.h, with the measurements behind it.)
-    // k_pktl's ILP form (512-lane workgroups) moves the 1 KiB mark down: 131072 x 1 KiB 592 by lanes against 500 by groups of 4, 98304: 454 / 456.
-    const size_t lanes_ilp = (size_t)n_cu * AESGCM_PKTL_WG_ILP;
-    if (n_pkts >= lanes_l || (pkt_len <= 1024 && 8 * n_pkts >= 7 * lanes_ilp) || (pkt_len <= 256 && n_pkts >= 32768) || (pkt_len <= 64 && n_pkts >= 16384)) return 0;
-    // Lane groups: the group that just fills the resident lanes.  Packets of 4 KiB and more round the fill UP to a power of two (half again as many lanes as
-    // are resident is cheaper than rows twice as long: 49152 x 4 KiB 474 with 4 lanes, 576 with 8; x 16 KiB 542 / 722), shorter ones down (49152 x 1 KiB 325 / 291).
-    size_t fill = lanes_total / n_pkts;
-    if (pkt_len >= 4096 && (fill & (fill - 1))) { size_t f = 1; while (f < fill) f <<= 1; fill = f; }
-    const size_t cap = n_pkts >= 16384 ? blocks / 8 : blocks / 4;
-    const size_t g = fill < cap ? fill : cap;
-    return g >= 64 ? 6 : g >= 16 ? 4 : g >= 8 ? 3 : 2;
+// (the shape rules themselves -- packets_pick_lg, batch_pick_lg, the ILP form, the deals, the grid -- are arithmetic: aesgcm_plan.h)
+#ifdef AESGCM_DEBUG_KNOBS
+// the forced lanes per packet as the kernels' log2, or -1: nothing forced
+static int forced_pkt_lg() { const int f = g_force.pkt_lanes; return !f ? -1 : f == 1 ? 0 : f == 64 ? 6 : f == 16 ? 4 : f == 8 ? 3 : 2; }
+static int forced_batch_lg() { const int f = g_force.batch_lanes; return !f ? -1 : f == 8 ? 3 : f == 16 ? 4 : 6; }
+#endif
+// The shape a call takes, as the planners choose it and as the shape queries report it (aesgcm_packets_shape, aesgcm_batch_shape): the rule, or the forced shape
+int packets_lg(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len) {
+#ifdef AESGCM_DEBUG_KNOBS
+    if (forced_pkt_lg() >= 0) return forced_pkt_lg();
+#endif
+    return packets_pick_lg((u32)c->G / 2, n_pkts, pkt_len);                  // c->G = two workgroups per CU
 }
-
-// Packets with their OWN key (k_batch3): lanes per packet as log2 (3, 4, 6 = 8 / 16 lanes, a whole wave; the two-pass kernel k_batch of rounds 2 - 3 that
-// the numbers below call by name is gone since round 4: k_batch3<.., 6> took its place, 4096 x 1 MiB 443 -> 637 GiB/s).  16 lanes once
-// there are packets enough to fill the machine that way (one 1024-lane workgroup per CU = 64 packets per CU) or the packets are short, else one wave per packet.
-// Measured, AES-128, GiB/s k_batch / k_batch3 (profiles/archive/r03/batch_sweep_aes128.txt): 4096 x 1 KiB 30 / 56, 4096 x 256 B 7.5 / 17, 1024 x 1 KiB 14 / 16.5; 1024 x 4 KiB
-// 45 / 33, 4096 x 4 KiB 108 / 120, 4096 x 16 KiB 286 / 168; from 16384 packets k_batch3 wins at every size (4 KiB 179 / 350).  8 lanes (eight packets per wave
-// share what a wave-iteration pays once) when there are packets enough to fill the chip that way and they are not long: 2^20 packets of 64 B 42 -> 74 GiB/s,
-// 256 B 163 -> 265, 1 KiB 424 -> 560, 1500 B 484 -> 598, 4 KiB 658 -> 706, 16 KiB 770 -> 736; 16384 packets: 1 KiB 125 -> 155, 4 KiB 352 -> 273
-// (profiles/archive/r03c/batch_sweep_lanes8_aes128.txt).  Batches with per-packet lengths (offset arrays on the device: the host does not know the lengths) go by count
-// alone and assume frames of MACsec size, where 8 lanes gain most; a batch of frames beyond 8 KiB loses ~5 % by it.
-int batch_pick_lg(int n_cu, size_t n_pkts, size_t pkt_len, bool var) {
-    int lg = (n_pkts >= (size_t)64 * n_cu || (!var && pkt_len <= 2048)) ? 4 : 6;
-    if (lg == 4 && (var ? n_pkts >= (size_t)64 * n_cu
-                        : ((n_pkts >= (size_t)256 * n_cu && pkt_len <= 8192) || (n_pkts >= (size_t)64 * n_cu && pkt_len <= 2048)))) lg = 3;
-    return lg;
+int batch_lg(const DeviceState *ds, size_t n_pkts, size_t pkt_len, bool var) {
+#ifdef AESGCM_DEBUG_KNOBS
+    if (forced_batch_lg() >= 0) return forced_batch_lg();
+#endif
+    return batch_pick_lg(ds->n_cu, n_pkts, pkt_len, var);
 }
 
 
@@ -732,7 +754,7 @@ int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktP
             const bool probe = decrypt == 2;                                 // aesgcm_frames_ceiling_probe_dev: the packet kernels' instruction stream without the data's traffic -- every message theirs, no row launch
             if (probe) { if (p.len_arr) return AESGCM_EARG; cfg.c_hi = cfg.c_lo = PKT_LEN_CLASSES; }
 #ifdef AESGCM_DEBUG_KNOBS
-            if (g_force.pkt_lanes) cfg.force_lg = g_force.pkt_lanes == 1 ? 0u : g_force.pkt_lanes == 64 ? (p.len_arr ? 4u : 6u) : g_force.pkt_lanes == 16 ? 4u : g_force.pkt_lanes == 8 ? 3u : 2u;      // (messages wherever they live have no wave-per-packet instance: 16 lanes)
+            if (forced_pkt_lg() >= 0) cfg.force_lg = forced_pkt_lg() == 6 && p.len_arr ? 4u : (u32)forced_pkt_lg();      // (messages wherever they live have no wave-per-packet instance: 16 lanes)
             if (g_force.pkt_deal >= 1 && g_force.pkt_deal <= (int)PKTG_MAX_DEAL) cfg.force_deal = (u32)g_force.pkt_deal;
 #endif
             // (the sort also checks every length: a call with one of 2^28 bytes or more is refused by its scan -- hdr->bad -- and every launch behind returns at once)
@@ -764,17 +786,9 @@ int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktP
             static const u32 shapes[] = {0u, 2u, 3u, 4u, 6u};
             for (u32 lg : shapes) {
                 if (lg < lg_min || lg > lg_max || cfg.c_hi == 0u) continue;                  // (c_hi = 0: everything by rows, forced)
-                if (lg == 0u) {
-                    const u32 waves_per_wg = AESGCM_PKTL_WG / 64, nb = (u32)((n + 63) / 64);
-                    u32 w = (nb + waves_per_wg - 1) / waves_per_wg;
-                    if (w > n_cu) w = n_cu;
-                    FORKCHK(klaunch_pktl(c->nr, decrypt, false, w, st, c->km, c->tables, *k));
-                } else {
-                    const u32 P = 64u >> lg, waves_per_wg = (u32)PKTG_WG(lg) / 64, nb = (u32)((n + P - 1) / P);
-                    u32 w = (nb + waves_per_wg - 1) / waves_per_wg;
-                    if (w > n_cu) w = n_cu;
-                    FORKCHK(klaunch_pktg(c->nr, decrypt, (int)lg, w, st, c->km, c->tables, *k));
-                }
+                const u32 w = pkt_grid(n_cu, n, (int)lg, false, 64u >> lg).wgs;                 // (the deal is the scan's: the grid is sized for a wave-iteration per fetch)
+                if (lg == 0u) FORKCHK(klaunch_pktl(c->nr, decrypt, false, w, st, c->km, c->tables, *k));
+                else FORKCHK(klaunch_pktg(c->nr, decrypt, (int)lg, w, st, c->km, c->tables, *k));
             }
             if (probe) { c->rows_dirty = false; return AESGCM_OK; }           // (nothing of the row path ran: its scratch is at rest)
         } else {
@@ -815,6 +829,38 @@ bool packets_by_rows(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len) {
     return true;
 }
 
+// Fixed-size records through the packet kernels: the shape, its form, the deal and the grid (aesgcm_plan.h), and the context's dispenser -- p.counter_base is where
+// the launch finds it, c->counter_base where it leaves it.  p: the caller's pointers, counts and lengths.
+void packets_plan(aesgcm_ctx *c, PktParams &p, PacketsPlan &b) {
+    const u32 n_cu = (u32)c->G / 2;                                                 // c->G = two workgroups per CU
+    const size_t n_pkts = p.n_pkts, pkt_len = p.pkt_len;
+    b.lg = packets_lg(c, n_pkts, pkt_len);
+    p.counter = c->d_counter; p.counter_base = c->counter_base;
+    if (b.lg == 0) {
+        b.ilp = pktl_pick_ilp(n_cu, n_pkts, pkt_len);
+#ifdef AESGCM_DEBUG_KNOBS
+        if (g_force.pkt_ilp) b.ilp = g_force.pkt_ilp == 1;
+#endif
+    } else {
+        p.plain = pktg_is_plain(b.lg, p.aad_off || p.aad_len, p.aligned != 0, pkt_len);
+        p.deal = pktg_pick_deal(n_cu, b.lg, n_pkts);
+#ifdef AESGCM_DEBUG_KNOBS
+        const u32 P = 64u >> b.lg;                                                  // packets per wave-iteration
+        if (g_force.pkt_deal >= 1 && g_force.pkt_deal <= (int)PKTG_MAX_DEAL) p.deal = ((u32)g_force.pkt_deal + P - 1) / P * P;
+#endif
+    }
+    const PktGrid g = pkt_grid(n_cu, n_pkts, b.lg, b.ilp, p.deal);
+    b.wgs = g.wgs;
+    c->counter_base += g.nb + g.wgs * g.waves_per_wg;                               // every wave ends on one failing fetch
+}
+int packets_launch(aesgcm_ctx *c, int decrypt, PktParams &p, hipStream_t st) {
+    PacketsPlan b;
+    packets_plan(c, p, b);
+    const hipError_t le = b.lg == 0 ? klaunch_pktl(c->nr, decrypt, b.ilp, b.wgs, st, c->km, c->tables, p) : klaunch_pktg(c->nr, decrypt, b.lg, b.wgs, st, c->km, c->tables, p);
+    if (le != hipSuccess) { c->counter_base = p.counter_base; return hip_fail(le, "k_pkt launch"); }      // nothing ran: the dispenser stands where it stood
+    return AESGCM_OK;
+}
+
 thread_local const RowsHdr *g_wipe_hdr = nullptr;
 // zero the output of every packet whose d_auth[] entry is 0 (behind the launch that wrote it, on the same stream)
 int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr, const u32 *d_len, const RowsHdr *hdr) {
@@ -849,37 +895,29 @@ int batch_plan(int device, int decrypt, size_t n_pkts, size_t key_len, BatchPara
     const int nr = (int)(key_len / 4 + 6);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(p.counter, 0, 4, st));
-    int lg = batch_pick_lg(ds->n_cu, n_pkts, p.pkt_len, p.data_off != nullptr);          // k_batch3 with 8 / 16 / 64 lanes per packet
-#ifdef AESGCM_DEBUG_KNOBS
-    if (g_force.batch_lanes) lg = g_force.batch_lanes == 8 ? 3 : g_force.batch_lanes == 16 ? 4 : 6;
-#endif
+    const int lg = batch_lg(ds, n_pkts, p.pkt_len, p.data_off != nullptr);                // k_batch3 with 8 / 16 / 64 lanes per packet
     if (decrypt == 2 && lg != 3) { snprintf(g_err, sizeof g_err, "the probe of the batch kernel exists in the 8-lanes-per-packet shape; this call takes %d", 1 << lg); return AESGCM_EARG; }
-    if (lg <= 6) {
-        // packets of mixed length: by falling length class once the batch fills the machine several times over (BATCH_ORDER_MIN; as aesgcm_packets_crypt_dev)
-        bool ordered = lg < 6 && p.data_off && n_pkts >= BATCH_ORDER_MIN(nr);
+    // packets of mixed length: by falling length class once the batch fills the machine several times over (BATCH_ORDER_MIN; as aesgcm_packets_crypt_dev)
+    bool ordered = lg < 6 && p.data_off && n_pkts >= BATCH_ORDER_MIN(nr);
 #ifdef AESGCM_DEBUG_KNOBS
-        if (g_force.batch_order) ordered = lg < 6 && p.data_off && g_force.batch_order == 1;
+    if (g_force.batch_order) ordered = lg < 6 && p.data_off && g_force.batch_order == 1;
 #endif
-        if (ordered) {
-            b.order_lock = std::unique_lock<std::mutex>(g_mu);                        // held from the choice of the slot to the event behind its reader: callers on other threads queue up here
-            b.oslot = &ds->order[ds->order_next++ & 3u];
-            if ((rc = order_launch(*b.oslot, p.data_off, n_pkts, st, &p.perm))) return rc;
-        }
-        p.plain = !p.data_off && !p.aad_off && !p.aad_len && p.aligned && p.pkt_len && p.pkt_len % (16u << lg) == 0;
-        const u32 waves_per_wg = (u32)BATCH3_LANES(nr) / 64;
-        const u32 P = 64u >> lg, per_wg = waves_per_wg * P;
-        u32 wgs = (u32)((n_pkts + per_wg - 1) / per_wg);
-        if (wgs > (u32)ds->n_cu) wgs = (u32)ds->n_cu;
-        u32 deal = (u32)(n_pkts / ((size_t)wgs * waves_per_wg * 16));
-        deal = deal < P ? P : deal > 8 * P ? 8 * P : (deal + P - 1) / P * P;
-#ifdef AESGCM_DEBUG_KNOBS
-        if (g_force.batch_deal >= 1 && g_force.batch_deal <= 4096) deal = ((u32)g_force.batch_deal + P - 1) / P * P;
-#endif
-        p.deal = deal;
-        b.nr = nr; b.lg = lg; b.wgs = wgs; b.st = st; b.tables = ds->tables;
-        return AESGCM_OK;
+    if (ordered) {
+        b.order_lock = std::unique_lock<std::mutex>(g_mu);                        // held from the choice of the slot to the event behind its reader: callers on other threads queue up here
+        b.oslot = &ds->order[ds->order_next++ & 3u];
+        if ((rc = order_launch(*b.oslot, p.data_off, n_pkts, st, &p.perm))) return rc;
     }
-    return AESGCM_EARG;                                         // batch_pick_lg gives 3, 4 or 6
+    p.plain = batch_is_plain(lg, p.data_off || p.aad_off || p.aad_len, p.aligned != 0, p.pkt_len);
+    const u32 waves_per_wg = (u32)BATCH3_LANES(nr) / 64;
+    const u32 P = 64u >> lg, per_wg = waves_per_wg * P;
+    u32 wgs = (u32)((n_pkts + per_wg - 1) / per_wg);
+    if (wgs > (u32)ds->n_cu) wgs = (u32)ds->n_cu;
+    p.deal = batch_pick_deal(wgs, waves_per_wg, lg, n_pkts);
+#ifdef AESGCM_DEBUG_KNOBS
+    if (g_force.batch_deal >= 1 && g_force.batch_deal <= 4096) p.deal = ((u32)g_force.batch_deal + P - 1) / P * P;
+#endif
+    b.nr = nr; b.lg = lg; b.wgs = wgs; b.st = st; b.tables = ds->tables;
+    return AESGCM_OK;
 }
 int batch_done(const BatchPlan &b, const BatchParams &p) {
     if (b.oslot && p.perm) HIPCHK(hipEventRecord(b.oslot->done, b.st));

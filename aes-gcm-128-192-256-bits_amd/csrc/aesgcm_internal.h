@@ -3,8 +3,10 @@
 //   aesgcm_kernels.hip   the kernels and, at its end, the LAUNCHERS: one plain function per kernel family (klaunch_*) that picks the template instance by the rules of
 //                        aesgcm_dispatch.h (which a host compiler alone can check) and launches it.  Nothing outside that file names a kernel, so the other two units hold no device code at all -- the host side builds and runs against
 //                        a fake HIP runtime on a machine without a GPU (tests/fake_hip: which device is current at every allocation, stream, event and launch).
-//   aesgcm_host.hip      the host runtime: contexts and per-device state, the launch planners (which launches a message takes), the shape rules of the packet
-//                        paths, the scratch of the row path, the pipelined host-buffer path.
+//   aesgcm_host.hip      the host runtime: contexts and per-device state, the launch planners (which launches a message takes; packets_plan, the routed loop of
+//                        packets_rows and batch_plan for the packet paths), the scratch of the row path, the pipelined host-buffer path.
+//   aesgcm_plan.h        the pure part of the packet paths' planning -- shape, ILP form, deal, `plain`, grid, from counts and lengths alone -- with the
+//                        measurements behind each rule; no HIP header, as aesgcm_dispatch.h.  The planners of aesgcm_host.hip call it.
 //   aesgcm_abi.hip       the C ABI of include/aesgcm.h: argument checks and the calls into the runtime.
 //   aesgcm_comm.hip      the inter-GPU exchange (RCCL through dlopen), as before.
 #pragma once
@@ -53,6 +55,7 @@
 #define LEN_SORT_ENTRIES (PKT_LEN_CLASSES * LEN_SORT_WGS)
 #define COMBINE_BATCH_MAX 8
 struct CombineBatch { CombineParams p[COMBINE_BATCH_MAX]; };
+#include "aesgcm_plan.h"                                          // (behind the geometry it plans with)
 
 // ---------------------------------------------------------------- launchers (aesgcm_kernels.hip); every one returns hipGetLastError() of its launch(es)
 hipError_t klaunch_set_attributes();                                          // hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every instance, on the current device
@@ -218,20 +221,27 @@ int enqueue_combine(aesgcm_ctx *c, const CombineParams &p0, hipStream_t st);
 int check_lengths(u64 aad_len, u64 len);
 int crypt_dev(aesgcm_ctx *c, int dec, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, hipStream_t st);
 int fetch_tag(aesgcm_ctx *c, hipStream_t st, uint8_t tag[16]);
+bool poll_gens(const volatile u64 *w, size_t n, size_t stride, u64 gen, long poll_ns);
 int ct_compare16(const uint8_t *a, const uint8_t *b);
 int grow(unsigned char **p, size_t *cap, size_t need);
 int ctx_load_key(aesgcm_ctx *c, const uint8_t *key, size_t key_len, int pre_nr);
 int ctx_create_common(aesgcm_ctx **out, int device, const uint8_t *key, size_t key_len, int pre_nr);
+int ctx_destroy(aesgcm_ctx *c);
 int stage_in(aesgcm_ctx *c, const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len);
 int stream_absorb(aesgcm_ctx *c, const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, u64 first_block, hipStream_t st = nullptr, bool large = false);
 int stream_open(aesgcm_ctx *c, const uint8_t iv[12], int decrypt, hipStream_t st);
-int packets_pick_lg(u32 n_cu, size_t n_pkts, size_t pkt_len);
-int batch_pick_lg(int n_cu, size_t n_pkts, size_t pkt_len, bool var);
+int packets_lg(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len);
+int batch_lg(const DeviceState *ds, size_t n_pkts, size_t pkt_len, bool var);
 int order_launch(OrderSlot &o, const u64 *d_off, size_t n_pkts, hipStream_t st, const u32 **perm);
 size_t rows_carve(unsigned char *base, size_t slots, size_t n, RowsScratch *r);
 int rows_scratch(aesgcm_ctx *c, size_t slots, size_t n, hipStream_t st, RowsScratch *r);
 int packets_rows(aesgcm_ctx *c, int decrypt, RowsParams &p, hipStream_t st, PktParams *k = nullptr);
 bool packets_by_rows(const aesgcm_ctx *c, size_t n_pkts, size_t pkt_len);
+// A launch of fixed-size records through the packet kernels as packets_plan chose it (fills p's dispenser, plain and deal, moves the context's dispenser on);
+// packets_launch makes it, and moves the dispenser back when nothing ran.
+struct PacketsPlan { int lg = 0; bool ilp = false; u32 wgs = 0; };
+void packets_plan(aesgcm_ctx *c, PktParams &p, PacketsPlan &b);
+int packets_launch(aesgcm_ctx *c, int decrypt, PktParams &p, hipStream_t st);
 int wipe_failed(int device, size_t n_pkts, void *d_out, size_t pkt_len, const u64 *d_data_off, const int *d_auth, hipStream_t st, const u64 *d_out_ptr = nullptr, const u32 *d_len = nullptr, const RowsHdr *hdr = nullptr);
 // A batch launch as batch_plan chose it (fills p's dispenser, order, plain and deal): the caller launches k_batch3 (batch_launch) or k_kt_batch
 // (aesgcm_keytab_crypt_dev) with it, then batch_done records the order slot's event behind that launch.  order_lock holds the order slots until then.

@@ -12,6 +12,12 @@
 //   * STREAM ORDER: every stream keeps a vector clock (its own count of enqueued operations, and what it has waited for through events), so a test can ask whether
 //     one stream is ordered behind another (fake_ordered_behind), or have every operation on another stream checked against a watched one (fake_watch);
 //   * fault injection: fake_fail_launch(k) makes the k-th kernel launch after a reset fail, to drive the library's error paths.
+//   * THE LAUNCH LOG: every launcher the packet, message and batch calls reach notes one line -- the kernel, the stream, its scalar arguments and the scalar fields
+//     of its parameter struct; every pointer as 0 or 1 (p=..., in the order of the note's own argument list), never as an address; the stream as the name the
+//     driver gave it (fake_name_stream; a name ends with its stream), "null", or "side" for a live stream nobody named.  A driver that names every stream it can
+//     reach -- its own as "caller", each context's own as "own" (plan_drive.py does) -- leaves unnamed only what the library made for itself and hands to nobody:
+//     a context's side stream.  A scalar that is 0 is left out.  fake_log reads it, fake_reset clears it: what a call decided, as text a test can compare
+//     (tests/fake_hip/plan_drive.py, tests/golden/launch_plan.txt).
 // To keep the host logic running, a launch that would publish a tag and its generation number to the pinned host slot publishes the number (no tag).
 #include <hip/hip_runtime.h>
 
@@ -48,8 +54,26 @@ const void *watched = nullptr;
 
 void note(const char *fmt, ...) {
     char b[512]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
-    log_lines.push_back(b);
+    // a field that is 0 is left out (most are, in most launches): what a line does not name is zero
+    std::string line;
+    for (const char *q = b; *q;) {
+        const char *e = strchr(q, ' ');
+        const size_t n = e ? (size_t)(e - q) : strlen(q);
+        if (!(n >= 3 && q[n - 1] == '0' && q[n - 2] == '=')) { if (!line.empty()) line += ' '; line.append(q, n); }
+        q += n + (e ? 1 : 0);
+    }
+    log_lines.push_back(line);
 }
+std::map<const void *, std::string> stream_names;
+const char *sname(hipStream_t s) {
+    if (!s) return "null";
+    auto it = stream_names.find((const void *)s);
+    return it == stream_names.end() ? "side" : it->second.c_str();
+}
+// a parameter struct's text in the log, or "same" when it repeats the line before (a routed call hands one PktParams to four launches, k_rows_close gets k_rows' RowsParams)
+std::string last_params;
+const char *params(const std::string &t) { if (t == last_params) return "same"; last_params = t; return last_params.c_str(); }
+template <class... Ps> std::string bits(Ps... ps) { std::string s; ((s += ps ? '1' : '0'), ...); return s; }      // pointers (and addresses held as integers): set or not
 void bad(const char *fmt, ...) {
     char b[512]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
     violations.push_back(b);
@@ -86,7 +110,7 @@ void publish(void *slot, unsigned long long gen) { if (slot) __atomic_store_n(re
 }  // namespace
 
 // ---------------------------------------------------------------- what the test reads
-EXPORT void fake_reset(void) { std::lock_guard<std::mutex> lk(mu); violations.clear(); log_lines.clear(); touched = 0; n_sync = n_dev_sync = n_launch = n_collective = fail_at = 0; clocks.clear(); watched = nullptr; }   // (attrs stays: set once per device and process)
+EXPORT void fake_reset(void) { std::lock_guard<std::mutex> lk(mu); violations.clear(); log_lines.clear(); last_params.clear(); touched = 0; n_sync = n_dev_sync = n_launch = n_collective = fail_at = 0; clocks.clear(); watched = nullptr; }   // (attrs stays: set once per device and process)
 EXPORT unsigned fake_touched(void) { return touched; }
 EXPORT unsigned fake_attrs(void) { return attrs; }
 EXPORT long fake_syncs(void) { return n_sync; }
@@ -113,6 +137,15 @@ EXPORT int fake_violations(char *buf, size_t n) {
     return (int)violations.size();
 }
 EXPORT size_t fake_live_allocations(void) { return allocs.size(); }
+// the launch log since the last reset, a line per launch; returns the bytes it needs (with the final 0), so a caller can see that its buffer was too short
+EXPORT size_t fake_log(char *buf, size_t n) {
+    std::lock_guard<std::mutex> lk(mu);
+    std::string s;
+    for (auto &v : log_lines) s += v + "\n";
+    if (buf && n) { strncpy(buf, s.c_str(), n - 1); buf[n - 1] = 0; }
+    return s.size() + 1;
+}
+EXPORT void fake_name_stream(hipStream_t s, const char *name) { std::lock_guard<std::mutex> lk(mu); if (s) stream_names[(const void *)s] = name; }
 // FAKEHIP_REPORT=1: one line on stderr when the process ends (for drivers that are not Python: bench.py as a child process)
 namespace { struct Report { ~Report() { if (getenv("FAKEHIP_REPORT")) fprintf(stderr, "fakehip: syncs=%ld launches=%ld collectives=%ld violations=%zu touched=%u\n", n_sync, n_launch, n_collective, violations.size(), touched); } } report; }
 
@@ -190,6 +223,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {
     std::lock_guard<std::mutex> lk(mu);
     chk_stream("hipStreamDestroy", s);
     live_streams.erase((void *)s);
+    stream_names.erase((const void *)s);                        // (the next stream may be made at this address)
     delete reinterpret_cast<FakeStream *>(s);
     return hipSuccess;
 }
@@ -271,28 +305,68 @@ static void pkt_ptrs(const char *W, const KeyMaterial *km, const DevTables *tb, 
     P(km); P(tb); P(p.ivs); P(p.aad); P(p.in); P(p.out); P(p.tags); P(p.expect); P(p.auth); P(p.data_off); P(p.aad_off); P(p.counter); P(p.perm);
     P(p.route);
 }
-hipError_t klaunch_pktl(int, int, bool, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const PktParams &p) { LAUNCH("k_pktl", st); BIG_LDS(); pkt_ptrs(W, km, tb, p); return hipSuccess; }
-hipError_t klaunch_pktg(int, int, int, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const PktParams &p) { LAUNCH("k_pktg", st); BIG_LDS(); pkt_ptrs(W, km, tb, p); return hipSuccess; }
-hipError_t klaunch_batch3(int, int, int, unsigned, hipStream_t st, const DevTables *tb, const BatchParams &p) {
+// the scalar fields PktParams and BatchParams share, under the log's short names: n = n_pkts, len = pkt_len, aad = aad_len, al = aligned, pl = plain, d = deal, cb = counter_base
+// (and w = the workgroups of the launch, sc = scattered)
+#define PKT_SCALARS_FMT "n=%u len=%u aad=%u al=%u pl=%u d=%u cb=%u"
+#define PKT_SCALARS(p) p.n_pkts, p.pkt_len, p.aad_len, p.aligned, p.plain, p.deal, p.counter_base
+static void pkt_note(const char *W, hipStream_t st, int nr, int dec, const char *form, int v, unsigned wgs, const PktParams &p) {
+    char b[256];
+    snprintf(b, sizeof b, "p=%s " PKT_SCALARS_FMT " sc=%u", bits(p.ivs, p.aad, p.in, p.out, p.tags, p.expect, p.auth, p.data_off, p.aad_off, p.counter, p.perm, p.route, p.desc).c_str(),
+             PKT_SCALARS(p), p.scattered);
+    note("%s %s nr=%d dec=%d %s=%d w=%u %s", W, sname(st), nr, dec, form, v, wgs, params(b));
+}
+hipError_t klaunch_pktl(int nr, int dec, bool ilp, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const PktParams &p) {
+    LAUNCH("k_pktl", st); BIG_LDS(); pkt_ptrs(W, km, tb, p); pkt_note(W, st, nr, dec, "ilp", ilp, wgs, p);
+    return hipSuccess;
+}
+hipError_t klaunch_pktg(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const PktParams &p) {
+    LAUNCH("k_pktg", st); BIG_LDS(); pkt_ptrs(W, km, tb, p); pkt_note(W, st, nr, dec, "lg", lg, wgs, p);
+    return hipSuccess;
+}
+hipError_t klaunch_batch3(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const BatchParams &p) {
     LAUNCH("k_batch3", st); BIG_LDS(); P(tb); P(p.keys); P(p.ivs); P(p.aad); P(p.in); P(p.out); P(p.tags); P(p.expect); P(p.auth); P(p.counter); P(p.data_off); P(p.aad_off); P(p.perm);
+    note("%s %s nr=%d dec=%d lg=%d w=%u p=%s " PKT_SCALARS_FMT, W, sname(st), nr, dec, lg, wgs,
+         bits(p.keys, p.ivs, p.aad, p.in, p.out, p.tags, p.expect, p.auth, p.counter, p.data_off, p.aad_off, p.perm).c_str(), PKT_SCALARS(p));
     return hipSuccess;
 }
-hipError_t klaunch_len_sort(hipStream_t st, const LenSrc &src, u32, u32 *bins, u32 *perm, const RouteCfg &rc, u64 *bad_part, u32 *host_status, const DescSrc &) {
+hipError_t klaunch_len_sort(hipStream_t st, const LenSrc &src, u32 n, u32 *bins, u32 *perm, const RouteCfg &rc, u64 *bad_part, u32 *host_status, const DescSrc &ds) {
     LAUNCH("k_len_*", st); P(bad_part); P(host_status); P(src.off); P(src.aoff); P(src.len_arr); P(src.alen_arr); P(bins); P(perm); P(rc.hdr); P((const void *)(uintptr_t)rc.sc_in); P((const void *)(uintptr_t)rc.sc_out); P((const void *)(uintptr_t)rc.sc_aad); P((const void *)(uintptr_t)rc.sc_len); P((const void *)(uintptr_t)rc.sc_alen);
+    note("%s %s n=%u aad=%u p=%s rc: n=%u n_cu=%u c_hi=%u c_lo=%u mid_min=%u force_lg=%u force_deal=%u blocks_min=%llu top_min=%u", W, sname(st), n, src.aad_len,
+         bits(src.off, src.aoff, src.len_arr, src.alen_arr, bins, perm, bad_part, host_status, ds.desc, ds.ivs, ds.in_ptr, ds.out_ptr, ds.aad_ptr, rc.hdr, rc.sc_in, rc.sc_out, rc.sc_aad, rc.sc_len, rc.sc_alen).c_str(),
+         rc.n, rc.n_cu, rc.c_hi, rc.c_lo, rc.mid_min, rc.force_lg, rc.force_deal, (unsigned long long)rc.blocks_min, rc.top_min);
     return hipSuccess;
 }
-hipError_t klaunch_rows_plan(hipStream_t st, const RowsParams &p, bool, u32, u32, u64 *part, u32 *host_status) {
+// RowsParams in the log: its pointers, then n = n_pkts, len = pkt_len, aad = aad_len and the cut under the struct's own names (cap = slot_cap, prio = prio_rows)
+static const char *rows_txt(const RowsParams &p) {
+    char b[320];
+    snprintf(b, sizeof b, "p=%s n=%u len=%u aad=%u U=%u S=%u G=%llu D=%u NB=%u dyn=%u SM=%u waves=%u cap=%u prio=%u",
+             bits(p.ivs, p.aad, p.in, p.out, p.tags, p.expect, p.auth, p.data_off, p.aad_off, p.in_ptr, p.out_ptr, p.aad_ptr, p.len_arr, p.alen_arr, p.hdr, p.prefix, p.sprefix, p.slot_base,
+                  p.rec, p.acc, p.cnt, p.queues).c_str(),
+             p.n_pkts, p.pkt_len, p.aad_len, p.U, p.S, (unsigned long long)p.G, p.D, p.NB, p.dyn, p.SM, p.waves, p.slot_cap, p.prio_rows);
+    return params(b);
+}
+hipError_t klaunch_rows_plan(hipStream_t st, const RowsParams &p, bool routed, u32 force_d, u32 nb_cap, u64 *part, u32 *host_status) {
     LAUNCH("k_rows_plan", st); P(p.data_off); P(p.aad_off); P(p.len_arr); P(p.alen_arr); P(part); P(p.hdr); P(p.prefix); P(p.sprefix); P(p.slot_base); P(host_status);
+    note("%s %s routed=%d force_d=%u nb_cap=%u q=%s %s", W, sname(st), routed, force_d, nb_cap, bits(part, host_status).c_str(), rows_txt(p));
     return hipSuccess;
 }
 static void rows_ptrs(const char *W, const KeyMaterial *km, const RowsParams &p) {
     P(km); P(p.ivs); P(p.aad); P(p.in); P(p.out); P(p.tags); P(p.expect); P(p.auth); P(p.data_off); P(p.aad_off); P(p.in_ptr); P(p.out_ptr); P(p.aad_ptr); P(p.len_arr); P(p.alen_arr); P(p.hdr); P(p.prefix); P(p.sprefix); P(p.slot_base);
     P(p.rec); P(p.acc); P(p.cnt); P(p.queues);
 }
-hipError_t klaunch_rows(int, int, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) { LAUNCH("k_rows", st); BIG_LDS(); P(tb); rows_ptrs(W, km, p); return hipSuccess; }
-hipError_t klaunch_rows_close(int, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) { LAUNCH("k_rows_close", st); P(tb); rows_ptrs(W, km, p); return hipSuccess; }
-hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32, u32, const u64 *out_ptr, const u32 *len_arr) {
+hipError_t klaunch_rows(int nr, int dec, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) {
+    LAUNCH("k_rows", st); BIG_LDS(); P(tb); rows_ptrs(W, km, p);
+    note("%s %s nr=%d dec=%d w=%u %s", W, sname(st), nr, dec, wgs, rows_txt(p));
+    return hipSuccess;
+}
+hipError_t klaunch_rows_close(int dec, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const RowsParams &p) {
+    LAUNCH("k_rows_close", st); P(tb); rows_ptrs(W, km, p);
+    note("%s %s dec=%d w=%u %s", W, sname(st), dec, wgs, rows_txt(p));
+    return hipSuccess;
+}
+hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr) {
     LAUNCH("k_wipe_failed", st); P(out); P(auth); P(data_off); P(out_ptr); P(len_arr); P(g_wipe_hdr);      // (the call's header: beside the arguments, aesgcm_internal.h)
+    note("%s %s n=%u len=%u p=%s", W, sname(st), n_pkts, pkt_len, bits(out, auth, data_off, out_ptr, len_arr, g_wipe_hdr).c_str());
     return hipSuccess;
 }
 

@@ -3,6 +3,8 @@
     stream wait for that chunk on the device before it enqueues anything, and export synchronises no device;
   * a routed packet call (offset arrays: the row launches fork to the context's side stream) whose k-th launch fails, for every k up to the first that is past its
     last launch: an error, the caller's stream ordered behind everything that reached the side stream, and the next call on the context clean;
+  * a call of fixed-size records through k_pktl and one through k_pktg whose launch fails: the context's packet dispenser stands where it stood -- the next call's
+    launch log (fake_log) is the one a context that never saw the failure writes;
   * a multi-launch aesgcm_stream_update_dev whose k-th launch fails: an error, and the session over (ESTATE) until it is begun again.
 Run by tests/test_fake_hip.py with AESGCM_LIB pointing at the fake library."""
 import ctypes
@@ -21,6 +23,8 @@ F = ctypes.CDLL(os.environ["AESGCM_LIB"])
 F.fake_launches.restype = F.fake_device_syncs.restype = ctypes.c_long
 F.fake_fail_launch.argtypes = [ctypes.c_long]
 F.fake_watch.argtypes = F.fake_ordered_behind_all.argtypes = [ctypes.c_void_p]
+F.fake_log.restype = ctypes.c_size_t
+F.fake_log.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
 
 
 def check(what):
@@ -108,6 +112,35 @@ for caller in (None, s1):
         call()                                                       # the next call, nothing injected
         assert F.fake_ordered_behind_all(st)
         check("the call after launch %d failed" % k)
+
+# ---- fixed-size records whose launch fails: the dispenser's base (cb in the log, left out while 0) is moved back
+def logged(call):
+    F.fake_reset()
+    call()
+    b = ctypes.create_string_buffer(1 << 12)
+    assert F.fake_log(b, len(b)) <= len(b)
+    return b.value.decode()
+
+
+for kernel, n_pkts, pkt_len in (("k_pktl", 65536, 256), ("k_pktg", 4096, 1024)):
+    fixed = lambda c: c.packets_crypt_dev(False, n_pkts, d_ivs.ptr, d_big_in.ptr, d_big_out.ptr, d_tags.ptr, pkt_len=pkt_len)
+    fresh = lib.Context(key)
+    want = [logged(lambda: fixed(fresh)) for _ in range(3)]          # what a context's first, second and third such call launch
+    launches = F.fake_launches()
+    assert launches == 1 and all(w.startswith(kernel + " ") for w in want) and " cb=" not in want[0] and " cb=" in want[1] and want[1] != want[2], want
+    for k in range(1, launches + 2):
+        c = lib.Context(key)
+        assert logged(lambda: fixed(c)) == want[0]
+        F.fake_reset()
+        F.fake_fail_launch(k)
+        if k <= launches:
+            refused(lambda: fixed(c), lib.EHIP)
+        else:
+            fixed(c)
+        check("%s call, launch %d of %d failing" % (kernel, k, launches))
+        got = logged(lambda: fixed(c))                               # the next call: the context's second if the one between launched nothing
+        assert got == want[1 if k <= launches else 2], "%s, launch %d of %d failed: the next call starts from another counter_base\n%swanted\n%s" % (kernel, k, launches, got, want[1])
+F.fake_reset()
 
 # ---- a multi-launch stream_update_dev whose k-th launch fails
 for length in (5 * MB + 16 * 7 + 3, 32 * MB + 5):

@@ -26,7 +26,8 @@ def test_host_side_keeps_to_its_device_on_four_fake_devices():
 def test_stream_order_and_error_paths_on_the_fake_runtime():
     """tests/fake_hip/order_drive.py: a streaming session's steps wait on the device for a chunk fed on a caller's stream (and export synchronises no device); a
     routed packet call whose k-th launch fails -- every k -- returns an error with the caller's stream joined behind the side stream, and the next call is clean; a
-    failed multi-launch stream_update_dev ends the session (ESTATE until it is begun again)"""
+    failed multi-launch stream_update_dev ends the session (ESTATE until it is begun again); a fixed-size packet call whose k_pktl or k_pktg launch fails leaves the
+    context's dispenser where it stood (the next call's launch log says so)"""
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc (the HIP headers)")
     d = os.path.join(HERE, "fake_hip")
@@ -34,6 +35,27 @@ def test_stream_order_and_error_paths_on_the_fake_runtime():
     env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"))
     out = subprocess.run([sys.executable, os.path.join(d, "order_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert out.returncode == 0 and "FAKE ORDER OK" in out.stdout, out.stdout[-3000:]
+
+
+def test_launch_plan_is_the_recorded_one():
+    """tests/fake_hip/plan_drive.py: what the planners of the packet, message and batch calls decide -- every launch with its stream, grid, shape, deal, `plain`,
+    dispenser base and which pointers it carries, and what the shape queries answer -- over a grid on both sides of every threshold, by the library's own rules
+    (libaesgcm_fake.so) and under every forced shape (libaesgcm_fake_dbg.so), line by line against tests/golden/launch_plan.txt.  The fixture was written by the
+    commit before the planners moved into aesgcm_host.hip / aesgcm_plan.h: a call that launches anything else, or reports another shape, shows here."""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s", "libaesgcm_fake.so", "dbg"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = {k: v for k, v in os.environ.items() if k != "AESGCM_LIB"}
+    out = subprocess.run([sys.executable, os.path.join(d, "plan_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    got, want = out.stdout.splitlines(), open(os.path.join(HERE, "golden", "launch_plan.txt")).read().splitlines()
+    call = "(before the first call)"
+    for i, (g, w) in enumerate(zip(got, want)):
+        if w.startswith("=="):
+            call = w
+        assert g == w, "line %d, in the call\n  %s\nthe launch log says\n  %s\nand the fixture\n  %s" % (i + 1, call, g, w)
+    assert len(got) == len(want), "the log has %d lines, the fixture %d; the first one without a partner: %s" % (len(got), len(want), (got + want)[min(len(got), len(want))])
 
 
 def test_bench_single_process_queues_its_messages_without_a_host_sync_per_message():
