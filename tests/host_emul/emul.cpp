@@ -1310,11 +1310,124 @@ static void test_packet_grid(int level) {
     for (int i = 0; i < 3; i++) delete E[i];
 }
 
+// ================================================================================================
+// The alignment grid at ROW scale (tests/rows_grid.py states the same rules for the GPU tests, tests/test_gpu_rows_grid.py): a message of 1024 R + t bytes is R whole
+// rows (a run of them one piece of body_rows_lane), a tail of up to 64 blocks -- up to ROWS_SMALL_TAIL of them on the closing launch's axis, more: one right-aligned row
+// (rows_tail_lane) -- and an AAD either side of ROWS_SMALL_AAD.  `lc`: nine lengths at every start mod 128; `full`: R in 0 1 2 3 4 5 9 x tails either side of every
+// boundary at every start mod 16.  Byte-packed arenas with canary guards through emu_rows_nr (the planner's prefix sums, the piece walk and the lane code of k_rows and
+// k_rows_close) with the library's cut and dealt blocks of 1 and 3 units: encrypt out of place with the output 5 residues off, decrypt of the ORACLE's ciphertext in
+// place; whole arenas compared, a difference names the first message and its cell.
+// ================================================================================================
+static_assert(ROWS_SMALL_TAIL == 16u && ROWS_SMALL_AAD == 64u, "the row grid's lengths lie either side of these");
+static const u32 ROWS_GRID_AADS[13] = {0, 1, 13, 16, 20, 1007, 1008, 1009, 1023, 1024, 1025, 1040, 2048 + 7};      // period 13; 64 blocks and 65
+static std::vector<u32> rows_grid_lengths(bool lc) {
+    if (lc) return {1023, 1024, 1024 + 1, 1024 + 16 * ROWS_SMALL_TAIL, 1024 + 16 * ROWS_SMALL_TAIL + 1, 2 * 1024 + 1023, 4 * 1024, 5 * 1024 + 17, 9 * 1024 + 257};
+    std::vector<u32> v;
+    for (u32 R : {0u, 1u, 2u, 3u, 4u, 5u, 9u})
+        for (u32 t : {0u, 1u, 15u, 16u, 17u, 255u, 256u, 257u, 272u, 511u, 512u, 1007u, 1008u, 1009u, 1023u}) if (R || t >= 257) v.push_back(1024 * R + t);
+    std::sort(v.begin(), v.end());
+    return v;
+}
+static GridLayout rows_grid_layout(const std::vector<u32> &l16, const std::vector<u32> &l128) {
+    GridLayout g;
+    g.packed = true;
+    u64 pos = 0;
+    grid_walk(g.lens, pos, 16, l16);
+    grid_walk(g.lens, pos, 128, l128);
+    const u32 n = (u32)g.lens.size();
+    u64 a = GRID_GUARD, c = GRID_GUARD;
+    for (u32 k = 0; k < n; k++) { g.aads.push_back(ROWS_GRID_AADS[k % 13]); g.in_at.push_back(a); g.aad_at.push_back(c); a += g.lens[k]; c += g.aads[k]; }
+    g.out_at = g.in_at;
+    g.size_in = g.size_out = a + GRID_GUARD; g.size_aad = c + GRID_GUARD;
+    // completeness: every (start, length) cell; AADs of 64 and of 65 blocks at every residue of their own
+    std::vector<u64> seen;                                                   // length << 8 | modulus bit << 7 | residue
+    for (u32 k = 0; k < n; k++) { seen.push_back((u64)g.lens[k] << 8 | (g.in_at[k] % 16)); seen.push_back((u64)g.lens[k] << 8 | 128 | (g.in_at[k] % 128)); }
+    std::sort(seen.begin(), seen.end());
+    u32 miss = 0, aad_res[2] = {0, 0};
+    for (u32 l : l16) for (u32 r = 0; r < 16; r++) miss += !std::binary_search(seen.begin(), seen.end(), (u64)l << 8 | r);
+    for (u32 l : l128) for (u32 r = 0; r < 128; r++) miss += !std::binary_search(seen.begin(), seen.end(), (u64)l << 8 | 128 | r);
+    for (u32 k = 0; k < n; k++) if (g.aads[k] == 1024 || g.aads[k] == 1025) aad_res[g.aads[k] - 1024] |= 1u << (g.aad_at[k] % 16);
+    CHECK(!miss && n && aad_res[0] == 0xFFFFu && aad_res[1] == 0xFFFFu, "row grid: %u cells missing, AAD residues %04x %04x", miss, aad_res[0], aad_res[1]);
+    return g;
+}
+// the first byte at which two arenas differ, named by the message that owns it (or the guard in front of which message)
+static void rows_grid_same(const GridArena &got, const GridArena &want, const GridLayout &g, u32 shift, u32 D, int key_len, const char *what) {
+    if (!memcmp(got.p, want.p, got.n)) return;
+    u64 i = 0;
+    while (got.p[i] == want.p[i]) i++;
+    u32 k = 0;
+    const u32 n = (u32)g.lens.size();
+    while (k < n && g.in_at[k] + shift + g.lens[k] <= i) k++;
+    const bool guard = k == n || i < g.in_at[k] + shift;
+    if (k == n) k = n - 1;
+    CHECK(false, "row grid AES-%d %s D %u: arena byte %llu is %02x, wanted %02x: %s message %u (byte %lld of it): start %% 16 = %u (%% 128 = %u), out %% 16 = %u, len %u = %u rows + %u tail blocks, aad %u (%u blocks) at %% 16 = %u",
+          8 * key_len, what, D, (unsigned long long)i, got.p[i], want.p[i], guard ? "a guard byte next to" : "inside", k, (long long)i - (long long)(g.in_at[k] + shift),
+          (u32)(g.in_at[k] % 16), (u32)(g.in_at[k] % 128), (u32)((g.in_at[k] + shift) % 16), g.lens[k], g.lens[k] >> 10, ((g.lens[k] & 1023u) + 15u) >> 4, g.aads[k], (g.aads[k] + 15u) >> 4, (u32)(g.aad_at[k] % 16));
+}
+static u32 rows_grid_run(const uint8_t *key, int key_len, const GridLayout &g, u32 waves, u32 D, u64 seed) {
+    Emu E(key, key_len, 0);
+    const u32 n = (u32)g.lens.size(), shift = 5;
+    const int fails_before = g_fail;
+    GridArena in(g.size_in, GRID_CANARY_IN), aad(g.size_aad, GRID_CANARY_IN), out(g.size_out + 16, GRID_CANARY_OUT);
+    auto ivs = rnd(12 * (size_t)n, seed + 2);
+    {
+        auto r = rnd(g.size_in, seed + 3), ra = rnd(g.size_aad, seed + 1);
+        for (u32 k = 0; k < n; k++) { memcpy(in.p + g.in_at[k], r.data() + g.in_at[k], g.lens[k]); memcpy(aad.p + g.aad_at[k], ra.data() + g.aad_at[k], g.aads[k]); }
+    }
+    const GridArena in0(in), aad0(aad);
+    GridArena want(out), ct(in);
+    std::vector<uint8_t> rtags(16 * (size_t)n), tags(16 * (size_t)n + 16);
+    for (u32 k = 0; k < n; k++) {
+        std::vector<uint8_t> ref(g.lens[k] + 16);
+        orc_gcm_crypt(0, key, key_len, ivs.data() + 12 * k, aad.p + g.aad_at[k], g.aads[k], in.p + g.in_at[k], g.lens[k], ref.data(), rtags.data() + 16 * k);
+        memcpy(want.p + shift + g.in_at[k], ref.data(), g.lens[k]);
+        memcpy(ct.p + g.in_at[k], ref.data(), g.lens[k]);
+    }
+    std::vector<u64> doff(n + 1), aoff(n + 1);
+    for (u32 k = 0; k < n; k++) { doff[k] = g.in_at[k]; aoff[k] = g.aad_at[k]; }
+    doff[n] = g.in_at[n - 1] + g.lens[n - 1]; aoff[n] = g.aad_at[n - 1] + g.aads[n - 1];
+    auto call = [&](int dec, const uint8_t *src, uint8_t *dst) {
+        RowsParams p; memset(&p, 0, sizeof p);
+        p.ivs = ivs.data(); p.tags = tags.data(); p.n_pkts = n; p.aad = aad.p; p.in = src; p.out = dst; p.data_off = doff.data(); p.aad_off = aoff.data();
+        memset(tags.data(), 0, tags.size());
+        if (E.km.nr == 10) emu_rows_nr<10>(&E.km, dec, p, waves, D); else if (E.km.nr == 12) emu_rows_nr<12>(&E.km, dec, p, waves, D); else emu_rows_nr<14>(&E.km, dec, p, waves, D);
+        for (u32 k = 0; k < n && g_fail == fails_before; k++)
+            CHECK(!memcmp(tags.data() + 16 * k, rtags.data() + 16 * k, 16), "row grid AES-%d %s D %u: tag of message %u: start %% 16 = %u (%% 128 = %u), len %u = %u rows + %u tail blocks, aad %u (%u blocks) at %% 16 = %u",
+                  8 * key_len, dec ? "dec" : "enc", D, k, (u32)(g.in_at[k] % 16), (u32)(g.in_at[k] % 128), g.lens[k], g.lens[k] >> 10, ((g.lens[k] & 1023u) + 15u) >> 4, g.aads[k], (g.aads[k] + 15u) >> 4, (u32)(g.aad_at[k] % 16));
+    };
+    call(0, in.p, out.p + shift);                                            // encrypt out of place, the output 5 residues off
+    rows_grid_same(out, want, g, shift, D, key_len, "enc");
+    rows_grid_same(in, in0, g, 0, D, key_len, "enc (input arena)");
+    rows_grid_same(aad, aad0, g, 0, D, key_len, "enc (AAD arena)");
+    if (g_fail != fails_before) return n;                                    // the first cell is the finding
+    GridArena back(ct);
+    call(1, back.p, back.p);                                                 // decrypt the oracle's ciphertext in place
+    rows_grid_same(back, in0, g, 0, D, key_len, "dec");
+    rows_grid_same(aad, aad0, g, 0, D, key_len, "dec (AAD arena)");
+    return 2 * n;
+}
+// Level 1 (the sanitizer build): the `lc` set at every start mod 128.  Level 2: also the `full` set at every start mod 16.  Each with the library's cut (one block per
+// wave) and with dealt blocks of 1 and of 3 units, the key sizes taking turns.
+static void test_rows_grid(int level) {
+    const int klens[3] = {16, 24, 32};
+    const u32 Ds[3] = {0, 1, 3};
+    u32 ran = 0;
+    const GridLayout lc = rows_grid_layout({}, rows_grid_lengths(true));
+    for (int i = 0; i < 3; i++) { auto key = rnd(klens[(i + 1) % 3], 7600 + i); ran += rows_grid_run(key.data(), klens[(i + 1) % 3], lc, 37, Ds[i], 7610 + 10 * i); }
+    if (level >= 2) {
+        const GridLayout full = rows_grid_layout(rows_grid_lengths(false), {});
+        for (int i = 0; i < 3; i++) { auto key = rnd(klens[i], 7700 + i); ran += rows_grid_run(key.data(), klens[i], full, 64, Ds[i], 7710 + 10 * i); }
+    }
+    CHECK(ran > 0, "row grid ran nothing");
+    printf("row grid: %u messages through the row code (level %d)\n", ran, level);
+}
+
 int main(int argc, char **argv) {
     int level = argc > 1 ? atoi(argv[1]) : 1;
     init_tables();
-    if (argc > 2 && !strcmp(argv[2], "grid")) {                 // the packet grid alone (what a change to the frame lane runs first)
+    if (argc > 2 && !strcmp(argv[2], "grid")) {                 // the alignment grids alone (what a change to the frame lane or to the row code runs first)
         test_packet_grid(level);
+        test_rows_grid(level);
         printf(g_fail ? "EMUL FAILED (%d)\n" : "EMUL OK\n", g_fail);
         return g_fail ? 1 : 0;
     }
@@ -1357,6 +1470,7 @@ int main(int argc, char **argv) {
     test_wipe();
     test_packets(16, 61); test_packets(24, 62); test_packets(32, 63);
     test_packet_grid(level);
+    test_rows_grid(level);
     // many messages by rows: offset arrays with every kind of length (empty, shorter than a block, tails of 63 blocks + 15 bytes = two tail rows, whole super-rows,
     // 1 .. 3 rows behind them), AAD of none / a ragged block / more than a row; fixed-size records; one block per wave for few and for many waves (cuts in the
     // middle of strands), dealt blocks of 1 / 2 / 3 / 7 units

@@ -140,28 +140,41 @@ class Scattered:
     and behind), 1 .. 19 guard bytes between neighbours.  inplace: one arena (pos_out is pos_in), every residue for all lengths; else every (input residue, output
     residue) pair for every length of L_c."""
 
+    AADS = AAD_CYCLE
+
+    def lengths(self):
+        """the lengths whose every cell must occur (tests/rows_grid.py lays its own lengths and AAD cycle out by the same rules)"""
+        return all_lengths() if self.inplace else compact_lengths(self.G)
+
     def __init__(self, G=0, inplace=False):
         self.G, self.inplace = G, inplace
-        cells = [(a, a, L) for L in all_lengths() for a in range(16)] if inplace else [(a, b, L) for L in compact_lengths(G) for a in range(16) for b in range(16)]
-        # neighbours of unlike length and residue: a stride coprime to the count walks the cells
+        self.lay(self.order())
+        self.check()
+
+    def order(self):
+        """the cells (input residue, output residue, length), neighbours of unlike length and residue: a stride coprime to the count walks the cells"""
+        cells = [(a, a, L) for L in self.lengths() for a in range(16)] if self.inplace else [(a, b, L) for L in self.lengths() for a in range(16) for b in range(16)]
         n = len(cells)
         step = next(s for s in range(n // 3 | 1, n, 2) if np.gcd(s, n) == 1)
-        order = [cells[(k * step) % n] for k in range(n)]
+        return [cells[(k * step) % n] for k in range(n)]
+
+    def lay(self, order, aads=None):
+        """place the messages of `order` in the three arenas; aads: their AAD lengths (default: the cycle)"""
+        n = len(order)
         self.n, self.lens = n, [c[2] for c in order]
-        self.aads = [AAD_CYCLE[i % len(AAD_CYCLE)] for i in range(n)]
+        self.aads = list(aads) if aads is not None else [self.AADS[i % len(self.AADS)] for i in range(n)]
         self.pos_in, self.pos_out, self.pos_aad = [], [], []
         a = b = c = GUARD - 1
         for i, (ra, rb, L) in enumerate(order):
             a = _place(a, ra, i); self.pos_in.append(a); a += L
             b = _place(b, rb, i + 1); self.pos_out.append(b); b += L
             c = _place(c, (5 * i + 3) % 16, i); self.pos_aad.append(c); c += self.aads[i]
-        if inplace:
+        if self.inplace:
             self.pos_out = self.pos_in
-        self.size_in, self.size_out, self.size_aad = a + 1 + GUARD, (a if inplace else b) + 1 + GUARD, c + 1 + GUARD
-        self.check()
+        self.size_in, self.size_out, self.size_aad = a + 1 + GUARD, (a if self.inplace else b) + 1 + GUARD, c + 1 + GUARD
 
     def check(self):
-        lens = all_lengths() if self.inplace else compact_lengths(self.G)
+        lens = self.lengths()
         seen = {(p % 16, q % 16, L) for p, q, L in zip(self.pos_in, self.pos_out, self.lens)}
         want = {(a, a, L) for L in lens for a in range(16)} if self.inplace else {(a, b, L) for L in lens for a in range(16) for b in range(16)}
         assert want <= seen and len(self.lens) == self.n == len(want), ("scattered grid incomplete", sorted(want - seen)[:5])

@@ -21,7 +21,8 @@ def _up(hip, b):
 
 def _check_var(hip, orc, ctx, key, lens, aads, seed, hint, misalign=0, forged=(), aad_array=True):
     """encrypt the messages (offset arrays) through ctx, compare with the oracle, decrypt in place with the tags of `forged` spoiled (aad_array = False: the call
-    has no AAD at all -- an empty message then has no unit of work in the row launch, its tag is the closing launch's alone)"""
+    has no AAD at all -- an empty message then has no unit of work in the row launch, its tag is the closing launch's alone); the `misalign` bytes in front of the
+    first message and 64 canary bytes behind the last one must come through both calls untouched"""
     m = len(lens)
     f = orc.Fast(key)
     doff, aoff = [misalign], [0]
@@ -29,15 +30,16 @@ def _check_var(hip, orc, ctx, key, lens, aads, seed, hint, misalign=0, forged=()
         doff.append(doff[-1] + a)
         aoff.append(aoff[-1] + b)
     ivs, aad, pt = splitmix_bytes(seed, 12 * m), splitmix_bytes(seed + 1, max(aoff[-1], 16)), splitmix_bytes(seed + 2, doff[-1])
-    d_ivs, d_aad, d_buf = _up(hip, ivs), _up(hip, aad), _up(hip, pt)
+    behind = bytes([0x5E]) * 64
+    d_ivs, d_aad, d_buf = _up(hip, ivs), _up(hip, aad), _up(hip, pt + behind)
     d_doff, d_aoff = _up(hip, struct.pack("<%dQ" % (m + 1), *doff)), _up(hip, struct.pack("<%dQ" % (m + 1), *aoff))
     d_tags, d_auth = hip.DeviceBuffer(16 * m), hip.DeviceBuffer(4 * m)
     akw = dict(d_aad=d_aad.ptr, d_aad_off=d_aoff.ptr) if aad_array else {}
     assert aad_array or not any(aads)
     ctx.packets_crypt_dev(False, m, d_ivs.ptr, d_buf.ptr, d_buf.ptr, d_tags.ptr, pkt_len=hint, d_data_off=d_doff.ptr, **akw)
     hip.dev_sync()
-    ct, tags = bytes(d_buf.download(doff[-1])), bytes(d_tags.download())
-    assert ct[:misalign] == pt[:misalign]
+    ct, tags = bytes(d_buf.download(doff[-1] + 64)), bytes(d_tags.download())
+    assert ct[:misalign] == pt[:misalign] and ct[doff[-1]:] == behind, (lens[-1], aads[-1], misalign)
     for p in range(m):
         want = f.encrypt(ivs[12 * p:12 * p + 12], aad[aoff[p]:aoff[p + 1]], pt[doff[p]:doff[p + 1]])
         assert tags[16 * p:16 * p + 16] == want[1], (p, lens[p], aads[p])
@@ -48,7 +50,7 @@ def _check_var(hip, orc, ctx, key, lens, aads, seed, hint, misalign=0, forged=()
     d_exp, d_t2 = _up(hip, bytes(bad)), hip.DeviceBuffer(16 * m)
     ctx.packets_crypt_dev(True, m, d_ivs.ptr, d_buf.ptr, d_buf.ptr, d_t2.ptr, pkt_len=hint, d_data_off=d_doff.ptr, d_expect_tags=d_exp.ptr, d_auth=d_auth.ptr, **akw)
     hip.dev_sync()
-    assert bytes(d_buf.download(doff[-1])) == pt
+    assert bytes(d_buf.download(doff[-1] + 64)) == pt + behind
     assert bytes(d_t2.download()) == tags
     auth = struct.unpack("<%di" % m, bytes(d_auth.download()))
     assert [i for i, a in enumerate(auth) if not a] == sorted(forged)
