@@ -10,13 +10,18 @@
 // sequence number, wx->seq[pkt]: 1.3 XORs it into the slot's 12-byte IV (KtSlot::xpn) and reads no nonce byte from the record, 1.2 puts it in front of the one AAD block.
 // KT_WIREX_QUIC (k_kt_quic, aesgcm_quic_kernels.hip): the frame is a QUIC packet header | payload | tag[16] whose header ends behind its packet-number field, at
 // wx->pn_off[pkt] + (first byte & 3) + 1 -- per packet, the first byte read through p.aad, where the header lies unprotected; nonce as TLS 1.3's from wx->seq[pkt], the full
-// packet number.  The header itself is k_kt_quic_hp's business: it is not copied here.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
+// packet number.  The header itself is k_kt_quic_hp's business: it is not copied here.  KT_WIREX_DTLS13 / KT_WIREX_DTLS12 (k_kt_dtls, aesgcm_dtls_kernels.hip): the frame is a
+// DTLS record.  1.3 (RFC 9147): unified_hdr | payload | tag[16], QUIC's structure -- the header ends behind the sequence-number field that starts at wx->pn_off[pkt], 1 or 2
+// bytes by the first byte's S bit, and behind the 2 length bytes that its L bit announces; the first byte, which is never masked, is read through p.in; nonce as TLS 1.3's
+// from wx->seq[pkt]; the header is k_kt_dtls_sn's business.  1.2 (RFC 6347): hdr[13] | explicit nonce[8] | payload | tag[16], TLS 1.2's structure with epoch and sequence
+// number read from the record's bytes 3 .. 10 where TLS 1.2 takes wx->seq[pkt]; no number comes from outside the record.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
 // what that cost there).  For the same reason the two key sources read a packet's offsets in different orders: each keeps its kernel's instruction stream.
     static_assert(DEC == 0 || DEC == 1 || (DEC == 2 && !SLOTS), "the probe (DEC == 2) takes raw keys");
     static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
     static_assert(!WIREX || WIRE, "the number that is not on the wire belongs to a frame in wire format");
-    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_QUIC, "one extension or none");
+    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_QUIC || WIREX == KT_WIREX_DTLS13 || WIREX == KT_WIREX_DTLS12, "one extension or none");
     constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN, x_t13 = WIREX == KT_WIREX_TLS13, x_t12 = WIREX == KT_WIREX_TLS12, x_quic = WIREX == KT_WIREX_QUIC;
+    constexpr bool x_d13 = WIREX == KT_WIREX_DTLS13, x_d12 = WIREX == KT_WIREX_DTLS12;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
@@ -64,10 +69,10 @@
         const unsigned char *ivp = p.ivs + (size_t)pkt * 12;
         u32 pkt_len = p.pkt_len, aad_len = p.aad_len;
         u64 doff = (u64)pkt * p.pkt_len, aoff = (u64)pkt * p.aad_len;
-        [[maybe_unused]] u64 qpn = 0;                    // QUIC: the packet's full number
+        [[maybe_unused]] u64 qpn = 0;                    // QUIC: the packet's full number; DTLS 1.3: the record's
         if constexpr (x_quic) {
             // a QUIC packet (RFC 9001 5.3): AAD = the header up to and including the packet-number field, whose length is in the unprotected first byte; payload behind
-            // it; the tag last.  Refused: what k_kt_quic_hp refuses (aesgcm_quic_kernels.hip: quic_refused) -- either slot, the offsets, more than 65535 bytes, pn_off 0,
+            // it; the tag last.  Refused: what k_kt_quic_hp refuses (aesgcm_mask.h: mask_take, and the number's range) -- either slot, the offsets, more than 65535 bytes, pn_off 0,
             // the sample's 16 bytes at pn_off + 4 not inside the packet (so header and tag fit for every pn_len), and on encrypt a number of 2^62 or more.  A refused
             // packet's number and first byte are not read
             const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
@@ -82,6 +87,25 @@
             pkt_len = bad ? 0u : (u32)(e - b) - 16u - hdr;
             doff = b + hdr;
         } else
+        if constexpr (x_d13) {
+            // a DTLS 1.3 record (RFC 9147 4): AAD = the unified header with the sequence-number bytes unprotected, read through p.aad; payload behind it; the tag last.
+            // Refused: what k_kt_dtls_sn refuses, by the same tests in the same order -- either slot, the offsets, more than 65535 bytes, pn_off 0, fewer than 17 bytes
+            // from the sequence-number field to the record's end (one sequence byte and the sample; only then is the first byte read, through p.in: it is never masked
+            // and k_kt_dtls_sn writes nothing of a record it refuses), a first byte that is not 001xxxxx, the sample's 16 bytes at the header's end not inside the record
+            // (so header and tag fit).  A refused record's number is not read
+            const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
+            const u32 hslot = wx->hp_slots[pkt], po = wx->pn_off[pkt];
+            bad |= hslot >= kt->n_slots || e < b || e - b > 65535u || po == 0u || (u64)po + 17u > e - b;
+            bad |= ks->set != KT_SET || kt->tab[bad ? 0u : hslot].set != KT_SET;
+            const u32 b0 = bad ? 0u : p.in[b];
+            const u32 hdr = bad ? 0u : po + (b0 & 0x08u ? 2u : 1u) + (b0 & 0x04u ? 2u : 0u);
+            bad |= (b0 & 0xE0u) != 0x20u || (u64)hdr + 16u > e - b;
+            qpn = bad ? (u64)0 : wx->seq[pkt];
+            aoff = b;
+            aad_len = bad ? 0u : hdr;
+            pkt_len = bad ? 0u : (u32)(e - b) - 16u - hdr;
+            doff = b + (bad ? 0u : hdr);
+        } else
         if constexpr (WIRE) {
             // the frame's one range: AAD from its first byte, payload behind the header, the ICV last; auth-only: everything in front of the ICV is AAD.  A frame too
             // short for header (nonce bytes included) and ICV is refused like a falling range
@@ -90,6 +114,7 @@
             const u32 nonce_end = wf->iv_off + 12u - wf->salt_len, front = auth_only && nonce_end > wf->hdr_len ? nonce_end : wf->hdr_len;
             bad |= e < b || e - b >= ((u64)1 << 28) || e - b < (u64)(front + wf->tag_len);
             if constexpr (x_t13 || x_t12) bad |= e - b > 5u + 65535u;                // a TLS record's length field says what follows its five header bytes
+            if constexpr (x_d12) bad |= e - b > 13u + 65535u;                        // ... and a DTLS 1.2 record's what follows its thirteen
             const u32 body = bad ? 0u : (u32)(e - b) - wf->tag_len;                  // the bytes in front of the ICV
             aoff = b;
             aad_len = auth_only ? body : wf->aad_len;
@@ -97,6 +122,7 @@
             doff = b + (auth_only ? body : wf->hdr_len);
             if constexpr (x_esn) aad_len = 12u;                                      // SPI | seq-hi | seq-lo (RFC 4303): the frame's first 8 bytes around hi[pkt]
             if constexpr (x_t12) aad_len = 13u;                                      // seq | type, version | payload length (RFC 5246 6.2.3.3): seq[pkt], three header bytes, pkt_len
+            if constexpr (x_d12) aad_len = 13u;                                      // epoch, seq | type, version | payload length (RFC 6347 4.1.2.1): eleven header bytes, pkt_len
             ivp = p.in + b + wf->iv_off;
         } else {
         if (p.data_off) {
@@ -135,8 +161,8 @@
         u32 iv0, iv1, iv2;
         if constexpr (WIRE) {
             // the nonce: salt_len (0, 4 or 8) bytes of the slot's salt, then header bytes -- whole words either way; a refused frame's header is not read
-            const u32 sw = x_xpn ? 2u : x_t13 || x_quic ? 3u : x_t12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
-            const u32 f0 = bad || x_t13 || x_quic ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
+            const u32 sw = x_xpn ? 2u : x_t13 || x_quic || x_d13 ? 3u : x_t12 || x_d12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
+            const u32 f0 = bad || x_t13 || x_quic || x_d13 ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
             iv0 = sw ? ks->salt[0] : f0;
             iv1 = sw > 1u ? ks->salt[1] : sw ? f0 : f1;
             iv2 = sw > 1u ? f0 : sw ? f1 : f2;
@@ -145,18 +171,18 @@
                 // not used; a refused frame's hi is not read
                 iv0 = ks->xpn[0] ^ ks->xpn[3]; iv1 = ks->xpn[1] ^ (bad ? 0u : bswap32(wx->hi[pkt])); iv2 = ks->xpn[2] ^ f0;
             }
-            if constexpr (x_t12) iv0 = ks->xpn[0];                    // TLS 1.2 (RFC 5288): the slot IV's first four bytes (aesgcm_keytab_set_tls_iv), then the record's explicit eight (f0, f1)
+            if constexpr (x_t12 || x_d12) iv0 = ks->xpn[0];           // TLS 1.2 (RFC 5288), and DTLS 1.2 the same: the slot IV's first four bytes (aesgcm_keytab_set_tls_iv), then the record's explicit eight (f0, f1)
             if constexpr (x_t13) {
                 // TLS 1.3 (RFC 8446 5.3): the slot's 12-byte IV XOR the sequence number, big-endian, right-aligned.  A refused record's number is not read
                 const u64 sq = bad ? (u64)0 : wx->seq[pkt];
                 iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(sq >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)sq);
             }
-            if constexpr (x_quic) {
-                // QUIC (RFC 9001 5.3): TLS 1.3's formula with the packet number
+            if constexpr (x_quic || x_d13) {
+                // QUIC (RFC 9001 5.3): TLS 1.3's formula with the packet number; DTLS 1.3 (RFC 9147 4.2.1 -> RFC 8446 5.3): with the record's sequence number
                 iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(qpn >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)qpn);
             }
-            // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through (QUIC: k_kt_quic_hp writes the header)
-            if constexpr (!x_quic)
+            // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through (QUIC: k_kt_quic_hp writes the header; DTLS 1.3: k_kt_dtls_sn)
+            if constexpr (!x_quic && !x_d13)
             if (p.in != p.out && st_ok) wire_copy_front(p.out + aoff, p.in + aoff, (u32)(doff - aoff), l, G);
         } else { iv0 = load_le32(ivp); iv1 = load_le32(ivp + 4); iv2 = load_le32(ivp + 8); }
         // ---- H on lane 0 and E_K(IV || 1) on lane 1 of the group: with a raw key H = E_K(0^128) in the same pass (gcm_gctr.vhd:141-145), with a slot its stored H
@@ -233,6 +259,10 @@
                     const u32 xpkt = batch_map(p, pk0 + xg < pk_end ? pk0 + xg : pk0);
                     const u64 sq = wx->seq[xpkt];
                     gin = make_uint4(bswap32((u32)(sq >> 32)), bswap32((u32)sq), (gload4_any(aad) & 0x00FFFFFFu) | ((pkt_len >> 8) << 24), pkt_len & 0xFFu);
+                } else if constexpr (x_d12) {
+                    // DTLS 1.2's one AAD block: epoch | sequence number as the record's bytes 3 .. 10 carry them, then as TLS 1.2's -- type, version | be16(payload length),
+                    // the length from the offsets (pkt_len < 2^16: the check above)
+                    gin = make_uint4(gload4_any(aad + 3), gload4_any(aad + 7), (gload4_any(aad) & 0x00FFFFFFu) | ((pkt_len >> 8) << 24), pkt_len & 0xFFu);
                 } else
                 gin = rem >= 16 ? gload16_any(aad + off) : load_block_bytes(aad + off, rem);
             } else {

@@ -7,3 +7,4 @@
 #include "aesgcm_wirex_kernels.hip"
 #include "aesgcm_tls_kernels.hip"
 #include "aesgcm_quic_kernels.hip"
+#include "aesgcm_dtls_kernels.hip"

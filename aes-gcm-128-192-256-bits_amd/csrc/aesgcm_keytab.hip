@@ -8,6 +8,7 @@
 //   wirex    aesgcm_keytab_frames_crypt_x_dev     k_kt_wirex   ... with a number per frame that is not on the wire (MACsec XPN, ESP ESN)
 //   tls      aesgcm_keytab_records_crypt_dev      k_kt_tls     TLS records with their 64-bit sequence numbers
 //   quic     aesgcm_keytab_quic_crypt_dev         k_kt_quic    QUIC packets, and a second launch, k_kt_quic_hp (header protection, a lane per packet)
+//   dtls     aesgcm_keytab_dtls_crypt_dev         k_kt_dtls    DTLS records; 1.3: and a second launch, k_kt_dtls_sn (record-number encryption, a lane per record)
 // The calls in wire format fill their kernel parameters by kt_wire_params.
 #include "aesgcm_keytab.h"
 
@@ -312,6 +313,48 @@ int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, c
     if (decrypt) HIPCHK(klaunch_kt_quic_hp(b.nr, 1, b.st, b.tables, hp));
     HIPCHK(klaunch_kt_quic(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
     if (!decrypt) HIPCHK(klaunch_kt_quic_hp(b.nr, 0, b.st, b.tables, hp));
+    return batch_done(b, p);
+}
+
+// ---------------------------------------------------------------- DTLS records
+int aesgcm_dtls_fmt_check(const aesgcm_dtls_fmt *f) {
+    if (!f || (f->version != AESGCM_DTLS_13 && f->version != AESGCM_DTLS_12) || f->reserved) return AESGCM_EARG;
+    return AESGCM_OK;
+}
+
+// 1.2: one k_kt_dtls launch, planned as kt_frames_crypt plans k_kt_tls; what the kernel takes from a wire format is the version's constant format.  1.3: the QUIC call's two
+// launches on the caller's stream -- encrypt: the AEAD first, then the mask from the fresh ciphertext; decrypt: the mask off first (k_kt_dtls_sn leaves the unprotected header
+// in d_out and the decoded numbers in d_seq_out, which is where the AEAD reads both).  No scratch memory, no host synchronisation: capture-safe.
+int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_dtls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint32_t *d_sn_slots,
+                                 const uint64_t *d_seq, uint64_t *d_seq_out, const uint32_t *d_sn_off, const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth,
+                                 void *stream) {
+    const int frc = aesgcm_dtls_fmt_check(fmt);
+    if (frc) return frc;
+    const bool v13 = fmt->version == AESGCM_DTLS_13;
+    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
+    if (!n_recs) return AESGCM_OK;
+    if (!d_slots || !d_in || !d_out || !d_rec_off || (decrypt && !d_auth) || n_recs >= ((size_t)1 << 31)) return AESGCM_EARG;
+    if (v13 && (!d_sn_slots || !d_seq || !d_sn_off || (decrypt && !d_seq_out))) return AESGCM_EARG;
+    KtWireXParams xp;
+    kt_wire_params(xp, t, decrypt, d_in, v13 && decrypt ? d_out : d_in, d_out, d_rec_off, d_slots, d_auth);      // 1.3's AAD: where the header lies unprotected
+    BatchParams &p = xp.w.k.b;
+    KtQuicHpParams sn;
+    if (v13) {
+        xp.w.f.tag_len = 16;                                                          // the rest of a wire format is per record here
+        xp.seq = decrypt ? d_seq_out : d_seq;
+        xp.pn_off = d_sn_off; xp.hp_slots = d_sn_slots;
+        sn.in = p.in; sn.out = p.out; sn.pkt_off = d_rec_off; sn.slots = d_slots; sn.hp_slots = d_sn_slots; sn.pn_off = d_sn_off;
+        sn.pn = d_seq; sn.pn_out = decrypt ? d_seq_out : nullptr; sn.tab = t->tab; sn.n_pkts = (u32)n_recs; sn.n_slots = (u32)t->n_slots;
+    } else {
+        static const aesgcm_wire_fmt f12 = {13, 21, 13, 4, 16, 0};                    // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
+        xp.w.f = f12;
+    }
+    BatchPlan b;
+    const int rc = batch_plan(t->device, decrypt, n_recs, t->key_len, p, stream, b);
+    if (rc) return rc;
+    if (v13 && decrypt) HIPCHK(klaunch_kt_dtls_sn(b.nr, 1, b.st, b.tables, sn));
+    HIPCHK(klaunch_kt_dtls(fmt->version, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
+    if (v13 && !decrypt) HIPCHK(klaunch_kt_dtls_sn(b.nr, 0, b.st, b.tables, sn));
     return batch_done(b, p);
 }
 

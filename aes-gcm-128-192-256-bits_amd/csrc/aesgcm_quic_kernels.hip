@@ -9,11 +9,12 @@
 //                           hp slot; the first byte's low bits and the pn_len packet-number bytes are XORed with it, byte by byte, inside the packet.  Decrypt: it also
 //                           decodes the full number from the truncated one and the expected one (RFC 9000 A.3) into pn_out[p].  Out of place it writes the whole header.
 // Encrypt runs k_kt_quic, then k_kt_quic_hp (the sample is fresh ciphertext); decrypt the other way round (the AEAD needs the unmasked header and the number).  Both refuse
-// the same packets by the same test (quic_refused below and the body's copy of it), so a refused packet is touched by neither; k_kt_quic alone reports it (status word,
+// the same packets by the same test (mask_take of aesgcm_mask.h, shared with the DTLS record-number kernel, and the body's copy of it), so a refused packet is touched by neither; k_kt_quic alone reports it (status word,
 // auth 0).  18 + 6 instances; every k_kt_quic one: no scratch, at most 128 registers.
 // A translation unit of its own: its ISA census (`make asm_quic`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_mask.h"
 #include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 decrypt
@@ -27,14 +28,8 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 #include "aesgcm_batch3_body.inc"
 }
 
-// RFC 9000 A.3 (DecodePacketNumber) on unsigned 64-bit values: the RFC's integers are unbounded, so each comparison is written so that it cannot wrap
-HD u64 quic_decode_pn(u64 expected, u32 truncated, u32 pn_nbits) {
-    const u64 win = (u64)1 << pn_nbits, hwin = win >> 1, mask = win - 1;
-    const u64 cand = (expected & ~mask) | truncated;
-    if (expected >= hwin && cand <= expected - hwin && cand < ((u64)1 << 62) - win) return cand + win;
-    if (expected <= ~(u64)0 - hwin && cand > expected + hwin && cand >= win) return cand - win;
-    return cand;
-}
+// RFC 9000 A.3 (DecodePacketNumber): the shared decode (aesgcm_mask.h) with QUIC's number space, whose last number is 2^62 - 1
+HD u64 quic_decode_pn(u64 expected, u32 truncated, u32 pn_nbits) { return wire_decode_num(expected, truncated, pn_nbits, ((u64)1 << 62) - 1u); }
 
 template <int NR, int DEC>
 __global__ __launch_bounds__(256) void k_kt_quic_hp(const DevTables *__restrict__ tb, const KtQuicHpParams q) {
@@ -44,36 +39,27 @@ __global__ __launch_bounds__(256) void k_kt_quic_hp(const DevTables *__restrict_
     __syncthreads();
     const u32 i = blockIdx.x * 256u + tid;
     if (i >= q.n_pkts) return;
-    // the refusals, as k_kt_quic makes them (aesgcm_batch3_body.inc, x_quic): a refused packet's number is not read and nothing of it is written
-    const u32 slot = q.slots[i], hslot = q.hp_slots[i], po = q.pn_off[i];
-    const u64 b = q.pkt_off[i], e = q.pkt_off[i + 1];
-    if (slot >= q.n_slots || hslot >= q.n_slots || e < b || e - b > 65535u || po == 0u || (u64)po + 20u > e - b) return;
-    const KtSlot *const hs = q.tab + hslot;
-    if (q.tab[slot].set != KT_SET || hs->set != KT_SET) return;
+    // the refusals, as k_kt_quic makes them (aesgcm_batch3_body.inc, x_quic): a refused packet's number is not read and nothing of it is written.  The sample's 16
+    // bytes at pn_off + 4 lie inside the packet: 20 bytes from the number field's start
+    MaskPkt m;
+    if (!mask_take(q, i, 20u, m)) return;
     const u64 pn = q.pn[i];
     if (DEC == 0 && (pn >> 62) != 0) return;
-    const unsigned char *const src = q.in + b;
-    unsigned char *const dst = q.out + b;
+    const unsigned char *const src = m.src;
+    unsigned char *const dst = m.dst;
+    const u32 po = m.po;
     // mask = AES-ECB(hp key, sample): the sample is ciphertext -- encrypt: what k_kt_quic has just written to `out`; decrypt: the protected packet's
-    const u32 lb = (tid & 31u) << 2;
-    u32 rk[4 * (NR + 1)];
-#pragma unroll
-    for (int r = 0; r < NR + 1; r++) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(hs->rk + 4 * r);
-        rk[4 * r] = v.x; rk[4 * r + 1] = v.y; rk[4 * r + 2] = v.z; rk[4 * r + 3] = v.w;
-    }
-    const uint4 sample = gload16_any((DEC ? src : (const unsigned char *)dst) + po + 4u);
-    u32 s0 = sample.x ^ rk[0], s1 = sample.y ^ rk[1], s2 = sample.z ^ rk[2], s3 = sample.w ^ rk[3];
-    aes_rounds_lds<NR>(s0, s1, s2, s3, rk, smem, lb);            // memory-order words: mask[0 .. 3] = the bytes of s0 from the lowest, mask[4] = the lowest of s1
+    u32 s0, s1, s2, s3;
+    mask_of_sample<NR>(m.ms, (DEC ? src : (const unsigned char *)dst) + po + 4u, smem, (tid & 31u) << 2, s0, s1, s2, s3);
     const u32 f_in = src[0];
     const u32 first = f_in ^ (s0 & (f_in & 0x80u ? 0x0Fu : 0x1Fu));      // (the form bit itself is never masked)
     const u32 pn_len = ((DEC ? first : f_in) & 3u) + 1u;
     if (q.in != q.out) wire_copy_front(dst, src, po, 0u, 1u);    // out of place: the header in front of the packet number, by this one lane
     dst[0] = (unsigned char)first;
-    const u32 m = (s0 >> 8) | (s1 << 24);                         // mask[1 .. 4]
+    const u32 mk = (s0 >> 8) | (s1 << 24);                        // mask[1 .. 4]
     u32 trunc = 0;
     for (u32 k = 0; k < pn_len; k++) {
-        const u32 x = src[po + k] ^ ((m >> (8u * k)) & 0xFFu);
+        const u32 x = src[po + k] ^ ((mk >> (8u * k)) & 0xFFu);
         dst[po + k] = (unsigned char)x;
         trunc = (trunc << 8) | x;
     }

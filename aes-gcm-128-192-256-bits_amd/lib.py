@@ -44,6 +44,7 @@ SYMBOLS = [
     "aesgcm_wire_xfmt_check", "aesgcm_keytab_set_xpn", "aesgcm_keytab_frames_crypt_x_dev",
     "aesgcm_tls_fmt_check", "aesgcm_keytab_set_tls_iv", "aesgcm_keytab_records_crypt_dev",
     "aesgcm_keytab_quic_crypt_dev",
+    "aesgcm_dtls_fmt_check", "aesgcm_keytab_dtls_crypt_dev",
 ]
 
 
@@ -724,6 +725,8 @@ def _keytab_typed(L):
         L.aesgcm_keytab_set_tls_iv.argtypes = [vp, sz, sz, vp, vp]
         L.aesgcm_keytab_records_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(TlsFormat), sz, vp, vp, vp, vp, vp, vp, vp]
         L.aesgcm_keytab_quic_crypt_dev.argtypes = [vp, cint, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_dtls_fmt_check.argtypes = [ctypes.POINTER(DtlsFormat)]
+        L.aesgcm_keytab_dtls_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(DtlsFormat), sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
 
@@ -805,6 +808,34 @@ class TlsFormat(ctypes.Structure):
 
     def __repr__(self):
         return "TlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
+
+
+DTLS_13 = 1             # AESGCM_DTLS_13
+DTLS_12 = 2             # AESGCM_DTLS_12
+
+
+class DtlsFormat(ctypes.Structure):
+    """aesgcm_dtls_fmt: which DTLS record a dtls call takes (include/aesgcm.h "DTLS RECORDS")"""
+    _fields_ = [("version", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    @classmethod
+    def dtls13(cls):
+        """RFC 9147: unified_hdr | payload | tag[16]; nonce = the slot's IV XOR the 64-bit record sequence number, AAD = the unprotected header, the sequence bytes
+        masked under a second slot"""
+        return cls(DTLS_13, 0)
+
+    @classmethod
+    def dtls12(cls):
+        """RFC 6347 / RFC 5288: hdr[13] | explicit nonce[8] | payload | tag[16]; nonce = the slot IV's four bytes | explicit nonce, AAD = epoch, sequence number (from
+        the record) | type, version | payload length"""
+        return cls(DTLS_12, 0)
+
+    def check(self):
+        """aesgcm_dtls_fmt_check -> OK or EARG (no device needed)"""
+        return _keytab_typed(load()).aesgcm_dtls_fmt_check(ctypes.byref(self))
+
+    def __repr__(self):
+        return "DtlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
 
 
 def _per_slot(x, width, what, pad=False):
@@ -955,6 +986,41 @@ class KeyTable:
                                 d_pn_out=b["pn_out"].ptr if decrypt else None, d_auth=b["auth"].ptr if decrypt else None)
         outs, got = self._packed_call(packets, up, {"auth": "i", "pn_out": "Q"} if decrypt else {}, call)
         return outs, got.get("auth"), got.get("pn_out")
+
+    def dtls_crypt_dev(self, decrypt, fmt, n_recs, d_slots, d_in, d_rec_off, d_out, d_sn_slots=None, d_seq=None, d_sn_off=None, d_seq_out=None, d_auth=None, stream=None):
+        """aesgcm_keytab_dtls_crypt_dev: DTLS record p = bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in / d_out, of the version fmt (DtlsFormat) says, under slot
+        d_slots[p] (key by set, IV by set_tls_iv).  DTLS 1.3 also takes the record-number slot d_sn_slots[p] (key by set), d_sn_off[p] (uint32: where the sequence-number
+        field starts) and d_seq[p] (uint64): the full record sequence number on encrypt, the expected one on decrypt, where the decoded number goes to d_seq_out[p] (may
+        be d_seq).  The verdict goes to d_auth[p]"""
+        _chk(self._lib.aesgcm_keytab_dtls_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_recs, d_slots, d_sn_slots, d_seq, d_seq_out, d_sn_off, d_in, d_rec_off,
+                                                    d_out, d_auth, stream))
+
+    def crypt_dtls(self, fmt, slots, records, decrypt=False, sn_slots=None, seqs=None, sn_offs=None):
+        """Host convenience (tests, examples), crypt_quic's counterpart: whole DTLS records (on encrypt the header is written, a 1.3 record's sequence bytes unprotected, and
+        the tag's bytes are placeholders) through one call, in place.  DTLS 1.3: sn_slots, sn_offs and seqs (the full numbers on encrypt, the expected ones on decrypt) per
+        record.  -> (records_out, auth, seqs_out); auth is None on encrypt, seqs_out unless DTLS 1.3 decrypts."""
+        n = len(slots)
+        v13 = fmt.version == DTLS_13
+        per = (sn_slots, seqs, sn_offs)
+        if len(records) != n or not n or (v13 and any(x is None or len(x) != n for x in per)) or (not v13 and any(x is not None for x in per)):
+            raise AesGcmError(EARG, "slots and records (DTLS 1.3: and sn_slots, seqs, sn_offs; DTLS 1.2: without them) must be equally long and not empty")
+        up = {"slots": ("I", slots)}
+        if v13:
+            up.update(sn=("I", sn_slots), seq=("Q", seqs), sn_off=("I", sn_offs))
+        if decrypt:
+            up.update(auth=bytes(4 * n))                                           # zero where a refused record leaves them alone
+            if v13:
+                up.update(seq_out=bytes(8 * n))
+
+        def call(b):
+            self.dtls_crypt_dev(decrypt, fmt, n, b["slots"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_sn_slots=b["sn"].ptr if v13 else None,
+                                d_seq=b["seq"].ptr if v13 else None, d_sn_off=b["sn_off"].ptr if v13 else None, d_seq_out=b["seq_out"].ptr if v13 and decrypt else None,
+                                d_auth=b["auth"].ptr if decrypt else None)
+        down = {"auth": "i"} if decrypt else {}
+        if v13 and decrypt:
+            down["seq_out"] = "Q"
+        outs, got = self._packed_call(records, up, down, call)
+        return outs, got.get("auth"), got.get("seq_out")
 
     def status(self):
         """aesgcm_keytab_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""

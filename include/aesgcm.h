@@ -38,7 +38,8 @@ extern "C" {
 #endif
 
 #define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
-                                  aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev)
+                                  aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
+                                  aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -534,7 +535,7 @@ AESGCM_API int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, c
  * One k_kt_tls launch per call; shape and order as aesgcm_keytab_frames_crypt_dev (8, 16 or 64 lanes per record by count, by falling length class from 262144 records, 98304
  * for the longer keys).  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: checking the header's version, type or length bytes against the offsets; padding and content type (the payload's last bytes in 1.3); generating sequence
- * numbers or explicit nonces; key derivation (INTEGRATION.md "TLS records" says which secret becomes what); DTLS; routing long records to the row kernels. */
+ * numbers or explicit nonces; key derivation (INTEGRATION.md "TLS records" says which secret becomes what); routing long records to the row kernels.  (DTLS records: aesgcm_keytab_dtls_crypt_dev below.) */
 #define AESGCM_TLS_13 1u   /* hdr[5] | payload | tag[16]; nonce = slot IV XOR (0^32 | be64(d_seq[p])); AAD = hdr */
 #define AESGCM_TLS_12 2u   /* hdr[5] | explicit nonce[8] | payload | tag[16]; nonce = slot IV[0..4) | explicit nonce; AAD = be64(d_seq[p]) | hdr[0..3) | be16(L - 29) */
 typedef struct aesgcm_tls_fmt {
@@ -577,10 +578,63 @@ AESGCM_API int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, co
  * k_kt_quic_hp (a lane per packet); decrypt the other way round.  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: Retry and Version Negotiation packets; coalesced datagrams (split them: one entry of d_pkt_off per packet); ChaCha20; key derivation (INTEGRATION.md "QUIC
  * packets" says which secret becomes what); choosing the slot from the Key Phase bit (the caller who needs it decrypts out of place and retries the failed packets under the
- * next-phase slot); DTLS; anti-replay; routing long packets to the row kernels. */
+ * next-phase slot); anti-replay; routing long packets to the row kernels. */
 AESGCM_API int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_hp_slots,
                                  const uint64_t *d_pn, uint64_t *d_pn_out, const uint32_t *d_pn_off,
                                  const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- key tables on DTLS RECORDS in wire format: DTLS 1.3 (RFC 9147) and DTLS 1.2 AES-GCM (RFC 6347, RFC 5288)
+ * What a WebRTC, VPN or IoT terminator holds is one buffer of DTLS records.  The TLS call cannot express one: a DTLS 1.2 record carries its own epoch and sequence number
+ * (its header is 13 bytes, and the AAD takes the number from the wire, not from d_seq), and a DTLS 1.3 record has a header of per-record length whose sequence-number bytes
+ * are encrypted -- AES-ECB of a ciphertext sample under a second key, QUIC's structure at other offsets.  aesgcm_keytab_dtls_crypt_dev takes the buffer as it is: record p is
+ * bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in and of d_out (the same n_recs + 1 offsets for both; d_in == d_out allowed; any byte alignment), L bytes long, ONE record,
+ * under slot d_slots[p].  fmt->version says which record:
+ *   AESGCM_DTLS_12  hdr[13] | explicit_nonce[8] | payload | tag[16], hdr = type | version[2] | epoch[2] | sequence number[6] | length[2]  (RFC 6347 4.1, RFC 5288 3).
+ *                   Nonce = the slot IV's first four bytes (aesgcm_keytab_set_tls_iv, as TLS 1.2), then the record's bytes [13, 21).  AAD = rec[3..11) (epoch | sequence
+ *                   number, FROM THE WIRE) | rec[0..3) | be16(L - 37), 13 bytes; the LENGTH FROM THE OFFSETS -- the header's own two length bytes are not read for it.
+ *                   Header and explicit nonce pass through.  ONE launch.  d_sn_slots, d_seq, d_seq_out and d_sn_off are ignored and may be NULL.  Refused beside the
+ *                   common refusals: L < 37, L - 13 > 65535.
+ *   AESGCM_DTLS_13  unified_hdr | payload | tag[16]  (RFC 9147 4).  The first byte b0 = 0 0 1 C S L E E is never masked.  d_sn_off[p] (DEVICE memory, n_recs uint32) is where
+ *                   the sequence-number field starts: 1 + the connection ID's length, which the caller knows and the device does not.  The field is 2 bytes if b0 & 0x08
+ *                   (S), else 1; 2 length bytes follow it if b0 & 0x04 (L): hdr = d_sn_off[p] + (S ? 2 : 1) + (L ? 2 : 0).  AAD = rec[0, hdr) with the sequence bytes
+ *                   UNPROTECTED.  Payload = [hdr, L - 16), length 0 is taken.  The length field, if present, is not interpreted.  Nonce = the slot's 12-byte IV
+ *                   (aesgcm_keytab_set_tls_iv, from the `iv`) XOR (00 00 00 00 | be64(seq)): the TLS 1.3 formula, and seq is the number that the caller passes -- RFC 9147's
+ *                   64-bit record sequence number, epoch in the upper 16 bits, is the caller's to form.
+ *                   Record-number encryption (RFC 9147 4.2.3): mask = AES-ECB of the 16 bytes rec[hdr, hdr + 16) of the PROTECTED record under the round keys of slot
+ *                   d_sn_slots[p], an ordinary slot of the same table set by aesgcm_keytab_set from the `sn` key; sequence byte i ^= mask[i], i < 1 or 2.
+ *     ENCRYPT   d_in holds the header with the truncated number already written by the caller, the plaintext, and 16 bytes of room for the tag.  d_seq[p] (DEVICE memory,
+ *               n_recs uint64) is the FULL number.  The AEAD launch runs first, then the mask launch on the fresh ciphertext.  d_seq_out and d_auth are ignored.
+ *     DECRYPT   d_in holds the protected record.  d_seq[p] is the EXPECTED number.  The mask launch runs first: it unmasks into d_out (out of place it writes the whole
+ *               header there) and decodes the full number into d_seq_out[p] (required; may be d_seq).  Then the AEAD launch, which reads the header through d_out and the
+ *               number from d_seq_out.
+ *     The decode is RFC 9000 Appendix A.3's on 8 or 16 bits: of the numbers whose low bits are the truncated ones, the one closest to the expected number, a tie (exactly
+ *     half a window away) going upwards.  No step wraps a 64-bit value: at expected 0 nothing is looked for below zero (an expected 0 and truncated bits t give t), and at
+ *     expected 2^64 - 1 nothing above it (the result is the candidate of the last window, (2^64 - 1) with its low bits replaced by the truncated ones).
+ *     Refused, by both kernels through the same tests in this order, and reported by the AEAD alone: either slot is n_slots or more, unset or cleared; the offsets fall;
+ *     L > 65535; d_sn_off[p] == 0; d_sn_off[p] + 17 > L (only after this test is b0 read); (b0 & 0xE0) != 0x20; hdr + 16 > L (the sample must lie inside the record,
+ *     which also guarantees that header and tag fit).
+ * Common to both: d_auth[p] (required for decrypt, ignored for encrypt) = 1 iff the record's tag equals the computed one.  Out of place every byte of an accepted record in
+ * d_out is defined (the header, the payload, and on decrypt the tag copied).  No byte outside an accepted record is written.  A REFUSED record writes nothing, d_seq_out[p]
+ * included; its d_seq[p] is not read; d_auth[p] = 0 on decrypt; and the LOWEST refused index goes to aesgcm_keytab_status.  Common refusals: the slot is n_slots or more,
+ * unset or cleared; the offsets fall.  FAIL-CLOSED: aesgcm_wipe_failed_dev(device, n_recs, d_out, 0, d_rec_off, d_auth, stream) behind a decrypt, as for TLS.
+ * aesgcm_dtls_fmt_check: AESGCM_EARG for NULL, a version other than AESGCM_DTLS_13 / AESGCM_DTLS_12, reserved != 0.  It touches no device; the crypt call runs it first.
+ * Then AESGCM_EARG, before the table or a device is touched, in aesgcm_keytab_quic_crypt_dev's order: t NULL; decrypt not 0 / 1; (n_recs == 0 is AESGCM_OK;) any of d_slots,
+ * d_in, d_out, d_rec_off NULL, for 1.3 also d_sn_slots, d_seq, d_sn_off; decrypt without d_auth, for 1.3 also without d_seq_out; n_recs >= 2^31.
+ * 1.2: one k_kt_dtls launch; 1.3: two launches on `stream`, k_kt_dtls and k_kt_dtls_sn (a lane per record).  No scratch memory, no host synchronisation, capture-safe and
+ * asynchronous; shape and order as aesgcm_keytab_records_crypt_dev.  Ordering and thread safety as the other key-table calls.
+ * OUT OF SCOPE: DTLS 1.2 connection IDs (RFC 9146: another header and another AAD); coalesced datagrams (split them: one entry of d_rec_off per record); choosing the slot
+ * from the epoch bits (E E of b0, or a 1.2 header's epoch: the caller maps them to slots); anti-replay; key derivation (INTEGRATION.md "DTLS records" says which secret
+ * becomes what); ChaCha20 and CCM suites; routing long records to the row kernels. */
+#define AESGCM_DTLS_13 1u   /* unified_hdr | payload | tag[16]; nonce = slot IV XOR (0^32 | be64(seq)); AAD = the unprotected header; record-number encryption under d_sn_slots[p] */
+#define AESGCM_DTLS_12 2u   /* hdr[13] | explicit nonce[8] | payload | tag[16]; nonce = slot IV[0..4) | explicit nonce; AAD = rec[3..11) | rec[0..3) | be16(L - 37) */
+typedef struct aesgcm_dtls_fmt {
+    uint32_t version;   /* AESGCM_DTLS_13 or AESGCM_DTLS_12 */
+    uint32_t reserved;  /* 0                                */
+} aesgcm_dtls_fmt;      /* 8 bytes */
+AESGCM_API int aesgcm_dtls_fmt_check(const aesgcm_dtls_fmt *fmt);
+AESGCM_API int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_dtls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint32_t *d_sn_slots,
+                                 const uint64_t *d_seq, uint64_t *d_seq_out, const uint32_t *d_sn_off,
+                                 const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth, void *stream);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
