@@ -14,14 +14,20 @@
 // DTLS record.  1.3 (RFC 9147): unified_hdr | payload | tag[16], QUIC's structure -- the header ends behind the sequence-number field that starts at wx->pn_off[pkt], 1 or 2
 // bytes by the first byte's S bit, and behind the 2 length bytes that its L bit announces; the first byte, which is never masked, is read through p.in; nonce as TLS 1.3's
 // from wx->seq[pkt]; the header is k_kt_dtls_sn's business.  1.2 (RFC 6347): hdr[13] | explicit nonce[8] | payload | tag[16], TLS 1.2's structure with epoch and sequence
-// number read from the record's bytes 3 .. 10 where TLS 1.2 takes wx->seq[pkt]; no number comes from outside the record.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
+// number read from the record's bytes 3 .. 10 where TLS 1.2 takes wx->seq[pkt]; no number comes from outside the record.  KT_WIREX_SRTP / KT_WIREX_SRTCP (k_kt_srtp,
+// aesgcm_srtp_kernels.hip; RFC 7714): the frame is an SRTP packet rtp_hdr | payload | tag[16] | mki or an SRTCP packet rtcp_hdr[8] | payload | tag[16] | W[4] | mki, the MKI
+// wx->mki_len bytes.  The RTP header's length is parsed from the packet (CSRC count, X bit, the extension's length field); nonce = the slot's 12-byte salt (KtSlot::xpn) XOR
+// SSRC, the rollover counter wx->hi[pkt] and the sequence number (SRTP) or SSRC and W's 31-bit index (SRTCP).  The tag is not the packet's last bytes, and SRTCP's AAD is in
+// two pieces: the packet's front and W, the word behind the tag -- with W's E bit clear nothing is encrypted and everything in front of the tag is AAD.  Text, not a __device__ function: as one, even force-inlined, k_batch3 compiled to another instruction stream (aesgcm_pktg_body.inc:
 // what that cost there).  For the same reason the two key sources read a packet's offsets in different orders: each keeps its kernel's instruction stream.
     static_assert(DEC == 0 || DEC == 1 || (DEC == 2 && !SLOTS), "the probe (DEC == 2) takes raw keys");
     static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
     static_assert(!WIREX || WIRE, "the number that is not on the wire belongs to a frame in wire format");
-    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_QUIC || WIREX == KT_WIREX_DTLS13 || WIREX == KT_WIREX_DTLS12, "one extension or none");
+    static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_QUIC || WIREX == KT_WIREX_DTLS13 || WIREX == KT_WIREX_DTLS12 ||
+                  WIREX == KT_WIREX_SRTP || WIREX == KT_WIREX_SRTCP, "one extension or none");
     constexpr bool x_xpn = WIREX == AESGCM_WIREX_XPN, x_esn = WIREX == AESGCM_WIREX_ESN, x_t13 = WIREX == KT_WIREX_TLS13, x_t12 = WIREX == KT_WIREX_TLS12, x_quic = WIREX == KT_WIREX_QUIC;
     constexpr bool x_d13 = WIREX == KT_WIREX_DTLS13, x_d12 = WIREX == KT_WIREX_DTLS12;
+    constexpr bool x_srtp = WIREX == KT_WIREX_SRTP, x_rtcp = WIREX == KT_WIREX_SRTCP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into
@@ -106,6 +112,41 @@
             pkt_len = bad ? 0u : (u32)(e - b) - 16u - hdr;
             doff = b + (bad ? 0u : hdr);
         } else
+        if constexpr (x_srtp || x_rtcp) {
+            // an SRTP / SRTCP packet (RFC 7714; RFC 3711 3.1, 3.4).  `tail` = what follows the payload: the tag, SRTCP's word W, the MKI.  Refused, in this order: the slot,
+            // the offsets, more than 65535 bytes, too short for the fixed header and the tail (only then is the first byte read), a version other than 2; RTP: the header
+            // with its CSRCs does not fit, with the X bit the extension's four fixed bytes do not fit (only then is its length read), the extension does not fit.  A refused
+            // packet's bytes are not read past the test that refuses it, its rollover counter never
+            const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
+            const u32 tail = 16u + wx->mki_len + (x_rtcp ? 4u : 0u);
+            bad |= ks->set != KT_SET;
+            bad |= e < b || e - b > 65535u || e - b < (u64)((x_rtcp ? 8u : 12u) + tail);
+            const u32 L = bad ? 0u : (u32)(e - b);
+            const u32 b0 = bad ? 0x80u : p.in[b];
+            bad |= (b0 & 0xC0u) != 0x80u;
+            aoff = b;
+            if constexpr (x_srtp) {
+                u32 hdr = 12u + 4u * (b0 & 15u);                                     // the fixed header and CC CSRCs
+                bad |= hdr + tail > L;
+                if (b0 & 0x10u) {                                                    // X: a header extension, 4 bytes and 4 * its length field
+                    bad |= hdr + 4u + tail > L;
+                    const u32 xl = bad ? 0u : ((u32)p.in[b + hdr + 2u] << 8) | p.in[b + hdr + 3u];
+                    hdr += 4u + 4u * xl;
+                    bad |= hdr + tail > L;
+                }
+                aad_len = bad ? 0u : hdr;
+                pkt_len = bad ? 0u : L - tail - hdr;
+                doff = b + (bad ? 0u : hdr);
+            } else {
+                // SRTCP: W = E | index lies behind the tag.  E set: AAD = the 8 header bytes | W, payload behind the header.  E clear: nothing is encrypted, AAD = everything
+                // in front of the tag | W, and all of it passes through (doff = where the tag starts, as an auth-only frame's)
+                const u32 body = bad ? 0u : L - tail;                                // the bytes in front of the tag: 8 or more
+                const bool enc = !bad && (p.in[b + body + 16u] & 0x80u) != 0;
+                aad_len = bad ? 0u : enc ? 12u : body + 4u;
+                pkt_len = enc ? body - 8u : 0u;
+                doff = b + (enc ? 8u : body);
+            }
+        } else
         if constexpr (WIRE) {
             // the frame's one range: AAD from its first byte, payload behind the header, the ICV last; auth-only: everything in front of the ICV is AAD.  A frame too
             // short for header (nonce bytes included) and ICV is refused like a falling range
@@ -161,8 +202,8 @@
         u32 iv0, iv1, iv2;
         if constexpr (WIRE) {
             // the nonce: salt_len (0, 4 or 8) bytes of the slot's salt, then header bytes -- whole words either way; a refused frame's header is not read
-            const u32 sw = x_xpn ? 2u : x_t13 || x_quic || x_d13 ? 3u : x_t12 || x_d12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
-            const u32 f0 = bad || x_t13 || x_quic || x_d13 ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
+            const u32 sw = x_xpn ? 2u : x_t13 || x_quic || x_d13 || x_srtp || x_rtcp ? 3u : x_t12 || x_d12 ? 1u : wf->salt_len >> 2;                    // (XPN: salt_len is 8 -- aesgcm_wire_xfmt_check; TLS 1.3: no frame bytes)
+            const u32 f0 = bad || x_t13 || x_quic || x_d13 || x_srtp || x_rtcp ? 0u : gload4_any(ivp), f1 = bad || sw > 1u ? 0u : gload4_any(ivp + 4), f2 = bad || sw > 0u ? 0u : gload4_any(ivp + 8);
             iv0 = sw ? ks->salt[0] : f0;
             iv1 = sw > 1u ? ks->salt[1] : sw ? f0 : f1;
             iv2 = sw > 1u ? f0 : sw ? f1 : f2;
@@ -180,6 +221,18 @@
             if constexpr (x_quic || x_d13) {
                 // QUIC (RFC 9001 5.3): TLS 1.3's formula with the packet number; DTLS 1.3 (RFC 9147 4.2.1 -> RFC 8446 5.3): with the record's sequence number
                 iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(qpn >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)qpn);
+            }
+            if constexpr (x_srtp) {
+                // SRTP (RFC 7714 8.1): the slot's 12-byte salt XOR (00 00 | SSRC | ROC | SEQ) -- SSRC = the packet's bytes 8 .. 11, SEQ its bytes 2, 3, the rollover counter
+                // hi[pkt], big-endian.  A refused packet's bytes and counter are not read
+                const u32 ssrc = bad ? 0u : gload4_any(p.in + aoff + 8), sq = bad ? 0u : gload4_any(p.in + aoff) & 0xFFFF0000u, roc = bad ? 0u : bswap32(wx->hi[pkt]);
+                iv0 = ks->xpn[0] ^ (ssrc << 16); iv1 = ks->xpn[1] ^ (ssrc >> 16) ^ (roc << 16); iv2 = ks->xpn[2] ^ (roc >> 16) ^ sq;
+            }
+            if constexpr (x_rtcp) {
+                // SRTCP (RFC 7714 9.1): the salt XOR (00 00 | SSRC | 00 00 | 0, the 31-bit index) -- SSRC = the packet's bytes 4 .. 7, the index = W without its E bit (the
+                // top bit of W's first byte).  W lies 16 bytes behind the payload, or behind the AAD's packet bytes when there is none
+                const u32 ssrc = bad ? 0u : gload4_any(p.in + aoff + 4), w = bad ? 0u : gload4_any(in + pkt_len + 16u) & 0xFFFFFF7Fu;
+                iv0 = ks->xpn[0] ^ (ssrc << 16); iv1 = ks->xpn[1] ^ (ssrc >> 16); iv2 = ks->xpn[2] ^ w;
             }
             // out of place: the bytes in front of the payload (header; auth-only: all but the ICV) pass through (QUIC: k_kt_quic_hp writes the header; DTLS 1.3: k_kt_dtls_sn)
             if constexpr (!x_quic && !x_d13)
@@ -263,6 +316,14 @@
                     // DTLS 1.2's one AAD block: epoch | sequence number as the record's bytes 3 .. 10 carry them, then as TLS 1.2's -- type, version | be16(payload length),
                     // the length from the offsets (pkt_len < 2^16: the check above)
                     gin = make_uint4(gload4_any(aad + 3), gload4_any(aad + 7), (gload4_any(aad) & 0x00FFFFFFu) | ((pkt_len >> 8) << 24), pkt_len & 0xFFu);
+                } else if constexpr (x_rtcp) {
+                    // SRTCP's AAD is in two pieces: packet bytes, then W from behind the tag (in + pkt_len + 16: see the nonce), fetched here by the lane that needs it.
+                    // 12 bytes (E set; E clear and a bare header): the one block header | W.  Longer (E clear): aad_len - 4 packet bytes; a block that lies inside them is a
+                    // plain load, the others take what is left of the packet bytes and as much of W as fits -- W may split over the last two blocks
+                    const u32 body = aad_len - 4u;
+                    if (aad_len == 12u) gin = make_uint4(gload4_any(aad), gload4_any(aad + 4), gload4_any(in + pkt_len + 16u), 0u);
+                    else if (off + 16u <= body) gin = gload16_any(aad + off);
+                    else gin = load_block_split(aad + off, off < body ? body - off : 0u, in + pkt_len + 16u, off > body ? off - body : 0u);
                 } else
                 gin = rem >= 16 ? gload16_any(aad + off) : load_block_bytes(aad + off, rem);
             } else {
@@ -316,13 +377,19 @@
         }
         { const uint4 ev = *reinterpret_cast<const uint4 *>(smem + hsA2 + 16u); acc.w[0] ^= ev.x; acc.w[1] ^= ev.y; acc.w[2] ^= ev.z; acc.w[3] ^= ev.w; }
         if constexpr (WIRE) {
-            // the ICV = the tag's first tag_len bytes, the frame's last: written (encrypt) or compared (decrypt; copied when out of place) with stores that end at the
+            // the ICV = the tag's first tag_len bytes, the frame's last (SRTP / SRTCP: in front of the trail): written (encrypt) or compared (decrypt; copied when out of place) with stores that end at the
             // frame's end.  A refused frame: nothing but auth 0.
             if (l2 == G - 1u && act2) {
                 int ok = 0;
                 if (!bad) {
                     const u32 tl = wf->tag_len;
-                    const u64 at = p.data_off[pkt2 + 1] - tl;
+                    u64 at = p.data_off[pkt2 + 1] - tl;
+                    if constexpr (x_srtp || x_rtcp) {
+                        // the tag is not last: SRTCP's W and the MKI follow it, and pass through out of place, copied by this lane
+                        const u32 trail = wx->mki_len + (x_rtcp ? 4u : 0u);
+                        at -= trail;
+                        if (p.in != p.out) wire_copy_front(p.out + at + tl, p.in + at + tl, trail, 0u, 1u);
+                    }
                     const uint4 tag = be_to_mo(acc);                       // (tl is 8, 12 or 16: whole words)
                     if (DEC == 1) {
                         const uint4 e = wire_load_icv(p.in + at, tl);

@@ -8,3 +8,4 @@
 #include "aesgcm_tls_kernels.hip"
 #include "aesgcm_quic_kernels.hip"
 #include "aesgcm_dtls_kernels.hip"
+#include "aesgcm_srtp_kernels.hip"

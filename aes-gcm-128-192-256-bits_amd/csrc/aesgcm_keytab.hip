@@ -9,6 +9,7 @@
 //   tls      aesgcm_keytab_records_crypt_dev      k_kt_tls     TLS records with their 64-bit sequence numbers
 //   quic     aesgcm_keytab_quic_crypt_dev         k_kt_quic    QUIC packets, and a second launch, k_kt_quic_hp (header protection, a lane per packet)
 //   dtls     aesgcm_keytab_dtls_crypt_dev         k_kt_dtls    DTLS records; 1.3: and a second launch, k_kt_dtls_sn (record-number encryption, a lane per record)
+//   srtp     aesgcm_keytab_srtp_crypt_dev         k_kt_srtp    SRTP and SRTCP packets (RFC 7714)
 // The calls in wire format fill their kernel parameters by kt_wire_params.
 #include "aesgcm_keytab.h"
 
@@ -355,6 +356,35 @@ int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_dtl
     if (v13 && decrypt) HIPCHK(klaunch_kt_dtls_sn(b.nr, 1, b.st, b.tables, sn));
     HIPCHK(klaunch_kt_dtls(fmt->version, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
     if (v13 && !decrypt) HIPCHK(klaunch_kt_dtls_sn(b.nr, 0, b.st, b.tables, sn));
+    return batch_done(b, p);
+}
+
+// ---------------------------------------------------------------- SRTP and SRTCP packets
+int aesgcm_srtp_fmt_check(const aesgcm_srtp_fmt *f) {
+    if (!f || (f->kind != AESGCM_SRTP_RTP && f->kind != AESGCM_SRTP_RTCP) || f->mki_len > 128u) return AESGCM_EARG;
+    return AESGCM_OK;
+}
+
+// One k_kt_srtp launch, planned as the DTLS 1.2 call's: everything the kernel needs beside the rollover counters and the MKI's length is in the packet.  No scratch
+// memory, no host synchronisation: capture-safe.
+int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srtp_fmt *fmt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_roc, const void *d_in,
+                                 const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream) {
+    const int frc = aesgcm_srtp_fmt_check(fmt);
+    if (frc) return frc;
+    const bool rtp = fmt->kind == AESGCM_SRTP_RTP;
+    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
+    if (!n_pkts) return AESGCM_OK;
+    if (!d_slots || !d_in || !d_pkt_off || !d_out || (rtp && !d_roc) || (decrypt && !d_auth) || n_pkts >= ((size_t)1 << 31)) return AESGCM_EARG;
+    KtWireXParams xp;
+    kt_wire_params(xp, t, decrypt, d_in, d_in, d_out, d_pkt_off, d_slots, d_auth);
+    xp.w.f.tag_len = 16;                                                              // the rest of a wire format is per packet here
+    xp.hi = rtp ? d_roc : nullptr;
+    xp.mki_len = fmt->mki_len;
+    BatchParams &p = xp.w.k.b;
+    BatchPlan b;
+    const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
+    if (rc) return rc;
+    HIPCHK(klaunch_kt_srtp(fmt->kind, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
     return batch_done(b, p);
 }
 

@@ -252,6 +252,15 @@ HD uint4 load_block_bytes(const unsigned char *p, u32 nbytes) {
     }
     return make_uint4(w0, w1, w2, w3);
 }
+// a block assembled from two places: n1 (< 16) bytes at p, then the bytes [skip, 4) of the dword at q (skip < 4) as far as they fit into the block, zero behind them
+// (SRTCP's AAD: packet bytes, then the word behind the tag -- aesgcm_batch3_body.inc).  The dword is one access at any byte address; constant word indices as above
+HD uint4 load_block_split(const unsigned char *p, u32 n1, const unsigned char *q, u32 skip) {
+    const uint4 v = load_block_bytes(p, n1);
+    const u64 t = (u64)(gload4_any(q) >> (8u * skip)) << (8u * (n1 & 3u));
+    const u32 lo = (u32)t, hi = (u32)(t >> 32), wi = n1 >> 2;
+    return make_uint4(v.x | (wi == 0u ? lo : 0u), v.y | (wi == 1u ? lo : wi == 0u ? hi : 0u), v.z | (wi == 2u ? lo : wi == 1u ? hi : 0u),
+                      v.w | (wi == 3u ? lo : wi == 2u ? hi : 0u));
+}
 HD void store_block_bytes(unsigned char *p, uint4 v, u32 nbytes, bool wt = false) {      // wt: through the L2 (gstore16_wt)
     if (nbytes == 16) {                                            // a whole block: one access at any byte address
         if (wt) gstore16_wt_at(p, v); else gstore16_any(p, v);

@@ -45,6 +45,7 @@ SYMBOLS = [
     "aesgcm_tls_fmt_check", "aesgcm_keytab_set_tls_iv", "aesgcm_keytab_records_crypt_dev",
     "aesgcm_keytab_quic_crypt_dev",
     "aesgcm_dtls_fmt_check", "aesgcm_keytab_dtls_crypt_dev",
+    "aesgcm_srtp_fmt_check", "aesgcm_keytab_srtp_crypt_dev",
 ]
 
 
@@ -727,6 +728,8 @@ def _keytab_typed(L):
         L.aesgcm_keytab_quic_crypt_dev.argtypes = [vp, cint, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.aesgcm_dtls_fmt_check.argtypes = [ctypes.POINTER(DtlsFormat)]
         L.aesgcm_keytab_dtls_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(DtlsFormat), sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_srtp_fmt_check.argtypes = [ctypes.POINTER(SrtpFormat)]
+        L.aesgcm_keytab_srtp_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(SrtpFormat), sz, vp, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
 
@@ -836,6 +839,34 @@ class DtlsFormat(ctypes.Structure):
 
     def __repr__(self):
         return "DtlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
+
+
+SRTP_RTP = 1            # AESGCM_SRTP_RTP
+SRTP_RTCP = 2           # AESGCM_SRTP_RTCP
+
+
+class SrtpFormat(ctypes.Structure):
+    """aesgcm_srtp_fmt: which packet an srtp call takes and how many bytes of MKI end it (include/aesgcm.h "SRTP AND SRTCP PACKETS")"""
+    _fields_ = [("kind", ctypes.c_uint32), ("mki_len", ctypes.c_uint32)]
+
+    @classmethod
+    def rtp(cls, mki_len=0):
+        """RFC 7714 over RFC 3711 3.1: rtp_hdr | payload | tag[16] | mki; the header's length from the packet, nonce = the slot's salt XOR (SSRC, the rollover counter,
+        the sequence number), AAD = the header"""
+        return cls(SRTP_RTP, mki_len)
+
+    @classmethod
+    def rtcp(cls, mki_len=0):
+        """RFC 7714 over RFC 3711 3.4: rtcp_hdr[8] | payload | tag[16] | W[4] | mki, W = E | index; nonce = the slot's salt XOR (SSRC, the index); AAD = the header | W, or
+        with E clear everything in front of the tag | W"""
+        return cls(SRTP_RTCP, mki_len)
+
+    def check(self):
+        """aesgcm_srtp_fmt_check -> OK or EARG (no device needed)"""
+        return _keytab_typed(load()).aesgcm_srtp_fmt_check(ctypes.byref(self))
+
+    def __repr__(self):
+        return "SrtpFormat(kind=%d, mki_len=%d)" % (self.kind, self.mki_len)
 
 
 def _per_slot(x, width, what, pad=False):
@@ -1021,6 +1052,30 @@ class KeyTable:
             down["seq_out"] = "Q"
         outs, got = self._packed_call(records, up, down, call)
         return outs, got.get("auth"), got.get("seq_out")
+
+    def srtp_crypt_dev(self, decrypt, fmt, n_pkts, d_slots, d_in, d_pkt_off, d_out, d_roc=None, d_auth=None, stream=None):
+        """aesgcm_keytab_srtp_crypt_dev: SRTP or SRTCP packet p (fmt, an SrtpFormat, says which) = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in / d_out under slot
+        d_slots[p] (key by set, salt by set_tls_iv).  SRTP also takes d_roc[p] (uint32), the packet's rollover counter.  The verdict goes to d_auth[p]"""
+        _chk(self._lib.aesgcm_keytab_srtp_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_pkts, d_slots, d_roc, d_in, d_pkt_off, d_out, d_auth, stream))
+
+    def crypt_srtp(self, fmt, slots, packets, decrypt=False, rocs=None):
+        """Host convenience (tests, examples), crypt_dtls's counterpart: whole SRTP or SRTCP packets (on encrypt the headers, SRTCP's word W and the MKI are written and
+        the tag's bytes are placeholders) through one call, in place.  SRTP: rocs, a rollover counter per packet.  -> (packets_out, auth); auth is None on encrypt."""
+        n = len(slots)
+        rtp = fmt.kind == SRTP_RTP
+        if len(packets) != n or not n or (rtp and (rocs is None or len(rocs) != n)) or (not rtp and rocs is not None):
+            raise AesGcmError(EARG, "slots and packets (SRTP: and rocs; SRTCP: without them) must be equally long and not empty")
+        up = {"slots": ("I", slots)}
+        if rtp:
+            up.update(roc=("I", rocs))
+        if decrypt:
+            up.update(auth=bytes(4 * n))                                           # zero where a refused packet leaves them alone
+
+        def call(b):
+            self.srtp_crypt_dev(decrypt, fmt, n, b["slots"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_roc=b["roc"].ptr if rtp else None,
+                                d_auth=b["auth"].ptr if decrypt else None)
+        outs, got = self._packed_call(packets, up, {"auth": "i"} if decrypt else {}, call)
+        return outs, got.get("auth")
 
     def status(self):
         """aesgcm_keytab_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""

@@ -39,7 +39,7 @@ extern "C" {
 
 #define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
-                                  aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev)
+                                  aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -635,6 +635,49 @@ AESGCM_API int aesgcm_dtls_fmt_check(const aesgcm_dtls_fmt *fmt);
 AESGCM_API int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_dtls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint32_t *d_sn_slots,
                                  const uint64_t *d_seq, uint64_t *d_seq_out, const uint32_t *d_sn_off,
                                  const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- key tables on SRTP AND SRTCP PACKETS in wire format: RFC 7714 AEAD_AES_128_GCM / AEAD_AES_256_GCM
+ * A WebRTC terminator uses DTLS for the handshake only: every media byte it moves is SRTP, every control packet SRTCP (RFC 3711).  Under RFC 7714 both are AES-GCM with the
+ * nonce and the AAD taken from the packet.  No other call can express them: the RTP header's length is in the packet (CSRC count, X bit, the extension's own length field);
+ * the tag is not the packet's last bytes (SRTCP's E-flag / index word and an optional MKI follow it); and SRTCP's AAD is not contiguous (the packet's front plus the word
+ * behind the tag).  aesgcm_keytab_srtp_crypt_dev takes the buffer as it is: packet p is bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in and of d_out (the same n_pkts + 1
+ * offsets for both; d_in == d_out allowed; any byte alignment), L bytes long, ONE packet, under slot d_slots[p].  The slot holds the session key (aesgcm_keytab_set) and the
+ * 12-byte session salt (aesgcm_keytab_set_tls_iv: the slot state that TLS, QUIC and DTLS use for their IV).  fmt->mki_len (0 .. 128) bytes of MKI end every packet of the
+ * call; they pass through and are not authenticated (RFC 3711 3.1).  fmt->kind says which packet:
+ *   AESGCM_SRTP_RTP   rtp_hdr | payload | tag[16] | mki  (RFC 7714 8, 9; RFC 3711 3.1).  hdr = 12 + 4 * (b0 & 15), b0 the first byte; if b0 & 0x10 (the X bit),
+ *                     hdr += 4 + 4 * be16(pkt[hdr + 2 .. hdr + 4)), the extension's length taken at the hdr of before.  AAD = pkt[0, hdr).  Payload = [hdr, L - 16 - mki_len),
+ *                     length 0 is taken; RTP padding is payload and is not interpreted.  Nonce = salt XOR (00 00 | pkt[8..12) | be32(d_roc[p]) | pkt[2..4)): SSRC, rollover
+ *                     counter, sequence number.  d_roc (DEVICE memory, n_pkts numeric uint32) is the rollover counter to use for each packet: a sender passes its own, a
+ *                     receiver estimates it from its highest sequence number before the call (RFC 3711 3.3.1), as an XPN receiver does for d_hi.
+ *   AESGCM_SRTP_RTCP  rtcp_hdr[8] | payload | tag[16] | W[4] | mki, W = E (1 bit) | index (31 bits), big-endian  (RFC 7714 9.2 - 10; RFC 3711 3.4).  W IS READ FROM THE WIRE
+ *                     in both directions: the sender writes W and the headers before the call, as a SecY writes its SecTAG.  Nonce = salt XOR (00 00 | pkt[4..8) | 00 00 |
+ *                     be32(W & 0x7FFFFFFF)).  E = 1: AAD = pkt[0, 8) | W, 12 bytes; payload = [8, L - 20 - mki_len).  E = 0: nothing is encrypted; AAD = pkt[0, L - 20 -
+ *                     mki_len) | W, and every byte passes through.  E is per packet: one call mixes both.  d_roc is ignored and may be NULL.
+ * d_auth[p] (required for decrypt, ignored for encrypt) = 1 iff the packet's tag equals the computed one.  Out of place every byte of an accepted packet in d_out is defined:
+ * what is not ciphertext or plaintext is copied -- the header, W, the MKI, and on decrypt the tag's bytes as they came.  No byte outside an accepted packet is written.
+ * A REFUSED packet is left untouched; d_auth[p] = 0 on decrypt; the LOWEST refused index goes to aesgcm_keytab_status; the rest of the call runs.  Its bytes and its d_roc[p]
+ * are not read past the test that refuses it.  The tests, in this order: the slot is n_slots or more, unset or cleared; the offsets fall; L > 65535; L < 12 + 16 + mki_len
+ * (RTP) or L < 8 + 20 + mki_len (RTCP); only now is b0 read: (b0 & 0xC0) != 0x80; RTP: hdr + 16 + mki_len > L behind the CSRC term; with X: hdr + 4 + 16 + mki_len > L,
+ * tested before the extension's length is read; with X: hdr + 16 + mki_len > L behind the extension.
+ * FAIL-CLOSED: aesgcm_wipe_failed_dev(device, n_pkts, d_out, 0, d_pkt_off, d_auth, stream) behind a decrypt, as for TLS.
+ * aesgcm_srtp_fmt_check: AESGCM_EARG for NULL, a kind other than AESGCM_SRTP_RTP / AESGCM_SRTP_RTCP, mki_len > 128.  It touches no device; the crypt call runs it first.
+ * Then AESGCM_EARG, before the table or a device is touched, in aesgcm_keytab_dtls_crypt_dev's order: t NULL; decrypt not 0 / 1; (n_pkts == 0 is AESGCM_OK;) any of d_slots,
+ * d_in, d_pkt_off, d_out NULL; RTP without d_roc; decrypt without d_auth; n_pkts >= 2^31.
+ * ONE k_kt_srtp launch: no scratch memory, no host synchronisation, capture-safe and asynchronous; shape, order and planning as aesgcm_keytab_dtls_crypt_dev's DTLS 1.2
+ * mode.  Ordering and thread safety as the other key-table calls.
+ * OUT OF SCOPE: ROC estimation and replay windows; key derivation (RFC 3711 4.3 KDF, the DTLS-SRTP exporter: INTEGRATION.md "SRTP and SRTCP packets" says which secret
+ * becomes what); the AES-CM / HMAC-SHA1 transforms; double encryption (RFC 8723); RFC 6904 header-extension encryption; MKI lookup (the caller maps an MKI to a slot, and one
+ * call has one mki_len); splitting reduced-size or multiplexed datagrams (one entry of d_pkt_off per packet; a compound RTCP packet is ONE packet). */
+#define AESGCM_SRTP_RTP  1u
+#define AESGCM_SRTP_RTCP 2u
+typedef struct aesgcm_srtp_fmt {
+    uint32_t kind;      /* AESGCM_SRTP_RTP or AESGCM_SRTP_RTCP */
+    uint32_t mki_len;   /* 0 .. 128: bytes of MKI that end the packet, passed through, not authenticated */
+} aesgcm_srtp_fmt;      /* 8 bytes */
+AESGCM_API int aesgcm_srtp_fmt_check(const aesgcm_srtp_fmt *fmt);
+AESGCM_API int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srtp_fmt *fmt, size_t n_pkts,
+                                 const uint32_t *d_slots, const uint32_t *d_roc,
+                                 const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
