@@ -1,4 +1,4 @@
-"""What the key-table tests share: for the GPU tests of the family (tests/test_gpu_keytab.py, _wire, _wirex, _tls, _quic) the upload and packing helpers, the layout of
+"""What the key-table tests share: for the GPU tests of the family (tests/test_gpu_keytab.py, _wire, _wirex, _tls, _quic, _dtls, _srtp) the upload and packing helpers, the layout of
 packets between guard bytes, the libcrypto handle and each family's expected frames from libcrypto (wire_ref_encrypt, x_ref_encrypt, tls_ref_encrypt: nonce and AAD
 by the standards' formulas in plain Python), and for tests/test_gpu_kt_grid.py and tests/test_kt_grid_cpu.py the reference of a grid of tests/kt_grid.py
 (grid_reference); for their CPU counterparts (tests/test_keytab_cpu.py, ...) the census of a family's gfx950 listing and what every
@@ -12,9 +12,11 @@ import sys
 import numpy as np
 import pytest
 
+import dtls_fixture as D
 import kt_grid as KG
 import pkt_grid as PG
 import quic_fixture as Q
+import srtp_fixture as S
 import tls_fixture as T
 from util import splitmix_bytes
 
@@ -192,20 +194,21 @@ class Guarded:
 
 def grid_format(lib, mode):
     """the library's format of a grid mode (None for QUIC, which has none)"""
-    W, X, F = lib.WireFormat, lib.WireFormatX, lib.TlsFormat
+    W, X, F, DF, SF = lib.WireFormat, lib.WireFormatX, lib.TlsFormat, lib.DtlsFormat, lib.SrtpFormat
     return {"macsec": W.macsec, "esp16": lambda: W.esp(16), "esp12": lambda: W.esp(12), "esp8": lambda: W.esp(8), "macsec_auth": lambda: W.macsec(sci=False, auth_only=True),
-            "xpn": X.macsec_xpn, "esn16": lambda: X.esp_esn(16), "tls13": F.tls13, "tls12": F.tls12, "quic": lambda: None}[mode]()
+            "xpn": X.macsec_xpn, "esn16": lambda: X.esp_esn(16), "tls13": F.tls13, "tls12": F.tls12, "quic": lambda: None, "dtls13": DF.dtls13, "dtls12": DF.dtls12,
+            "srtp": lambda: SF.rtp(0), "srtp_mki": lambda: SF.rtp(4), "srtcp": lambda: SF.rtcp(0), "srtcp_clear": lambda: SF.rtcp(3)}[mode]()
 
 
 class GridRef:
     """what a grid of tests/kt_grid.py must become under one key size, from the family's own fixture (libcrypto through evp_by_slot with nonce and AAD by the
-    family's formulas; QUIC: tests/quic_fixture.py) -- never from a GPU path:
-      keys, salts / sa / ivs   what the table's slots hold
+    family's formulas; QUIC: tests/quic_fixture.py; DTLS: tests/dtls_fixture.py; SRTP and SRTCP: tests/srtp_fixture.py) -- never from a GPU path:
+      keys, salts / sa / ivs   what the table's slots hold (DTLS and SRTP: ivs, the 12-byte IV or session salt that set_tls_iv takes)
       enc         the arena with the reference's frames in place of the plaintext ones
-      dec_in      ... with the ICVs of g.forged forged (one bit inside the first tag_len bytes)
-      dec_out     what decrypting dec_in in place leaves: front and plaintext, the ICV's bytes as they came (QUIC: a forged packet's bytes are what the
-                  fixture's unprotect makes of it -- a forged tag that lies in the sample changes the header's mask)
-      auth, pn_out  the verdicts, and for QUIC the decoded numbers"""
+      dec_in      ... with the ICVs of g.forged forged (one bit inside the first tag_len bytes of the ICV, which SRTP and SRTCP have in front of their trailer)
+      dec_out     what decrypting dec_in in place leaves: front and plaintext, the ICV's bytes as they came, the trailer (QUIC and DTLS 1.3: a forged packet's
+                  bytes are what the fixture's unprotect makes of it -- a forged tag that lies in the sample changes the header's mask)
+      auth, pn_out  the verdicts, and for QUIC and DTLS 1.3 the decoded numbers"""
 
 
 _REFS = {}
@@ -217,8 +220,8 @@ def grid_reference(lib, evp, mode, key_len):
     g = KG.grid(mode)
     R = GridRef()
     R.g, R.key_len, R.fmt = g, key_len, grid_format(lib, mode)
-    n_slots = KG.N_AEAD + (KG.N_HP if g.family == "quic" else 0)
-    seed = 0x6B7E0000 + 256 * sorted(KG.MODES).index(mode) + key_len
+    n_slots = KG.N_AEAD + (KG.N_HP if g.hps is not None else 0)
+    seed = 0x6B7E0000 + 256 * KG.SEED_ORDER.index(mode) + key_len
     R.keys = splitmix_bytes(seed, key_len * n_slots)
     frames = g.frames()
     f = R.fmt.f if g.family == "wirex" else R.fmt
@@ -240,20 +243,35 @@ def grid_reference(lib, evp, mode, key_len):
         ib = splitmix_bytes(seed + 1, 12 * KG.N_AEAD)
         R.ivs = [ib[12 * s:12 * s + 12] for s in range(KG.N_AEAD)]
         R.key = lambda s: R.keys[key_len * s:key_len * (s + 1)]
-        enc = [Q.protect(R.key(g.slots[i]), R.ivs[g.slots[i]], R.key(g.hps[i]), g.nums[i], g.pn_off[i], frames[i]) for i in range(g.n)]
+        R.mki_len = 0
+        if g.family == "quic":
+            enc = [Q.protect(R.key(g.slots[i]), R.ivs[g.slots[i]], R.key(g.hps[i]), g.nums[i], g.pn_off[i], frames[i]) for i in range(g.n)]
+        elif mode == "dtls13":
+            enc = [D.protect13(R.key(g.slots[i]), R.ivs[g.slots[i]], R.key(g.hps[i]), g.nums[i], g.sn_off[i], frames[i]) for i in range(g.n)]
+        elif mode == "dtls12":
+            enc = [D.protect12(R.key(g.slots[i]), R.ivs[g.slots[i]], frames[i]) for i in range(g.n)]
+        else:
+            R.kind, R.mki_len = (S.RTCP, g.trail[0] - 4) if g.rtcp else (S.RTP, g.trail[0])
+            assert (R.fmt.kind, R.fmt.mki_len) == (R.kind, R.mki_len), mode
+            enc = [S.protect(R.kind, R.key(g.slots[i]), R.ivs[g.slots[i]], 0 if g.rtcp else g.nums[i], frames[i], R.mki_len) for i in range(g.n)]
     assert [len(e) for e in enc] == g.flen
     tl = g.tag_len
     bad = list(enc)
     for i in g.forged:
         b = bytearray(enc[i])
-        b[len(b) - tl + i % tl] ^= 1 << (i % 8)
+        b[g.tag_at(i) + i % tl] ^= 1 << (i % 8)
         bad[i] = bytes(b)
-    dec = [p[:-tl] + e[-tl:] for p, e in zip(frames, bad)]
+    dec = [p[:g.tag_at(i)] + e[g.tag_at(i):] for i, (p, e) in enumerate(zip(frames, bad))]
     R.auth = [0 if i in set(g.forged) else 1 for i in range(g.n)]
     if g.family == "quic":
         R.pn_out = list(g.nums)
         for i in g.forged:
             dec[i], R.pn_out[i], ok = Q.unprotect(R.key(g.slots[i]), R.ivs[g.slots[i]], R.key(g.hps[i]), g.expected_pns[i], g.pn_off[i], bad[i])
+            assert not ok
+    if mode == "dtls13":
+        R.pn_out = list(g.nums)
+        for i in g.forged:
+            dec[i], R.pn_out[i], ok = D.unprotect13(R.key(g.slots[i]), R.ivs[g.slots[i]], R.key(g.hps[i]), g.expected_seqs[i], g.sn_off[i], bad[i])
             assert not ok
     lo, hi = PG.GUARD, int(g.off[-1])
 
