@@ -9,3 +9,4 @@
 #include "aesgcm_quic_kernels.hip"
 #include "aesgcm_dtls_kernels.hip"
 #include "aesgcm_srtp_kernels.hip"
+#include "aesgcm_rxwin_kernels.hip"

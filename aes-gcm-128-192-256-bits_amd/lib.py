@@ -46,6 +46,8 @@ SYMBOLS = [
     "aesgcm_keytab_quic_crypt_dev",
     "aesgcm_dtls_fmt_check", "aesgcm_keytab_dtls_crypt_dev",
     "aesgcm_srtp_fmt_check", "aesgcm_keytab_srtp_crypt_dev",
+    "aesgcm_rxwin_create", "aesgcm_rxwin_set", "aesgcm_rxwin_get", "aesgcm_rxwin_fmt_check", "aesgcm_rxwin_recover_dev", "aesgcm_rxwin_commit_dev", "aesgcm_rxwin_status",
+    "aesgcm_rxwin_destroy",
 ]
 
 
@@ -1129,6 +1131,185 @@ class KeyTable:
         finally:
             for b in bufs.values():
                 b.free()
+
+
+# ---------------------------------------------------------------- receive windows (aesgcm_rxwin_*)
+def _rxwin_typed(L):
+    """type the aesgcm_rxwin_* symbols on first use, as _keytab_typed does: the fake runtime of tests/fake_hip links no such unit and still loads"""
+    if not getattr(L, "_rxwin_typed", False):
+        pu64 = ctypes.POINTER(u64)
+        L.aesgcm_rxwin_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_rxwin_set.argtypes = [vp, sz, sz, pu64, pu64, vp]
+        L.aesgcm_rxwin_get.argtypes = [vp, sz, sz, pu64, pu64, vp]
+        L.aesgcm_rxwin_fmt_check.argtypes = [ctypes.POINTER(RxFormat)]
+        L.aesgcm_rxwin_recover_dev.argtypes = [vp, ctypes.POINTER(RxFormat), sz, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_rxwin_commit_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_rxwin_status.argtypes = [vp, ctypes.POINTER(cint), pu64]
+        L.aesgcm_rxwin_destroy.argtypes = [vp]
+        L._rxwin_typed = True
+    return L
+
+
+RXWIN_NONE = (1 << 64) - 1                                          # AESGCM_RXWIN_NONE
+RXWIN_WIRE, RXWIN_LOWEST, RXWIN_SRTP, RXWIN_EXPECT = 1, 2, 3, 4     # AESGCM_RXWIN_WIRE ...
+RXWIN_FROM_END, RXWIN_CLEAR_TOP = 1, 2                              # AESGCM_RXWIN_FROM_END, AESGCM_RXWIN_CLEAR_TOP
+RXWIN_WHY = ("not authenticated", "accepted", "old", "replay", "refused")      # d_why's values 0 .. 4
+
+
+class RxFormat(ctypes.Structure):
+    """aesgcm_rxwin_fmt: where a packet's truncated number lies and how the full one is formed from it and the window (include/aesgcm.h "RECEIVE WINDOWS")"""
+    _fields_ = [("rule", ctypes.c_uint32), ("num_off", ctypes.c_uint32), ("num_len", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+    @classmethod
+    def macsec(cls):
+        """IEEE 802.1AE: the SecTAG's 32-bit PN is the number"""
+        return cls(RXWIN_WIRE, 16, 4, 0)
+
+    @classmethod
+    def macsec_xpn(cls):
+        """IEEE 802.1AEbw 10.6.2: the 64-bit PN at or above the lowest acceptable one; hi = the d_hi of frames_crypt_x_dev"""
+        return cls(RXWIN_LOWEST, 16, 4, 0)
+
+    @classmethod
+    def esp(cls):
+        """RFC 4303: the 32-bit sequence number"""
+        return cls(RXWIN_WIRE, 4, 4, 0)
+
+    @classmethod
+    def esp_esn(cls):
+        """RFC 4303 Appendix A2.1: the 64-bit sequence number; hi = seq-hi, the d_hi of frames_crypt_x_dev"""
+        return cls(RXWIN_LOWEST, 4, 4, 0)
+
+    @classmethod
+    def dtls12(cls):
+        """RFC 6347: the record's 48-bit sequence number (a window is an epoch)"""
+        return cls(RXWIN_WIRE, 5, 6, 0)
+
+    @classmethod
+    def srtp(cls):
+        """RFC 3711 3.3.1: ROC << 16 | SEQ; hi = the d_roc of srtp_crypt_dev"""
+        return cls(RXWIN_SRTP, 2, 2, 0)
+
+    @classmethod
+    def srtcp(cls, mki_len=0):
+        """RFC 3711 3.4: the 31-bit SRTCP index behind the tag, in front of the MKI"""
+        return cls(RXWIN_WIRE, 4 + mki_len, 4, RXWIN_FROM_END | RXWIN_CLEAR_TOP)
+
+    @classmethod
+    def expect(cls):
+        """QUIC and DTLS 1.3: the expected number, the window's next; no packet byte is read"""
+        return cls(RXWIN_EXPECT, 0, 0, 0)
+
+    def check(self):
+        """aesgcm_rxwin_fmt_check -> OK or EARG (no device needed)"""
+        return _rxwin_typed(load()).aesgcm_rxwin_fmt_check(ctypes.byref(self))
+
+    def __repr__(self):
+        return "RxFormat(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+class RxWindows:
+    """aesgcm_rxwin: n_wins device-resident receive windows of `window` bits; recover_dev gives a decrypt call its per-packet numbers, commit_dev drops replays and
+    advances the windows behind it (include/aesgcm.h "RECEIVE WINDOWS")."""
+
+    def __init__(self, n_wins, window=64, device=0):
+        self._w = None
+        L = _rxwin_typed(load())
+        w = vp()
+        _chk(L.aesgcm_rxwin_create(ctypes.byref(w), device, n_wins, window))
+        self._w, self._lib = w.value, L
+        self.n_wins, self.window, self.device = n_wins, window, device
+
+    _lib = None
+
+    def close(self):
+        if self._w:
+            self._lib.aesgcm_rxwin_destroy(self._w)
+            self._w = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set(self, first, nexts, seens=None, stream=None):
+        """aesgcm_rxwin_set: windows first, first + 1, ... get next = nexts[k] and seen = seens[k], an int whose bit i says "number next - 1 - i was seen" (None: nothing)"""
+        n, sw = len(nexts), self.window // 64
+        nx = (u64 * max(n, 1))(*nexts)
+        sn = None
+        if seens is not None:
+            if len(seens) != n or any(s < 0 or s >> self.window for s in seens):
+                raise AesGcmError(EARG, "one seen value of at most `window` bits per window")
+            sn = (u64 * max(n * sw, 1))(*[(s >> (64 * j)) & RXWIN_NONE for s in seens for j in range(sw)])
+        _chk(self._lib.aesgcm_rxwin_set(self._w, first, n, nx, sn, stream))
+        return self
+
+    def get(self, first=0, n=None, stream=None):
+        """aesgcm_rxwin_get -> (nexts, seens) of windows first .. first + n - 1 in set's form; waits on the stream"""
+        n = self.n_wins - first if n is None else n
+        sw = self.window // 64
+        nx, sn = (u64 * max(n, 1))(), (u64 * max(n * sw, 1))()
+        _chk(self._lib.aesgcm_rxwin_get(self._w, first, n, nx, sn, stream))
+        return list(nx[:n]), [sum(sn[k * sw + j] << (64 * j) for j in range(sw)) for k in range(n)]
+
+    def recover_dev(self, fmt, n_pkts, d_win, d_in, d_pkt_off, d_num_out, d_hi_out=None, stream=None):
+        """aesgcm_rxwin_recover_dev: d_num_out[p] (uint64) = packet p's full number by fmt (an RxFormat) and window d_win[p] (uint32); d_hi_out[p] (uint32, optional) = what
+        the decrypt call takes as d_hi / d_roc.  RxFormat.expect(): d_in and d_pkt_off may be None"""
+        _chk(self._lib.aesgcm_rxwin_recover_dev(self._w, ctypes.byref(fmt), n_pkts, d_win, d_in, d_pkt_off, d_num_out, d_hi_out, stream))
+
+    def commit_dev(self, n_pkts, d_win, d_num, d_auth, d_accept, d_why=None, stream=None):
+        """aesgcm_rxwin_commit_dev: behind the decrypt call; d_accept[p] (int, may be d_auth) = 1 for the packets to deliver, d_why[p] (int, optional) an index of RXWIN_WHY"""
+        _chk(self._lib.aesgcm_rxwin_commit_dev(self._w, n_pkts, d_win, d_num, d_auth, d_accept, d_why, stream))
+
+    def status(self):
+        """aesgcm_rxwin_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""
+        code, detail = cint(0), u64(0)
+        _chk(self._lib.aesgcm_rxwin_status(self._w, ctypes.byref(code), ctypes.byref(detail)))
+        return code.value, detail.value
+
+    def _call(self, up, down, call):
+        n = len(up["win"][1])
+        up = {k: v if isinstance(v, bytes) else struct.pack("<%d%s" % (len(v[1]), v[0]), *v[1]) for k, v in up.items()}
+        size = {k: len(v) for k, v in up.items()}
+        size.update({k: n * struct.calcsize("<" + code) for k, code in down.items()})
+        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in size.items()}
+        try:
+            for k, v in up.items():
+                if v:
+                    bufs[k].upload(v)
+            call(bufs)
+            _chk(load().aesgcm_dev_sync(self.device))
+            return {k: list(struct.unpack("<" + code * n, bytes(bufs[k].download(n * struct.calcsize("<" + code))))) for k, code in down.items()}
+        finally:
+            for b in bufs.values():
+                b.free()
+
+    def recover(self, fmt, wins, packets=None):
+        """Host convenience (tests, examples): -> (nums, his) of whole packets (RxFormat.expect(): packets may be None)"""
+        n = len(wins)
+        if not n or (packets is not None and len(packets) != n):
+            raise AesGcmError(EARG, "wins and packets must be equally long and not empty")
+        up = {"win": ("I", wins)}
+        if packets is not None:
+            off = [0]
+            for x in packets:
+                off.append(off[-1] + len(x))
+            up.update(data=b"".join(bytes(x) for x in packets), off=("Q", off))
+        got = self._call(up, {"num": "Q", "hi": "I"}, lambda b: self.recover_dev(fmt, n, b["win"].ptr, b["data"].ptr if packets is not None else None,
+                                                                                   b["off"].ptr if packets is not None else None, b["num"].ptr, b["hi"].ptr))
+        return got["num"], got["hi"]
+
+    def commit(self, wins, nums, auths):
+        """Host convenience (tests, examples): -> (accepts, whys)"""
+        n = len(wins)
+        if not n or len(nums) != n or len(auths) != n:
+            raise AesGcmError(EARG, "wins, nums and auths must be equally long and not empty")
+        got = self._call({"win": ("I", wins), "num": ("Q", nums), "auth": ("i", auths)}, {"accept": "i", "why": "i"},
+                         lambda b: self.commit_dev(n, b["win"].ptr, b["num"].ptr, b["auth"].ptr, b["accept"].ptr, b["why"].ptr))
+        return got["accept"], got["why"]
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

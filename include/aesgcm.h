@@ -459,7 +459,7 @@ AESGCM_API int aesgcm_keytab_destroy(aesgcm_keytab *t);
  *   ESP, RFC 4106           {8, 16, 8, 4, 16 | 12 | 8, 0}   SPI, sequence number | 8-byte IV field | payload | ICV; the slot's salt = the SA's 4-byte salt
  *   MACsec confidentiality offset 30 / 50   {28 + 30, 28 + 30, 16, 8, 16, 0}: the offset's bytes are authenticated header
  * MACsec XPN and ESP with extended sequence numbers need a number that is not in the frame: aesgcm_keytab_frames_crypt_x_dev, below.
- * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows, and routing long frames to the row kernels (a frame runs on one lane
+ * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows (not this call's: aesgcm_rxwin_*, "RECEIVE WINDOWS" below), and routing long frames to the row kernels (a frame runs on one lane
  * group).  TLS records (their AAD is not a span of the wire bytes) are not a format of this call: aesgcm_keytab_records_crypt_dev, further below. */
 #define AESGCM_WIRE_AUTH_ONLY 1u   /* nothing is encrypted: every byte in front of the ICV is AAD (MACsec integrity-only, E = 0; GMAC) */
 typedef struct aesgcm_wire_fmt {
@@ -480,7 +480,7 @@ AESGCM_API int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, con
  * At this library's frame rates a 32-bit packet number lasts seconds.  Both standards answer with a 64-bit number of which only the LOWER half is in the frame; the upper
  * half enters the nonce (XPN) or the AAD (ESN).  aesgcm_keytab_frames_crypt_x_dev is aesgcm_keytab_frames_crypt_dev with that half as one more array: d_hi, DEVICE memory,
  * n_frames numeric 32-bit values indexed by frame like d_slots.  A transmitter's d_hi[p] is pn >> 32 of the number it assigned; a receiver recovers it from its replay
- * window before the call (802.1AEbw 10.6.2, RFC 4303 Appendix A).  The format is aesgcm_wire_xfmt = a base format f and ext:
+ * window before the call (802.1AEbw 10.6.2, RFC 4303 Appendix A: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_LOWEST writes exactly this array).  The format is aesgcm_wire_xfmt = a base format f and ext:
  *   ext 0                 d_hi is ignored (NULL allowed); the call IS aesgcm_keytab_frames_crypt_dev with f
  *   AESGCM_WIREX_XPN      f a MACsec format {28 | 20, 28 | 20, 16, 8, 16, 0 | AESGCM_WIRE_AUTH_ONLY} (salt_len must be 8).  Everything about the frame is as f says but the
  *                         nonce = xsalt[0..12) XOR (ssci[0..4) | be32(d_hi[p]) | frame[iv_off, iv_off + 4)): the SSCI XORs the salt's first four bytes, the 64-bit PN, big-endian,
@@ -496,7 +496,7 @@ AESGCM_API int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, con
  * frame's d_hi is not read.  One k_kt_wirex launch per call (ext 0: one k_kt_wire launch).
  * TLS 1.3 records (their nonce takes a 64-bit number with no wire part) are not a mode of this call either: d_hi holds 32-bit values.  They have a call of their own,
  * aesgcm_keytab_records_crypt_dev, below.
- * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself, generating packet numbers, writing the PN into the SecTAG, ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
+ * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself (neither is this call's: aesgcm_rxwin_recover_dev / _commit_dev, "RECEIVE WINDOWS" below), generating packet numbers, writing the PN into the SecTAG, ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
 #define AESGCM_WIREX_XPN 1u   /* nonce = the slot's 12-byte XPN salt XOR (the slot's SSCI | be32(d_hi[p]) | the 4 frame bytes at iv_off) */
 #define AESGCM_WIREX_ESN 2u   /* AAD = frame[0,4) | be32(d_hi[p]) | frame[4,8): 12 bytes; nonce as the base format says */
 typedef struct aesgcm_wire_xfmt {
@@ -578,7 +578,8 @@ AESGCM_API int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, co
  * k_kt_quic_hp (a lane per packet); decrypt the other way round.  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: Retry and Version Negotiation packets; coalesced datagrams (split them: one entry of d_pkt_off per packet); ChaCha20; key derivation (INTEGRATION.md "QUIC
  * packets" says which secret becomes what); choosing the slot from the Key Phase bit (the caller who needs it decrypts out of place and retries the failed packets under the
- * next-phase slot); anti-replay; routing long packets to the row kernels. */
+ * next-phase slot); anti-replay and the expected packet number (not this call's: aesgcm_rxwin_* with AESGCM_RXWIN_EXPECT gives d_pn and takes d_pn_out); routing long packets
+ * to the row kernels. */
 AESGCM_API int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_hp_slots,
                                  const uint64_t *d_pn, uint64_t *d_pn_out, const uint32_t *d_pn_off,
                                  const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
@@ -623,7 +624,7 @@ AESGCM_API int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_
  * 1.2: one k_kt_dtls launch; 1.3: two launches on `stream`, k_kt_dtls and k_kt_dtls_sn (a lane per record).  No scratch memory, no host synchronisation, capture-safe and
  * asynchronous; shape and order as aesgcm_keytab_records_crypt_dev.  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: DTLS 1.2 connection IDs (RFC 9146: another header and another AAD); coalesced datagrams (split them: one entry of d_rec_off per record); choosing the slot
- * from the epoch bits (E E of b0, or a 1.2 header's epoch: the caller maps them to slots); anti-replay; key derivation (INTEGRATION.md "DTLS records" says which secret
+ * from the epoch bits (E E of b0, or a 1.2 header's epoch: the caller maps them to slots); anti-replay (not this call's: aesgcm_rxwin_*, AESGCM_RXWIN_EXPECT for 1.3's d_seq, {WIRE, 5, 6} for 1.2); key derivation (INTEGRATION.md "DTLS records" says which secret
  * becomes what); ChaCha20 and CCM suites; routing long records to the row kernels. */
 #define AESGCM_DTLS_13 1u   /* unified_hdr | payload | tag[16]; nonce = slot IV XOR (0^32 | be64(seq)); AAD = the unprotected header; record-number encryption under d_sn_slots[p] */
 #define AESGCM_DTLS_12 2u   /* hdr[13] | explicit nonce[8] | payload | tag[16]; nonce = slot IV[0..4) | explicit nonce; AAD = rec[3..11) | rec[0..3) | be16(L - 37) */
@@ -665,7 +666,7 @@ AESGCM_API int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const
  * d_in, d_pkt_off, d_out NULL; RTP without d_roc; decrypt without d_auth; n_pkts >= 2^31.
  * ONE k_kt_srtp launch: no scratch memory, no host synchronisation, capture-safe and asynchronous; shape, order and planning as aesgcm_keytab_dtls_crypt_dev's DTLS 1.2
  * mode.  Ordering and thread safety as the other key-table calls.
- * OUT OF SCOPE: ROC estimation and replay windows; key derivation (RFC 3711 4.3 KDF, the DTLS-SRTP exporter: INTEGRATION.md "SRTP and SRTCP packets" says which secret
+ * OUT OF SCOPE: ROC estimation and replay windows (not this call's: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_SRTP writes d_roc, aesgcm_rxwin_commit_dev keeps the window); key derivation (RFC 3711 4.3 KDF, the DTLS-SRTP exporter: INTEGRATION.md "SRTP and SRTCP packets" says which secret
  * becomes what); the AES-CM / HMAC-SHA1 transforms; double encryption (RFC 8723); RFC 6904 header-extension encryption; MKI lookup (the caller maps an MKI to a slot, and one
  * call has one mki_len); splitting reduced-size or multiplexed datagrams (one entry of d_pkt_off per packet; a compound RTCP packet is ONE packet). */
 #define AESGCM_SRTP_RTP  1u
@@ -678,6 +679,84 @@ AESGCM_API int aesgcm_srtp_fmt_check(const aesgcm_srtp_fmt *fmt);
 AESGCM_API int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srtp_fmt *fmt, size_t n_pkts,
                                  const uint32_t *d_slots, const uint32_t *d_roc,
                                  const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- RECEIVE WINDOWS: anti-replay and number recovery on the device, for every wire format above
+ * A receiver needs, BEFORE a decrypt call, a per-packet value that depends on per-association state -- ESN's seq-hi, XPN's upper PN half, SRTP's rollover counter, the
+ * expected number of QUIC and DTLS 1.3 -- and AFTER it must drop replays and advance that state.  aesgcm_rxwin is that state on the device: n_wins independent windows
+ * of `window` bits each (a power of two, 64 .. 4096).  A window belongs to whatever the protocol numbers: a MACsec SA, an ESP SA, a DTLS epoch, a QUIC packet-number
+ * space, an SRTP SSRC.  It is NOT tied to a key slot (SRTP shares a key across SSRCs, QUIC keeps its number space across key updates): calls name a window per packet
+ * with d_win[p] (DEVICE memory, uint32), which is often the same array as d_slots.
+ * A window's state: `next`, a uint64 = the highest accepted number + 1, or 0 if nothing was accepted yet; and the set of SEEN numbers in [next - window, next), clamped
+ * at 0.  Numbers are 0 .. 2^64 - 2; 2^64 - 1 is AESGCM_RXWIN_NONE, "no number".
+ *   aesgcm_rxwin_create   all windows empty.  AESGCM_EARG for a window that is no power of two in 64 .. 4096, n_wins == 0 or n_wins >= 2^31.
+ *   aesgcm_rxwin_set      HOST arrays into windows first .. first + n - 1: next[n], and seen[n][window / 64] or NULL for "nothing seen".  The form is NORMALISED and says
+ *                         nothing about how the device stores it: bit i of a window's little-endian bit string (bit i & 63 of word i / 64) says "number next - 1 - i was
+ *                         seen".  Bits for numbers below 0 must be 0 (AESGCM_EARG).  Stream-ordered through a staging buffer, like aesgcm_keytab_set.
+ *   aesgcm_rxwin_get      the same form back (seen may be NULL).  It WAITS on `stream`.  For tests and checkpoints.
+ *   aesgcm_rxwin_status   as aesgcm_keytab_status: the LOWEST packet index a recover or commit call refused since the last read, which clears it.
+ *   aesgcm_rxwin_destroy  waits for the device, frees.
+ * RECOVER, before the decrypt: aesgcm_rxwin_recover_dev writes d_num_out[p] (required, uint64: the packet's full number) and d_hi_out[p] (optional, uint32).  *fmt says
+ * where the truncated number lies in packet p = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in and how the full one is formed; T = the window's next, W = window, t = the
+ * big-endian field of num_len bytes at byte num_off:
+ *   AESGCM_RXWIN_WIRE     num_len 2, 4, 6 or 8.  full = t.  AESGCM_RXWIN_FROM_END: the field starts num_off bytes before the packet's END.  AESGCM_RXWIN_CLEAR_TOP: the
+ *                         field's top bit is cleared.  d_hi_out[p] = full >> 32.  MACsec {WIRE, 16, 4}; ESP {WIRE, 4, 4}; DTLS 1.2 {WIRE, 5, 6} (a window is an epoch);
+ *                         SRTCP {WIRE, 4 + mki_len, 4, FROM_END | CLEAR_TOP} (the index without its E bit).
+ *   AESGCM_RXWIN_LOWEST   num_len 2 or 4.  full = the smallest n >= B with n = t (mod 2^(8 num_len)), B = T >= W ? T - W : 0: the number is taken to lie at or above the
+ *                         lowest acceptable one (RFC 4303 Appendix A2.1, 802.1AEbw 10.6.2).  d_hi_out[p] = full >> (8 num_len) (its low 32 bits), which is exactly the
+ *                         d_hi of aesgcm_keytab_frames_crypt_x_dev.  ESN {LOWEST, 4, 4}; XPN {LOWEST, 16, 4}.
+ *   AESGCM_RXWIN_SRTP     num_len 2 (RTP: num_off 2).  RFC 3711 3.3.1 and Appendix A on s_l = (T - 1) & 0xFFFF, ROC = (T - 1) >> 16: if s_l < 32768, v = ROC - 1 when
+ *                         SEQ - s_l > 32768, else ROC; otherwise v = ROC + 1 when s_l - 32768 > SEQ, else ROC.  Nothing goes below ROC 0: then v stays 0.  T == 0 gives
+ *                         v = 0 (a receiver that joins mid-stream uses aesgcm_rxwin_set first).  full = v << 16 | SEQ; d_hi_out[p] = v is aesgcm_keytab_srtp_crypt_dev's d_roc.
+ *   AESGCM_RXWIN_EXPECT   num_len 0.  No packet byte is read; d_in and d_pkt_off may be NULL.  d_num_out[p] = T: the d_pn / d_seq that the QUIC and DTLS 1.3 decrypt calls
+ *                         take as the EXPECTED number (d_hi_out[p] = T >> 32).  Their d_pn_out / d_seq_out then go to the commit as d_num.
+ * A packet is REFUSED on its own when its window is n_wins or more; (EXPECT: T is 2^64 - 1;) its offsets fall; its number field is not inside the packet; the result would
+ * be 2^64 - 1 or more; the rollover counter would pass 2^32 - 1.  The tests run in this order and nothing of the packet is read past the one that refuses it.  Then
+ * d_num_out[p] = AESGCM_RXWIN_NONE, d_hi_out[p] = 0xFFFFFFFF, and the lowest such index goes to aesgcm_rxwin_status.  Recover changes no window.
+ * aesgcm_rxwin_fmt_check: AESGCM_EARG for NULL, an unknown rule or flag, a num_len the rule does not take, flags on a rule other than WIRE, num_off >= 2^16.  It touches no
+ * device; the recover call runs it first, then AESGCM_EARG for w NULL, (n_pkts == 0 is AESGCM_OK,) d_win or d_num_out NULL, d_in or d_pkt_off NULL unless EXPECT,
+ * n_pkts >= 2^31 -- all before any device is touched.
+ * COMMIT, behind the decrypt: aesgcm_rxwin_commit_dev(w, n_pkts, d_win, d_num, d_auth, d_accept, d_why).  S = the call's packets with d_auth[p] != 0, d_win[p] < n_wins and
+ * d_num[p] != AESGCM_RXWIN_NONE.  Per window M = max(next, 1 + the largest d_num in S).  A packet of S is
+ *   OLD      if num + W < M;
+ *   REPLAY   if it is not old and its number was seen before the call, or another packet of S with the same window and number is accepted;
+ *   ACCEPT   otherwise: of the non-old packets of one (window, number) not seen before, EXACTLY ONE is accepted -- which one is unspecified (they authenticated under
+ *            one key and nonce).
+ * Afterwards next = M and seen = (seen before, and the accepted) within [M - W, M).  This is RFC 4303 A2's sequential check-and-update applied to the call's
+ * authenticated packets in DESCENDING number order: the window advances first.  No number is ever accepted twice, across any sequence of calls.  A packet with
+ * d_auth[p] == 0 changes nothing, whatever its number: a forgery cannot move a window.  A call that spans more than W numbers loses its oldest: SIZE `window` FOR THE
+ * REORDERING YOU TOLERATE PLUS THE SPAN OF ONE CALL.
+ * d_accept[p] (required) = 1 or 0; it MAY BE d_auth, and aesgcm_wipe_failed_dev on it then wipes replays as it wipes forgeries.  d_why[p] (optional, int) = 0 not
+ * authenticated, 1 accepted, 2 old, 3 replay, 4 refused: authenticated, but its window is out of range or its number is NONE; the lowest such index goes to
+ * aesgcm_rxwin_status.  AESGCM_EARG, before any device is touched: w NULL; (n_pkts == 0 is AESGCM_OK;) d_win, d_num, d_auth or d_accept NULL; n_pkts >= 2^31.
+ * One launch per recover, three per commit (the per-window maximum; clearing what the window moves over; marking), a lane per packet, atomics on the window's own words: no
+ * scratch memory, no host synchronisation, capture-safe and asynchronous on `stream`.  Every call but aesgcm_rxwin_get is stream-ordered; two calls that name the same
+ * window on different streams are the caller's to order; the calls of one table are thread-safe; a table belongs to the device it was created on.
+ * OUT OF SCOPE: skipping the decryption of packets a pre-check could already reject; per-window counters; MACsec's replayProtect = false mode; choosing a window from a
+ * wire field (SCI, SPI, SSRC lookup); TLS, which has no replay window. */
+#define AESGCM_RXWIN_NONE 0xFFFFFFFFFFFFFFFFull   /* "no number" */
+#define AESGCM_RXWIN_WIRE   1u   /* full = the wire field */
+#define AESGCM_RXWIN_LOWEST 2u   /* full = the smallest number at or above next - window with the wire field's low bits */
+#define AESGCM_RXWIN_SRTP   3u   /* full = ROC estimate << 16 | SEQ (RFC 3711 Appendix A) */
+#define AESGCM_RXWIN_EXPECT 4u   /* d_num_out = next; no packet byte is read */
+#define AESGCM_RXWIN_FROM_END  1u   /* WIRE: the field starts num_off bytes before the packet's end */
+#define AESGCM_RXWIN_CLEAR_TOP 2u   /* WIRE: the field's top bit is cleared */
+typedef struct aesgcm_rxwin aesgcm_rxwin;
+typedef struct aesgcm_rxwin_fmt {
+    uint32_t rule;      /* AESGCM_RXWIN_WIRE, _LOWEST, _SRTP or _EXPECT                      */
+    uint32_t num_off;   /* where the truncated number starts (FROM_END: before the end), < 2^16 */
+    uint32_t num_len;   /* its bytes: WIRE 2 / 4 / 6 / 8, LOWEST 2 / 4, SRTP 2, EXPECT 0        */
+    uint32_t flags;     /* WIRE: 0 or AESGCM_RXWIN_FROM_END | AESGCM_RXWIN_CLEAR_TOP; else 0    */
+} aesgcm_rxwin_fmt;     /* 16 bytes */
+AESGCM_API int aesgcm_rxwin_create(aesgcm_rxwin **out, int device, size_t n_wins, size_t window);
+AESGCM_API int aesgcm_rxwin_set(aesgcm_rxwin *w, size_t first, size_t n, const uint64_t *next, const uint64_t *seen, void *stream);
+AESGCM_API int aesgcm_rxwin_get(aesgcm_rxwin *w, size_t first, size_t n, uint64_t *next, uint64_t *seen, void *stream);
+AESGCM_API int aesgcm_rxwin_fmt_check(const aesgcm_rxwin_fmt *fmt);
+AESGCM_API int aesgcm_rxwin_recover_dev(aesgcm_rxwin *w, const aesgcm_rxwin_fmt *fmt, size_t n_pkts, const uint32_t *d_win, const void *d_in, const uint64_t *d_pkt_off,
+                             uint64_t *d_num_out, uint32_t *d_hi_out, void *stream);
+AESGCM_API int aesgcm_rxwin_commit_dev(aesgcm_rxwin *w, size_t n_pkts, const uint32_t *d_win, const uint64_t *d_num, const int *d_auth, int *d_accept, int *d_why,
+                            void *stream);
+AESGCM_API int aesgcm_rxwin_status(aesgcm_rxwin *w, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_rxwin_destroy(aesgcm_rxwin *w);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
