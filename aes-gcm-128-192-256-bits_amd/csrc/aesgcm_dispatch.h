@@ -55,6 +55,17 @@ using batch3_set = kset<nr_list, dec_list, klist<3, 4, 6>>;
 template <class F> auto batch3_dispatch(int nr, int dec, int lg, F &&f) { return set_pick(batch3_set{}, f, nr, dec, lg); }
 template <class F> auto batch3_each(F &&f) { return set_each(batch3_set{}, f); }
 
+// ... with one more two-valued template argument, the family's variant (k_kt_wirex's extension, k_kt_tls's and k_kt_dtls's version, k_kt_srtp's kind): f(NR, DEC, LG, V),
+// 36 instances.  v A -> A, anything else -> B: a launcher refuses an unknown variant before it dispatches
+template <int A, int B> using batch3v_set = kset<nr_list, dec_list, klist<3, 4, 6>, klist<A, B>>;
+template <int A, int B, class F> auto batch3v_dispatch(int nr, int dec, int lg, int v, F &&f) { return set_pick(batch3v_set<A, B>{}, f, nr, dec, lg, v); }
+template <int A, int B, class F> auto batch3v_each(F &&f) { return set_each(batch3v_set<A, B>{}, f); }
+
+// the two mask kernels, a lane per packet (k_kt_quic_hp, k_kt_dtls_sn): f(NR, DEC), 6 instances
+using mask_set = kset<nr_list, dec_list>;
+template <class F> auto mask_dispatch(int nr, int dec, F &&f) { return set_pick(mask_set{}, f, nr, dec); }
+template <class F> auto mask_each(F &&f) { return set_each(mask_set{}, f); }
+
 // k_main: f(NR, MODE); mode ENC / DEC / KS, anything else ECB.  12 instances
 template <int ENC, int DEC, int KS, int ECB> using main_set = kset<nr_list, klist<ENC, DEC, KS, ECB>>;
 

@@ -14,12 +14,13 @@
 //                             round keys of the record's sn slot; the 1 or 2 sequence bytes are XORed with mask[0], mask[1].  Decrypt: it also decodes the full number from
 //                             the truncated one and the expected one (wire_decode_num, aesgcm_mask.h) into pn_out[p].  Out of place it writes the whole header.  The
 //                             refusals that read no byte, the mask and the decode are k_kt_quic_hp's, shared through aesgcm_mask.h.
-// Encrypt runs k_kt_dtls, then k_kt_dtls_sn (the sample is fresh ciphertext); decrypt the other way round.  Both refuse the same records by the same tests in the same
-// order, so a refused record is touched by neither; k_kt_dtls alone reports it (status word, auth 0).  36 + 6 instances; the loop for fixed-size records
+// Encrypt runs k_kt_dtls, then k_kt_dtls_sn (the sample is fresh ciphertext); decrypt the other way round.  Both refuse the same records by the same functions
+// (aesgcm_wirecut.h: wire_front, dtls13_hdr), so a refused record is touched by neither; k_kt_dtls alone reports it (status word, auth 0).  36 + 6 instances; the loop for fixed-size records
 // (BatchParams::plain) is not compiled in; every k_kt_dtls one: no scratch, at most 128 registers.
 // A translation unit of its own: its ISA census (`make asm_dtls`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_mask.h"
 #include "aesgcm_dispatch.h"
 
@@ -43,16 +44,16 @@ __global__ __launch_bounds__(256) void k_kt_dtls_sn(const DevTables *__restrict_
     __syncthreads();
     const u32 i = blockIdx.x * 256u + tid;
     if (i >= q.n_pkts) return;
-    // the refusals, as k_kt_dtls makes them (aesgcm_batch3_body.inc, x_d13): 17 bytes from the sequence-number field's start (one sequence byte and the sample) before
-    // the first byte is read; a refused record's number is not read and nothing of it is written
+    // the refusals are k_kt_dtls's, by the functions its cut calls (aesgcm_wirecut.h: cut_dtls13): a refused record's number is not read and nothing of it is written
     MaskPkt m;
-    if (!mask_take(q, i, 17u, m)) return;
+    if (!mask_take(q, i, DTLS13_TAIL, m)) return;
     const unsigned char *const src = m.src;
     unsigned char *const dst = m.dst;
     const u32 po = m.po;
     const u32 b0 = src[0];                                       // 0 0 1 C S L E E: never masked, so the same byte before and behind either pass
-    const u32 sn_len = b0 & 0x08u ? 2u : 1u, hdr = po + sn_len + (b0 & 0x04u ? 2u : 0u);
-    if ((b0 & 0xE0u) != 0x20u || hdr + 16u > m.len) return;
+    bool bad = false;
+    const u32 hdr = dtls13_hdr(b0, po, m.len, bad), sn_len = b0 & 0x08u ? 2u : 1u;
+    if (bad) return;
     // mask = AES-ECB(sn key, sample): the first 16 ciphertext bytes -- encrypt: what k_kt_dtls has just written to `out`; decrypt: the protected record's
     u32 s0, s1, s2, s3;
     mask_of_sample<NR>(m.ms, (DEC ? src : (const unsigned char *)dst) + hdr, smem, (tid & 31u) << 2, s0, s1, s2, s3);
@@ -72,30 +73,22 @@ __global__ __launch_bounds__(256) void k_kt_dtls_sn(const DevTables *__restrict_
 // ------------------------------------------------------------------------------------------------ launchers
 #define KT_DTLS_SN_LDS (AESGCM_LDS_AES_OFF + AESGCM_LDS_AES)
 hipError_t klaunch_dtls_attributes() {
-    const hipError_t e = batch3_each([](auto NR, auto D, auto LG) {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_dtls<NR(), D(), LG(), AESGCM_DTLS_13>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
-        return e0 != hipSuccess ? e0 : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_dtls<NR(), D(), LG(), AESGCM_DTLS_12>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+    const hipError_t e = batch3v_each<AESGCM_DTLS_13, AESGCM_DTLS_12>([](auto NR, auto D, auto LG, auto V) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_dtls<NR(), D(), LG(), V()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
     });
-    return e != hipSuccess ? e : nr_each([](auto NR) {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_dtls_sn<NR(), 0>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_DTLS_SN_LDS);
-        return e0 != hipSuccess ? e0 : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_dtls_sn<NR(), 1>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_DTLS_SN_LDS);
-    });
+    return e != hipSuccess ? e : mask_each([](auto NR, auto D) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_dtls_sn<NR(), D()>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_DTLS_SN_LDS); });
 }
 
 hipError_t klaunch_kt_dtls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
     if (version != AESGCM_DTLS_13 && version != AESGCM_DTLS_12) return hipErrorInvalidValue;
-    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) {
-        if (version == AESGCM_DTLS_13) hipLaunchKernelGGL((k_kt_dtls<NR(), D(), LG(), AESGCM_DTLS_13>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
-        else hipLaunchKernelGGL((k_kt_dtls<NR(), D(), LG(), AESGCM_DTLS_12>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+    batch3v_dispatch<AESGCM_DTLS_13, AESGCM_DTLS_12>(nr, dec, lg, (int)version, [&](auto NR, auto D, auto LG, auto V) {
+        hipLaunchKernelGGL((k_kt_dtls<NR(), D(), LG(), V()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
     });
     return hipGetLastError();
 }
 
 hipError_t klaunch_kt_dtls_sn(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) {
     const unsigned wgs = (p.n_pkts + 255u) / 256u;
-    nr_dispatch(nr, [&](auto NR) {
-        if (dec) hipLaunchKernelGGL((k_kt_dtls_sn<NR(), 1>), dim3(wgs), dim3(256), KT_DTLS_SN_LDS, st, tb, p);
-        else hipLaunchKernelGGL((k_kt_dtls_sn<NR(), 0>), dim3(wgs), dim3(256), KT_DTLS_SN_LDS, st, tb, p);
-    });
+    mask_dispatch(nr, dec, [&](auto NR, auto D) { hipLaunchKernelGGL((k_kt_dtls_sn<NR(), D()>), dim3(wgs), dim3(256), KT_DTLS_SN_LDS, st, tb, p); });
     return hipGetLastError();
 }

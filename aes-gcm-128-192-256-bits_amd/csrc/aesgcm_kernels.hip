@@ -24,6 +24,7 @@
 // The tag is (P*H ^ L)*H ^ E_K(J0) = P*H^2 ^ L*H ^ E_K(J0).
 #include "aesgcm_internal.h"
 #include "aesgcm_keytab.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_lanes.h"
 #include "aesgcm_dispatch.h"
 

@@ -1,7 +1,7 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
 // Shared by the kernels -- aesgcm_keytab_kernels.hip: k_kt_setup, and k_kt_batch, which runs k_batch3's body (aesgcm_batch3_body.inc) with the key material read from
 // slots; aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip, aesgcm_quic_kernels.hip, aesgcm_dtls_kernels.hip, aesgcm_srtp_kernels.hip: the same body on packets in wire format, one source per
-// family (aesgcm_keytab.hip lists them) -- and the host (aesgcm_keytab.hip, which launches each as aesgcm_host.hip's batch_plan plans k_batch3).  Every launcher below
+// family (aesgcm_keytab.hip lists them), what each format decides in aesgcm_wirecut.h -- and the host (aesgcm_keytab.hip, which launches each as aesgcm_host.hip's batch_plan plans k_batch3).  Every launcher below
 // picks its instance by aesgcm_dispatch.h.
 #pragma once
 #include "aesgcm_internal.h"
@@ -67,7 +67,7 @@ struct KtWireXParams {
         u32 mki_len;                       // k_kt_srtp only, in the place of a pointer it does not use: the bytes of MKI that end every packet (the parameters' size stays what it was)
             const u32 *pn_off;                 // k_kt_quic and k_kt_dtls 1.3 only (behind everything the other kernels read): where packet p's packet-number / sequence-number field starts, n_pkts values
     };
-    const u32 *hp_slots;                   // ... and its header-protection / record-number slot, which the AEAD checks as the mask kernel does: a packet is refused by both kernels or by neither
+    const u32 *hp_slots;                   // ... and its header-protection / record-number slot: the AEAD and the mask kernel refuse a packet by the same function (aesgcm_wirecut.h: wire_front)
 };
 
 // A QUIC call's header-protection pass (k_kt_quic_hp, a lane per packet): packet p = bytes [pkt_off[p], pkt_off[p + 1]) of in / out.  A DTLS 1.3 call's record-number
@@ -82,22 +82,6 @@ struct KtQuicHpParams {
     const KtSlot *tab;
     u32 n_pkts, n_slots;
 };
-
-// The frame-side accesses of k_kt_wire (aesgcm_batch3_body.inc, WIRE), all inside the frame and at any byte address.  The ICV is 8, 12 or 16 bytes: dwords.
-HD uint4 wire_load_icv(const unsigned char *p, u32 tag_len) {          // zero beyond tag_len
-    return make_uint4(gload4_any(p), gload4_any(p + 4), tag_len > 8u ? gload4_any(p + 8) : 0u, tag_len > 12u ? gload4_any(p + 12) : 0u);
-}
-HD void wire_store_icv(unsigned char *p, uint4 v, u32 tag_len) {
-    gstore4_any(p, v.x); gstore4_any(p + 4, v.y);
-    if (tag_len > 8u) gstore4_any(p + 8, v.z);
-    if (tag_len > 12u) gstore4_any(p + 12, v.w);
-}
-// out of place: the `front` bytes in front of the payload pass through, copied by the frame's G lanes (l = the lane's number) in 16-byte pieces; the last piece ends at
-// `front` and may overlap the one before (the same bytes twice).  Fewer than 16 bytes: byte by byte.
-HD void wire_copy_front(unsigned char *dst, const unsigned char *src, u32 front, u32 l, u32 G) {
-    if (front >= 16u) for (u32 o = 16u * l; o < front; o += 16u * G) { const u32 q = o + 16u <= front ? o : front - 16u; gstore16_any(dst + q, gload16_any(src + q)); }
-    else for (u32 o = l; o < front; o += G) dst[o] = src[o];
-}
 
 // per family: klaunch_*_attributes = hipFuncSetAttribute(MaxDynamicSharedMemorySize) of every instance, on the current device (klaunch_set_attributes calls them all)
 hipError_t klaunch_kt_attributes();

@@ -2,15 +2,15 @@
 // A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word.  Host data reaches the slots through the table's staging buffer
 // (kt_stage_set): keys by k_kt_setup, the other fields (salt, XPN state, TLS IV) by strided copies.  A crypt call is one launch of a kernel that runs k_batch3's body,
 // planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.
-//   family   entry point                          kernel
-//   keytab   aesgcm_keytab_crypt_dev              k_kt_batch   packets as five arrays
-//   wire     aesgcm_keytab_frames_crypt_dev       k_kt_wire    frames in wire format
-//   wirex    aesgcm_keytab_frames_crypt_x_dev     k_kt_wirex   ... with a number per frame that is not on the wire (MACsec XPN, ESP ESN)
-//   tls      aesgcm_keytab_records_crypt_dev      k_kt_tls     TLS records with their 64-bit sequence numbers
-//   quic     aesgcm_keytab_quic_crypt_dev         k_kt_quic    QUIC packets, and a second launch, k_kt_quic_hp (header protection, a lane per packet)
-//   dtls     aesgcm_keytab_dtls_crypt_dev         k_kt_dtls    DTLS records; 1.3: and a second launch, k_kt_dtls_sn (record-number encryption, a lane per record)
-//   srtp     aesgcm_keytab_srtp_crypt_dev         k_kt_srtp    SRTP and SRTCP packets (RFC 7714)
-// The calls in wire format fill their kernel parameters by kt_wire_params.
+//   family   entry point                          kernel       the format's cut (aesgcm_wirecut.h)
+//   keytab   aesgcm_keytab_crypt_dev              k_kt_batch   -                       packets as five arrays
+//   wire     aesgcm_keytab_frames_crypt_dev       k_kt_wire    cut_wire                frames in wire format
+//   wirex    aesgcm_keytab_frames_crypt_x_dev     k_kt_wirex   cut_wire                ... with a number per frame that is not on the wire (MACsec XPN, ESP ESN)
+//   tls      aesgcm_keytab_records_crypt_dev      k_kt_tls     cut_wire                TLS records with their 64-bit sequence numbers
+//   quic     aesgcm_keytab_quic_crypt_dev         k_kt_quic    cut_quic                QUIC packets, and a second launch, k_kt_quic_hp (header protection, a lane per packet)
+//   dtls     aesgcm_keytab_dtls_crypt_dev         k_kt_dtls    cut_dtls13, cut_wire    DTLS records; 1.3: and a second launch, k_kt_dtls_sn (record-number encryption, a lane per record)
+//   srtp     aesgcm_keytab_srtp_crypt_dev         k_kt_srtp    (body text), cut_srtcp    SRTP and SRTCP packets (RFC 7714)
+// The calls in wire format all go through kt_wire_crypt.
 #include "aesgcm_keytab.h"
 
 #include <stddef.h>
@@ -213,55 +213,75 @@ int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf) {
     return AESGCM_OK;
 }
 
-// What every call of packets in wire format passes to its kernel the same way (the arguments checked by the caller): packet p = bytes [d_off[p], d_off[p + 1]) of d_in and
-// d_out under slot d_slots[p], its AAD read from d_aad at the same offsets.  The format (w.f) and the per-packet numbers are the caller's.
-static void kt_wire_params(KtWireXParams &xp, const aesgcm_keytab *t, int decrypt, const void *d_in, const void *d_aad, void *d_out, const uint64_t *d_off,
-                           const uint32_t *d_slots, int *d_auth) {
+// What every call of packets in wire format does behind its own format check (and the pointer checks that the ABI puts in front of the table's): packet p = bytes
+// [d_off[p], d_off[p + 1]) of d_in and d_out under slot d_slots[p].  In this order: the common argument checks (table and direction; n == 0 is OK; then the pointers,
+// `own_ok` standing for the caller's own); the kernel parameters; the plan, as aesgcm_keytab_crypt_dev's offset-array call (the lengths are on the device: shape by count,
+// order by falling frame length class); the launches; batch_done.  `aead(b, xp)` sets what its format adds to xp (w.f, the per-packet numbers) and launches its kernel.
+// `mask`, or NULL: the call's second launch on the same stream, a lane per packet (QUIC: header protection; DTLS 1.3: record-number encryption).  Encrypt: the AEAD first,
+// then the mask from the fresh ciphertext.  Decrypt: the mask off first -- that kernel leaves the unprotected header in d_out and the decoded numbers in d_pn_out, which is
+// where the AEAD reads both.  No scratch memory, no host synchronisation: capture-safe.
+struct KtMaskCall {
+    hipError_t (*launch)(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p);
+    const uint32_t *d_hp_slots, *d_pn_off;
+    const uint64_t *d_pn;
+    uint64_t *d_pn_out;
+};
+template <class Aead>
+static int kt_wire_crypt(aesgcm_keytab *t, int decrypt, size_t n, bool own_ok, const uint32_t *d_slots, const void *d_in, const uint64_t *d_off, void *d_out, int *d_auth,
+                         void *stream, const KtMaskCall *mask, Aead aead) {
+    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
+    if (!n) return AESGCM_OK;
+    if (!own_ok || !d_slots || !d_in || !d_out || !d_off || (decrypt && !d_auth) || n >= ((size_t)1 << 31)) return AESGCM_EARG;
+    if (mask && (!mask->d_hp_slots || !mask->d_pn || !mask->d_pn_off || (decrypt && !mask->d_pn_out))) return AESGCM_EARG;
+    KtWireXParams xp;
     memset(&xp, 0, sizeof xp);
     BatchParams &p = xp.w.k.b;
-    p.in = (const unsigned char *)d_in; p.aad = (const unsigned char *)d_aad; p.out = (unsigned char *)d_out;
+    p.in = (const unsigned char *)d_in; p.out = (unsigned char *)d_out;
+    p.aad = mask && decrypt ? p.out : p.in;                                      // the AAD: where the header lies unprotected
     p.auth = decrypt ? d_auth : nullptr;
     p.data_off = d_off;
     p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per packet, in the kernel)
     xp.w.k.slots = d_slots; xp.w.k.tab = t->tab; xp.w.k.n_slots = (u32)t->n_slots; xp.w.k.status = t->status;
-}
-
-// One launch: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in and d_out, laid out by *fmt (checked by the caller).  Planned as aesgcm_keytab_crypt_dev's
-// offset-array call (the lengths are on the device: shape by count, order by falling frame length class).  tls (AESGCM_TLS_13 / AESGCM_TLS_12, or 0): k_kt_tls with
-// d_seq, the records laid out by *fmt as aesgcm_tls_kernels.hip says; otherwise ext (or 0): k_kt_wirex with d_hi; neither: k_kt_wire.
-static int kt_frames_crypt(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, u32 ext, const uint32_t *d_hi, u32 tls, const uint64_t *d_seq, size_t n_frames,
-                           const uint32_t *d_slots, const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
-    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
-    if (!n_frames) return AESGCM_OK;
-    if (!d_slots || !d_in || !d_out || !d_frame_off || (decrypt && !d_auth) || n_frames >= ((size_t)1 << 31)) return AESGCM_EARG;
-    KtWireXParams xp;
-    kt_wire_params(xp, t, decrypt, d_in, d_in, d_out, d_frame_off, d_slots, d_auth);
-    xp.w.f = *fmt;
-    if (tls) xp.seq = d_seq; else xp.hi = d_hi;
-    BatchParams &p = xp.w.k.b;
+    KtQuicHpParams m = {};
+    if (mask) {
+        xp.seq = decrypt ? mask->d_pn_out : mask->d_pn;
+        xp.pn_off = mask->d_pn_off; xp.hp_slots = mask->d_hp_slots;
+        m.in = p.in; m.out = p.out; m.pkt_off = d_off; m.slots = d_slots; m.hp_slots = mask->d_hp_slots; m.pn_off = mask->d_pn_off;
+        m.pn = mask->d_pn; m.pn_out = decrypt ? mask->d_pn_out : nullptr; m.tab = t->tab; m.n_pkts = (u32)n; m.n_slots = (u32)t->n_slots;
+    }
     BatchPlan b;
-    const int rc = batch_plan(t->device, decrypt, n_frames, t->key_len, p, stream, b);
+    const int rc = batch_plan(t->device, decrypt, n, t->key_len, p, stream, b);
     if (rc) return rc;
-    if (tls) HIPCHK(klaunch_kt_tls(tls, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
-    else if (ext) HIPCHK(klaunch_kt_wirex(ext, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
-    else HIPCHK(klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp.w));
+    if (mask && decrypt) HIPCHK(mask->launch(b.nr, 1, b.st, b.tables, m));
+    HIPCHK(aead(b, xp));
+    if (mask && !decrypt) HIPCHK(mask->launch(b.nr, 0, b.st, b.tables, m));
     return batch_done(b, p);
 }
 
+// frame p laid out by *fmt: one k_kt_wire launch
 int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_fmt *fmt, size_t n_frames, const uint32_t *d_slots, const void *d_in,
                                    const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
     const int frc = aesgcm_wire_fmt_check(fmt);
     if (frc) return frc;
-    return kt_frames_crypt(t, decrypt, fmt, 0u, nullptr, 0u, nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
+    return kt_wire_crypt(t, decrypt, n_frames, true, d_slots, d_in, d_frame_off, d_out, d_auth, stream, nullptr, [&](const BatchPlan &b, KtWireXParams &xp) {
+        xp.w.f = *fmt;
+        return klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp.w);
+    });
 }
 
-// ... with hi[p], the half of frame p's 64-bit number that is not on the wire (MACsec XPN: into the nonce; ESP ESN: into the AAD).  ext 0 is the call above.
+// ... with hi[p], the half of frame p's 64-bit number that is not on the wire (MACsec XPN: into the nonce; ESP ESN: into the AAD): one k_kt_wirex launch.  ext 0 is the
+// call above.
 int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, const aesgcm_wire_xfmt *xf, size_t n_frames, const uint32_t *d_slots, const uint32_t *d_hi,
                                      const void *d_in, const uint64_t *d_frame_off, void *d_out, int *d_auth, void *stream) {
     const int frc = aesgcm_wire_xfmt_check(xf);
     if (frc) return frc;
     if (xf->ext && !d_hi) return AESGCM_EARG;
-    return kt_frames_crypt(t, decrypt, &xf->f, xf->ext, xf->ext ? d_hi : nullptr, 0u, nullptr, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream);
+    return kt_wire_crypt(t, decrypt, n_frames, true, d_slots, d_in, d_frame_off, d_out, d_auth, stream, nullptr, [&](const BatchPlan &b, KtWireXParams &xp) {
+        xp.w.f = xf->f;
+        if (!xf->ext) return klaunch_kt_wire(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp.w);
+        xp.hi = d_hi;
+        return klaunch_kt_wirex(xf->ext, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
+    });
 }
 
 // ---------------------------------------------------------------- TLS records
@@ -287,34 +307,22 @@ int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_
     if (frc) return frc;
     if (!d_seq) return AESGCM_EARG;
     static const aesgcm_wire_fmt f13 = {5, 5, 5, 0, 16, 0}, f12 = {13, 13, 5, 4, 16, 0};          // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
-    return kt_frames_crypt(t, decrypt, fmt->version == AESGCM_TLS_13 ? &f13 : &f12, 0u, nullptr, fmt->version, d_seq, n_recs, d_slots, d_in, d_rec_off, d_out, d_auth, stream);
+    return kt_wire_crypt(t, decrypt, n_recs, true, d_slots, d_in, d_rec_off, d_out, d_auth, stream, nullptr, [&](const BatchPlan &b, KtWireXParams &xp) {
+        xp.w.f = fmt->version == AESGCM_TLS_13 ? f13 : f12;
+        xp.seq = d_seq;
+        return klaunch_kt_tls(fmt->version, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
+    });
 }
 
 // ---------------------------------------------------------------- QUIC packets
-// Two launches on the caller's stream: the AEAD (k_kt_quic, planned as kt_frames_crypt plans k_kt_wire) and header protection (k_kt_quic_hp, a lane per packet).  Encrypt:
-// AEAD first, then the mask from the fresh ciphertext.  Decrypt: the mask off first -- that kernel leaves the unprotected header in d_out and the decoded numbers in
-// d_pn_out, which is where the AEAD reads both.  No scratch memory, no host synchronisation: capture-safe.
+// Two launches: the AEAD (k_kt_quic) and header protection (k_kt_quic_hp), in kt_wire_crypt's order
 int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_hp_slots, const uint64_t *d_pn, uint64_t *d_pn_out,
                                  const uint32_t *d_pn_off, const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream) {
-    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
-    if (!n_pkts) return AESGCM_OK;
-    if (!d_slots || !d_hp_slots || !d_pn || !d_pn_off || !d_in || !d_out || !d_pkt_off || (decrypt && (!d_auth || !d_pn_out)) || n_pkts >= ((size_t)1 << 31)) return AESGCM_EARG;
-    KtWireXParams xp;
-    kt_wire_params(xp, t, decrypt, d_in, decrypt ? d_out : d_in, d_out, d_pkt_off, d_slots, d_auth);      // the AAD: where the header lies unprotected
-    BatchParams &p = xp.w.k.b;
-    xp.w.f.tag_len = 16;                                                              // the rest of a wire format is per packet here
-    xp.seq = decrypt ? d_pn_out : d_pn;
-    xp.pn_off = d_pn_off; xp.hp_slots = d_hp_slots;
-    KtQuicHpParams hp;
-    hp.in = p.in; hp.out = p.out; hp.pkt_off = d_pkt_off; hp.slots = d_slots; hp.hp_slots = d_hp_slots; hp.pn_off = d_pn_off;
-    hp.pn = d_pn; hp.pn_out = decrypt ? d_pn_out : nullptr; hp.tab = t->tab; hp.n_pkts = (u32)n_pkts; hp.n_slots = (u32)t->n_slots;
-    BatchPlan b;
-    const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
-    if (rc) return rc;
-    if (decrypt) HIPCHK(klaunch_kt_quic_hp(b.nr, 1, b.st, b.tables, hp));
-    HIPCHK(klaunch_kt_quic(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
-    if (!decrypt) HIPCHK(klaunch_kt_quic_hp(b.nr, 0, b.st, b.tables, hp));
-    return batch_done(b, p);
+    const KtMaskCall hp = {klaunch_kt_quic_hp, d_hp_slots, d_pn_off, d_pn, d_pn_out};
+    return kt_wire_crypt(t, decrypt, n_pkts, true, d_slots, d_in, d_pkt_off, d_out, d_auth, stream, &hp, [&](const BatchPlan &b, KtWireXParams &xp) {
+        xp.w.f.tag_len = 16;                                                          // the rest of a wire format is per packet here
+        return klaunch_kt_quic(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
+    });
 }
 
 // ---------------------------------------------------------------- DTLS records
@@ -323,40 +331,21 @@ int aesgcm_dtls_fmt_check(const aesgcm_dtls_fmt *f) {
     return AESGCM_OK;
 }
 
-// 1.2: one k_kt_dtls launch, planned as kt_frames_crypt plans k_kt_tls; what the kernel takes from a wire format is the version's constant format.  1.3: the QUIC call's two
-// launches on the caller's stream -- encrypt: the AEAD first, then the mask from the fresh ciphertext; decrypt: the mask off first (k_kt_dtls_sn leaves the unprotected header
-// in d_out and the decoded numbers in d_seq_out, which is where the AEAD reads both).  No scratch memory, no host synchronisation: capture-safe.
+// 1.2: one k_kt_dtls launch; what the kernel takes from a wire format is the version's constant format.  1.3: the QUIC call's two launches, the second k_kt_dtls_sn
+// (record-number encryption)
 int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_dtls_fmt *fmt, size_t n_recs, const uint32_t *d_slots, const uint32_t *d_sn_slots,
                                  const uint64_t *d_seq, uint64_t *d_seq_out, const uint32_t *d_sn_off, const void *d_in, const uint64_t *d_rec_off, void *d_out, int *d_auth,
                                  void *stream) {
     const int frc = aesgcm_dtls_fmt_check(fmt);
     if (frc) return frc;
     const bool v13 = fmt->version == AESGCM_DTLS_13;
-    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
-    if (!n_recs) return AESGCM_OK;
-    if (!d_slots || !d_in || !d_out || !d_rec_off || (decrypt && !d_auth) || n_recs >= ((size_t)1 << 31)) return AESGCM_EARG;
-    if (v13 && (!d_sn_slots || !d_seq || !d_sn_off || (decrypt && !d_seq_out))) return AESGCM_EARG;
-    KtWireXParams xp;
-    kt_wire_params(xp, t, decrypt, d_in, v13 && decrypt ? d_out : d_in, d_out, d_rec_off, d_slots, d_auth);      // 1.3's AAD: where the header lies unprotected
-    BatchParams &p = xp.w.k.b;
-    KtQuicHpParams sn;
-    if (v13) {
-        xp.w.f.tag_len = 16;                                                          // the rest of a wire format is per record here
-        xp.seq = decrypt ? d_seq_out : d_seq;
-        xp.pn_off = d_sn_off; xp.hp_slots = d_sn_slots;
-        sn.in = p.in; sn.out = p.out; sn.pkt_off = d_rec_off; sn.slots = d_slots; sn.hp_slots = d_sn_slots; sn.pn_off = d_sn_off;
-        sn.pn = d_seq; sn.pn_out = decrypt ? d_seq_out : nullptr; sn.tab = t->tab; sn.n_pkts = (u32)n_recs; sn.n_slots = (u32)t->n_slots;
-    } else {
-        static const aesgcm_wire_fmt f12 = {13, 21, 13, 4, 16, 0};                    // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
-        xp.w.f = f12;
-    }
-    BatchPlan b;
-    const int rc = batch_plan(t->device, decrypt, n_recs, t->key_len, p, stream, b);
-    if (rc) return rc;
-    if (v13 && decrypt) HIPCHK(klaunch_kt_dtls_sn(b.nr, 1, b.st, b.tables, sn));
-    HIPCHK(klaunch_kt_dtls(fmt->version, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
-    if (v13 && !decrypt) HIPCHK(klaunch_kt_dtls_sn(b.nr, 0, b.st, b.tables, sn));
-    return batch_done(b, p);
+    const KtMaskCall sn = {klaunch_kt_dtls_sn, d_sn_slots, d_sn_off, d_seq, d_seq_out};
+    static const aesgcm_wire_fmt f12 = {13, 21, 13, 4, 16, 0};                        // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
+    return kt_wire_crypt(t, decrypt, n_recs, true, d_slots, d_in, d_rec_off, d_out, d_auth, stream, v13 ? &sn : nullptr, [&](const BatchPlan &b, KtWireXParams &xp) {
+        if (v13) xp.w.f.tag_len = 16;                                                 // the rest of a wire format is per record here
+        else xp.w.f = f12;
+        return klaunch_kt_dtls(fmt->version, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
+    });
 }
 
 // ---------------------------------------------------------------- SRTP and SRTCP packets
@@ -365,27 +354,18 @@ int aesgcm_srtp_fmt_check(const aesgcm_srtp_fmt *f) {
     return AESGCM_OK;
 }
 
-// One k_kt_srtp launch, planned as the DTLS 1.2 call's: everything the kernel needs beside the rollover counters and the MKI's length is in the packet.  No scratch
-// memory, no host synchronisation: capture-safe.
+// One k_kt_srtp launch: everything the kernel needs beside the rollover counters and the MKI's length is in the packet
 int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srtp_fmt *fmt, size_t n_pkts, const uint32_t *d_slots, const uint32_t *d_roc, const void *d_in,
                                  const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream) {
     const int frc = aesgcm_srtp_fmt_check(fmt);
     if (frc) return frc;
     const bool rtp = fmt->kind == AESGCM_SRTP_RTP;
-    if (!t || (decrypt != 0 && decrypt != 1)) return AESGCM_EARG;
-    if (!n_pkts) return AESGCM_OK;
-    if (!d_slots || !d_in || !d_pkt_off || !d_out || (rtp && !d_roc) || (decrypt && !d_auth) || n_pkts >= ((size_t)1 << 31)) return AESGCM_EARG;
-    KtWireXParams xp;
-    kt_wire_params(xp, t, decrypt, d_in, d_in, d_out, d_pkt_off, d_slots, d_auth);
-    xp.w.f.tag_len = 16;                                                              // the rest of a wire format is per packet here
-    xp.hi = rtp ? d_roc : nullptr;
-    xp.mki_len = fmt->mki_len;
-    BatchParams &p = xp.w.k.b;
-    BatchPlan b;
-    const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
-    if (rc) return rc;
-    HIPCHK(klaunch_kt_srtp(fmt->kind, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp));
-    return batch_done(b, p);
+    return kt_wire_crypt(t, decrypt, n_pkts, !rtp || d_roc, d_slots, d_in, d_pkt_off, d_out, d_auth, stream, nullptr, [&](const BatchPlan &b, KtWireXParams &xp) {
+        xp.w.f.tag_len = 16;                                                          // the rest of a wire format is per packet here
+        xp.hi = rtp ? d_roc : nullptr;
+        xp.mki_len = fmt->mki_len;
+        return klaunch_kt_srtp(fmt->kind, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
+    });
 }
 
 int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {

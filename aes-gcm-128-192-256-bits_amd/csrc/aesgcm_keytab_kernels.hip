@@ -7,6 +7,7 @@
 //                           slot number and offsets: output untouched, tag zero, auth 0, its index into the table's status word (atomicMin).
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_dispatch.h"
 
 template <int NR>

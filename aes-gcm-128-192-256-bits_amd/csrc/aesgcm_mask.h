@@ -1,11 +1,12 @@
 // aesgcm_mask.h -- what the two mask kernels share, a lane per packet each: k_kt_quic_hp (aesgcm_quic_kernels.hip: QUIC header protection, RFC 9001 5.4) and k_kt_dtls_sn
 // (aesgcm_dtls_kernels.hip: DTLS 1.3 record-number encryption, RFC 9147 4.2.3).  Both protocols mask a truncated number in the header with AES-ECB of a 16-byte ciphertext
-// sample under a second key, and both decode the full number from the truncated one and an expected one.  Here: the refusals that need no byte of the packet
-// (mask_take), the mask from a sample under the mask slot's round keys (mask_of_sample), and the decode (wire_decode_num).  Where the sample lies, which bytes the mask
-// covers and what the header's first byte means are the protocol's, and stay in its kernel.
+// sample under a second key, and both decode the full number from the truncated one and an expected one.  Here: a packet of the pass if the AEAD kernel takes it too
+// (mask_take: the front tests of aesgcm_wirecut.h, the very function the AEAD's cut calls), the mask from a sample under the mask slot's round keys (mask_of_sample), and
+// the decode (wire_decode_num).  Where the sample lies and which bytes the mask covers are the protocol's, and stay in its kernel.
 #pragma once
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 
 // RFC 9000 A.3 (DecodePacketNumber) on unsigned 64-bit values: the candidate closest to `expected` among those whose low nbits bits are `truncated`, a tie going upwards.
 // The RFC's integers are unbounded, so each comparison is written so that it cannot wrap.  `last` is the largest number there is (QUIC: 2^62 - 1, the RFC's
@@ -19,9 +20,8 @@ HD u64 wire_decode_num(u64 expected, u32 truncated, u32 nbits, u64 last) {
     return cand;
 }
 
-// Packet i of a mask pass, if it passes the tests that read no byte of it -- the first ones of the AEAD kernel's refusals (aesgcm_batch3_body.inc, x_quic / x_d13), in
-// the same order: either slot out of range, falling offsets, more than 65535 bytes, a number field at byte 0, fewer than `tail` bytes from the number field's start to the
-// packet's end, either slot unset.  -> false: refused, and nothing of the packet is read or written.
+// Packet i of a mask pass, if it passes wire_front with `tail` bytes from the number field's start to the packet's end.  -> false: refused, and nothing of the packet
+// is read or written.
 struct MaskPkt {
     const unsigned char *src;              // the packet in q.in
     unsigned char *dst;                    // ... and in q.out
@@ -29,11 +29,12 @@ struct MaskPkt {
     u32 po, len;                           // where the number field starts; the packet's length
 };
 HD bool mask_take(const KtQuicHpParams &q, u32 i, u32 tail, MaskPkt &m) {
-    const u32 slot = q.slots[i], hslot = q.hp_slots[i], po = q.pn_off[i];
     const u64 b = q.pkt_off[i], e = q.pkt_off[i + 1];
-    if (slot >= q.n_slots || hslot >= q.n_slots || e < b || e - b > 65535u || po == 0u || (u64)po + tail > e - b) return false;
-    m.ms = q.tab + hslot;
-    if (q.tab[slot].set != KT_SET || m.ms->set != KT_SET) return false;
+    const u32 po = q.pn_off[i];
+    bool bad;
+    const KtSlot *const ks = kt_slot(q.tab, q.n_slots, q.slots[i], bad);
+    m.ms = wire_front(q.tab, q.n_slots, ks, q.hp_slots[i], po, b, e, tail, bad);
+    if (bad) return false;
     m.src = q.in + b; m.dst = q.out + b; m.po = po; m.len = (u32)(e - b);
     return true;
 }

@@ -9,11 +9,12 @@
 //                           hp slot; the first byte's low bits and the pn_len packet-number bytes are XORed with it, byte by byte, inside the packet.  Decrypt: it also
 //                           decodes the full number from the truncated one and the expected one (RFC 9000 A.3) into pn_out[p].  Out of place it writes the whole header.
 // Encrypt runs k_kt_quic, then k_kt_quic_hp (the sample is fresh ciphertext); decrypt the other way round (the AEAD needs the unmasked header and the number).  Both refuse
-// the same packets by the same test (mask_take of aesgcm_mask.h, shared with the DTLS record-number kernel, and the body's copy of it), so a refused packet is touched by neither; k_kt_quic alone reports it (status word,
+// the same packets by the same functions (aesgcm_wirecut.h: wire_front, quic_pn_bad), so a refused packet is touched by neither; k_kt_quic alone reports it (status word,
 // auth 0).  18 + 6 instances; every k_kt_quic one: no scratch, at most 128 registers.
 // A translation unit of its own: its ISA census (`make asm_quic`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_mask.h"
 #include "aesgcm_dispatch.h"
 
@@ -39,12 +40,11 @@ __global__ __launch_bounds__(256) void k_kt_quic_hp(const DevTables *__restrict_
     __syncthreads();
     const u32 i = blockIdx.x * 256u + tid;
     if (i >= q.n_pkts) return;
-    // the refusals, as k_kt_quic makes them (aesgcm_batch3_body.inc, x_quic): a refused packet's number is not read and nothing of it is written.  The sample's 16
-    // bytes at pn_off + 4 lie inside the packet: 20 bytes from the number field's start
+    // the refusals are k_kt_quic's, by the functions its cut calls (aesgcm_wirecut.h: cut_quic): a refused packet's number is not read and nothing of it is written
     MaskPkt m;
-    if (!mask_take(q, i, 20u, m)) return;
+    if (!mask_take(q, i, QUIC_TAIL, m)) return;
     const u64 pn = q.pn[i];
-    if (DEC == 0 && (pn >> 62) != 0) return;
+    if (quic_pn_bad(pn, DEC)) return;
     const unsigned char *const src = m.src;
     unsigned char *const dst = m.dst;
     const u32 po = m.po;
@@ -70,10 +70,7 @@ __global__ __launch_bounds__(256) void k_kt_quic_hp(const DevTables *__restrict_
 #define KT_QUIC_HP_LDS (AESGCM_LDS_AES_OFF + AESGCM_LDS_AES)
 hipError_t klaunch_quic_attributes() {
     const hipError_t e = batch3_each([](auto NR, auto D, auto LG) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic<NR(), D(), LG()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG())); });
-    return e != hipSuccess ? e : nr_each([](auto NR) {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR(), 0>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS);
-        return e0 != hipSuccess ? e0 : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR(), 1>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS);
-    });
+    return e != hipSuccess ? e : mask_each([](auto NR, auto D) { return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_quic_hp<NR(), D()>), hipFuncAttributeMaxDynamicSharedMemorySize, KT_QUIC_HP_LDS); });
 }
 
 hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
@@ -83,9 +80,6 @@ hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st
 
 hipError_t klaunch_kt_quic_hp(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) {
     const unsigned wgs = (p.n_pkts + 255u) / 256u;
-    nr_dispatch(nr, [&](auto NR) {
-        if (dec) hipLaunchKernelGGL((k_kt_quic_hp<NR(), 1>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p);
-        else hipLaunchKernelGGL((k_kt_quic_hp<NR(), 0>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p);
-    });
+    mask_dispatch(nr, dec, [&](auto NR, auto D) { hipLaunchKernelGGL((k_kt_quic_hp<NR(), D()>), dim3(wgs), dim3(256), KT_QUIC_HP_LDS, st, tb, p); });
     return hipGetLastError();
 }

@@ -16,6 +16,7 @@
 // A translation unit of its own: its ISA census (`make asm_srtp`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG, u32 KIND>             // DEC: 0 encrypt, 1 decrypt; KIND: AESGCM_SRTP_RTP or AESGCM_SRTP_RTCP
@@ -32,17 +33,15 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t klaunch_srtp_attributes() {
-    return batch3_each([](auto NR, auto D, auto LG) {
-        const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_srtp<NR(), D(), LG(), AESGCM_SRTP_RTP>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
-        return e0 != hipSuccess ? e0 : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_srtp<NR(), D(), LG(), AESGCM_SRTP_RTCP>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+    return batch3v_each<AESGCM_SRTP_RTP, AESGCM_SRTP_RTCP>([](auto NR, auto D, auto LG, auto V) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_srtp<NR(), D(), LG(), V()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
     });
 }
 
 hipError_t klaunch_kt_srtp(unsigned kind, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
     if (kind != AESGCM_SRTP_RTP && kind != AESGCM_SRTP_RTCP) return hipErrorInvalidValue;
-    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) {
-        if (kind == AESGCM_SRTP_RTP) hipLaunchKernelGGL((k_kt_srtp<NR(), D(), LG(), AESGCM_SRTP_RTP>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
-        else hipLaunchKernelGGL((k_kt_srtp<NR(), D(), LG(), AESGCM_SRTP_RTCP>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+    batch3v_dispatch<AESGCM_SRTP_RTP, AESGCM_SRTP_RTCP>(nr, dec, lg, (int)kind, [&](auto NR, auto D, auto LG, auto V) {
+        hipLaunchKernelGGL((k_kt_srtp<NR(), D(), LG(), V()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
     });
     return hipGetLastError();
 }

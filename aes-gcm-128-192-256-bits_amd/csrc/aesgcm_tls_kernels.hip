@@ -14,6 +14,7 @@
 // A translation unit of its own: its ISA census (`make asm_tls`) is read apart from the others', whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG, u32 VER>              // DEC: 0 encrypt, 1 decrypt; VER: AESGCM_TLS_13 or AESGCM_TLS_12
@@ -30,17 +31,15 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t klaunch_tls_attributes() {
-    return batch3_each([](auto NR, auto D, auto LG) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_tls<NR(), D(), LG(), AESGCM_TLS_13>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
-        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_tls<NR(), D(), LG(), AESGCM_TLS_12>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+    return batch3v_each<AESGCM_TLS_13, AESGCM_TLS_12>([](auto NR, auto D, auto LG, auto V) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_tls<NR(), D(), LG(), V()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
     });
 }
 
 hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
     if (version != AESGCM_TLS_13 && version != AESGCM_TLS_12) return hipErrorInvalidValue;
-    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) {
-        if (version == AESGCM_TLS_13) hipLaunchKernelGGL((k_kt_tls<NR(), D(), LG(), AESGCM_TLS_13>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
-        else hipLaunchKernelGGL((k_kt_tls<NR(), D(), LG(), AESGCM_TLS_12>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+    batch3v_dispatch<AESGCM_TLS_13, AESGCM_TLS_12>(nr, dec, lg, (int)version, [&](auto NR, auto D, auto LG, auto V) {
+        hipLaunchKernelGGL((k_kt_tls<NR(), D(), LG(), V()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
     });
     return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 // A translation unit of its own: its ISA census (`make asm_wire`) is read apart from the key tables' (`make asm_keytab`).
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG>                       // DEC: 0 encrypt, 1 decrypt

@@ -14,6 +14,7 @@
 // A translation unit of its own: its ISA census (`make asm_wirex`) is read apart from k_kt_wire's (`make asm_wire`), whose instruction streams stay what they were.
 #include "aesgcm_keytab.h"
 #include "aesgcm_lanes.h"
+#include "aesgcm_wirecut.h"
 #include "aesgcm_dispatch.h"
 
 template <int NR, int DEC, int LG, u32 EXT>              // DEC: 0 encrypt, 1 decrypt; EXT: AESGCM_WIREX_XPN or AESGCM_WIREX_ESN
@@ -30,17 +31,15 @@ __global__ __launch_bounds__(BATCH3_LANES(NR), (BATCH3_LANES(NR) + 255) / 256) v
 
 // ------------------------------------------------------------------------------------------------ launchers
 hipError_t klaunch_wirex_attributes() {
-    return batch3_each([](auto NR, auto D, auto LG) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_XPN>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
-        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_ESN>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
+    return batch3v_each<AESGCM_WIREX_XPN, AESGCM_WIREX_ESN>([](auto NR, auto D, auto LG, auto V) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_kt_wirex<NR(), D(), LG(), V()>), hipFuncAttributeMaxDynamicSharedMemorySize, BATCH3_LDS_BYTES_LG(LG()));
     });
 }
 
 hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
     if (ext != AESGCM_WIREX_XPN && ext != AESGCM_WIREX_ESN) return hipErrorInvalidValue;
-    batch3_dispatch(nr, dec, lg, [&](auto NR, auto D, auto LG) {
-        if (ext == AESGCM_WIREX_XPN) hipLaunchKernelGGL((k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_XPN>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
-        else hipLaunchKernelGGL((k_kt_wirex<NR(), D(), LG(), AESGCM_WIREX_ESN>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
+    batch3v_dispatch<AESGCM_WIREX_XPN, AESGCM_WIREX_ESN>(nr, dec, lg, (int)ext, [&](auto NR, auto D, auto LG, auto V) {
+        hipLaunchKernelGGL((k_kt_wirex<NR(), D(), LG(), V()>), dim3(wgs), dim3(BATCH3_LANES(NR())), BATCH3_LDS_BYTES_LG(LG()), st, tb, p);
     });
     return hipGetLastError();
 }

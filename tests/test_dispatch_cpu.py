@@ -61,6 +61,26 @@ int main() {
         const int e = nr_each([&](auto NR) { seen++; return seen == fail_at ? 900 + (int)NR() : 0; });
         std::printf("nr_each_fail %d seen %d returned %d\n", fail_at, seen, e);
     }
+    // the wire families' sets: the body kernels with a two-valued variant (here 1, 2), and the two mask kernels
+    const int vs[] = {1, 2, 0, 3};
+    for (int nr : nrs) for (int dec : decs) for (int lg : lgs) for (int v : vs) {
+        int calls = 0;
+        const int back = batch3v_dispatch<1, 2>(nr, dec, lg, v, [&](auto NR, auto D, auto LG, auto V) { calls++; return 100000 * NR() + 1000 * D() + 10 * LG() + V(); });
+        std::printf("b3v %d %d %d %d -> %d %d\n", nr, dec, lg, v, calls, back);
+    }
+    for (int nr : nrs) for (int dec : decs) {
+        int calls = 0;
+        const int back = mask_dispatch(nr, dec, [&](auto NR, auto D) { calls++; return 100 * NR() + D(); });
+        std::printf("mask %d %d -> %d %d\n", nr, dec, calls, back);
+    }
+    for (int fail_at = 0; fail_at <= 37; fail_at++) {
+        int seen = 0;
+        const int e = batch3v_each<1, 2>([&](auto NR, auto D, auto LG, auto V) { seen++; if (!fail_at) std::printf("b3v_each %d %d %d %d\n", NR(), D(), LG(), V()); return seen == fail_at ? 600 + seen : 0; });
+        std::printf("b3v_fail %d seen %d returned %d\n", fail_at, seen, e);
+        seen = 0;
+        const int em = mask_each([&](auto NR, auto D) { seen++; if (!fail_at) std::printf("mask_each %d %d\n", NR(), D()); return seen == fail_at ? 600 + seen : 0; });
+        std::printf("mask_fail %d seen %d returned %d\n", fail_at, seen, em);
+    }
     prim("p2", klist<7, 9>{});
     prim("p3", klist<3, 4, 6>{});
     prim("p4", klist<2, 3, 4, 6>{});
@@ -162,6 +182,30 @@ def test_each_visits_18_instances_once_and_stops_at_the_first_error(lines):
     assert fails == [(0, 18, 0)] + [(k, k, 700 + k) for k in range(1, 19)]   # (fail_at, calls made, value returned)
     nr_fails = [tuple(int(x) for x in ln.split()[1::2]) for ln in lines if ln.startswith("nr_each_fail ")]
     assert nr_fails == [(0, 3, 0), (1, 1, 910), (2, 2, 912), (3, 3, 914)]
+
+
+def test_wire_family_sets(lines):
+    """the body kernels with a variant (k_kt_wirex, k_kt_tls, k_kt_dtls, k_kt_srtp: 36 instances) and the two mask kernels (6): every input reaches exactly one instance by
+    the fall-through rules -- a variant that is not the first lands on the second, which is why the launchers refuse an unknown one first -- and the walks visit every
+    instance once and stop at the first error"""
+    got = [_ints(ln) for ln in lines if ln.startswith("b3v ")]
+    want = []
+    for nr in NRS:
+        for dec in DECS:
+            for lg in LGS:
+                for v in (1, 2, 0, 3):
+                    a, b, c = _rule(nr, dec, lg)
+                    want.append([nr, dec, lg, v, 1, 100000 * a + 1000 * b + 10 * c + (1 if v == 1 else 2)])
+    assert got == want
+    got = [_ints(ln) for ln in lines if ln.startswith("mask ")]
+    assert got == [[nr, dec, 1, 100 * _rule_nr(nr) + (0 if dec == 0 else 1)] for nr in NRS for dec in DECS]
+    seen = [tuple(_ints(ln)) for ln in lines if ln.startswith("b3v_each ")]
+    assert len(seen) == 36 and set(seen) == {(nr, d, lg, v) for nr in (10, 12, 14) for d in (0, 1) for lg in (3, 4, 6) for v in (1, 2)}
+    seen = [tuple(_ints(ln)) for ln in lines if ln.startswith("mask_each ")]
+    assert len(seen) == 6 and set(seen) == {(nr, d) for nr in (10, 12, 14) for d in (0, 1)}
+    for name, size in (("b3v", 36), ("mask", 6)):
+        fails = [_ints(ln) for ln in lines if ln.startswith("%s_fail " % name)]
+        assert fails == [[k, size if k == 0 or k > size else k, 0 if k == 0 or k > size else 600 + k] for k in range(0, 38)], name
 
 
 # ---- the two primitives, and the compositions the launchers of aesgcm_kernels.hip use (the rules: what those launchers did as macro ladders)
