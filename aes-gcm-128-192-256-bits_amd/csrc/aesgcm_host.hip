@@ -11,6 +11,10 @@
 #include <string.h>
 #include <time.h>
 
+// The one HIP entry point this library can do without: batch_plan asks it whether a call's stream is being captured.  A weak reference, so that the library still loads
+// over a HIP runtime that has no stream capture (an older one, a test double); there no stream captures, and batch_plan does not ask.
+#pragma weak hipStreamIsCapturing
+
 thread_local char g_err[256] = "";
 int hip_fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
@@ -902,6 +906,14 @@ int batch_plan(int device, int decrypt, size_t n_pkts, size_t key_len, BatchPara
 #ifdef AESGCM_DEBUG_KNOBS
     if (g_force.batch_order) ordered = lg < 6 && p.data_off && g_force.batch_order == 1;
 #endif
+    if (ordered) {
+        // A stream that is being captured takes the packets in array order, as a call without memory for the order does: slower, never wrong.  The order's scratch
+        // belongs to the device, not to the graph -- a later, larger call frees it under a graph that would hold its address -- and neither the slot's event nor an
+        // allocation belongs into a capture.  Asked only here: a call that would not be ordered pays nothing.  (include/aesgcm.h, CAPTURE)
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing) HIPCHK(hipStreamIsCapturing(st, &cap));         // a weak reference (above): a runtime without stream capture has no stream that captures
+        if (cap != hipStreamCaptureStatusNone) ordered = false;
+    }
     if (ordered) {
         b.order_lock = std::unique_lock<std::mutex>(g_mu);                        // held from the choice of the slot to the event behind its reader: callers on other threads queue up here
         b.oslot = &ds->order[ds->order_next++ & 3u];

@@ -219,7 +219,7 @@ int aesgcm_wire_xfmt_check(const aesgcm_wire_xfmt *xf) {
 // order by falling frame length class); the launches; batch_done.  `aead(b, xp)` sets what its format adds to xp (w.f, the per-packet numbers) and launches its kernel.
 // `mask`, or NULL: the call's second launch on the same stream, a lane per packet (QUIC: header protection; DTLS 1.3: record-number encryption).  Encrypt: the AEAD first,
 // then the mask from the fresh ciphertext.  Decrypt: the mask off first -- that kernel leaves the unprotected header in d_out and the decoded numbers in d_pn_out, which is
-// where the AEAD reads both.  No scratch memory, no host synchronisation: capture-safe.
+// where the AEAD reads both.  No scratch memory, no host synchronisation: capture-safe (include/aesgcm.h, CAPTURE; batch_plan never orders a captured call).
 struct KtMaskCall {
     hipError_t (*launch)(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p);
     const uint32_t *d_hp_slots, *d_pn_off;

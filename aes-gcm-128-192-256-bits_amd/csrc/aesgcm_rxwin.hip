@@ -1,7 +1,7 @@
 // aesgcm_rxwin.hip -- receive windows (include/aesgcm.h "RECEIVE WINDOWS"): the host side of aesgcm_rxwin_*.  The kernels are in aesgcm_rxwin_kernels.hip, the lane code and
 // the layout of the state in aesgcm_rxwin.h.  A table is one device allocation of n_wins window records and a status word.  Host state reaches the records through the
 // table's staging buffer, as a key table's keys do; aesgcm_rxwin_get copies records back and waits.  The normalised form of set / get and the records' ring are converted
-// into one another here, on the host (rx_norm_to_ring, rx_ring_to_norm).  recover is one launch, commit three; neither synchronises or allocates: capture-safe.
+// into one another here, on the host (rx_norm_to_ring, rx_ring_to_norm).  recover is one launch, commit three; neither synchronises or allocates: capture-safe (include/aesgcm.h, CAPTURE).
 #include "aesgcm_internal.h"
 #include "aesgcm_rxwin.h"
 

@@ -414,7 +414,23 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * ORDERING: every call is asynchronous and stream-ordered on `stream` (NULL = the null stream).  A set or clear on stream A and a crypt call on stream B that names
  * the same slot are NOT ordered by the library: the caller orders them (an event, or one stream for both).  Key rotation: set the new key into an unused slot,
  * switch the packets' slot numbers to it, clear the old slot once no call in flight names it (INTEGRATION.md "Key tables").  The calls of one table are
- * thread-safe; a table belongs to the device it was created on. */
+ * thread-safe; a table belongs to the device it was created on.
+ * CAPTURE (key tables and receive windows): every aesgcm_keytab_*_crypt_dev call, aesgcm_rxwin_recover_dev, aesgcm_rxwin_commit_dev and aesgcm_wipe_failed_dev is a
+ * fixed sequence of launches (and one 4-byte memset node per crypt call) on `stream` for given pointers and counts: no allocation, no host synchronisation, nothing read
+ * back, no event.  They may run under hipStreamBeginCapture on `stream` (a created stream; thread-local capture mode suffices), several of them behind one another, and
+ * the graph may be replayed over other slots, numbers, lengths, offsets and bytes in the same buffers; a receive loop's window state travels from replay to replay in
+ * the window records.  (The five-array aesgcm_batch_crypt_dev / _var_dev plan their launch the same way and follow the same rules.)
+ *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
+ *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, and ONE of the device's 256 launch dispensers (a word the
+ *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
+ *   ORDERING         a captured call is never ordered by falling length class, whatever its count: the order's scratch belongs to the device, not to the graph.  The
+ *                    packets are taken in array order -- the same bytes, slower from the counts at which an ordinary call is ordered.
+ *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy (staging buffers
+ *                    that grow, events, synchronous copies, waits): call them outside the capture.
+ *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
+ *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
+ *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
+ * tests/test_gpu_capture.py replays every family against libcrypto; tests/fake_hip/capture_drive.py holds the host side to the list above. */
 typedef struct aesgcm_keytab aesgcm_keytab;
 AESGCM_API int aesgcm_keytab_create(aesgcm_keytab **out, int device, size_t key_len, size_t n_slots);
 AESGCM_API int aesgcm_keytab_set(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *keys, void *stream);
@@ -574,7 +590,7 @@ AESGCM_API int aesgcm_keytab_records_crypt_dev(aesgcm_keytab *t, int decrypt, co
  * goes to aesgcm_keytab_status.  FAIL-CLOSED: aesgcm_wipe_failed_dev(device, n_pkts, d_out, 0, d_pkt_off, d_auth, stream) behind a decrypt.
  * AESGCM_EARG, before the table or a device is touched: t NULL; decrypt not 0 / 1; (n_pkts == 0 is AESGCM_OK;) any of d_slots, d_hp_slots, d_pn, d_pn_off, d_in, d_out,
  * d_pkt_off NULL; decrypt without d_auth or d_pn_out; n_pkts >= 2^31.
- * Two launches per call on `stream`, no scratch memory, capture-safe and asynchronous: encrypt k_kt_quic (the AEAD; shape and order as aesgcm_keytab_records_crypt_dev) then
+ * Two launches per call on `stream`, no scratch memory, capture-safe (CAPTURE, under "key tables" above) and asynchronous: encrypt k_kt_quic (the AEAD; shape and order as aesgcm_keytab_records_crypt_dev) then
  * k_kt_quic_hp (a lane per packet); decrypt the other way round.  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: Retry and Version Negotiation packets; coalesced datagrams (split them: one entry of d_pkt_off per packet); ChaCha20; key derivation (INTEGRATION.md "QUIC
  * packets" says which secret becomes what); choosing the slot from the Key Phase bit (the caller who needs it decrypts out of place and retries the failed packets under the
@@ -621,7 +637,7 @@ AESGCM_API int aesgcm_keytab_quic_crypt_dev(aesgcm_keytab *t, int decrypt, size_
  * aesgcm_dtls_fmt_check: AESGCM_EARG for NULL, a version other than AESGCM_DTLS_13 / AESGCM_DTLS_12, reserved != 0.  It touches no device; the crypt call runs it first.
  * Then AESGCM_EARG, before the table or a device is touched, in aesgcm_keytab_quic_crypt_dev's order: t NULL; decrypt not 0 / 1; (n_recs == 0 is AESGCM_OK;) any of d_slots,
  * d_in, d_out, d_rec_off NULL, for 1.3 also d_sn_slots, d_seq, d_sn_off; decrypt without d_auth, for 1.3 also without d_seq_out; n_recs >= 2^31.
- * 1.2: one k_kt_dtls launch; 1.3: two launches on `stream`, k_kt_dtls and k_kt_dtls_sn (a lane per record).  No scratch memory, no host synchronisation, capture-safe and
+ * 1.2: one k_kt_dtls launch; 1.3: two launches on `stream`, k_kt_dtls and k_kt_dtls_sn (a lane per record).  No scratch memory, no host synchronisation, capture-safe (CAPTURE, under "key tables" above) and
  * asynchronous; shape and order as aesgcm_keytab_records_crypt_dev.  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: DTLS 1.2 connection IDs (RFC 9146: another header and another AAD); coalesced datagrams (split them: one entry of d_rec_off per record); choosing the slot
  * from the epoch bits (E E of b0, or a 1.2 header's epoch: the caller maps them to slots); anti-replay (not this call's: aesgcm_rxwin_*, AESGCM_RXWIN_EXPECT for 1.3's d_seq, {WIRE, 5, 6} for 1.2); key derivation (INTEGRATION.md "DTLS records" says which secret
@@ -664,7 +680,7 @@ AESGCM_API int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const
  * aesgcm_srtp_fmt_check: AESGCM_EARG for NULL, a kind other than AESGCM_SRTP_RTP / AESGCM_SRTP_RTCP, mki_len > 128.  It touches no device; the crypt call runs it first.
  * Then AESGCM_EARG, before the table or a device is touched, in aesgcm_keytab_dtls_crypt_dev's order: t NULL; decrypt not 0 / 1; (n_pkts == 0 is AESGCM_OK;) any of d_slots,
  * d_in, d_pkt_off, d_out NULL; RTP without d_roc; decrypt without d_auth; n_pkts >= 2^31.
- * ONE k_kt_srtp launch: no scratch memory, no host synchronisation, capture-safe and asynchronous; shape, order and planning as aesgcm_keytab_dtls_crypt_dev's DTLS 1.2
+ * ONE k_kt_srtp launch: no scratch memory, no host synchronisation, capture-safe (CAPTURE, under "key tables" above) and asynchronous; shape, order and planning as aesgcm_keytab_dtls_crypt_dev's DTLS 1.2
  * mode.  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: ROC estimation and replay windows (not this call's: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_SRTP writes d_roc, aesgcm_rxwin_commit_dev keeps the window); key derivation (RFC 3711 4.3 KDF, the DTLS-SRTP exporter: INTEGRATION.md "SRTP and SRTCP packets" says which secret
  * becomes what); the AES-CM / HMAC-SHA1 transforms; double encryption (RFC 8723); RFC 6904 header-extension encryption; MKI lookup (the caller maps an MKI to a slot, and one
@@ -729,7 +745,7 @@ AESGCM_API int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const
  * authenticated, 1 accepted, 2 old, 3 replay, 4 refused: authenticated, but its window is out of range or its number is NONE; the lowest such index goes to
  * aesgcm_rxwin_status.  AESGCM_EARG, before any device is touched: w NULL; (n_pkts == 0 is AESGCM_OK;) d_win, d_num, d_auth or d_accept NULL; n_pkts >= 2^31.
  * One launch per recover, three per commit (the per-window maximum; clearing what the window moves over; marking), a lane per packet, atomics on the window's own words: no
- * scratch memory, no host synchronisation, capture-safe and asynchronous on `stream`.  Every call but aesgcm_rxwin_get is stream-ordered; two calls that name the same
+ * scratch memory, no host synchronisation, capture-safe (CAPTURE, under "key tables" above: the precondition, what a graph holds) and asynchronous on `stream`.  Every call but aesgcm_rxwin_get is stream-ordered; two calls that name the same
  * window on different streams are the caller's to order; the calls of one table are thread-safe; a table belongs to the device it was created on.
  * OUT OF SCOPE: skipping the decryption of packets a pre-check could already reject; per-window counters; MACsec's replayProtect = false mode; choosing a window from a
  * wire field (SCI, SPI, SSRC lookup); TLS, which has no replay window. */

@@ -18,6 +18,12 @@
 //     reach -- its own as "caller", each context's own as "own" (plan_drive.py does) -- leaves unnamed only what the library made for itself and hands to nobody:
 //     a context's side stream.  A scalar that is 0 is left out.  fake_log reads it, fake_reset clears it: what a call decided, as text a test can compare
 //     (tests/fake_hip/plan_drive.py, tests/golden/launch_plan.txt).
+//   * CAPTURE DISCIPLINE: hipStreamBeginCapture / hipStreamEndCapture / hipStreamIsCapturing on the fake streams (the "graph" is a count of what was enqueued).  While
+//     any stream captures, what a capture cannot carry is noted with the HIP call's name in a list of its own (fake_capture_violations, fake_capture_clear; fake_reset
+//     leaves it alone): hipMalloc, hipFree, a synchronous copy or memset, hipStreamSynchronize, hipDeviceSynchronize, hipEventSynchronize, hipEventQuery.  An event
+//     remembers whether its last record was inside a capture; a hipStreamWaitEvent on such an event from a stream that is not capturing is noted too, also after the
+//     capture has ended.  The key tables' and receive windows' host sides (csrc/aesgcm_keytab.hip, aesgcm_rxwin.hip) are linked in for this, with launchers that note a
+//     log line as the others do (tests/fake_hip/capture_drive.py).
 // To keep the host logic running, a launch that would publish a tag and its generation number to the pinned host slot publishes the number (no tag).
 #include <hip/hip_runtime.h>
 
@@ -32,6 +38,8 @@
 #include <vector>
 
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_internal.h"
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_keytab.h"
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_rxwin.h"
 #include <rccl/rccl.h>
 
 #define FAKE_DEVICES 4
@@ -42,11 +50,12 @@ std::mutex mu;
 thread_local int cur = 0;
 struct Alloc { size_t size; int dev; };                     // dev -2 = pinned host memory (valid everywhere)
 std::map<uintptr_t, Alloc> allocs;
-struct FakeStream { int dev; };
-struct FakeEvent { int dev; std::map<const void *, long> clock; };      // clock: the stream clock it captured when it was last recorded
+struct FakeStream { int dev; bool capturing = false; long captured = 0; };      // captured: operations enqueued since hipStreamBeginCapture
+struct FakeEvent { int dev; std::map<const void *, long> clock; bool in_capture = false; };      // clock: the stream clock it captured when it was last recorded; in_capture: ... inside a capture
 std::set<void *> live_streams, live_events;
 FakeStream null_stream[FAKE_DEVICES] = {{0}, {1}, {2}, {3}};
-std::vector<std::string> violations, log_lines;
+std::vector<std::string> violations, log_lines, cap_violations;
+int n_capturing = 0;                                          // streams between hipStreamBeginCapture and hipStreamEndCapture
 unsigned touched = 0, attrs = 0;                              // bit masks of devices
 long n_sync = 0, n_dev_sync = 0, n_launch = 0, n_collective = 0, fail_at = 0;
 std::map<const void *, std::map<const void *, long>> clocks;  // per stream: its own count of enqueued operations and the counts of the others it is ordered behind
@@ -79,6 +88,9 @@ void bad(const char *fmt, ...) {
     violations.push_back(b);
 }
 void touch() { touched |= 1u << cur; }
+// a call that no capture can carry, made while a stream captures
+void cap_bad(const char *call) { if (n_capturing) cap_violations.push_back(std::string(call) + " while a stream is capturing"); }
+bool capturing(hipStream_t s) { return s && live_streams.count((void *)s) && reinterpret_cast<FakeStream *>(s)->capturing; }
 // the device of an address (or -1: not device memory the fake handed out, -2: pinned host)
 int dev_of(const void *p) {
     if (!p) return -1;
@@ -99,6 +111,7 @@ void enqueue(const char *what, hipStream_t s) {
     if (watched && k != watched && clocks[k][watched] < clocks[watched][watched])
         bad("%s: enqueued on a stream not ordered behind the watched stream (%ld of its %ld operations)", what, clocks[k][watched], clocks[watched][watched]);
     ++clocks[k][k];
+    if (capturing(s)) ++reinterpret_cast<FakeStream *>(s)->captured;
 }
 void chk_stream(const char *what, hipStream_t s) {
     if (s && !live_streams.count((void *)s)) { bad("%s: unknown stream", what); return; }
@@ -136,6 +149,15 @@ EXPORT int fake_violations(char *buf, size_t n) {
     if (buf && n) { strncpy(buf, s.c_str(), n - 1); buf[n - 1] = 0; }
     return (int)violations.size();
 }
+// what was done that a capture cannot carry (the list of its own: fake_reset leaves it, fake_capture_clear empties it)
+EXPORT int fake_capture_violations(char *buf, size_t n) {
+    std::lock_guard<std::mutex> lk(mu);
+    std::string s;
+    for (auto &v : cap_violations) s += v + "\n";
+    if (buf && n) { strncpy(buf, s.c_str(), n - 1); buf[n - 1] = 0; }
+    return (int)cap_violations.size();
+}
+EXPORT void fake_capture_clear(void) { std::lock_guard<std::mutex> lk(mu); cap_violations.clear(); }
 EXPORT size_t fake_live_allocations(void) { return allocs.size(); }
 // the launch log since the last reset, a line per launch; returns the bytes it needs (with the final 0), so a caller can see that its buffer was too short
 EXPORT size_t fake_log(char *buf, size_t n) {
@@ -163,10 +185,10 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int d) {
     p->multiProcessorCount = 256;
     return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { std::lock_guard<std::mutex> lk(mu); touch(); ++n_sync; ++n_dev_sync; return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipDeviceSynchronize"); ++n_sync; ++n_dev_sync; return hipSuccess; }
 hipError_t hipMalloc(void **p, size_t n) {
     std::lock_guard<std::mutex> lk(mu);
-    touch();
+    touch(); cap_bad("hipMalloc");
     void *q = calloc(1, n ? n : 1);
     if (!q) return hipErrorOutOfMemory;
     allocs[(uintptr_t)q] = {n ? n : 1, cur};
@@ -176,6 +198,7 @@ hipError_t hipMalloc(void **p, size_t n) {
 hipError_t hipFree(void *p) {
     std::lock_guard<std::mutex> lk(mu);
     if (!p) return hipSuccess;
+    cap_bad("hipFree");
     auto it = allocs.find((uintptr_t)p);
     if (it == allocs.end()) { bad("hipFree of an unknown pointer"); return hipErrorInvalidValue; }
     if (it->second.dev != cur) bad("hipFree: memory of device %d freed while device %d is current", it->second.dev, cur);
@@ -198,22 +221,37 @@ static hipError_t copy(const char *what, void *dst, const void *src, size_t n, h
     touch();
     chk_ptr(what, "dst", dst); chk_ptr(what, "src", src);
     if (async) { chk_stream(what, st); enqueue(what, st); }
+    else cap_bad(what);
     if (n) memmove(dst, src, n);
     return hipSuccess;
 }
 hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) { return copy("hipMemcpy", dst, src, n, nullptr, false); }
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind, hipStream_t st) { return copy("hipMemcpyAsync", dst, src, n, st, true); }
-hipError_t hipMemset(void *dst, int v, size_t n) { std::lock_guard<std::mutex> lk(mu); touch(); chk_ptr("hipMemset", "dst", dst); memset(dst, v, n); return hipSuccess; }
+hipError_t hipMemset(void *dst, int v, size_t n) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipMemset"); chk_ptr("hipMemset", "dst", dst); memset(dst, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t st) {
     std::lock_guard<std::mutex> lk(mu);
     touch(); chk_ptr("hipMemsetAsync", "dst", dst); chk_stream("hipMemsetAsync", st); enqueue("hipMemsetAsync", st);
     memset(dst, v, n);
     return hipSuccess;
 }
+// (the strided forms: a key table's setters move their fields from the staging buffer into the slots with them)
+hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(mu);
+    touch(); chk_ptr("hipMemcpy2DAsync", "dst", dst); chk_ptr("hipMemcpy2DAsync", "src", src); chk_stream("hipMemcpy2DAsync", st); enqueue("hipMemcpy2DAsync", st);
+    for (size_t r = 0; r < height; r++) memmove((char *)dst + r * dpitch, (const char *)src + r * spitch, width);
+    return hipSuccess;
+}
+hipError_t hipMemset2DAsync(void *dst, size_t pitch, int v, size_t width, size_t height, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(mu);
+    touch(); chk_ptr("hipMemset2DAsync", "dst", dst); chk_stream("hipMemset2DAsync", st); enqueue("hipMemset2DAsync", st);
+    for (size_t r = 0; r < height; r++) memset((char *)dst + r * pitch, v, width);
+    return hipSuccess;
+}
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
     std::lock_guard<std::mutex> lk(mu);
     touch();
-    FakeStream *f = new FakeStream{cur};
+    FakeStream *f = new FakeStream();
+    f->dev = cur;
     live_streams.insert(f);
     *s = reinterpret_cast<hipStream_t>(f);
     return hipSuccess;
@@ -222,16 +260,38 @@ hipError_t hipStreamCreate(hipStream_t *s) { return hipStreamCreateWithFlags(s, 
 hipError_t hipStreamDestroy(hipStream_t s) {
     std::lock_guard<std::mutex> lk(mu);
     chk_stream("hipStreamDestroy", s);
+    if (capturing(s)) { --n_capturing; bad("hipStreamDestroy: the stream is capturing"); }
     live_streams.erase((void *)s);
     stream_names.erase((const void *)s);                        // (the next stream may be made at this address)
     delete reinterpret_cast<FakeStream *>(s);
     return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t s) { std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamSynchronize", s); ++n_sync; return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipStreamSynchronize"); chk_stream("hipStreamSynchronize", s); ++n_sync; return hipSuccess; }
+// Capture: a created stream (never the null stream) notes what is enqueued on it; the graph that comes back is the count, as an opaque handle
+hipError_t hipStreamBeginCapture(hipStream_t s, hipStreamCaptureMode) {
+    std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamBeginCapture", s);
+    if (!s || !live_streams.count((void *)s) || capturing(s)) return hipErrorInvalidValue;
+    FakeStream *f = reinterpret_cast<FakeStream *>(s);
+    f->capturing = true; f->captured = 0; ++n_capturing;
+    return hipSuccess;
+}
+hipError_t hipStreamEndCapture(hipStream_t s, hipGraph_t *g) {
+    std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamEndCapture", s);
+    if (!capturing(s)) return hipErrorInvalidValue;
+    FakeStream *f = reinterpret_cast<FakeStream *>(s);
+    f->capturing = false; --n_capturing;
+    if (g) *g = reinterpret_cast<hipGraph_t>((uintptr_t)f->captured + 1);
+    return hipSuccess;
+}
+hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus *st) {
+    std::lock_guard<std::mutex> lk(mu);
+    *st = capturing(s) ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
+    return hipSuccess;
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
     std::lock_guard<std::mutex> lk(mu);
     touch();
-    FakeEvent *f = new FakeEvent{cur, {}};
+    FakeEvent *f = new FakeEvent{cur, {}, false};
     live_events.insert(f);
     *e = reinterpret_cast<hipEvent_t>(f);
     return hipSuccess;
@@ -244,20 +304,30 @@ static void chk_event(const char *what, hipEvent_t e) {
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     std::lock_guard<std::mutex> lk(mu); touch(); chk_event("hipEventRecord", e); chk_stream("hipEventRecord", s);
-    if (live_events.count((void *)e)) reinterpret_cast<FakeEvent *>(e)->clock = clocks[stream_key(s)];
+    if (live_events.count((void *)e)) { FakeEvent *f = reinterpret_cast<FakeEvent *>(e); f->clock = clocks[stream_key(s)]; f->in_capture = capturing(s); }
     return hipSuccess;
 }
-hipError_t hipEventSynchronize(hipEvent_t e) { std::lock_guard<std::mutex> lk(mu); touch(); chk_event("hipEventSynchronize", e); ++n_sync; return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipEventSynchronize"); chk_event("hipEventSynchronize", e); ++n_sync; return hipSuccess; }
+hipError_t hipEventQuery(hipEvent_t e) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipEventQuery"); chk_event("hipEventQuery", e); return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { std::lock_guard<std::mutex> lk(mu); chk_event("hipEventElapsedTime", a); chk_event("hipEventElapsedTime", b); *ms = 1.0f; return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamWaitEvent", s); chk_event("hipStreamWaitEvent", e);
     if (live_events.count((void *)e)) {
+        // an event whose last record belongs to a capture is a node of that graph: a stream outside it cannot wait for it (now, or once the capture has ended)
+        if (reinterpret_cast<FakeEvent *>(e)->in_capture && !capturing(s))
+            cap_violations.push_back("hipStreamWaitEvent from a stream that is not capturing on an event last recorded inside a capture");
         auto &mine = clocks[stream_key(s)];
         for (auto &kv : reinterpret_cast<FakeEvent *>(e)->clock) if (mine[kv.first] < kv.second) mine[kv.first] = kv.second;
     }
     return hipSuccess;
 }
 }  // extern "C"
+// capture for a driver (the runtime's own names are not exported): begin -> 0 or the HIP error; end -> the operations the capture holds, or -1
+EXPORT int fake_begin_capture(hipStream_t s) { return (int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal); }
+EXPORT long fake_end_capture(hipStream_t s) {
+    hipGraph_t g = nullptr;
+    return hipStreamEndCapture(s, &g) == hipSuccess ? (long)(uintptr_t)g - 1 : -1;
+}
 
 // ---------------------------------------------------------------- launchers (csrc/aesgcm_internal.h): record, check, launch nothing
 #define LAUNCH(what, st) std::lock_guard<std::mutex> lk(mu); touch(); ++n_launch; if (fail_at && n_launch == fail_at) return hipErrorLaunchFailure; \
@@ -367,6 +437,78 @@ hipError_t klaunch_rows_close(int dec, unsigned wgs, hipStream_t st, const KeyMa
 hipError_t klaunch_wipe_failed(hipStream_t st, unsigned char *out, const int *auth, const u64 *data_off, u32 n_pkts, u32 pkt_len, const u64 *out_ptr, const u32 *len_arr) {
     LAUNCH("k_wipe_failed", st); P(out); P(auth); P(data_off); P(out_ptr); P(len_arr); P(g_wipe_hdr);      // (the call's header: beside the arguments, aesgcm_internal.h)
     note("%s %s n=%u len=%u p=%s", W, sname(st), n_pkts, pkt_len, bits(out, auth, data_off, out_ptr, len_arr, g_wipe_hdr).c_str());
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- key tables and receive windows (csrc/aesgcm_keytab.h, aesgcm_rxwin.h)
+// a key-table launch in the log: the batch part as k_batch3's (keys is unused there), then q = the slots, the table and the status word, and what the family adds
+static void kt_ptrs(const char *W, const DevTables *tb, const KtParams &k) {
+    const BatchParams &p = k.b;
+    P(tb); P(p.ivs); P(p.aad); P(p.in); P(p.out); P(p.tags); P(p.expect); P(p.auth); P(p.counter); P(p.data_off); P(p.aad_off); P(p.perm); P(k.slots); P(k.tab); P(k.status);
+}
+static std::string kt_txt(const KtParams &k) {
+    const BatchParams &p = k.b;
+    char b[256];
+    snprintf(b, sizeof b, "p=%s " PKT_SCALARS_FMT " q=%s slots=%u", bits(p.keys, p.ivs, p.aad, p.in, p.out, p.tags, p.expect, p.auth, p.counter, p.data_off, p.aad_off, p.perm).c_str(), PKT_SCALARS(p),
+             bits(k.slots, k.tab, k.status).c_str(), k.n_slots);
+    return b;
+}
+static std::string fmt_txt(const aesgcm_wire_fmt &f) {
+    char b[96];
+    snprintf(b, sizeof b, "f=%u/%u/%u/%u/%u/%u", f.aad_len, f.hdr_len, f.iv_off, f.salt_len, f.tag_len, f.flags);
+    return b;
+}
+hipError_t klaunch_kt_setup(int nr, hipStream_t st, const DevTables *tb, const KtSetupParams &s) {
+    LAUNCH("k_kt_setup", st); P(tb); P(s.keys); P(s.slots); P(s.tab); P(s.status);
+    note("%s %s nr=%d p=%s first=%u n=%u slots=%u", W, sname(st), nr, bits(s.keys, s.slots, s.tab, s.status).c_str(), s.first, s.n, s.n_slots);
+    return hipSuccess;
+}
+hipError_t klaunch_kt_batch(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtParams &p) {
+    LAUNCH("k_kt_batch", st); BIG_LDS(); kt_ptrs(W, tb, p);
+    note("%s %s nr=%d dec=%d lg=%d w=%u %s", W, sname(st), nr, dec, lg, wgs, kt_txt(p).c_str());
+    return hipSuccess;
+}
+hipError_t klaunch_kt_wire(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireParams &p) {
+    LAUNCH("k_kt_wire", st); BIG_LDS(); kt_ptrs(W, tb, p.k);
+    note("%s %s nr=%d dec=%d lg=%d w=%u %s %s", W, sname(st), nr, dec, lg, wgs, kt_txt(p.k).c_str(), fmt_txt(p.f).c_str());
+    return hipSuccess;
+}
+// the kernels of the WIREX body: v = the extension, version or kind; x = hi / seq, pn_off (k_kt_srtp: the MKI's length stands there and is logged as mki), hp_slots
+static hipError_t wirex_launch(const char *what, bool three, unsigned v, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p, bool srtp = false) {
+    LAUNCH(what, st); BIG_LDS(); kt_ptrs(W, tb, p.w.k); P(p.seq);
+    if (three) { P(p.pn_off); P(p.hp_slots); }
+    note("%s %s v=%u nr=%d dec=%d lg=%d w=%u %s %s x=%s mki=%u", W, sname(st), v, nr, dec, lg, wgs, kt_txt(p.w.k).c_str(), fmt_txt(p.w.f).c_str(),
+         bits(p.seq, srtp ? nullptr : p.pn_off, p.hp_slots).c_str(), srtp ? p.mki_len : 0u);
+    return hipSuccess;
+}
+hipError_t klaunch_kt_wirex(unsigned ext, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) { return wirex_launch("k_kt_wirex", false, ext, nr, dec, lg, wgs, st, tb, p); }
+hipError_t klaunch_kt_tls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) { return wirex_launch("k_kt_tls", false, version, nr, dec, lg, wgs, st, tb, p); }
+hipError_t klaunch_kt_quic(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) { return wirex_launch("k_kt_quic", true, 0, nr, dec, lg, wgs, st, tb, p); }
+hipError_t klaunch_kt_dtls(unsigned version, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) {
+    return wirex_launch("k_kt_dtls", version == AESGCM_DTLS_13, version, nr, dec, lg, wgs, st, tb, p);
+}
+hipError_t klaunch_kt_srtp(unsigned kind, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p) { return wirex_launch("k_kt_srtp", false, kind, nr, dec, lg, wgs, st, tb, p, true); }
+static hipError_t mask_launch(const char *what, int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) {
+    LAUNCH(what, st); P(tb); P(p.in); P(p.out); P(p.pkt_off); P(p.slots); P(p.hp_slots); P(p.pn_off); P(p.pn); P(p.pn_out); P(p.tab);
+    note("%s %s nr=%d dec=%d p=%s n=%u slots=%u", W, sname(st), nr, dec, bits(p.in, p.out, p.pkt_off, p.slots, p.hp_slots, p.pn_off, p.pn, p.pn_out, p.tab).c_str(), p.n_pkts, p.n_slots);
+    return hipSuccess;
+}
+hipError_t klaunch_kt_quic_hp(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) { return mask_launch("k_kt_quic_hp", nr, dec, st, tb, p); }
+hipError_t klaunch_kt_dtls_sn(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p) { return mask_launch("k_kt_dtls_sn", nr, dec, st, tb, p); }
+static std::string rx_txt(const RxTable &t) {
+    char b[96];
+    snprintf(b, sizeof b, "t=%s wins=%u W=%u stride=%u", bits(t.state, t.status).c_str(), t.n_wins, t.window, t.stride);
+    return b;
+}
+hipError_t klaunch_rxwin_recover(hipStream_t st, const RxRecoverParams &p) {
+    LAUNCH("k_rxwin_recover", st); P(p.t.state); P(p.t.status); P(p.win); P(p.in); P(p.pkt_off); P(p.num_out); P(p.hi_out);
+    note("%s %s %s rule=%u off=%u len=%u flags=%u p=%s n=%u", W, sname(st), rx_txt(p.t).c_str(), p.f.rule, p.f.num_off, p.f.num_len, p.f.flags,
+         bits(p.win, p.in, p.pkt_off, p.num_out, p.hi_out).c_str(), p.n_pkts);
+    return hipSuccess;
+}
+hipError_t klaunch_rxwin_commit(hipStream_t st, const RxCommitParams &p) {
+    LAUNCH("k_rxwin_commit*", st); P(p.t.state); P(p.t.status); P(p.win); P(p.num); P(p.auth); P(p.accept); P(p.why);
+    note("%s %s %s p=%s n=%u", W, sname(st), rx_txt(p.t).c_str(), bits(p.win, p.num, p.auth, p.accept, p.why).c_str(), p.n_pkts);
     return hipSuccess;
 }
 

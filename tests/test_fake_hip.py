@@ -58,6 +58,50 @@ def test_launch_plan_is_the_recorded_one():
     assert len(got) == len(want), "the log has %d lines, the fixture %d; the first one without a partner: %s" % (len(got), len(want), (got + want)[min(len(got), len(want))])
 
 
+@pytest.mark.parametrize("so,line", [("libaesgcm_fake.so", "FAKE CAPTURE OK ("), ("libaesgcm_fake_dbg.so", "FAKE CAPTURE OK (forced order: ")])
+def test_captured_calls_keep_capture_discipline_on_the_fake_runtime(so, line):
+    """tests/fake_hip/capture_drive.py: every key-table call, recover and commit, the receive loop and the five-array batch calls, once as an ordinary warm-up call and
+    once while the caller's (fake) stream captures, at 300 packets and -- where the library's rule orders the launch -- at 262 144; on the debug-knob build with
+    batch_order forced at 300.  Under capture: no hipMalloc / hipFree, no synchronous copy or memset, no host synchronisation, no wait from outside on an event the
+    capture recorded (each would be reported with the HIP call's name); the launch log is the warm-up's, except that a captured call is never ordered (no k_len_*
+    launch, no perm); ordinary ordered calls afterwards, one per order slot, are clean.  Without the guard in batch_plan the first ordered case fails with
+    "hipMalloc while a stream is capturing"."""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s", "libaesgcm_fake.so", "dbg"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, AESGCM_LIB=os.path.join(d, so))
+    out = subprocess.run([sys.executable, os.path.join(d, "capture_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert out.returncode == 0 and line in out.stdout and " 0 ordered calls" not in out.stdout, out.stdout[-3000:]
+
+
+def test_the_fake_runtime_reports_what_a_capture_cannot_carry():
+    """the detector itself, through the fake runtime's own entry points: each offending call made while a stream captures is listed by name, a clean capture lists
+    nothing, and a wait from outside on an event that a capture recorded is listed after the capture has ended as well"""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"))
+    out = subprocess.run([sys.executable, os.path.join(d, "capture_drive.py"), "--selftest"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert out.returncode == 0 and "FAKE CAPTURE SELFTEST OK" in out.stdout, out.stdout[-3000:]
+
+
+def test_the_host_side_loads_over_a_runtime_without_stream_capture():
+    """the host side needs hipStreamIsCapturing only to drop the order of a captured call: its reference is weak, in both builds, so a HIP runtime (or a fake one) that
+    has no stream capture still loads the library -- an undefined strong reference fails the load of every entry point, not only of the ordered calls"""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s", "libaesgcm_fake.so", "dbg"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    for o in ("host.o", "host.dbg.o"):
+        syms = subprocess.run(["nm", os.path.join(d, o)], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()
+        kinds = [s.split()[-2] for s in syms if s.split()[-1] == "hipStreamIsCapturing"]
+        assert kinds == ["w"], (o, kinds)
+        for other in ("hipStreamWaitEvent", "hipMemsetAsync"):                    # the check tells weak from strong
+            assert [s.split()[-2] for s in syms if s.split()[-1] == other] == ["U"], (o, other)
+
+
 def test_bench_single_process_queues_its_messages_without_a_host_sync_per_message():
     """bench.py --gpus 4 --single-process (the fallback of the N-rank launch on a box where RCCL comes up inside one process only) over the fake runtime: the line is
     printed, no call leaves its device, and the number of host synchronisations does not grow with the number of timed steps -- the messages of a step are
