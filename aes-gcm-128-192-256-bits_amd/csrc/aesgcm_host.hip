@@ -458,6 +458,67 @@ int grow(unsigned char **p, size_t *cap, size_t need) {
     return AESGCM_OK;
 }
 
+// ---------------------------------------------------------------- device tables (aesgcm_internal.h, DevTable)
+int devtab_create(DevTable *b, int device, size_t state_bytes, void **state, const char *who) {
+    DeviceState *ds;
+    int rc = device_state(device, &ds);            // (AESGCM_EHIP without a device)
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    b->device = device;
+    hipError_t e = hipMalloc(state, state_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&b->status, sizeof(u32));
+    if (e == hipSuccess) e = hipMemset(*state, 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(b->status, 0xFF, sizeof(u32));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (*state) (void)hipFree(*state);
+        if (b->status) (void)hipFree(b->status);
+        *state = nullptr; b->status = nullptr;
+        return e == hipErrorOutOfMemory ? AESGCM_ENOMEM : hip_fail(e, who);
+    }
+    return AESGCM_OK;
+}
+
+int devtab_stage(DevTable *b, size_t bytes, hipStream_t st) {
+    if (bytes > b->stage_cap) {
+        if (b->stage) { HIPCHK(hipFree(b->stage)); b->stage = nullptr; b->stage_cap = 0; }   // hipFree waits for the launches and copies that may still read it
+        const hipError_t e = hipMalloc((void **)&b->stage, bytes);
+        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+        b->stage_cap = bytes;
+    }
+    if (!b->stage_done) HIPCHK(hipEventCreateWithFlags(&b->stage_done, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent(st, b->stage_done, 0));
+    return AESGCM_OK;
+}
+
+int devtab_status(DevTable *b, int *code, uint64_t *detail) {
+    HIPCHK(hipSetDevice(b->device));
+    u32 w = ~0u;
+    HIPCHK(hipMemcpy(&w, b->status, sizeof w, hipMemcpyDeviceToHost));
+    *code = w == ~0u ? AESGCM_OK : AESGCM_EARG;
+    if (detail) *detail = w == ~0u ? 0 : w;
+    if (w != ~0u) HIPCHK(hipMemset(b->status, 0xFF, sizeof(u32)));
+    return AESGCM_OK;
+}
+
+int devtab_destroy(DevTable *b, void *state, size_t wipe_bytes, const char *who) {
+    int rc = AESGCM_OK;
+    hipError_t e = hipSetDevice(b->device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();                       // calls in flight may still use the state
+    if (wipe_bytes) {
+        if (e == hipSuccess) e = hipMemset(state, 0, wipe_bytes);
+        if (e == hipSuccess && b->stage) e = hipMemset(b->stage, 0, b->stage_cap);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess) rc = hip_fail(e, who);
+    (void)hipFree(state);
+    (void)hipFree(b->status);
+    if (b->stage) (void)hipFree(b->stage);
+    if (b->stage_done) (void)hipEventDestroy(b->stage_done);
+    return rc;
+}
+
 
 // Key material of a context from a key (or a pre-expanded schedule): aes_kexp, H, the H-power tables -- k_setup and k_setup_ptab on the context's stream, waited
 // for.  The staging buffer for the key bytes belongs to the context (aesgcm_ctx_rekey comes through here without an allocation) and is wiped behind the kernels.

@@ -253,6 +253,29 @@ void pipeline_release(aesgcm_ctx *c);
 int pipeline_prepare(aesgcm_ctx *c, size_t chunk);
 int crypt_pipelined(aesgcm_ctx *c, int dec, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out, uint8_t tag[16], size_t chunk);
 
+// ---------------------------------------------------------------- device tables: what the host sides of a key table (aesgcm_keytab.hip) and of receive windows
+// (aesgcm_rxwin.hip) share.  A table is one device allocation of state (slots, window records), a status word that its kernels lower to the first entry they refuse,
+// and a staging buffer through which host data reaches the state.  Each table struct holds a DevTable beside its own fields.
+struct DevTable {
+    int device = 0;
+    u32 *status = nullptr;             // device: the lowest refused packet (or set entry) since the last devtab_status, ~0 = none
+    unsigned char *stage = nullptr;    // device: host data waits here for its way into the state
+    size_t stage_cap = 0;
+    hipEvent_t stage_done = nullptr;   // behind the last use of `stage`, on whichever stream it ran
+    std::mutex mu;
+};
+// the table's state (state_bytes, zeroed, into *state) and its status word on `device`, waited for; on failure nothing is left allocated: AESGCM_ENOMEM, or
+// AESGCM_EHIP with `who` in the message (without a device: from device_state)
+int devtab_create(DevTable *b, int device, size_t state_bytes, void **state, const char *who);
+// `bytes` of the staging buffer for a host-to-device copy on `st`, behind the buffer's previous user on whatever stream that ran; the caller holds b->mu and
+// records b->stage_done behind its own last use
+int devtab_stage(DevTable *b, size_t bytes, hipStream_t st);
+int devtab_status(DevTable *b, int *code, uint64_t *detail);          // read and clear; the caller has checked its pointers
+// waits for the device, then frees the state, the status word, the stage and the event.  wipe_bytes != 0: that much of the state and the whole stage are zeroed
+// first, and waited for (a key table: both held key material)
+int devtab_destroy(DevTable *b, void *state, size_t wipe_bytes, const char *who);
+static inline bool devtab_in_range(size_t first, size_t n, size_t total) { return first < total && n <= total - first; }
+
 #ifdef AESGCM_DEBUG_KNOBS
 struct ForceShape { int pkt_lanes, pkt_deal, batch_lanes, batch_deal, batch_order, pkt_ilp, pkt_rows; };
 extern ForceShape g_force;

@@ -1,6 +1,7 @@
 // aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_<family>_kernels.hip, one source per family.
-// A table is one device allocation of n_slots KtSlot records (aesgcm_keytab.h) and a status word.  Host data reaches the slots through the table's staging buffer
-// (kt_stage_set): keys by k_kt_setup, the other fields (salt, XPN state, TLS IV) by strided copies.  A crypt call is one launch of a kernel that runs k_batch3's body,
+// A table is a DevTable (aesgcm_internal.h: create, the staging buffer, status, destroy, the range check; defined in aesgcm_host.hip) whose state is n_slots KtSlot
+// records (aesgcm_keytab.h).  Host data reaches the slots through the staging buffer, zeroed behind every use (kt_stage_set): keys by k_kt_setup, the other fields
+// (salt, XPN state, TLS IV) by strided copies.  A crypt call is one launch of a kernel that runs k_batch3's body,
 // planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.
 //   family   entry point                          kernel       the format's cut (aesgcm_wirecut.h)
 //   keytab   aesgcm_keytab_crypt_dev              k_kt_batch   -                       packets as five arrays
@@ -17,39 +18,19 @@
 #include <string.h>
 
 struct aesgcm_keytab {
-    int device = 0;
+    DevTable base;                     // base.stage: host keys wait there for k_kt_setup, zeroed behind it on the same stream; base.stage_done: behind that zeroing
     int nr = 0;
     size_t key_len = 0, n_slots = 0;
     KtSlot *tab = nullptr;
-    u32 *status = nullptr;             // device: the lowest refused packet (or set entry) since the last aesgcm_keytab_status, ~0 = none
-    unsigned char *stage = nullptr;    // device: host keys wait here for k_kt_setup; zeroed behind it on the same stream
-    size_t stage_cap = 0;
-    hipEvent_t stage_done = nullptr;   // behind the last zeroing of `stage`, on whichever stream it ran
-    std::mutex mu;
 };
-
-// `bytes` of the table's staging buffer for a host-to-device copy on `st`, behind the buffer's previous user on whatever stream that ran; the caller holds t->mu and
-// records t->stage_done behind its own last use
-static int kt_stage(aesgcm_keytab *t, size_t bytes, hipStream_t st) {
-    if (bytes > t->stage_cap) {
-        if (t->stage) { HIPCHK(hipFree(t->stage)); t->stage = nullptr; t->stage_cap = 0; }   // hipFree waits for the launches that may still read it
-        const hipError_t e = hipMalloc((void **)&t->stage, bytes);
-        if (e == hipErrorOutOfMemory) return AESGCM_ENOMEM;
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-        t->stage_cap = bytes;
-    }
-    if (!t->stage_done) HIPCHK(hipEventCreateWithFlags(&t->stage_done, hipEventDisableTiming));
-    else HIPCHK(hipStreamWaitEvent(st, t->stage_done, 0));
-    return AESGCM_OK;
-}
 
 static int kt_setup(aesgcm_keytab *t, const unsigned char *d_keys, const u32 *d_slots, size_t first, size_t n, hipStream_t st) {
     DeviceState *ds;
-    int rc = device_state(t->device, &ds);
+    int rc = device_state(t->base.device, &ds);
     if (rc) return rc;
-    if ((rc = set_lds_attrs(t->device, ds))) return rc;
+    if ((rc = set_lds_attrs(t->base.device, ds))) return rc;
     KtSetupParams s;
-    s.keys = d_keys; s.slots = d_slots; s.first = (u32)first; s.n = (u32)n; s.n_slots = (u32)t->n_slots; s.tab = t->tab; s.status = t->status;
+    s.keys = d_keys; s.slots = d_slots; s.first = (u32)first; s.n = (u32)n; s.n_slots = (u32)t->n_slots; s.tab = t->tab; s.status = t->base.status;
     HIPCHK(klaunch_kt_setup(t->nr, st, ds->tables, s));
     return AESGCM_OK;
 }
@@ -58,49 +39,37 @@ int aesgcm_keytab_create(aesgcm_keytab **out, int device, size_t key_len, size_t
     if (!out) return AESGCM_EARG;
     *out = nullptr;
     if ((key_len != 16 && key_len != 24 && key_len != 32) || !n_slots || n_slots >= ((size_t)1 << 31)) return AESGCM_EARG;
-    DeviceState *ds;
-    int rc = device_state(device, &ds);            // (AESGCM_EHIP without a device)
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(device));
     aesgcm_keytab *t = new aesgcm_keytab();
-    t->device = device; t->key_len = key_len; t->n_slots = n_slots; t->nr = (int)(key_len / 4 + 6);
-    hipError_t e = hipMalloc((void **)&t->tab, n_slots * sizeof(KtSlot));
-    if (e == hipSuccess) e = hipMalloc((void **)&t->status, sizeof(u32));
-    if (e == hipSuccess) e = hipMemset(t->tab, 0, n_slots * sizeof(KtSlot));
-    if (e == hipSuccess) e = hipMemset(t->status, 0xFF, sizeof(u32));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        if (t->tab) (void)hipFree(t->tab);
-        if (t->status) (void)hipFree(t->status);
-        delete t;
-        return e == hipErrorOutOfMemory ? AESGCM_ENOMEM : hip_fail(e, "aesgcm_keytab_create");
-    }
+    t->key_len = key_len; t->n_slots = n_slots; t->nr = (int)(key_len / 4 + 6);
+    const int rc = devtab_create(&t->base, device, n_slots * sizeof(KtSlot), (void **)&t->tab, "aesgcm_keytab_create");
+    if (rc) { delete t; return rc; }
     *out = t;
     return AESGCM_OK;
 }
 
-// What every host-to-slot setter does, under t->mu: `parts` side by side through the table's staging buffer on `st` -- the host copies into the stage, `into_slots` (the
-// expansion kernel, or a strided copy per part) from there into the slots, the stage zeroed behind it whatever into_slots returned (raw key material does not outlive
-// the call), t->stage_done recorded.  The caller has checked its arguments.
+// What every host-to-slot setter does, under the base's mutex: `parts` side by side through the table's staging buffer (devtab_stage) on `st` -- the host copies into the
+// stage, `into_slots` (the expansion kernel, or a strided copy per part) from there into the slots, the stage zeroed behind it whatever into_slots returned (raw key
+// material does not outlive the call), the stage's event recorded.  The caller has checked its arguments.
 struct KtPart {
     const uint8_t *src;                // host: n * width bytes; NULL = the field becomes zero (nothing staged)
     size_t width, field;               // bytes per slot; offset inside KtSlot
 };
 template <size_t N, class F>
 static int kt_stage_set(aesgcm_keytab *t, size_t n, const KtPart (&parts)[N], hipStream_t st, F into_slots) {
-    std::lock_guard<std::mutex> lk(t->mu);
-    HIPCHK(hipSetDevice(t->device));
+    DevTable &b = t->base;
+    std::lock_guard<std::mutex> lk(b.mu);
+    HIPCHK(hipSetDevice(b.device));
     size_t bytes = 0;
     for (const KtPart &p : parts) if (p.src) bytes += n * p.width;
-    int rc = kt_stage(t, bytes, st);                                            // (behind the previous set's kernel and zeroing)
+    int rc = devtab_stage(&b, bytes, st);                                       // (behind the previous set's kernel and zeroing)
     if (rc) return rc;
     size_t at = 0;
-    for (const KtPart &p : parts) if (p.src) { HIPCHK(hipMemcpyAsync(t->stage + at, p.src, n * p.width, hipMemcpyHostToDevice, st)); at += n * p.width; }
+    for (const KtPart &p : parts) if (p.src) { HIPCHK(hipMemcpyAsync(b.stage + at, p.src, n * p.width, hipMemcpyHostToDevice, st)); at += n * p.width; }
     rc = into_slots();
-    const hipError_t ez = hipMemsetAsync(t->stage, 0, bytes, st);
+    const hipError_t ez = hipMemsetAsync(b.stage, 0, bytes, st);
     if (rc) return rc;
     HIPCHK(ez);
-    HIPCHK(hipEventRecord(t->stage_done, st));
+    HIPCHK(hipEventRecord(b.stage_done, st));
     return AESGCM_OK;
 }
 
@@ -111,7 +80,7 @@ static int kt_set_fields(aesgcm_keytab *t, size_t first_slot, size_t n, const Kt
         size_t at = 0;
         for (const KtPart &p : parts) {
             unsigned char *const dst = (unsigned char *)(t->tab + first_slot) + p.field;
-            if (p.src) { HIPCHK(hipMemcpy2DAsync(dst, sizeof(KtSlot), t->stage + at, p.width, p.width, n, hipMemcpyDeviceToDevice, st)); at += n * p.width; }
+            if (p.src) { HIPCHK(hipMemcpy2DAsync(dst, sizeof(KtSlot), t->base.stage + at, p.width, p.width, n, hipMemcpyDeviceToDevice, st)); at += n * p.width; }
             else HIPCHK(hipMemset2DAsync(dst, sizeof(KtSlot), 0, p.width, n, st));
         }
         return AESGCM_OK;
@@ -121,25 +90,25 @@ static int kt_set_fields(aesgcm_keytab *t, size_t first_slot, size_t n, const Kt
 int aesgcm_keytab_set(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *keys, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
-    if (!keys || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    if (!keys || !devtab_in_range(first_slot, n, t->n_slots)) return AESGCM_EARG;
     hipStream_t st = (hipStream_t)stream;
     const KtPart parts[] = {{keys, t->key_len, 0}};
-    return kt_stage_set(t, n, parts, st, [&] { return kt_setup(t, t->stage, nullptr, first_slot, n, st); });
+    return kt_stage_set(t, n, parts, st, [&] { return kt_setup(t, t->base.stage, nullptr, first_slot, n, st); });
 }
 
 int aesgcm_keytab_set_dev(aesgcm_keytab *t, size_t n, const uint32_t *d_slots, const void *d_keys, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!d_slots || !d_keys || n >= ((size_t)1 << 31)) return AESGCM_EARG;
-    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipSetDevice(t->base.device));
     return kt_setup(t, (const unsigned char *)d_keys, d_slots, 0, n, (hipStream_t)stream);
 }
 
 int aesgcm_keytab_clear(aesgcm_keytab *t, size_t first_slot, size_t n, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
-    if (first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
-    HIPCHK(hipSetDevice(t->device));
+    if (!devtab_in_range(first_slot, n, t->n_slots)) return AESGCM_EARG;
+    HIPCHK(hipSetDevice(t->base.device));
     HIPCHK(hipMemsetAsync(t->tab + first_slot, 0, n * sizeof(KtSlot), (hipStream_t)stream));
     return AESGCM_OK;
 }
@@ -166,9 +135,9 @@ int aesgcm_keytab_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const 
     else if (!var) { p.aad = aad_len ? (const unsigned char *)d_aad : nullptr; p.aad_len = (u32)aad_len; }
     p.pkt_len = var ? 0u : (u32)pkt_len;
     p.aligned = (var || pkt_len % 16 == 0) && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;     // offset arrays: and the packet's offset is a multiple of 16
-    kp.slots = d_slots; kp.tab = t->tab; kp.n_slots = (u32)t->n_slots; kp.status = t->status;
+    kp.slots = d_slots; kp.tab = t->tab; kp.n_slots = (u32)t->n_slots; kp.status = t->base.status;
     BatchPlan b;
-    const int rc = batch_plan(t->device, decrypt, n_pkts, t->key_len, p, stream, b);
+    const int rc = batch_plan(t->base.device, decrypt, n_pkts, t->key_len, p, stream, b);
     if (rc) return rc;
     HIPCHK(klaunch_kt_batch(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, kp));
     return batch_done(b, p);
@@ -189,7 +158,7 @@ int aesgcm_wire_fmt_check(const aesgcm_wire_fmt *f) {
 int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
-    if (!salts || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    if (!salts || !devtab_in_range(first_slot, n, t->n_slots)) return AESGCM_EARG;
     const KtPart parts[] = {{salts, 8, offsetof(KtSlot, salt)}};
     return kt_set_fields(t, first_slot, n, parts, (hipStream_t)stream);
 }
@@ -198,7 +167,7 @@ int aesgcm_keytab_set_salt(aesgcm_keytab *t, size_t first_slot, size_t n, const 
 int aesgcm_keytab_set_xpn(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *salts, const uint8_t *sscis, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
-    if (!salts || !sscis || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    if (!salts || !sscis || !devtab_in_range(first_slot, n, t->n_slots)) return AESGCM_EARG;
     const KtPart parts[] = {{salts, 12, offsetof(KtSlot, xpn)}, {sscis, 4, offsetof(KtSlot, xpn) + 12}};
     return kt_set_fields(t, first_slot, n, parts, (hipStream_t)stream);
 }
@@ -241,7 +210,7 @@ static int kt_wire_crypt(aesgcm_keytab *t, int decrypt, size_t n, bool own_ok, c
     p.auth = decrypt ? d_auth : nullptr;
     p.data_off = d_off;
     p.aligned = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;                // ... and the payload's offset is a multiple of 16 (per packet, in the kernel)
-    xp.w.k.slots = d_slots; xp.w.k.tab = t->tab; xp.w.k.n_slots = (u32)t->n_slots; xp.w.k.status = t->status;
+    xp.w.k.slots = d_slots; xp.w.k.tab = t->tab; xp.w.k.n_slots = (u32)t->n_slots; xp.w.k.status = t->base.status;
     KtQuicHpParams m = {};
     if (mask) {
         xp.seq = decrypt ? mask->d_pn_out : mask->d_pn;
@@ -250,7 +219,7 @@ static int kt_wire_crypt(aesgcm_keytab *t, int decrypt, size_t n, bool own_ok, c
         m.pn = mask->d_pn; m.pn_out = decrypt ? mask->d_pn_out : nullptr; m.tab = t->tab; m.n_pkts = (u32)n; m.n_slots = (u32)t->n_slots;
     }
     BatchPlan b;
-    const int rc = batch_plan(t->device, decrypt, n, t->key_len, p, stream, b);
+    const int rc = batch_plan(t->base.device, decrypt, n, t->key_len, p, stream, b);
     if (rc) return rc;
     if (mask && decrypt) HIPCHK(mask->launch(b.nr, 1, b.st, b.tables, m));
     HIPCHK(aead(b, xp));
@@ -294,7 +263,7 @@ int aesgcm_tls_fmt_check(const aesgcm_tls_fmt *f) {
 int aesgcm_keytab_set_tls_iv(aesgcm_keytab *t, size_t first_slot, size_t n, const uint8_t *ivs, void *stream) {
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
-    if (!ivs || first_slot >= t->n_slots || n > t->n_slots - first_slot) return AESGCM_EARG;
+    if (!ivs || !devtab_in_range(first_slot, n, t->n_slots)) return AESGCM_EARG;
     const KtPart parts[] = {{ivs, 12, offsetof(KtSlot, xpn)}, {nullptr, 4, offsetof(KtSlot, xpn) + 12}};
     return kt_set_fields(t, first_slot, n, parts, (hipStream_t)stream);
 }
@@ -370,28 +339,12 @@ int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srt
 
 int aesgcm_keytab_status(aesgcm_keytab *t, int *code, uint64_t *detail) {
     if (!t || !code) return AESGCM_EARG;
-    HIPCHK(hipSetDevice(t->device));
-    u32 w = ~0u;
-    HIPCHK(hipMemcpy(&w, t->status, sizeof w, hipMemcpyDeviceToHost));
-    *code = w == ~0u ? AESGCM_OK : AESGCM_EARG;
-    if (detail) *detail = w == ~0u ? 0 : w;
-    if (w != ~0u) HIPCHK(hipMemset(t->status, 0xFF, sizeof(u32)));
-    return AESGCM_OK;
+    return devtab_status(&t->base, code, detail);
 }
 
 int aesgcm_keytab_destroy(aesgcm_keytab *t) {
     if (!t) return AESGCM_OK;
-    int rc = AESGCM_OK;
-    hipError_t e = hipSetDevice(t->device);
-    if (e == hipSuccess) e = hipDeviceSynchronize();                       // calls in flight may still read the slots
-    if (e == hipSuccess) e = hipMemset(t->tab, 0, t->n_slots * sizeof(KtSlot));
-    if (e == hipSuccess && t->stage) e = hipMemset(t->stage, 0, t->stage_cap);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) rc = hip_fail(e, "aesgcm_keytab_destroy");
-    (void)hipFree(t->tab);
-    (void)hipFree(t->status);
-    if (t->stage) (void)hipFree(t->stage);
-    if (t->stage_done) (void)hipEventDestroy(t->stage_done);
+    const int rc = devtab_destroy(&t->base, t->tab, t->n_slots * sizeof(KtSlot), "aesgcm_keytab_destroy");      // the slots and the stage wiped: both held key material
     delete t;
     return rc;
 }

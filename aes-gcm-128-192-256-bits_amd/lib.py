@@ -736,13 +736,27 @@ def _keytab_typed(L):
     return L
 
 
+class _Format:
+    """what the format structs share: check() through the C symbol the class names in _check (typed on first use by _typed), and the repr of the fields by name"""
+    _typed = staticmethod(_keytab_typed)
+
+    def check(self):
+        """aesgcm_*_fmt_check -> OK or EARG (no device needed)"""
+        return getattr(self._typed(load()), self._check)(ctypes.byref(self))
+
+    def __repr__(self):
+        vals = [(f, getattr(self, f)) for f, _ in self._fields_]
+        return "%s(%s)" % (type(self).__name__, ", ".join("%s=%d" % fv if isinstance(fv[1], int) else repr(fv[1]) for fv in vals))      # a nested format: positionally
+
+
 WIRE_AUTH_ONLY = 1      # AESGCM_WIRE_AUTH_ONLY
 
 
-class WireFormat(ctypes.Structure):
+class WireFormat(_Format, ctypes.Structure):
     """aesgcm_wire_fmt: how a frame header | payload | ICV is laid out (include/aesgcm.h "frames in WIRE FORMAT")"""
     _fields_ = [("aad_len", ctypes.c_uint32), ("hdr_len", ctypes.c_uint32), ("iv_off", ctypes.c_uint32), ("salt_len", ctypes.c_uint32),
                 ("tag_len", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+    _check = "aesgcm_wire_fmt_check"
 
     @classmethod
     def macsec(cls, sci=True, auth_only=False):
@@ -755,21 +769,15 @@ class WireFormat(ctypes.Structure):
         """RFC 4106: SPI, sequence number | 8-byte IV field | payload | ICV of 16, 12 or 8 bytes; the slot's salt = the SA's 4-byte salt"""
         return cls(8, 16, 8, 4, tag_len, 0)
 
-    def check(self):
-        """aesgcm_wire_fmt_check -> OK or EARG (no device needed)"""
-        return _keytab_typed(load()).aesgcm_wire_fmt_check(ctypes.byref(self))
-
-    def __repr__(self):
-        return "WireFormat(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
-
 
 WIREX_XPN = 1           # AESGCM_WIREX_XPN
 WIREX_ESN = 2           # AESGCM_WIREX_ESN
 
 
-class WireFormatX(ctypes.Structure):
+class WireFormatX(_Format, ctypes.Structure):
     """aesgcm_wire_xfmt: a WireFormat and what the 32-bit number per frame that is not on the wire does (include/aesgcm.h "wire frames with 64-BIT NUMBERS")"""
     _fields_ = [("f", WireFormat), ("ext", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+    _check = "aesgcm_wire_xfmt_check"
 
     @classmethod
     def macsec_xpn(cls, sci=True, auth_only=False):
@@ -781,21 +789,15 @@ class WireFormatX(ctypes.Structure):
         """RFC 4303 / RFC 4106 section 5: an ESP frame whose AAD is SPI | seq-hi | seq-lo; hi = seq-hi, which is never transmitted"""
         return cls(WireFormat.esp(tag_len), WIREX_ESN, 0)
 
-    def check(self):
-        """aesgcm_wire_xfmt_check -> OK or EARG (no device needed)"""
-        return _keytab_typed(load()).aesgcm_wire_xfmt_check(ctypes.byref(self))
-
-    def __repr__(self):
-        return "WireFormatX(%r, ext=%d, reserved=%d)" % (self.f, self.ext, self.reserved)
-
 
 TLS_13 = 1              # AESGCM_TLS_13
 TLS_12 = 2              # AESGCM_TLS_12
 
 
-class TlsFormat(ctypes.Structure):
+class TlsFormat(_Format, ctypes.Structure):
     """aesgcm_tls_fmt: which TLS record header | ciphertext | tag a records call takes (include/aesgcm.h "TLS RECORDS")"""
     _fields_ = [("version", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+    _check = "aesgcm_tls_fmt_check"
 
     @classmethod
     def tls13(cls):
@@ -807,21 +809,15 @@ class TlsFormat(ctypes.Structure):
         """RFC 5288: hdr[5] | explicit nonce[8] | payload | tag[16]; nonce = the slot IV's four bytes | explicit nonce, AAD = seq | type, version | payload length"""
         return cls(TLS_12, 0)
 
-    def check(self):
-        """aesgcm_tls_fmt_check -> OK or EARG (no device needed)"""
-        return _keytab_typed(load()).aesgcm_tls_fmt_check(ctypes.byref(self))
-
-    def __repr__(self):
-        return "TlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
-
 
 DTLS_13 = 1             # AESGCM_DTLS_13
 DTLS_12 = 2             # AESGCM_DTLS_12
 
 
-class DtlsFormat(ctypes.Structure):
+class DtlsFormat(_Format, ctypes.Structure):
     """aesgcm_dtls_fmt: which DTLS record a dtls call takes (include/aesgcm.h "DTLS RECORDS")"""
     _fields_ = [("version", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+    _check = "aesgcm_dtls_fmt_check"
 
     @classmethod
     def dtls13(cls):
@@ -835,21 +831,15 @@ class DtlsFormat(ctypes.Structure):
         the record) | type, version | payload length"""
         return cls(DTLS_12, 0)
 
-    def check(self):
-        """aesgcm_dtls_fmt_check -> OK or EARG (no device needed)"""
-        return _keytab_typed(load()).aesgcm_dtls_fmt_check(ctypes.byref(self))
-
-    def __repr__(self):
-        return "DtlsFormat(version=%d, reserved=%d)" % (self.version, self.reserved)
-
 
 SRTP_RTP = 1            # AESGCM_SRTP_RTP
 SRTP_RTCP = 2           # AESGCM_SRTP_RTCP
 
 
-class SrtpFormat(ctypes.Structure):
+class SrtpFormat(_Format, ctypes.Structure):
     """aesgcm_srtp_fmt: which packet an srtp call takes and how many bytes of MKI end it (include/aesgcm.h "SRTP AND SRTCP PACKETS")"""
     _fields_ = [("kind", ctypes.c_uint32), ("mki_len", ctypes.c_uint32)]
+    _check = "aesgcm_srtp_fmt_check"
 
     @classmethod
     def rtp(cls, mki_len=0):
@@ -863,13 +853,6 @@ class SrtpFormat(ctypes.Structure):
         with E clear everything in front of the tag | W"""
         return cls(SRTP_RTCP, mki_len)
 
-    def check(self):
-        """aesgcm_srtp_fmt_check -> OK or EARG (no device needed)"""
-        return _keytab_typed(load()).aesgcm_srtp_fmt_check(ctypes.byref(self))
-
-    def __repr__(self):
-        return "SrtpFormat(kind=%d, mki_len=%d)" % (self.kind, self.mki_len)
-
 
 def _per_slot(x, width, what, pad=False):
     """a setter's host data: one bytes-like of n * width bytes, or a list of n items (pad: shorter ones zero-padded to width) -> (bytes, n)"""
@@ -880,24 +863,51 @@ def _per_slot(x, width, what, pad=False):
     return b, len(b) // width
 
 
-class KeyTable:
-    """aesgcm_keytab: n_slots device-resident slots of one key size; the key schedule, H and its powers are computed on the GPU once per `set`, and a crypt call
-    names a slot per packet (include/aesgcm.h "key tables").  Belongs to the library that made it (create it inside a debug_library block to force shapes)."""
+def _joined(items):
+    """a byte string per packet -> (the packets side by side, their n + 1 offsets)"""
+    off = [0]
+    for x in items:
+        off.append(off[-1] + len(x))
+    return b"".join(bytes(x) for x in items), off
 
-    def __init__(self, key_len, n_slots, device=0):
-        self._t = None
-        L = _keytab_typed(load())
-        t = vp()
-        _chk(L.aesgcm_keytab_create(ctypes.byref(t), device, key_len, n_slots))
-        self._t, self._lib = t.value, L
-        self.key_len, self.n_slots, self.device = key_len, n_slots, device
 
-    _lib = None
+def _device_call(device, up, down, call):
+    """What the tables' host conveniences share.  Every entry of `up` -- name: bytes, or (struct code, values) -- uploaded into a DeviceBuffer of its name; every entry
+    of `down` -- name: (struct code, count) of the values that come back -- allocated (a name in both is one buffer); then call(bufs) over the DeviceBuffers by name, a
+    device sync and the downloads.  -> {name: list of count values}"""
+    up = {k: v if isinstance(v, bytes) else struct.pack("<%d%s" % (len(v[1]), v[0]), *v[1]) for k, v in up.items()}
+    down = {k: (code, count, count * struct.calcsize("<" + code)) for k, (code, count) in down.items()}
+    size = {k: len(v) for k, v in up.items()}
+    for k, (_, _, nb) in down.items():
+        size[k] = max(size.get(k, 0), nb)
+    bufs = {k: DeviceBuffer(max(nb, 16), device) for k, nb in size.items()}
+    try:
+        for k, v in up.items():
+            if v:
+                bufs[k].upload(v)
+        call(bufs)
+        _chk(load().aesgcm_dev_sync(device))
+        return {k: list(struct.unpack("<" + code * count, bytes(bufs[k].download(nb)) if nb else b"")) for k, (code, count, nb) in down.items()}
+    finally:
+        for b in bufs.values():
+            b.free()
+
+
+class _Table:
+    """what KeyTable and RxWindows share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
+    context manager, status()"""
+    _h = _lib = None
+
+    def _create(self, typed, device, *args):
+        L = typed(load())
+        h = vp()
+        _chk(getattr(L, self._prefix + "_create")(ctypes.byref(h), device, *args))
+        self._h, self._lib, self.device = h.value, L, device
 
     def close(self):
-        if self._t:
-            self._lib.aesgcm_keytab_destroy(self._t)
-            self._t = None
+        if self._h:
+            getattr(self._lib, self._prefix + "_destroy")(self._h)
+            self._h = None
 
     __del__ = close
 
@@ -907,38 +917,54 @@ class KeyTable:
     def __exit__(self, *a):
         self.close()
 
+    def status(self):
+        """aesgcm_keytab_status / aesgcm_rxwin_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""
+        code, detail = cint(0), u64(0)
+        _chk(getattr(self._lib, self._prefix + "_status")(self._h, ctypes.byref(code), ctypes.byref(detail)))
+        return code.value, detail.value
+
+
+class KeyTable(_Table):
+    """aesgcm_keytab: n_slots device-resident slots of one key size; the key schedule, H and its powers are computed on the GPU once per `set`, and a crypt call
+    names a slot per packet (include/aesgcm.h "key tables").  Belongs to the library that made it (create it inside a debug_library block to force shapes)."""
+    _prefix = "aesgcm_keytab"
+
+    def __init__(self, key_len, n_slots, device=0):
+        self._create(_keytab_typed, device, key_len, n_slots)
+        self.key_len, self.n_slots = key_len, n_slots
+
     def set(self, first_slot, keys, stream=None):
         """aesgcm_keytab_set: host keys (one bytes-like of n * key_len bytes, or a list of keys) into slots first_slot, first_slot + 1, ..."""
         kb, n = _per_slot(keys, self.key_len, "keys must be a multiple of %d bytes" % self.key_len)
-        _chk(self._lib.aesgcm_keytab_set(self._t, first_slot, n, kb, stream))
+        _chk(self._lib.aesgcm_keytab_set(self._h, first_slot, n, kb, stream))
         return self
 
     def set_dev(self, n, d_slots, d_keys, stream=None):
         """aesgcm_keytab_set_dev: n keys from device memory (n x key_len bytes) into the slots d_slots (n uint32, device memory)"""
-        _chk(self._lib.aesgcm_keytab_set_dev(self._t, n, d_slots, d_keys, stream))
+        _chk(self._lib.aesgcm_keytab_set_dev(self._h, n, d_slots, d_keys, stream))
         return self
 
     def clear(self, first_slot, n=1, stream=None):
         """aesgcm_keytab_clear: retire slots first_slot .. first_slot + n - 1 (zeroed, unset: their packets are refused)"""
-        _chk(self._lib.aesgcm_keytab_clear(self._t, first_slot, n, stream))
+        _chk(self._lib.aesgcm_keytab_clear(self._h, first_slot, n, stream))
         return self
 
     def crypt_dev(self, decrypt, n_pkts, d_slots, d_ivs, d_in, d_data_off, d_out, d_tags, d_aad=None, d_aad_off=None,
                   d_expect_tags=None, d_auth=None, pkt_len=0, aad_len=0, stream=None):
         """aesgcm_keytab_crypt_dev: packet p under slot d_slots[p] (uint32, device memory); the rest as batch_crypt_var_dev.  d_data_off = None: fixed-size
         records of pkt_len bytes (and aad_len bytes of AAD each unless d_aad_off is given)."""
-        _chk(self._lib.aesgcm_keytab_crypt_dev(self._t, int(bool(decrypt)), n_pkts, d_slots, d_ivs, d_aad, aad_len, d_aad_off,
+        _chk(self._lib.aesgcm_keytab_crypt_dev(self._h, int(bool(decrypt)), n_pkts, d_slots, d_ivs, d_aad, aad_len, d_aad_off,
                                                d_in, pkt_len, d_data_off, d_out, d_tags, d_expect_tags, d_auth, stream))
 
     def set_salt(self, first_slot, salts, stream=None):
         """aesgcm_keytab_set_salt: 8 bytes per slot (one bytes-like of n * 8 bytes, or a list; shorter entries are zero-padded) into slots first_slot, ..."""
         sb, n = _per_slot(salts, 8, "a salt is 8 bytes", pad=True)
-        _chk(self._lib.aesgcm_keytab_set_salt(self._t, first_slot, n, sb, stream))
+        _chk(self._lib.aesgcm_keytab_set_salt(self._h, first_slot, n, sb, stream))
         return self
 
     def frames_crypt_dev(self, decrypt, fmt, n_frames, d_slots, d_in, d_frame_off, d_out, d_auth=None, stream=None):
         """aesgcm_keytab_frames_crypt_dev: frame p = bytes [d_frame_off[p], d_frame_off[p + 1]) of d_in / d_out in the wire format fmt, under slot d_slots[p]"""
-        _chk(self._lib.aesgcm_keytab_frames_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream))
+        _chk(self._lib.aesgcm_keytab_frames_crypt_dev(self._h, int(bool(decrypt)), ctypes.byref(fmt), n_frames, d_slots, d_in, d_frame_off, d_out, d_auth, stream))
 
     def set_xpn(self, first_slot, salts, sscis, stream=None):
         """aesgcm_keytab_set_xpn: MACsec XPN's 12-byte salt and 4-byte SSCI per slot (each one bytes-like of n * 12 / n * 4 bytes, or a list) into slots first_slot, ..."""
@@ -946,13 +972,13 @@ class KeyTable:
         (sb, n), (cb, nc) = _per_slot(salts, 12, what), _per_slot(sscis, 4, what)
         if n != nc:
             raise AesGcmError(EARG, what)
-        _chk(self._lib.aesgcm_keytab_set_xpn(self._t, first_slot, n, sb, cb, stream))
+        _chk(self._lib.aesgcm_keytab_set_xpn(self._h, first_slot, n, sb, cb, stream))
         return self
 
     def frames_crypt_x_dev(self, decrypt, xfmt, n_frames, d_slots, d_hi, d_in, d_frame_off, d_out, d_auth=None, stream=None):
         """aesgcm_keytab_frames_crypt_x_dev: frames_crypt_dev in the format xfmt (WireFormatX) with d_hi[p] (uint32, device memory) = the upper half of frame p's
         64-bit packet / sequence number"""
-        _chk(self._lib.aesgcm_keytab_frames_crypt_x_dev(self._t, int(bool(decrypt)), ctypes.byref(xfmt), n_frames, d_slots, d_hi, d_in, d_frame_off, d_out, d_auth, stream))
+        _chk(self._lib.aesgcm_keytab_frames_crypt_x_dev(self._h, int(bool(decrypt)), ctypes.byref(xfmt), n_frames, d_slots, d_hi, d_in, d_frame_off, d_out, d_auth, stream))
 
     def crypt_frames(self, fmt, slots, frames, decrypt=False, hi=None):
         """Host convenience (tests, examples): whole frames (header | payload | ICV; on encrypt the ICV bytes are placeholders) through one call, in place.
@@ -977,13 +1003,13 @@ class KeyTable:
         """aesgcm_keytab_set_tls_iv: a TLS connection direction's 12-byte write IV per slot (one bytes-like of n * 12 bytes, or a list) into slots first_slot, ...;
         it takes the place of the slot's XPN state"""
         ib, n = _per_slot(ivs, 12, "a TLS write IV is 12 bytes")
-        _chk(self._lib.aesgcm_keytab_set_tls_iv(self._t, first_slot, n, ib, stream))
+        _chk(self._lib.aesgcm_keytab_set_tls_iv(self._h, first_slot, n, ib, stream))
         return self
 
     def records_crypt_dev(self, decrypt, fmt, n_recs, d_slots, d_seq, d_in, d_rec_off, d_out, d_auth=None, stream=None):
         """aesgcm_keytab_records_crypt_dev: TLS record p = bytes [d_rec_off[p], d_rec_off[p + 1]) of d_in / d_out, of the version fmt (TlsFormat) says, under slot
         d_slots[p] with the 64-bit sequence number d_seq[p] (uint64, device memory)"""
-        _chk(self._lib.aesgcm_keytab_records_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_recs, d_slots, d_seq, d_in, d_rec_off, d_out, d_auth, stream))
+        _chk(self._lib.aesgcm_keytab_records_crypt_dev(self._h, int(bool(decrypt)), ctypes.byref(fmt), n_recs, d_slots, d_seq, d_in, d_rec_off, d_out, d_auth, stream))
 
     def crypt_records(self, fmt, slots, seqs, records, decrypt=False):
         """Host convenience (tests, examples), crypt_frames' counterpart: whole TLS records (header | (1.2: explicit nonce |) payload | tag; on encrypt the tag's bytes are
@@ -1001,7 +1027,7 @@ class KeyTable:
         """aesgcm_keytab_quic_crypt_dev: QUIC packet p = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in / d_out, its packet-number field at byte d_pn_off[p] (uint32), under
         the AEAD slot d_slots[p] (key by set, IV by set_tls_iv) and the header-protection slot d_hp_slots[p] (key by set).  d_pn[p] (uint64): the full packet number on
         encrypt, the expected one on decrypt, where the decoded number goes to d_pn_out[p] (may be d_pn) and the verdict to d_auth[p]"""
-        _chk(self._lib.aesgcm_keytab_quic_crypt_dev(self._t, int(bool(decrypt)), n_pkts, d_slots, d_hp_slots, d_pn, d_pn_out, d_pn_off, d_in, d_pkt_off, d_out, d_auth, stream))
+        _chk(self._lib.aesgcm_keytab_quic_crypt_dev(self._h, int(bool(decrypt)), n_pkts, d_slots, d_hp_slots, d_pn, d_pn_out, d_pn_off, d_in, d_pkt_off, d_out, d_auth, stream))
 
     def crypt_quic(self, slots, hp_slots, pns, pn_offs, packets, decrypt=False):
         """Host convenience (tests, examples), crypt_records' counterpart: whole QUIC packets (header | payload | tag; on encrypt the header is unprotected with the truncated
@@ -1025,7 +1051,7 @@ class KeyTable:
         d_slots[p] (key by set, IV by set_tls_iv).  DTLS 1.3 also takes the record-number slot d_sn_slots[p] (key by set), d_sn_off[p] (uint32: where the sequence-number
         field starts) and d_seq[p] (uint64): the full record sequence number on encrypt, the expected one on decrypt, where the decoded number goes to d_seq_out[p] (may
         be d_seq).  The verdict goes to d_auth[p]"""
-        _chk(self._lib.aesgcm_keytab_dtls_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_recs, d_slots, d_sn_slots, d_seq, d_seq_out, d_sn_off, d_in, d_rec_off,
+        _chk(self._lib.aesgcm_keytab_dtls_crypt_dev(self._h, int(bool(decrypt)), ctypes.byref(fmt), n_recs, d_slots, d_sn_slots, d_seq, d_seq_out, d_sn_off, d_in, d_rec_off,
                                                     d_out, d_auth, stream))
 
     def crypt_dtls(self, fmt, slots, records, decrypt=False, sn_slots=None, seqs=None, sn_offs=None):
@@ -1058,7 +1084,7 @@ class KeyTable:
     def srtp_crypt_dev(self, decrypt, fmt, n_pkts, d_slots, d_in, d_pkt_off, d_out, d_roc=None, d_auth=None, stream=None):
         """aesgcm_keytab_srtp_crypt_dev: SRTP or SRTCP packet p (fmt, an SrtpFormat, says which) = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in / d_out under slot
         d_slots[p] (key by set, salt by set_tls_iv).  SRTP also takes d_roc[p] (uint32), the packet's rollover counter.  The verdict goes to d_auth[p]"""
-        _chk(self._lib.aesgcm_keytab_srtp_crypt_dev(self._t, int(bool(decrypt)), ctypes.byref(fmt), n_pkts, d_slots, d_roc, d_in, d_pkt_off, d_out, d_auth, stream))
+        _chk(self._lib.aesgcm_keytab_srtp_crypt_dev(self._h, int(bool(decrypt)), ctypes.byref(fmt), n_pkts, d_slots, d_roc, d_in, d_pkt_off, d_out, d_auth, stream))
 
     def crypt_srtp(self, fmt, slots, packets, decrypt=False, rocs=None):
         """Host convenience (tests, examples), crypt_dtls's counterpart: whole SRTP or SRTCP packets (on encrypt the headers, SRTCP's word W and the MKI are written and
@@ -1078,12 +1104,6 @@ class KeyTable:
                                 d_auth=b["auth"].ptr if decrypt else None)
         outs, got = self._packed_call(packets, up, {"auth": "i"} if decrypt else {}, call)
         return outs, got.get("auth")
-
-    def status(self):
-        """aesgcm_keytab_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""
-        code, detail = cint(0), u64(0)
-        _chk(self._lib.aesgcm_keytab_status(self._t, ctypes.byref(code), ctypes.byref(detail)))
-        return code.value, detail.value
 
     def crypt(self, slots, ivs, aads, datas, decrypt=False, tags=None):
         """Host convenience (tests, examples): packet p = (slots[p], ivs[p], aads[p], datas[p]) through one offset-array call.
@@ -1106,31 +1126,13 @@ class KeyTable:
         return (outs, got["tags"], got["auth"]) if decrypt else (outs, got["tags"])
 
     def _packed_call(self, items, up, down, call):
-        """What the host conveniences share.  `items`, a byte string per packet, joined in the buffer "data" with their n + 1 offsets in "off"; every entry of `up` --
-        name: bytes, or (struct code, values) -- uploaded; every entry of `down` -- name: struct code of the n values that come back -- allocated; then call(bufs) over
-        the DeviceBuffers by name (in place on "data") and a device sync.  -> (items_out, {name: list of n values})"""
+        """What the host conveniences share.  `items`, a byte string per packet, joined in the buffer "data" with their n + 1 offsets in "off"; `up` as _device_call's;
+        every entry of `down` -- name: struct code of the n values that come back; call(bufs) works in place on "data".  -> (items_out, {name: list of n values})"""
         n = len(items)
-        off = [0]
-        for x in items:
-            off.append(off[-1] + len(x))
-        up = dict(up, data=b"".join(bytes(x) for x in items), off=("Q", off))
-        up = {k: v if isinstance(v, bytes) else struct.pack("<%d%s" % (len(v[1]), v[0]), *v[1]) for k, v in up.items()}
-        size = {k: len(v) for k, v in up.items()}
-        for k, code in down.items():
-            size[k] = max(size.get(k, 0), n * struct.calcsize("<" + code))
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in size.items()}
-        try:
-            for k, v in up.items():
-                if v:
-                    bufs[k].upload(v)
-            call(bufs)
-            _chk(load().aesgcm_dev_sync(self.device))
-            out = bytes(bufs["data"].download(off[n])) if off[n] else b""
-            got = {k: list(struct.unpack("<" + code * n, bytes(bufs[k].download(n * struct.calcsize("<" + code))))) for k, code in down.items()}
-            return [out[off[p]:off[p + 1]] for p in range(n)], got
-        finally:
-            for b in bufs.values():
-                b.free()
+        data, off = _joined(items)
+        got = _device_call(self.device, dict(up, data=data, off=("Q", off)), dict({k: (code, n) for k, code in down.items()}, data=("%ds" % off[n], 1)), call)
+        out = got.pop("data")[0]
+        return [out[off[p]:off[p + 1]] for p in range(n)], got
 
 
 # ---------------------------------------------------------------- receive windows (aesgcm_rxwin_*)
@@ -1156,9 +1158,10 @@ RXWIN_FROM_END, RXWIN_CLEAR_TOP = 1, 2                              # AESGCM_RXW
 RXWIN_WHY = ("not authenticated", "accepted", "old", "replay", "refused")      # d_why's values 0 .. 4
 
 
-class RxFormat(ctypes.Structure):
+class RxFormat(_Format, ctypes.Structure):
     """aesgcm_rxwin_fmt: where a packet's truncated number lies and how the full one is formed from it and the window (include/aesgcm.h "RECEIVE WINDOWS")"""
     _fields_ = [("rule", ctypes.c_uint32), ("num_off", ctypes.c_uint32), ("num_len", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+    _check, _typed = "aesgcm_rxwin_fmt_check", staticmethod(_rxwin_typed)
 
     @classmethod
     def macsec(cls):
@@ -1200,40 +1203,15 @@ class RxFormat(ctypes.Structure):
         """QUIC and DTLS 1.3: the expected number, the window's next; no packet byte is read"""
         return cls(RXWIN_EXPECT, 0, 0, 0)
 
-    def check(self):
-        """aesgcm_rxwin_fmt_check -> OK or EARG (no device needed)"""
-        return _rxwin_typed(load()).aesgcm_rxwin_fmt_check(ctypes.byref(self))
 
-    def __repr__(self):
-        return "RxFormat(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
-
-
-class RxWindows:
+class RxWindows(_Table):
     """aesgcm_rxwin: n_wins device-resident receive windows of `window` bits; recover_dev gives a decrypt call its per-packet numbers, commit_dev drops replays and
     advances the windows behind it (include/aesgcm.h "RECEIVE WINDOWS")."""
+    _prefix = "aesgcm_rxwin"
 
     def __init__(self, n_wins, window=64, device=0):
-        self._w = None
-        L = _rxwin_typed(load())
-        w = vp()
-        _chk(L.aesgcm_rxwin_create(ctypes.byref(w), device, n_wins, window))
-        self._w, self._lib = w.value, L
-        self.n_wins, self.window, self.device = n_wins, window, device
-
-    _lib = None
-
-    def close(self):
-        if self._w:
-            self._lib.aesgcm_rxwin_destroy(self._w)
-            self._w = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        self._create(_rxwin_typed, device, n_wins, window)
+        self.n_wins, self.window = n_wins, window
 
     def set(self, first, nexts, seens=None, stream=None):
         """aesgcm_rxwin_set: windows first, first + 1, ... get next = nexts[k] and seen = seens[k], an int whose bit i says "number next - 1 - i was seen" (None: nothing)"""
@@ -1244,7 +1222,7 @@ class RxWindows:
             if len(seens) != n or any(s < 0 or s >> self.window for s in seens):
                 raise AesGcmError(EARG, "one seen value of at most `window` bits per window")
             sn = (u64 * max(n * sw, 1))(*[(s >> (64 * j)) & RXWIN_NONE for s in seens for j in range(sw)])
-        _chk(self._lib.aesgcm_rxwin_set(self._w, first, n, nx, sn, stream))
+        _chk(self._lib.aesgcm_rxwin_set(self._h, first, n, nx, sn, stream))
         return self
 
     def get(self, first=0, n=None, stream=None):
@@ -1252,40 +1230,17 @@ class RxWindows:
         n = self.n_wins - first if n is None else n
         sw = self.window // 64
         nx, sn = (u64 * max(n, 1))(), (u64 * max(n * sw, 1))()
-        _chk(self._lib.aesgcm_rxwin_get(self._w, first, n, nx, sn, stream))
+        _chk(self._lib.aesgcm_rxwin_get(self._h, first, n, nx, sn, stream))
         return list(nx[:n]), [sum(sn[k * sw + j] << (64 * j) for j in range(sw)) for k in range(n)]
 
     def recover_dev(self, fmt, n_pkts, d_win, d_in, d_pkt_off, d_num_out, d_hi_out=None, stream=None):
         """aesgcm_rxwin_recover_dev: d_num_out[p] (uint64) = packet p's full number by fmt (an RxFormat) and window d_win[p] (uint32); d_hi_out[p] (uint32, optional) = what
         the decrypt call takes as d_hi / d_roc.  RxFormat.expect(): d_in and d_pkt_off may be None"""
-        _chk(self._lib.aesgcm_rxwin_recover_dev(self._w, ctypes.byref(fmt), n_pkts, d_win, d_in, d_pkt_off, d_num_out, d_hi_out, stream))
+        _chk(self._lib.aesgcm_rxwin_recover_dev(self._h, ctypes.byref(fmt), n_pkts, d_win, d_in, d_pkt_off, d_num_out, d_hi_out, stream))
 
     def commit_dev(self, n_pkts, d_win, d_num, d_auth, d_accept, d_why=None, stream=None):
         """aesgcm_rxwin_commit_dev: behind the decrypt call; d_accept[p] (int, may be d_auth) = 1 for the packets to deliver, d_why[p] (int, optional) an index of RXWIN_WHY"""
-        _chk(self._lib.aesgcm_rxwin_commit_dev(self._w, n_pkts, d_win, d_num, d_auth, d_accept, d_why, stream))
-
-    def status(self):
-        """aesgcm_rxwin_status -> (code, detail): (EARG, lowest refused packet) or (OK, 0).  Reading clears it.  Synchronise first."""
-        code, detail = cint(0), u64(0)
-        _chk(self._lib.aesgcm_rxwin_status(self._w, ctypes.byref(code), ctypes.byref(detail)))
-        return code.value, detail.value
-
-    def _call(self, up, down, call):
-        n = len(up["win"][1])
-        up = {k: v if isinstance(v, bytes) else struct.pack("<%d%s" % (len(v[1]), v[0]), *v[1]) for k, v in up.items()}
-        size = {k: len(v) for k, v in up.items()}
-        size.update({k: n * struct.calcsize("<" + code) for k, code in down.items()})
-        bufs = {k: DeviceBuffer(max(nb, 16), self.device) for k, nb in size.items()}
-        try:
-            for k, v in up.items():
-                if v:
-                    bufs[k].upload(v)
-            call(bufs)
-            _chk(load().aesgcm_dev_sync(self.device))
-            return {k: list(struct.unpack("<" + code * n, bytes(bufs[k].download(n * struct.calcsize("<" + code))))) for k, code in down.items()}
-        finally:
-            for b in bufs.values():
-                b.free()
+        _chk(self._lib.aesgcm_rxwin_commit_dev(self._h, n_pkts, d_win, d_num, d_auth, d_accept, d_why, stream))
 
     def recover(self, fmt, wins, packets=None):
         """Host convenience (tests, examples): -> (nums, his) of whole packets (RxFormat.expect(): packets may be None)"""
@@ -1294,12 +1249,11 @@ class RxWindows:
             raise AesGcmError(EARG, "wins and packets must be equally long and not empty")
         up = {"win": ("I", wins)}
         if packets is not None:
-            off = [0]
-            for x in packets:
-                off.append(off[-1] + len(x))
-            up.update(data=b"".join(bytes(x) for x in packets), off=("Q", off))
-        got = self._call(up, {"num": "Q", "hi": "I"}, lambda b: self.recover_dev(fmt, n, b["win"].ptr, b["data"].ptr if packets is not None else None,
-                                                                                   b["off"].ptr if packets is not None else None, b["num"].ptr, b["hi"].ptr))
+            data, off = _joined(packets)
+            up.update(data=data, off=("Q", off))
+        got = _device_call(self.device, up, {"num": ("Q", n), "hi": ("I", n)},
+                           lambda b: self.recover_dev(fmt, n, b["win"].ptr, b["data"].ptr if packets is not None else None, b["off"].ptr if packets is not None else None,
+                                                      b["num"].ptr, b["hi"].ptr))
         return got["num"], got["hi"]
 
     def commit(self, wins, nums, auths):
@@ -1307,8 +1261,8 @@ class RxWindows:
         n = len(wins)
         if not n or len(nums) != n or len(auths) != n:
             raise AesGcmError(EARG, "wins, nums and auths must be equally long and not empty")
-        got = self._call({"win": ("I", wins), "num": ("Q", nums), "auth": ("i", auths)}, {"accept": "i", "why": "i"},
-                         lambda b: self.commit_dev(n, b["win"].ptr, b["num"].ptr, b["auth"].ptr, b["accept"].ptr, b["why"].ptr))
+        got = _device_call(self.device, {"win": ("I", wins), "num": ("Q", nums), "auth": ("i", auths)}, {"accept": ("i", n), "why": ("i", n)},
+                           lambda b: self.commit_dev(n, b["win"].ptr, b["num"].ptr, b["auth"].ptr, b["accept"].ptr, b["why"].ptr))
         return got["accept"], got["why"]
 
 

@@ -5,12 +5,16 @@ CSRC  := ../../aes-gcm-128-192-256-bits_amd/csrc
 SAN   ?= -fsanitize=address,undefined
 TAG   ?= asan
 FLAGS := -DAESGCM_LOG_WG=10 -O1 -g -fno-omit-frame-pointer -std=c++17 --offload-arch=gfx950 --cuda-host-only -Wno-unused-value -Wno-unused-function $(SAN)
-OBJS  := host.$(TAG).o abi.$(TAG).o comm.$(TAG).o fakehip.$(TAG).o mt_drive.$(TAG).o
+OBJS  := host.$(TAG).o abi.$(TAG).o comm.$(TAG).o keytab.$(TAG).o rxwin.$(TAG).o fakehip.$(TAG).o mt_drive.$(TAG).o
 mt_drive_$(TAG): $(OBJS)
 	$(HIPCC) $(SAN) -rdynamic -o $@ $(OBJS) -ldl -lpthread
 host.$(TAG).o: $(CSRC)/aesgcm_host.hip $(wildcard $(CSRC)/*.h)
 	$(HIPCC) $(FLAGS) -c -o $@ $<
 abi.$(TAG).o: $(CSRC)/aesgcm_abi.hip $(wildcard $(CSRC)/*.h)
+	$(HIPCC) $(FLAGS) -c -o $@ $<
+keytab.$(TAG).o: $(CSRC)/aesgcm_keytab.hip $(wildcard $(CSRC)/*.h)
+	$(HIPCC) $(FLAGS) -c -o $@ $<
+rxwin.$(TAG).o: $(CSRC)/aesgcm_rxwin.hip $(wildcard $(CSRC)/*.h)
 	$(HIPCC) $(FLAGS) -c -o $@ $<
 # the fake RCCL lives in the executable itself: dlopen(NULL) and -rdynamic
 comm.$(TAG).o: $(CSRC)/aesgcm_comm.hip

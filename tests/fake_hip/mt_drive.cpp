@@ -5,7 +5,8 @@
 // fake HIP runtime of this directory (fakehip.cpp: no GPU, launches launch nothing) and driven through the C ABI by eight threads over four fake devices, every
 // thread for itself: create, messages queued with tag = NULL and collected with aesgcm_last_tag, packets (fixed-size records by rows and through the packet kernels,
 // offset arrays: the routed call with its fork to the side stream), messages wherever they live, a streaming session exported and imported into a second context,
-// rekey, status, destroy; one thread more drives the four-device object.  asan.mk / tsan.mk build it; tests/test_fake_hip.py runs both.  The fake records device
+// rekey, status, destroy; one thread more drives the four-device object; and the two threads of each device set their halves of the device's shared key table and
+// receive windows (csrc/aesgcm_keytab.hip, aesgcm_rxwin.hip: table_sets below).  asan.mk / tsan.mk build it; tests/test_fake_hip.py runs both.  The fake records device
 // discipline as always: its violation count must be zero at the end.
 #include <pthread.h>
 #include <stdint.h>
@@ -22,6 +23,55 @@ extern "C" int fake_violations(char *buf, size_t n);
 static const size_t MB = 1 << 20;
 static int g_rounds = 6;
 
+// The device tables: a key table (AES-256) and receive windows (64 bits) per fake device, made by main and shared by the two threads of the device.  Each thread sets
+// its own TAB_PER entries twenty times on a stream of its own, in pieces whose sizes make the shared staging buffer grow again and again -- the tables' mutex and
+// the stage's cross-stream event under the sanitizers; main then reads the windows back (aesgcm_rxwin_get: the fake copies for real) and compares.
+static const size_t TAB_PER = 32;
+static aesgcm_keytab *g_kt[4];
+static aesgcm_rxwin *g_rw[4];
+static uint64_t g_want_next[8][TAB_PER], g_want_seen[8][TAB_PER];
+
+static void table_sets(int t, aesgcm_ctx *c) {
+    const int dev = t % 4;
+    const size_t base = (size_t)(t / 4) * TAB_PER;
+    void *st = nullptr;
+    CHECK(aesgcm_ctx_stream(c, &st));
+    std::vector<unsigned char> bytes(32 * TAB_PER, (unsigned char)t);
+    for (int i = 0; i < 20; i++) {
+        const size_t n = i == 19 ? TAB_PER : 1 + (size_t)(i * 7 + t) % TAB_PER, first = (size_t)(i * 5) % (TAB_PER - n + 1);
+        uint64_t *next = g_want_next[t] + first, *seen = g_want_seen[t] + first;
+        for (size_t k = 0; k < n; k++) { next[k] = 1000 + 64 * (uint64_t)i + k; seen[k] = 0x8000000000000001ull ^ ((uint64_t)t << 32) ^ (k << 8) ^ (uint64_t)i; }
+        CHECK(aesgcm_rxwin_set(g_rw[dev], base + first, n, next, seen, st));
+        switch (i % 4) {
+        case 0: CHECK(aesgcm_keytab_set(g_kt[dev], base + first, n, bytes.data(), st)); break;
+        case 1: CHECK(aesgcm_keytab_set_salt(g_kt[dev], base + first, n, bytes.data(), st)); break;
+        case 2: CHECK(aesgcm_keytab_set_xpn(g_kt[dev], base + first, n, bytes.data(), bytes.data(), st)); break;
+        default: CHECK(aesgcm_keytab_set_tls_iv(g_kt[dev], base + first, n, bytes.data(), st)); break;
+        }
+    }
+}
+
+static void tables_create(void) {
+    const int t = -1;
+    for (int d = 0; d < 4; d++) { CHECK(aesgcm_keytab_create(&g_kt[d], d, 32, 2 * TAB_PER)); CHECK(aesgcm_rxwin_create(&g_rw[d], d, 2 * TAB_PER, 64)); }
+}
+
+static void tables_compare_and_destroy(void) {
+    const int t = -1;
+    for (int d = 0; d < 4; d++) {
+        uint64_t next[2 * TAB_PER], seen[2 * TAB_PER];
+        CHECK(aesgcm_rxwin_get(g_rw[d], 0, 2 * TAB_PER, next, seen, nullptr));
+        for (size_t k = 0; k < 2 * TAB_PER; k++) {
+            const int w = d + 4 * (int)(k / TAB_PER);
+            if (next[k] != g_want_next[w][k % TAB_PER] || seen[k] != g_want_seen[w][k % TAB_PER]) { fprintf(stderr, "device %d, window %zu: not what thread %d set last\n", d, k, w); exit(1); }
+        }
+        int code = -1; uint64_t detail = 0;
+        CHECK(aesgcm_keytab_status(g_kt[d], &code, &detail)); CHECK(code);
+        CHECK(aesgcm_rxwin_status(g_rw[d], &code, &detail)); CHECK(code);
+        CHECK(aesgcm_keytab_destroy(g_kt[d])); CHECK(aesgcm_rxwin_destroy(g_rw[d]));
+    }
+}
+
 static void *worker(void *arg) {
     const int t = (int)(intptr_t)arg, dev = t % 4;
     unsigned char key[32], iv[12] = {0}, tag[16], blob[AESGCM_STREAM_STATE_BYTES];
@@ -30,6 +80,7 @@ static void *worker(void *arg) {
         aesgcm_ctx *a = nullptr, *b = nullptr;
         CHECK(aesgcm_ctx_create(&a, dev, key, 16 + 8 * (size_t)((r + t) % 3)));
         CHECK(aesgcm_ctx_create(&b, dev, key, 16 + 8 * (size_t)((r + t) % 3)));
+        if (r == 0) table_sets(t, a);
         void *d_in = nullptr, *d_out = nullptr, *d_ivs = nullptr, *d_tags = nullptr, *d_off = nullptr, *d_ptr = nullptr, *d_len = nullptr, *d_auth = nullptr;
         const size_t n = 3000;
         CHECK(aesgcm_dev_alloc(dev, &d_in, 8 * MB)); CHECK(aesgcm_dev_alloc(dev, &d_out, 8 * MB)); CHECK(aesgcm_dev_alloc(dev, &d_ivs, 12 * n)); CHECK(aesgcm_dev_alloc(dev, &d_tags, 16 * n));
@@ -96,9 +147,11 @@ int main(int argc, char **argv) {
     if (argc > 1) g_rounds = atoi(argv[1]);
     const int T = 8;
     pthread_t th[T + 1];
+    tables_create();
     for (int t = 0; t < T; t++) pthread_create(&th[t], nullptr, worker, (void *)(intptr_t)t);
     pthread_create(&th[T], nullptr, mgpu_worker, (void *)(intptr_t)T);
     for (int t = 0; t <= T; t++) pthread_join(th[t], nullptr);
+    tables_compare_and_destroy();
     static char buf[1 << 16];
     const int bad = fake_violations(buf, sizeof buf);
     if (bad) { fprintf(stderr, "%d violations of device discipline\n%s", bad, buf); return 1; }

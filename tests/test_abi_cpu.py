@@ -77,6 +77,55 @@ def test_strerror_covers_all_codes():
     assert L.aesgcm_strerror(-99).decode() == "unknown error"
 
 
+def test_format_reprs_are_the_recorded_ones():
+    """repr() of the six format structs by every constructor: the strings stand in failure messages and logs, and are literals recorded from the commit before
+    check() and __repr__ moved into one mixin.  WireFormatX prints its nested WireFormat positionally.  No device, no library."""
+    W, X, T, D, S, R = lib.WireFormat, lib.WireFormatX, lib.TlsFormat, lib.DtlsFormat, lib.SrtpFormat, lib.RxFormat
+    want = [
+        ('W()', 'WireFormat(aad_len=0, hdr_len=0, iv_off=0, salt_len=0, tag_len=0, flags=0)'),
+        ('W(1, 2, 3, 4, 5, 6)', 'WireFormat(aad_len=1, hdr_len=2, iv_off=3, salt_len=4, tag_len=5, flags=6)'),
+        ('W.macsec()', 'WireFormat(aad_len=28, hdr_len=28, iv_off=16, salt_len=8, tag_len=16, flags=0)'),
+        ('W.macsec(sci=False)', 'WireFormat(aad_len=20, hdr_len=20, iv_off=16, salt_len=8, tag_len=16, flags=0)'),
+        ('W.macsec(auth_only=True)', 'WireFormat(aad_len=28, hdr_len=28, iv_off=16, salt_len=8, tag_len=16, flags=1)'),
+        ('W.macsec(sci=False, auth_only=True)', 'WireFormat(aad_len=20, hdr_len=20, iv_off=16, salt_len=8, tag_len=16, flags=1)'),
+        ('W.esp()', 'WireFormat(aad_len=8, hdr_len=16, iv_off=8, salt_len=4, tag_len=16, flags=0)'),
+        ('W.esp(12)', 'WireFormat(aad_len=8, hdr_len=16, iv_off=8, salt_len=4, tag_len=12, flags=0)'),
+        ('W.esp(tag_len=8)', 'WireFormat(aad_len=8, hdr_len=16, iv_off=8, salt_len=4, tag_len=8, flags=0)'),
+        ('X()', 'WireFormatX(WireFormat(aad_len=0, hdr_len=0, iv_off=0, salt_len=0, tag_len=0, flags=0), ext=0, reserved=0)'),
+        ('X(W.esp(8), 2, 7)', 'WireFormatX(WireFormat(aad_len=8, hdr_len=16, iv_off=8, salt_len=4, tag_len=8, flags=0), ext=2, reserved=7)'),
+        ('X.macsec_xpn()', 'WireFormatX(WireFormat(aad_len=28, hdr_len=28, iv_off=16, salt_len=8, tag_len=16, flags=0), ext=1, reserved=0)'),
+        ('X.macsec_xpn(sci=False, auth_only=True)', 'WireFormatX(WireFormat(aad_len=20, hdr_len=20, iv_off=16, salt_len=8, tag_len=16, flags=1), ext=1, reserved=0)'),
+        ('X.esp_esn()', 'WireFormatX(WireFormat(aad_len=8, hdr_len=16, iv_off=8, salt_len=4, tag_len=16, flags=0), ext=2, reserved=0)'),
+        ('X.esp_esn(12)', 'WireFormatX(WireFormat(aad_len=8, hdr_len=16, iv_off=8, salt_len=4, tag_len=12, flags=0), ext=2, reserved=0)'),
+        ('T()', 'TlsFormat(version=0, reserved=0)'),
+        ('T.tls13()', 'TlsFormat(version=1, reserved=0)'),
+        ('T.tls12()', 'TlsFormat(version=2, reserved=0)'),
+        ('T(9, 1)', 'TlsFormat(version=9, reserved=1)'),
+        ('D()', 'DtlsFormat(version=0, reserved=0)'),
+        ('D.dtls13()', 'DtlsFormat(version=1, reserved=0)'),
+        ('D.dtls12()', 'DtlsFormat(version=2, reserved=0)'),
+        ('D(9, 1)', 'DtlsFormat(version=9, reserved=1)'),
+        ('S()', 'SrtpFormat(kind=0, mki_len=0)'),
+        ('S.rtp()', 'SrtpFormat(kind=1, mki_len=0)'),
+        ('S.rtp(4)', 'SrtpFormat(kind=1, mki_len=4)'),
+        ('S.rtcp()', 'SrtpFormat(kind=2, mki_len=0)'),
+        ('S.rtcp(mki_len=128)', 'SrtpFormat(kind=2, mki_len=128)'),
+        ('R()', 'RxFormat(rule=0, num_off=0, num_len=0, flags=0)'),
+        ('R.macsec()', 'RxFormat(rule=1, num_off=16, num_len=4, flags=0)'),
+        ('R.macsec_xpn()', 'RxFormat(rule=2, num_off=16, num_len=4, flags=0)'),
+        ('R.esp()', 'RxFormat(rule=1, num_off=4, num_len=4, flags=0)'),
+        ('R.esp_esn()', 'RxFormat(rule=2, num_off=4, num_len=4, flags=0)'),
+        ('R.dtls12()', 'RxFormat(rule=1, num_off=5, num_len=6, flags=0)'),
+        ('R.srtp()', 'RxFormat(rule=3, num_off=2, num_len=2, flags=0)'),
+        ('R.srtcp()', 'RxFormat(rule=1, num_off=4, num_len=4, flags=3)'),
+        ('R.srtcp(4)', 'RxFormat(rule=1, num_off=8, num_len=4, flags=3)'),
+        ('R.expect()', 'RxFormat(rule=4, num_off=0, num_len=0, flags=0)'),
+    ]
+    assert {c.split("(")[0].split(".")[0] for c, _ in want} == set("WXTDSR")
+    for expr, text in want:
+        assert repr(eval(expr)) == text, expr
+
+
 def test_header_compiles_as_plain_c():
     # the boundary is a C ABI: the header must be consumable by gcc -std=c99 with no HIP/C++ types
     code = '#include "aesgcm.h"\nint main(void){return AESGCM_ABI_VERSION==3?0:1;}\n'

@@ -87,6 +87,20 @@ def test_the_fake_runtime_reports_what_a_capture_cannot_carry():
     assert out.returncode == 0 and "FAKE CAPTURE SELFTEST OK" in out.stdout, out.stdout[-3000:]
 
 
+def test_device_tables_stage_check_and_free_as_recorded_on_the_fake_runtime():
+    """tests/fake_hip/table_drive.py: a key table and receive windows of both sizes through create, every host-to-table setter on three fresh streams (the second
+    grows the staging buffer; each is ordered behind the one before), set -> get through the stage and both conversions, the range check of every entry point at its
+    edges, status, destroy (allocations back where they were, the recorded number of device synchronisations) and a set whose launch fails -- every answer a literal
+    recorded from the commit before both host sides moved onto one base"""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"))
+    out = subprocess.run([sys.executable, os.path.join(d, "table_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert out.returncode == 0 and "FAKE TABLE OK" in out.stdout, out.stdout[-3000:]
+
+
 def test_the_host_side_loads_over_a_runtime_without_stream_capture():
     """the host side needs hipStreamIsCapturing only to drop the order of a captured call: its reference is weak, in both builds, so a HIP runtime (or a fake one) that
     has no stream capture still loads the library -- an undefined strong reference fails the load of every entry point, not only of the ordered calls"""
