@@ -6,7 +6,8 @@ written from the standards and from the contract in include/aesgcm.h "RECEIVE WI
   recover         a whole recover call: the refusals in the header's order, the rule, (num, hi) per packet
   Window          a SEQUENTIAL window -- the set of seen numbers and `next` -- that takes a call's authenticated packets in descending number order, RFC 4303 A2's
                   check-and-update one packet at a time; normalised() = the form of aesgcm_rxwin_set / _get
-and the cases both test files run: call_sequence, sequences of commit calls placed around the windows' edges, with what the sequential window makes of each."""
+and the cases both test files run: call_sequence, sequences of commit calls placed around the windows' edges, with what the sequential window makes of each, and
+ring_sequence, which adds the placements that a ring of more than one word needs (RING_MOVES; ring_move_kinds reads them off a sequence of states)."""
 NONE = (1 << 64) - 1
 WIRE, LOWEST, SRTP, EXPECT = 1, 2, 3, 4
 FROM_END, CLEAR_TOP = 1, 2
@@ -197,4 +198,59 @@ def call_sequence(rng, n_wins, W, n_pkts=None, sequence=10, first_next=0):
         refused = [p for p in range(len(pool)) if why[p] == REFUSED]
         calls.append((wins, nums, auths, why, [state[w].normalised() for w in range(n_wins)], refused[0] if refused else None))
         prev = pool
+    return sets, calls
+
+
+# The partial clear of [next, M) on a ring of more than one word (W >= 128), as (next mod W, M - next): inside one word; ending exactly on a word boundary; over three
+# or more words (at W = 128 the third is the first again); from the ring's last word into its first
+RING_MOVES = {"inside": lambda W: (64 + 5, 20), "boundary": lambda W: (40, 24), "three": lambda W: (60, min(W - 8, 150)), "wrap": lambda W: (W - 10, 30)}
+
+
+def ring_move_kinds(W, at, d):
+    """which of RING_MOVES' kinds the clear of d positions from ring position `at` is (none for no move and for the full clear)"""
+    kinds = set()
+    if 0 < d < W:
+        first, last = at >> 6, (at + d - 1) >> 6                                # the words of the unwrapped range
+        if first == last:
+            kinds.add("inside")
+        if (at + d) % 64 == 0:
+            kinds.add("boundary")
+        if last - first >= 2:
+            kinds.add("three")
+        if at >> 6 == W // 64 - 1 and at + d > W:
+            kinds.add("wrap")
+    return kinds
+
+
+def ring_sequence(rng, n_wins, W, n_pkts, first_next=0):
+    """call_sequence's ten calls, then for each kind of RING_MOVES two more: one that brings a window's next to the kind's ring position (a full clear), one that moves it
+    by the kind's distance over positions that the call before filled one and all, and up to one that it filled too and that must stay.  The window is the first that has room above it; the other windows carry reordered traffic meanwhile.
+    Same return form as call_sequence; test_rxwin_cpu.py's recorded sequences come from call_sequence alone and do not change."""
+    assert W >= 128 and n_pkts >= 200
+    sets, calls = call_sequence(rng, n_wins, W, n_pkts=n_pkts, first_next=first_next)
+    state = {w: Window.from_normalised(W, *calls[-1][4][w]) for w in range(n_wins)}
+    r = next(w for w in range(n_wins) if state[w].next + 16 * W < 2 ** 63)
+
+    def call(top, more=()):
+        """n_pkts packets; window r's largest authenticated number is `top`, its others are `more` and numbers of the 2 W below"""
+        pool = [(r, top, 1), (r, top, 1), (r, min(top + 50 * W, 2 ** 64 - 2), 0)] + [(r, x, 1) for x in more]
+        while len(pool) < n_pkts:
+            w = rng.randrange(n_wins)
+            c = top - rng.randrange(0, 2 * W) if w == r else state[w].next + rng.randrange(-2 * W, 2 * W)
+            pool.append((w, min(max(c, 0), 2 ** 64 - 2), 1 if rng.randrange(8) else 0))
+        rng.shuffle(pool)
+        wins, nums, auths = zip(*pool)
+        why = commit(state, wins, nums, auths)
+        assert REFUSED not in why
+        calls.append((wins, nums, auths, why, [state[w].normalised() for w in range(n_wins)], None))
+
+    for kind in ("inside", "boundary", "three", "wrap"):
+        at, d = RING_MOVES[kind](W)
+        nx = state[r].next
+        top = nx + 2 * W + (at - nx) % W - 1                                     # next = at (mod W) behind this call
+        low = top + 1 - W                                                        # ... and these numbers hold the positions the move clears, and the first behind them
+        call(top, [low + j for j in range(d + 1)])
+        assert state[r].next % W == at and low + d in state[r].seen
+        call(state[r].next + d - 1)
+        assert kind in ring_move_kinds(W, at, d) and low + d in state[r].seen and low + d - 1 not in state[r].seen
     return sets, calls

@@ -2,7 +2,9 @@
 RFC 4303 A2 that takes a call's authenticated packets in descending number order, and the recovery rules from the standards' pseudo-code.
   grid        sequences of ten commit calls of 1 .. 4097 packets (duplicates inside one wave, across waves, across workgroups) on 1, 3 and 64 windows of 64 and 1024 bits,
               numbers placed at every edge of the window, around 2^32 and at 2^64 - 2: d_why against the reference (the copies of one number as a multiset), exactly one
-              accept per fresh (window, number), and the state through aesgcm_rxwin_get after every call
+              accept per fresh (window, number), and the state through aesgcm_rxwin_get after every call; on 3 windows of 128, 256, 512, 2048 and 4096 bits, 257 and 4097
+              packets, eight calls more that place the partial clear of [next, M) inside one ring word, up to a word boundary, over three words and around the ring's end
+              (asserted from the reference's states)
   forged      d_auth = 0 with numbers far ahead leaves the state as it was
   end to end  on the key-table fixtures: ESN and XPN traffic crossing 2^32 with reordering and loss, SRTP across a sequence rollover, QUIC with the expected number from
               the window -- recover, decrypt, commit; then the same buffer again: every packet a REPLAY, the state unchanged, aesgcm_wipe_failed_dev on d_accept zeroes them
@@ -32,14 +34,27 @@ def _set(rw, sets):
         rw.set(w, [nx], [seen])
 
 
-@pytest.mark.parametrize("n_wins", [1, 3, 64])
-@pytest.mark.parametrize("W", [64, 1024])
-@pytest.mark.parametrize("n_pkts", N_PKTS)
+# every (n_pkts, W, n_wins) of 1 .. 4097 packets x 64 / 1024 bits x 1 / 3 / 64 windows, and the other ring sizes (2, 4, 8, 32 and 64 words) on 3 windows: those run
+# R.ring_sequence, whose last eight calls place the partial clear of [next, M) inside one word, up to a word boundary, over three words and around the ring's end
+GRID = [(n_pkts, W, n_wins) for n_wins in (1, 3, 64) for W in (64, 1024) for n_pkts in N_PKTS] + [(n_pkts, W, 3) for W in (128, 256, 512, 2048, 4096) for n_pkts in (257, 4097)]
+
+
+@pytest.mark.parametrize("n_pkts, W, n_wins", GRID)
 def test_commit_grid_against_the_sequential_window(hip, n_pkts, W, n_wins):
     rng = random.Random("grid %d %d %d" % (n_pkts, W, n_wins))
     first_next = (0, 2 ** 32 - W // 2, 2 ** 64 - 2)[N_PKTS.index(n_pkts) % 3]      # one window alone meets every starting point over the grid
-    sets, calls = R.call_sequence(rng, n_wins, W, n_pkts=n_pkts, first_next=first_next)
-    assert len(calls) == 10
+    if W in (64, 1024):
+        sets, calls = R.call_sequence(rng, n_wins, W, n_pkts=n_pkts, first_next=first_next)
+        assert len(calls) == 10
+    else:
+        sets, calls = R.ring_sequence(rng, n_wins, W, n_pkts, first_next=first_next)
+        assert len(calls) == 18
+        kinds, prev = set(), {w: nx for w, nx, _ in sets}
+        for c in calls:                                                         # the placements, read off the reference's states: next mod W and M - next
+            for w, (nx, _) in enumerate(c[4]):
+                kinds |= R.ring_move_kinds(W, prev[w] % W, nx - prev[w])
+                prev[w] = nx
+        assert kinds == set(R.RING_MOVES), (W, kinds)
     with hip.RxWindows(n_wins, W) as rw:
         assert rw.get() == ([0] * n_wins, [0] * n_wins)
         _set(rw, sets)

@@ -264,6 +264,92 @@ def test_forged_packets_do_not_move_a_window(emul):
     assert emul(script) == [["c", "0", "0"]] * 4 + [["g", "0", "1000", "%016x" % 0xff], ["n", "0", "1000"], ["g", "1", "0", "0" * 16], ["n", "1", "0"], ["x", str(2 ** 32 - 1)]]
 
 
+@pytest.mark.parametrize("W", [128, 4096])
+def test_commit_phases_on_a_ring_of_several_words(emul, W):
+    """R.ring_sequence (tests/test_gpu_rxwin.py runs it on the device): the partial clear inside a word, up to a word boundary, over three words, around the ring's end"""
+    sets, calls = R.ring_sequence(random.Random("ring %d" % W), 3, W, 257, first_next=0)
+    script = ["T 3 %d" % W] + ["S %d %d %x" % s for s in sets]
+    for wins, nums, auths, _, _, _ in calls:
+        script += ["C %d %d" % (len(wins), 31 * len(script))] + ["%d %d %d" % p for p in zip(wins, nums, auths)] + ["G", "X"]
+    got = emul(script)
+    at = 0
+    for k, (wins, nums, auths, why, state, bad) in enumerate(calls):
+        rows = got[at:at + len(wins)]
+        at += len(wins)
+        err = R.same_verdicts(wins, nums, [int(r[2]) for r in rows], why)
+        assert err is None, (k, err)
+        for w in range(3):
+            g = got[at]
+            at += 2
+            assert (g[0], int(g[1]), int(g[2]), int(g[3], 16)) == ("g", w) + state[w], (k, w)
+        at += 1
+    assert at == len(got)
+
+
+# ---------------------------------------------------------------- the new receive flows of tests/rx_loop.py, without a device
+def _wire_number(name, pkt):
+    """the truncated number of a packet, by a slice written out from the standard's field position"""
+    if name in ("macsec", "xpn"):
+        return int.from_bytes(pkt[16:20], "big")         # IEEE 802.1AE 9.3: DA[6] SA[6] | EtherType[2] TCI-AN[1] SL[1] PN[4] SCI[8]
+    if name == "esp":
+        return int.from_bytes(pkt[4:8], "big")           # RFC 4303 2: SPI[4] sequence number[4]
+    if name == "dtls12":
+        return int.from_bytes(pkt[5:11], "big")          # RFC 6347 4.1: type[1] version[2] epoch[2] sequence_number[6] length[2]
+    assert name == "srtcp_mki"
+    return int.from_bytes(pkt[-8:-4], "big") & 0x7FFFFFFF  # RFC 3711 3.4 / RFC 7714 9.2: ... | E[1 bit] index[31 bits] | MKI[4]
+
+
+@pytest.mark.parametrize("name", ["macsec", "esp", "xpn", "dtls12", "srtcp_mki"])
+def test_new_flows_open_what_they_make_and_presets_sit_on_the_wire(name):
+    import rx_loop
+    flow = rx_loop.Flow(lib, name, 16, 4)
+    W = 64
+    f = flow.fmt
+    assert f.check() == lib.OK
+    bits = {"macsec": 32, "esp": 32, "xpn": 32, "dtls12": 48, "srtcp_mki": 31}[name]
+    nums = [0, 1, 2 ** 30 + 3, 2 ** bits - 1, flow.top, min(flow.top, 2 ** 33 + 77)] + flow.starts(W)
+    for i, num in enumerate(nums):
+        w, L = i % 4, (0, 1, 16, 33, 100)[i % 5]
+        plain, pkt = flow.plain(w, num, i, L), flow.make(w, num, i, L)
+        t = len(pkt) - flow.trail - 16
+        assert len(pkt) == len(plain) and plain[t:t + 16] == rx_loop.TAG
+        # the number on the wire is the one the packet was made with: by the standard's position, and by the preset's (num_off, num_len, flags)
+        assert _wire_number(name, pkt) == num & (2 ** bits - 1), (name, num)
+        at = len(pkt) - f.num_off if f.flags & R.FROM_END else f.num_off
+        field = int.from_bytes(pkt[at:at + f.num_len], "big")
+        if f.flags & R.CLEAR_TOP:
+            field &= ~(1 << (8 * f.num_len - 1))
+        assert field == num & (2 ** bits - 1) and 8 * f.num_len == (bits + 7) // 8 * 8, (name, num, f)
+        # open(make(...)) is the identity, under the true number alone
+        out, ok, cnum = flow.open(w, (num, num >> 32), pkt)
+        assert ok == 1 and cnum == num and out[:t] == plain[:t] and out[t + 16:] == plain[t + 16:] and out[t:t + 16] == pkt[t:t + 16], (name, num)
+        for bit in (0, 77, 127):
+            bad = bytearray(pkt)
+            bad[t + bit // 8] ^= 1 << (bit % 8)
+            assert flow.open(w, (num, num >> 32), bytes(bad))[1] == 0, (name, num, bit)
+        if name == "xpn":
+            assert flow.open(w, (num, (num >> 32) ^ 1), pkt)[1] == 0             # the upper half is in the nonce
+    if name == "srtcp_mki":
+        e_of = lambda num: flow.make(0, num, 0, 9)[-8] >> 7
+        assert e_of(0) == 1 and e_of(2 ** 30 + 1) == 0 and e_of(2 ** 31 - 1) == 0 and e_of(2 ** 31 - 2) == 1
+    if name == "dtls12":
+        assert [flow.make(w, 5, 0, 9)[3:5] for w in range(4)] == [b"\0\1", b"\0\2"] * 2 and len({flow.slot(w) for w in range(4)}) == 4
+
+
+def test_loop_references_of_the_new_flows():
+    """the three batches of every loop tests/test_gpu_rxwin_grid.py runs, as the reference sees them: what each must contain"""
+    import rx_loop
+    for name, top_bits in (("macsec", 32), ("esp", 32), ("dtls12", 48), ("srtcp_mki", 31), ("xpn", None)):
+        for W in (64, 1024):
+            flow, starts, (b1, b2, b3) = rx_loop.loop_reference(lib, name, W, 16)
+            assert starts[0] == (2 ** 32 - 20 if name == "xpn" else 0) and len(b1.wins) == len(b3.wins) == rx_loop.N
+            if top_bits:
+                assert flow.top == 2 ** top_bits - 1 and b3.state[flow.top_win][0] == 2 ** top_bits and (flow.top_win, flow.top) in zip(b3.wins, b3.cnum)
+            if name == "srtcp_mki":
+                words = [(num, int.from_bytes(pkt[-8:-4], "big")) for b in (b1, b3) for num, pkt, y in zip(b.cnum, b.pkts, b.why) if y == R.ACCEPT]
+                assert (0, 0x80000000) in words and any(wd >> 30 == 1 and num == wd for num, wd in words)
+
+
 # ---------------------------------------------------------------- the kernels' assembly
 @pytest.fixture(scope="module")
 def census():
