@@ -10,3 +10,4 @@
 #include "aesgcm_dtls_kernels.hip"
 #include "aesgcm_srtp_kernels.hip"
 #include "aesgcm_rxwin_kernels.hip"
+#include "aesgcm_txnum_kernels.hip"

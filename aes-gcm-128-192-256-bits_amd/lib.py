@@ -48,6 +48,7 @@ SYMBOLS = [
     "aesgcm_srtp_fmt_check", "aesgcm_keytab_srtp_crypt_dev",
     "aesgcm_rxwin_create", "aesgcm_rxwin_set", "aesgcm_rxwin_get", "aesgcm_rxwin_fmt_check", "aesgcm_rxwin_recover_dev", "aesgcm_rxwin_commit_dev", "aesgcm_rxwin_status",
     "aesgcm_rxwin_destroy",
+    "aesgcm_txnum_create", "aesgcm_txnum_set", "aesgcm_txnum_get", "aesgcm_txnum_fmt_check", "aesgcm_txnum_assign_dev", "aesgcm_txnum_status", "aesgcm_txnum_destroy",
 ]
 
 
@@ -894,7 +895,7 @@ def _device_call(device, up, down, call):
 
 
 class _Table:
-    """what KeyTable and RxWindows share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
+    """what KeyTable, RxWindows and TxCounters share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
     context manager, status()"""
     _h = _lib = None
 
@@ -1264,6 +1265,120 @@ class RxWindows(_Table):
         got = _device_call(self.device, {"win": ("I", wins), "num": ("Q", nums), "auth": ("i", auths)}, {"accept": ("i", n), "why": ("i", n)},
                            lambda b: self.commit_dev(n, b["win"].ptr, b["num"].ptr, b["auth"].ptr, b["accept"].ptr, b["why"].ptr))
         return got["accept"], got["why"]
+
+
+# ---------------------------------------------------------------- send counters (aesgcm_txnum_*)
+def _txnum_typed(L):
+    """type the aesgcm_txnum_* symbols on first use, as _rxwin_typed does: the fake runtime of tests/fake_hip links no such unit and still loads"""
+    if not getattr(L, "_txnum_typed", False):
+        pu64 = ctypes.POINTER(u64)
+        L.aesgcm_txnum_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_txnum_set.argtypes = [vp, sz, sz, pu64, pu64, vp]
+        L.aesgcm_txnum_get.argtypes = [vp, sz, sz, pu64, pu64, vp]
+        L.aesgcm_txnum_fmt_check.argtypes = [ctypes.POINTER(TxFormat)]
+        L.aesgcm_txnum_assign_dev.argtypes = [vp, ctypes.POINTER(TxFormat), sz, vp, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_txnum_status.argtypes = [vp, ctypes.POINTER(cint), pu64]
+        L.aesgcm_txnum_destroy.argtypes = [vp]
+        L._txnum_typed = True
+    return L
+
+
+TXNUM_FROM_END, TXNUM_KEEP_TOP, TXNUM_WHOLE = 1, 2, 4                # AESGCM_TXNUM_FROM_END, AESGCM_TXNUM_KEEP_TOP, AESGCM_TXNUM_WHOLE
+
+
+class TxFormat(_Format, ctypes.Structure):
+    """aesgcm_txnum_fmt: where a packet's number is written, how many of its low bytes, and what the field means (include/aesgcm.h "SEND COUNTERS")"""
+    _fields_ = [("num_off", ctypes.c_uint32), ("num_len", ctypes.c_uint32), ("dup_off", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+    _check, _typed = "aesgcm_txnum_fmt_check", staticmethod(_txnum_typed)
+
+    @classmethod
+    def macsec(cls):
+        """IEEE 802.1AE: the SecTAG's 32-bit PN is the whole number; a counter that reaches 2^32 refuses"""
+        return cls(16, 4, 0, TXNUM_WHOLE)
+
+    @classmethod
+    def macsec_xpn(cls):
+        """IEEE 802.1AEbw: the SecTAG holds the 64-bit PN's lower half; hi = the d_hi of frames_crypt_x_dev"""
+        return cls(16, 4, 0, 0)
+
+    @classmethod
+    def esp(cls):
+        """RFC 4303: the 32-bit sequence number is the whole number"""
+        return cls(4, 4, 0, TXNUM_WHOLE)
+
+    @classmethod
+    def esp_esn(cls):
+        """RFC 4303 / RFC 4106 section 5: the header holds seq-lo; hi = seq-hi, the d_hi of frames_crypt_x_dev"""
+        return cls(4, 4, 0, 0)
+
+    @classmethod
+    def tls12(cls):
+        """RFC 5288: the record's 8-byte explicit nonce = the sequence number (nums = the d_seq of records_crypt_dev)"""
+        return cls(5, 8, 0, TXNUM_WHOLE)
+
+    @classmethod
+    def dtls12(cls):
+        """RFC 6347 / RFC 5288: the record's 48-bit sequence number, and again as the sequence half of the explicit nonce; the epoch bytes are the caller's"""
+        return cls(5, 6, 15, TXNUM_WHOLE)
+
+    @classmethod
+    def srtcp(cls, mki_len=0):
+        """RFC 3711 3.4: the 31-bit SRTCP index behind the tag, in front of the MKI; the E bit stays as the caller set it"""
+        return cls(4 + mki_len, 4, 0, TXNUM_FROM_END | TXNUM_KEEP_TOP | TXNUM_WHOLE)
+
+    @classmethod
+    def number_only(cls):
+        """TLS 1.3, QUIC, DTLS 1.3: nums = the d_seq / d_pn of their calls, which place their own bytes; no packet byte is written"""
+        return cls(0, 0, 0, 0)
+
+
+class TxCounters(_Table):
+    """aesgcm_txnum: n_ctrs device-resident send counters (next, limit); assign_dev hands the packets of a call their numbers in array order and writes them into the
+    packets, before the encrypt call (include/aesgcm.h "SEND COUNTERS").  max_pkts = the largest call."""
+    _prefix = "aesgcm_txnum"
+
+    def __init__(self, n_ctrs, max_pkts, device=0):
+        self._create(_txnum_typed, device, n_ctrs, max_pkts)
+        self.n_ctrs, self.max_pkts = n_ctrs, max_pkts
+
+    def set(self, first, nexts, limits, stream=None):
+        """aesgcm_txnum_set: counters first, first + 1, ... get next = nexts[k] and limit = limits[k] (exclusive)"""
+        n = len(nexts)
+        if len(limits) != n:
+            raise AesGcmError(EARG, "one limit per next")
+        _chk(self._lib.aesgcm_txnum_set(self._h, first, n, (u64 * max(n, 1))(*nexts), (u64 * max(n, 1))(*limits), stream))
+        return self
+
+    def get(self, first=0, n=None, stream=None):
+        """aesgcm_txnum_get -> (nexts, limits) of counters first .. first + n - 1; waits on the stream"""
+        n = self.n_ctrs - first if n is None else n
+        nx, lm = (u64 * max(n, 1))(), (u64 * max(n, 1))()
+        _chk(self._lib.aesgcm_txnum_get(self._h, first, n, nx, lm, stream))
+        return list(nx[:n]), list(lm[:n])
+
+    def assign_dev(self, fmt, n_pkts, d_ctr, d_pkts, d_pkt_off, d_num_out, d_hi_out=None, d_slots=None, stream=None):
+        """aesgcm_txnum_assign_dev: d_num_out[p] (uint64) = packet p's number from counter d_ctr[p] (uint32), in array order per counter; d_hi_out[p] (uint32, optional)
+        = its upper half; fmt (a TxFormat) says which bytes of the packet get it (TxFormat.number_only(): d_pkts and d_pkt_off may be None); d_slots[p] (uint32,
+        optional, in/out, never the array d_ctr) = 0xFFFFFFFF for a refused packet"""
+        _chk(self._lib.aesgcm_txnum_assign_dev(self._h, ctypes.byref(fmt), n_pkts, d_ctr, d_pkts, d_pkt_off, d_num_out, d_hi_out, d_slots, stream))
+
+    def assign(self, fmt, ctrs, packets=None):
+        """Host convenience (tests, examples): -> (packets, nums, his, refused) of whole packets (TxFormat.number_only(): packets may be None and come back as None);
+        refused[p] = the packet was refused"""
+        n = len(ctrs)
+        if not n or (packets is not None and len(packets) != n):
+            raise AesGcmError(EARG, "ctrs and packets must be equally long and not empty")
+        up, down = {"ctr": ("I", ctrs), "slots": ("I", [0] * n)}, {"num": ("Q", n), "hi": ("I", n), "slots": ("I", n)}
+        off = None
+        if packets is not None:
+            data, off = _joined(packets)
+            up.update(data=data, off=("Q", off))
+            down.update(data=("%ds" % off[n], 1))
+        got = _device_call(self.device, up, down,
+                           lambda b: self.assign_dev(fmt, n, b["ctr"].ptr, b["data"].ptr if packets is not None else None, b["off"].ptr if packets is not None else None,
+                                                     b["num"].ptr, b["hi"].ptr, b["slots"].ptr))
+        out = None if packets is None else [got["data"][0][off[p]:off[p + 1]] for p in range(n)]
+        return out, got["num"], got["hi"], [s == 0xFFFFFFFF for s in got["slots"]]
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

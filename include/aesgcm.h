@@ -39,7 +39,8 @@ extern "C" {
 
 #define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
-                                  aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev)
+                                  aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
+                                  the send counters aesgcm_txnum_* / aesgcm_txnum_fmt)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -415,17 +416,17 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * the same slot are NOT ordered by the library: the caller orders them (an event, or one stream for both).  Key rotation: set the new key into an unused slot,
  * switch the packets' slot numbers to it, clear the old slot once no call in flight names it (INTEGRATION.md "Key tables").  The calls of one table are
  * thread-safe; a table belongs to the device it was created on.
- * CAPTURE (key tables and receive windows): every aesgcm_keytab_*_crypt_dev call, aesgcm_rxwin_recover_dev, aesgcm_rxwin_commit_dev and aesgcm_wipe_failed_dev is a
+ * CAPTURE (key tables and receive windows): every aesgcm_keytab_*_crypt_dev call, aesgcm_rxwin_recover_dev, aesgcm_rxwin_commit_dev, aesgcm_txnum_assign_dev and aesgcm_wipe_failed_dev is a
  * fixed sequence of launches (and one 4-byte memset node per crypt call) on `stream` for given pointers and counts: no allocation, no host synchronisation, nothing read
  * back, no event.  They may run under hipStreamBeginCapture on `stream` (a created stream; thread-local capture mode suffices), several of them behind one another, and
  * the graph may be replayed over other slots, numbers, lengths, offsets and bytes in the same buffers; a receive loop's window state travels from replay to replay in
  * the window records.  (The five-array aesgcm_batch_crypt_dev / _var_dev plan their launch the same way and follow the same rules.)
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
- *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, and ONE of the device's 256 launch dispensers (a word the
+ *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
  *   ORDERING         a captured call is never ordered by falling length class, whatever its count: the order's scratch belongs to the device, not to the graph.  The
  *                    packets are taken in array order -- the same bytes, slower from the counts at which an ordinary call is ordered.
- *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy (staging buffers
+ *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
  *                    that grow, events, synchronous copies, waits): call them outside the capture.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
@@ -475,7 +476,7 @@ AESGCM_API int aesgcm_keytab_destroy(aesgcm_keytab *t);
  *   ESP, RFC 4106           {8, 16, 8, 4, 16 | 12 | 8, 0}   SPI, sequence number | 8-byte IV field | payload | ICV; the slot's salt = the SA's 4-byte salt
  *   MACsec confidentiality offset 30 / 50   {28 + 30, 28 + 30, 16, 8, 16, 0}: the offset's bytes are authenticated header
  * MACsec XPN and ESP with extended sequence numbers need a number that is not in the frame: aesgcm_keytab_frames_crypt_x_dev, below.
- * OUT OF SCOPE: generating packet numbers / sequence numbers, anti-replay windows (not this call's: aesgcm_rxwin_*, "RECEIVE WINDOWS" below), and routing long frames to the row kernels (a frame runs on one lane
+ * OUT OF SCOPE: generating packet numbers / sequence numbers (not this call's: aesgcm_txnum_assign_dev, "SEND COUNTERS" below, hands them out and writes them into the frames), anti-replay windows (not this call's: aesgcm_rxwin_*, "RECEIVE WINDOWS" below), and routing long frames to the row kernels (a frame runs on one lane
  * group).  TLS records (their AAD is not a span of the wire bytes) are not a format of this call: aesgcm_keytab_records_crypt_dev, further below. */
 #define AESGCM_WIRE_AUTH_ONLY 1u   /* nothing is encrypted: every byte in front of the ICV is AAD (MACsec integrity-only, E = 0; GMAC) */
 typedef struct aesgcm_wire_fmt {
@@ -512,7 +513,7 @@ AESGCM_API int aesgcm_keytab_frames_crypt_dev(aesgcm_keytab *t, int decrypt, con
  * frame's d_hi is not read.  One k_kt_wirex launch per call (ext 0: one k_kt_wire launch).
  * TLS 1.3 records (their nonce takes a 64-bit number with no wire part) are not a mode of this call either: d_hi holds 32-bit values.  They have a call of their own,
  * aesgcm_keytab_records_crypt_dev, below.
- * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself (neither is this call's: aesgcm_rxwin_recover_dev / _commit_dev, "RECEIVE WINDOWS" below), generating packet numbers, writing the PN into the SecTAG, ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
+ * OUT OF SCOPE: recovering d_hi from a replay window, anti-replay itself (neither is this call's: aesgcm_rxwin_recover_dev / _commit_dev, "RECEIVE WINDOWS" below), generating packet numbers, writing the PN into the SecTAG (neither is this call's: aesgcm_txnum_assign_dev, "SEND COUNTERS" below, writes d_hi and the SecTAG's / the ESP header's lower half), ESN with AESGCM_WIRE_AUTH_ONLY (RFC 4543), routing long frames to the row kernels. */
 #define AESGCM_WIREX_XPN 1u   /* nonce = the slot's 12-byte XPN salt XOR (the slot's SSCI | be32(d_hi[p]) | the 4 frame bytes at iv_off) */
 #define AESGCM_WIREX_ESN 2u   /* AAD = frame[0,4) | be32(d_hi[p]) | frame[4,8): 12 bytes; nonce as the base format says */
 typedef struct aesgcm_wire_xfmt {
@@ -551,7 +552,7 @@ AESGCM_API int aesgcm_keytab_frames_crypt_x_dev(aesgcm_keytab *t, int decrypt, c
  * One k_kt_tls launch per call; shape and order as aesgcm_keytab_frames_crypt_dev (8, 16 or 64 lanes per record by count, by falling length class from 262144 records, 98304
  * for the longer keys).  Ordering and thread safety as the other key-table calls.
  * OUT OF SCOPE: checking the header's version, type or length bytes against the offsets; padding and content type (the payload's last bytes in 1.3); generating sequence
- * numbers or explicit nonces; key derivation (INTEGRATION.md "TLS records" says which secret becomes what); routing long records to the row kernels.  (DTLS records: aesgcm_keytab_dtls_crypt_dev below.) */
+ * numbers or explicit nonces (not this call's: aesgcm_txnum_assign_dev, "SEND COUNTERS" below, gives d_seq and writes 1.2's explicit nonce); key derivation (INTEGRATION.md "TLS records" says which secret becomes what); routing long records to the row kernels.  (DTLS records: aesgcm_keytab_dtls_crypt_dev below.) */
 #define AESGCM_TLS_13 1u   /* hdr[5] | payload | tag[16]; nonce = slot IV XOR (0^32 | be64(d_seq[p])); AAD = hdr */
 #define AESGCM_TLS_12 2u   /* hdr[5] | explicit nonce[8] | payload | tag[16]; nonce = slot IV[0..4) | explicit nonce; AAD = be64(d_seq[p]) | hdr[0..3) | be16(L - 29) */
 typedef struct aesgcm_tls_fmt {
@@ -773,6 +774,69 @@ AESGCM_API int aesgcm_rxwin_commit_dev(aesgcm_rxwin *w, size_t n_pkts, const uin
                             void *stream);
 AESGCM_API int aesgcm_rxwin_status(aesgcm_rxwin *w, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_rxwin_destroy(aesgcm_rxwin *w);
+
+/* ---------------------------------------------------------------- SEND COUNTERS: packet numbers handed out on the device, in packet order, for every wire format above
+ * A sender needs, BEFORE an encrypt call, a fresh number per packet from per-association state -- and that state must never go wrong: a number used twice under one key
+ * gives away the authentication key.  aesgcm_txnum is that state on the device: n_ctrs independent counters.  A counter is `next` (uint64: the number the next packet
+ * gets) and `limit` (uint64, EXCLUSIVE: only numbers below limit are ever handed out; limit is at most 2^64 - 1, so AESGCM_RXWIN_NONE is never a number).  Like a
+ * receive window a counter belongs to whatever the protocol numbers and is NOT tied to a key slot: calls name a counter per packet with d_ctr[p] (DEVICE memory,
+ * uint32), which often holds the same numbers as d_slots (in an array of its own: see d_slots below).
+ *   aesgcm_txnum_create   every counter next = 0, limit = 0: an unset counter refuses everything.  All scratch memory an assign call needs is allocated HERE, sized by
+ *                         max_pkts: a call allocates nothing.  AESGCM_EARG for n_ctrs == 0, n_ctrs >= 2^31, max_pkts == 0, max_pkts >= 2^31.
+ *   aesgcm_txnum_set      HOST arrays next[n], limit[n] into counters first .. first + n - 1.  AESGCM_EARG for next[k] > limit[k].  Stream-ordered through a staging
+ *                         buffer, like aesgcm_rxwin_set.
+ *   aesgcm_txnum_get      the same arrays back (limit may be NULL).  It WAITS on `stream`.  For tests, checkpoints and rekey polling (rekey when limit - next runs low).
+ *   aesgcm_txnum_status   as aesgcm_rxwin_status: the LOWEST packet index an assign call refused since the last read, which clears it.
+ *   aesgcm_txnum_destroy  waits for the device, frees.
+ * ASSIGN, before the encrypt: aesgcm_txnum_assign_dev(t, fmt, n_pkts, d_ctr, d_pkts, d_pkt_off, d_num_out, d_hi_out, d_slots, stream).
+ * ORDER: the packets of one call that name counter c, taken in ASCENDING ARRAY INDEX, get next_c, next_c + 1, ...; afterwards next_c has grown by their count, capped at
+ * limit_c.  The result is deterministic, and no number is handed out twice, across any sequence of calls on one stream.  (Receivers' windows are sized for the
+ * network's reordering, not for a shuffled call.)
+ * d_num_out[p] (required, uint64) is the full number: the d_seq / d_pn of the TLS 1.3, QUIC and DTLS 1.3 calls.  d_hi_out[p] (optional, uint32) = num >> 32: the d_hi of
+ * aesgcm_keytab_frames_crypt_x_dev.  *fmt says what is written into packet p = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_pkts, IN PLACE, before the encrypt: the low
+ * num_len bytes of the number, big-endian, at byte num_off.  num_len is 0, 2, 4, 6 or 8; with 0 no packet byte is written and d_pkts / d_pkt_off may be NULL (TLS 1.3,
+ * QUIC, DTLS 1.3: their calls place their own bytes).  dup_off != 0 writes the same bytes a second time at dup_off.
+ *   AESGCM_TXNUM_FROM_END  num_off and dup_off count back from the packet's END, as AESGCM_RXWIN_FROM_END does.
+ *   AESGCM_TXNUM_KEEP_TOP  the field's top bit is left as it is and the number takes 8 num_len - 1 bits (SRTCP's E bit).
+ *   AESGCM_TXNUM_WHOLE     the field is the WHOLE number: a number that does not fit the field's bits refuses the packet.  The fail-closed stop of classic MACsec and
+ *                          ESP at 2^32, whatever `limit` says.
+ *   MACsec {16, 4, 0, WHOLE}; MACsec XPN {16, 4, 0, 0}; ESP {4, 4, 0, WHOLE}; ESP ESN {4, 4, 0, 0}; TLS 1.2 {5, 8, 0, WHOLE} (the explicit nonce); DTLS 1.2
+ *   {5, 6, 15, WHOLE} (the record's sequence number, and again as the sequence half of the explicit nonce; the epoch bytes of both are the caller's); SRTCP
+ *   {4 + mki_len, 4, 0, FROM_END | KEEP_TOP | WHOLE}; number only {0, 0, 0, 0}.
+ * A packet is REFUSED on its own, by these tests in this order, and no packet byte is touched past the one that refuses: (1) d_ctr[p] >= n_ctrs; (2) its number would be
+ * at or above limit; (3) WHOLE and the number does not fit; (4) falling offsets; (5) the field or its duplicate not inside the packet.  Then d_num_out[p] =
+ * AESGCM_RXWIN_NONE, d_hi_out[p] = 0xFFFFFFFF, none of its bytes is written, and, if d_slots (optional, uint32, in/out) is given, d_slots[p] = 0xFFFFFFFF: the encrypt
+ * call behind refuses exactly these packets and never encrypts under a number that was not granted.  d_slots MUST NOT BE d_ctr, however equal their contents: the
+ * entry of a refused packet is overwritten while other lanes still read the counter numbers.  The lowest such index goes to aesgcm_txnum_status.  A packet
+ * refused by tests 3 to 5 HAS BEEN COUNTED: its number is BURNT, not reused.
+ * aesgcm_txnum_fmt_check: AESGCM_EARG for NULL, an unknown flag, a num_len other than 0 / 2 / 4 / 6 / 8, num_off or dup_off >= 2^16, a duplicate that overlaps the
+ * field, KEEP_TOP, WHOLE or dup_off with num_len == 0.  It touches no device; the assign call runs it first, then AESGCM_EARG for t NULL, (n_pkts == 0 is AESGCM_OK,)
+ * d_ctr or d_num_out NULL, d_pkts or d_pkt_off NULL with num_len != 0, n_pkts > max_pkts -- all before any device is touched.
+ * The call is a stable radix sort of the packet indices by counter (three launches per 8 bits of n_ctrs: one pass up to 255 counters, two up to 65 535) and two
+ * launches a lane per packet; no workgroup waits for another, and no atomic but the status word's: the cost does not depend on how many packets share a counter.  Its
+ * launch sequence is fixed for given n_pkts and table; no allocation, no host synchronisation, nothing read back: capture-safe (CAPTURE, under "key tables" above) and
+ * asynchronous on `stream`.  Every call but aesgcm_txnum_get is stream-ordered.  TWO ASSIGN CALLS OF ONE TABLE MUST NOT RUN CONCURRENTLY on different streams -- they
+ * share the table's scratch, whichever counters they name: the caller orders them.  The host calls of one table are thread-safe; a table belongs to its device.
+ * OUT OF SCOPE: SRTP's sequence number (the application's) and its rollover counter (the caller's); DTLS epochs and the epoch bytes; choosing a counter from a wire
+ * field; a single-launch path for small calls. */
+#define AESGCM_TXNUM_FROM_END 1u   /* num_off / dup_off count back from the packet's end */
+#define AESGCM_TXNUM_KEEP_TOP 2u   /* the field's top bit is left as it is; the number takes 8 num_len - 1 bits */
+#define AESGCM_TXNUM_WHOLE    4u   /* the field is the whole number: one that does not fit refuses the packet */
+typedef struct aesgcm_txnum aesgcm_txnum;
+typedef struct aesgcm_txnum_fmt {
+    uint32_t num_off;   /* where the number's field starts (FROM_END: before the end), < 2^16 */
+    uint32_t num_len;   /* its bytes: 0 (nothing is written), 2, 4, 6 or 8                     */
+    uint32_t dup_off;   /* 0, or where the same bytes are written a second time, < 2^16       */
+    uint32_t flags;     /* AESGCM_TXNUM_FROM_END | AESGCM_TXNUM_KEEP_TOP | AESGCM_TXNUM_WHOLE  */
+} aesgcm_txnum_fmt;     /* 16 bytes */
+AESGCM_API int aesgcm_txnum_create(aesgcm_txnum **out, int device, size_t n_ctrs, size_t max_pkts);
+AESGCM_API int aesgcm_txnum_set(aesgcm_txnum *t, size_t first, size_t n, const uint64_t *next, const uint64_t *limit, void *stream);
+AESGCM_API int aesgcm_txnum_get(aesgcm_txnum *t, size_t first, size_t n, uint64_t *next, uint64_t *limit, void *stream);
+AESGCM_API int aesgcm_txnum_fmt_check(const aesgcm_txnum_fmt *fmt);
+AESGCM_API int aesgcm_txnum_assign_dev(aesgcm_txnum *t, const aesgcm_txnum_fmt *fmt, size_t n_pkts, const uint32_t *d_ctr, void *d_pkts, const uint64_t *d_pkt_off,
+                            uint64_t *d_num_out, uint32_t *d_hi_out, uint32_t *d_slots, void *stream);
+AESGCM_API int aesgcm_txnum_status(aesgcm_txnum *t, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_txnum_destroy(aesgcm_txnum *t);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
