@@ -1,6 +1,7 @@
 // aesgcm_abi.hip -- the C ABI of include/aesgcm.h: every exported entry point of libaesgcm_hip.so except the inter-GPU exchange (aesgcm_comm.hip).  Argument checks
 // and the order of calls into the host runtime (aesgcm_host.hip), which plans and makes every launch; no device code (aesgcm_internal.h).
 #include "aesgcm_internal.h"
+#include "aesgcm_msgplan.h"
 
 #include <new>
 #include <stdio.h>
@@ -216,7 +217,7 @@ int aesgcm_ctx_split(const aesgcm_ctx *c, size_t len, uint64_t first_block, uint
         }
     }
     BodySplit b;
-    const bool split = ctx_body_split(c, len, first_block, &b);
+    const bool split = plan_body_split(len, first_block, c->tw_override, c->body_min, &b);
     if (head_blocks) *head_blocks = split ? b.head_blocks : 0;
     if (body_blocks) *body_blocks = split ? b.body_blocks : 0;
     return AESGCM_OK;
@@ -348,7 +349,7 @@ int aesgcm_ecb_encrypt(aesgcm_ctx *c, const uint8_t *in, size_t nblocks, uint8_t
     HIPCHK(hipSetDevice(c->device));
     int rc;
     if ((rc = stage_in(c, nullptr, 0, in, 16 * nblocks))) return rc;
-    if ((rc = enqueue_main(c, MODE_ECB, nullptr, nullptr, 0, c->st_in, 16 * (u64)nblocks, c->st_out, 0, c->stream, nullptr))) return rc;
+    if ((rc = msg_run(c, MsgCall{MSG_RAW, MODE_ECB, nullptr, nullptr, 0, c->st_in, 16 * (u64)nblocks, c->st_out, 0, nullptr, 0, true}, c->stream))) return rc;
     HIPCHK(hipMemcpyAsync(out, c->st_out, 16 * nblocks, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return AESGCM_OK;
@@ -360,7 +361,7 @@ int aesgcm_keystream_dev(aesgcm_ctx *c, const uint8_t iv[12], uint64_t first_blo
     if (first_block + nblocks > (((u64)1) << 32) - 2) return AESGCM_ETOOLONG;
     if (!nblocks) return AESGCM_OK;
     HIPCHK(hipSetDevice(c->device));
-    return enqueue_main(c, MODE_KS, iv, nullptr, 0, d_out /*unused in*/, 16 * nblocks, d_out, first_block, pick_stream(c, stream), nullptr);
+    return msg_run(c, MsgCall{MSG_RAW, MODE_KS, iv, nullptr, 0, d_out /*unused in*/, 16 * nblocks, d_out, first_block, nullptr, 0, true}, pick_stream(c, stream));
 }
 
 int aesgcm_keystream(aesgcm_ctx *c, const uint8_t iv[12], uint64_t first_block, uint64_t nblocks, uint8_t *out) {
@@ -382,11 +383,9 @@ int aesgcm_ghash(aesgcm_ctx *c, const uint8_t *data, size_t len, uint8_t y[16]) 
     HIPCHK(hipSetDevice(c->device));
     int rc;
     if ((rc = stage_in(c, data, len, nullptr, 0))) return rc;
-    Partials pp;
     uint8_t iv0[12] = {0};
-    // the data rides in the AAD slot of the GHASH sequence (GHASH only, no AES)
-    if ((rc = enqueue_main(c, MODE_ENC, iv0, c->st_aad, len, c->st_in, 0, c->st_out, 0, c->stream, &pp))) return rc;
-    if ((rc = enqueue_combine(c, combine_with_items(plan_combine_poly(pp.ptr, pp.np, pp.kind, 1, c->d_tag), pp.eA), c->stream))) return rc;   // Y = P * H
+    // the data rides in the AAD slot of the GHASH sequence (GHASH only, no AES): one k_main launch, then Y = P * H
+    if ((rc = msg_run(c, MsgCall{MSG_POLY, MODE_ENC, iv0, c->st_aad, len, c->st_in, 0, c->st_out, 0, c->d_tag, 1, true}, c->stream))) return rc;
     HIPCHK(hipMemcpyAsync(y, c->d_tag, 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return AESGCM_OK;
@@ -408,31 +407,8 @@ int aesgcm_shard_crypt_dev(aesgcm_ctx *c, int decrypt, const uint8_t iv[12], con
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, stream);
     const u64 after = total_blocks - (first_block + my_blocks);            // blocks of the message behind this shard
-    {   // mid-size shards: one k_body launch of cyclic rows, its items straight to the weighted partial W = P H^after
-        Partials pc;
-        bool took;
-        if ((rc = enqueue_cyc(c, decrypt ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, first_block, st, &pc, &took))) return rc;
-        if (took) return enqueue_combine(c, combine_with_items(plan_combine_poly(pc.ptr, pc.np, pc.kind, after, (uint4 *)d_partial), pc.eA, pc.tail_item, pc.tail_blocks), st);
-    }
-    BodySplit b;
-    if (ctx_body_split(c, len, first_block, &b)) {
-        if (!aad_len && !b.head_blocks && len == 16 * b.body_blocks) {
-            // the shard is one aligned body (the 8-GPU job's shape: 4 GiB at a multiple of 256 blocks): its items go straight to the
-            // weighted partial W = P H^after -- no chaining value, one k_combine instead of memset + carry combine + weighting combine
-            Partials pb;
-            if ((rc = enqueue_body(c, decrypt ? MODE_DEC : MODE_ENC, iv, b, d_in, d_out, first_block, st, &pb))) return rc;
-            return enqueue_combine(c, combine_with_items(plan_combine_poly(pb.ptr, pb.np, pb.kind, after, (uint4 *)d_partial), pb.eA), st);
-        }
-        uint4 *state = c->d_tag + 2;
-        HIPCHK(hipMemsetAsync(state, 0, 16, st));
-        if ((rc = absorb_range(c, decrypt ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, first_block, st, state))) return rc;
-        CombineParams q = plan_combine_poly(nullptr, 0, PARTS_NONE, 0, (uint4 *)d_partial);       // W = Y * H^after
-        q.carry = state; q.has_carry = 1; q.e_carry = after;
-        return enqueue_combine(c, q, st);
-    }
-    Partials pp;
-    if ((rc = enqueue_main(c, decrypt ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, first_block, st, &pp))) return rc;
-    return enqueue_combine(c, combine_with_items(plan_combine_poly(pp.ptr, pp.np, pp.kind, after, (uint4 *)d_partial), pp.eA), st);
+    // the launches a range of this size takes (cyclic rows, dealt chunks, k_main), closed by the weighted partial W = P H^after
+    return msg_run(c, MsgCall{MSG_POLY, decrypt ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, first_block, (uint4 *)d_partial, after, false}, st);
 }
 
 int aesgcm_shard_finalize_strided_dev(aesgcm_ctx *c, const uint8_t iv[12], const void *d_partials, size_t n_partials, size_t stride_bytes,
@@ -443,7 +419,7 @@ int aesgcm_shard_finalize_strided_dev(aesgcm_ctx *c, const uint8_t iv[12], const
     hipStream_t st = pick_stream(c, stream);
     CombineParams q = plan_combine_tag((const uint4 *)d_partials, (u32)n_partials, PARTS_GATHERED, iv, aad_len, total_len, c->d_tag);
     q.stride = (u32)(stride_bytes / 16);
-    int rc = enqueue_combine(c, q, st);
+    int rc = launch_combine(c, q, st);
     if (rc) return rc;
     if (tag) return fetch_tag(c, st, tag);
     return AESGCM_OK;
@@ -581,7 +557,7 @@ int aesgcm_stream_final(aesgcm_ctx *c, uint8_t tag[16]) {
     HIPCHK(hipSetDevice(c->device));
     int rc;
     if ((rc = session_wait(c, c->stream))) return rc;
-    if ((rc = enqueue_combine(c, plan_combine_final(c->d_tag + 1, c->s.iv, c->s.aad_len, c->s.len, c->d_tag), c->stream))) return rc;
+    if ((rc = launch_combine(c, plan_combine_final(c->d_tag + 1, c->s.iv, c->s.aad_len, c->s.len, c->d_tag), c->stream))) return rc;
     if ((rc = fetch_tag(c, c->stream, tag))) return rc;
     c->s.active = false;
     return AESGCM_OK;
@@ -960,12 +936,11 @@ int aesgcm_ctx_ceiling_probe(aesgcm_ctx *c, size_t nbytes, double *ms, uint64_t 
     BodySplit b;
     if (!plan_body_split(nbytes, 0, c->tw_override, 0, &b)) return AESGCM_EARG;
     const uint8_t iv[12] = {0};
-    Partials pp;
     const bool was = c->timing;
     c->timing = true;
     HIPCHK(hipStreamSynchronize(c->stream));
     const size_t mark = c->ev.size();
-    int rc = enqueue_body(c, MODE_PROBE, iv, b, nullptr, nullptr, 0, c->stream, &pp);
+    int rc = msg_run(c, MsgCall{MSG_PROBE, MODE_PROBE, iv, nullptr, 0, nullptr, nbytes, nullptr, 0, nullptr, 0, false}, c->stream);
     c->timing = was;
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));

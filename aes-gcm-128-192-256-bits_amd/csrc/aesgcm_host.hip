@@ -1,7 +1,15 @@
-// aesgcm_host.hip -- the host runtime of libaesgcm_hip.so: contexts and per-device state, the launch planners (which launches a message takes: DESIGN.md section 6),
-// the shape rules of the packet paths (section 8), the scratch and the cut of the row path (aesgcm_rows.h), the pipelined host-buffer path.  No device code and no
-// kernel name in this file: launches go through the klaunch_* functions of aesgcm_kernels.hip (aesgcm_internal.h).
+// aesgcm_host.hip -- the host runtime of libaesgcm_hip.so: contexts and per-device state, the runner of single messages, the shape rules of the packet paths
+// (DESIGN.md section 8), the scratch and the cut of the row path (aesgcm_rows.h), the pipelined host-buffer path.  No device code and no kernel name in this file:
+// launches go through the klaunch_* functions of aesgcm_kernels.hip (aesgcm_internal.h).
+// Single messages are PLAN, THEN RUN.  Which launches a whole message, a shard, a streaming chunk or aesgcm_ghash takes is decided by
+// msg_plan (aesgcm_msgplan.h: no HIP call, no context) from the call, the context's options and the addresses of its scratch -- k_main, k_body dealt or cyclic and
+// in which shape, the k_fold levels, who closes the tag, the k_combine launches, each with its finished parameter struct.  msg_run below walks that list on a stream
+// and owns everything that touches the runtime, once: growing `parts` to what the plan needs, the trace and the event pair of a timed launch, last_np and
+// last_shape, the fused-launch event, the queue sets' toggle behind a dealt launch, a generation number taken for every launch that publishes and given back when
+// it fails, the error texts, and the stop at the first step that fails.  The CPU harness walks the same plans with its kernel emulators (tests/host_emul), and
+// tests/golden/launch_plan_msg.txt pins them launch by launch (tests/fake_hip/msg_drive.py).
 #include "aesgcm_internal.h"
+#include "aesgcm_msgplan.h"
 
 #include <algorithm>
 #include <new>
@@ -73,155 +81,7 @@ int grow_parts(aesgcm_ctx *c, size_t need) {
     return AESGCM_OK;
 }
 
-// device address of the key's precomputed table of H^e, or NULL
-static const uint4 *ptab_ptr(const aesgcm_ctx *c, u64 e) {
-    const int k = ptab_index(e);
-    return k < 0 ? nullptr : reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(c->km) + offsetof(KeyMaterial, ptab)) + (size_t)k * 512;
-}
-// k_fold levels: n items (period, eA, eB as in FoldParams) -> one item (left in parts, fold_a or fold_b)
-int enqueue_fold(aesgcm_ctx *c, const uint4 *items, u32 n, u32 period, u64 eA, u64 eB, hipStream_t st, Partials *po, const FoldClose *close) {
-    const uint4 *cur = items;
-    int which = 0;
-    while (n > 1) {
-        // the last level(s) can be k_combine's own: up to 64 items whose spacing has precomputed tables
-        if (period <= 1 && n <= COMBINE_MAX_ITEMS && ptab_ptr(c, eA) && (n <= 4 || ptab_ptr(c, 4 * eA)) && (n <= 16 || ptab_ptr(c, 16 * eA))) {
-            po->ptr = cur; po->np = n; po->kind = PARTS_ITEM; po->eA = eA;
-            return AESGCM_OK;
-        }
-        FoldParams f;
-        plan_fold(f, cur, which ? c->fold_b : c->fold_a, n, period, eA, eB);
-        f.tabA = ptab_ptr(c, f.eA); f.tabB = ptab_ptr(c, f.eB); f.tabC = ptab_ptr(c, f.eC);
-        const u32 G = fold_wgs(n, f.group);
-        if (close && G <= FOLD_CLOSE_MAX_WGS) {
-            // a whole message: this level closes the tag itself (FoldClose) -- no further level, no k_combine.  Every closing workgroup stages the lanes' tables (33 KB)
-            // and spends ~4 us: the 256 workgroups of a 1 GiB message's first level are one round on the chip and the step gains 11 us (cfg2: 976 -> 963 us); the
-            // 2048 of 16 GiB would be eight rounds and cost what they save (profiles/archive/r03c/fold_close_ab.txt), so there the first level stays plain and the second
-            // (64 workgroups) closes
-            f.close = *close;
-            f.close.on = 1; f.close.step = fold_out_step(f);
-            HIPCHK(klaunch_fold(G, true, st, c->km, f));
-            po->done = true;
-            return AESGCM_OK;
-        }
-        if (G > (which ? FOLD_B_ITEMS : FOLD_A_ITEMS)) { snprintf(g_err, sizeof g_err, "k_fold: %u output items do not fit the level's buffer", G); return AESGCM_EHIP; }
-        HIPCHK(klaunch_fold(G, false, st, c->km, f));
-        eA = fold_out_step(f); eB = 0; period = 1;
-        cur = f.out; n = G; which ^= 1;
-    }
-    po->ptr = cur; po->np = 1; po->kind = PARTS_ITEM;
-    return AESGCM_OK;
-}
-
-// the context's cut of a range into head / k_body (dealt chunks) / tail
-bool ctx_body_split(const aesgcm_ctx *c, u64 len, u64 first_block, BodySplit *b) {
-    return plan_body_split(len, first_block, c->tw_override, c->body_min, b);
-}
-// Enqueue the fused kernel over (aad, data) and the k_fold levels over its chunk items; describe the result for k_combine.  mode ENC/DEC: GHASH partials.  mode KS/ECB: no GHASH.
-int enqueue_main(aesgcm_ctx *c, int mode, const uint8_t iv[12], const void *d_aad, u64 aad_len,
-                        const void *d_in, u64 len, void *d_out, u64 first_block, hipStream_t st, Partials *po, bool want_tail) {
-    const bool gh = (mode == MODE_ENC || mode == MODE_DEC);
-    if (po) *po = Partials();
-    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return AESGCM_EALIGN;
-    MainParams p;
-    memset(&p, 0, sizeof p);
-    const u32 C = plan_main(p, mode, c->tw_override, iv, d_aad, aad_len, d_in, len, d_out, first_block, nullptr);
-    if (!C) return AESGCM_OK;
-    int rc;
-    if (gh && (rc = grow_parts(c, C))) return rc;
-    p.parts = c->parts;
-    u32 wgs = (C + 1 + AESGCM_MAIN_WG / 64 - 1) / (AESGCM_MAIN_WG / 64);      // one wave per chunk is enough for small inputs (+ one spare for E_K(J0))
-    if (wgs > (u32)c->G) wgs = (u32)c->G;
-    plan_queues(C, &p.nq, &p.seg);
-    if ((u64)wgs * (AESGCM_MAIN_WG / 64) >= (u64)C + 1) p.nq = 0;   // a wave per chunk and a spare: static assignment, the dispensers are not touched
-    p.counter = c->d_counter + 16 * (1 + AESGCM_NQ * c->qset);
-    p.counter_zero = c->d_counter + 16 * (1 + AESGCM_NQ * (c->qset ^ 1u));
-    if (gh && po) { p.ej0 = c->d_tag + 3; po->ej0 = p.ej0; }
-    if (gh && po && want_tail && C == 1) { p.tail = 1; p.tag_out = c->d_tag; p.tag_host = c->h_tag_dev; p.gen = gen_take(c); po->done = true; }
-    p.trace = nullptr;
-    const bool timed = c->timing && !c->timing_mute;
-    if (timed) {
-        p.trace = c->d_trace;
-        HIPCHK(hipMemsetAsync(c->d_trace, 0, sizeof(u64) * 4 * AESGCM_GMAX, st));
-    }
-    if (!c->timing_mute) c->last_np = wgs;
-    std::pair<hipEvent_t, hipEvent_t> evp;
-    if (timed) {
-        if (!c->ev_pool.empty()) { evp = c->ev_pool.back(); c->ev_pool.pop_back(); }
-        else { HIPCHK(hipEventCreate(&evp.first)); HIPCHK(hipEventCreate(&evp.second)); }
-        HIPCHK(hipEventRecord(evp.first, st));
-    }
-    {
-        const hipError_t le = klaunch_main(mode, c->nr, wgs, st, c->km, c->tables, p);
-        if (le != hipSuccess) {                      // nothing ran: the queues were not touched on the device
-            if (timed) c->ev_pool.push_back(evp);
-            if (p.tail) gen_give_back(c);
-            return hip_fail(le, "k_main launch");
-        }
-        if (p.nq) c->qset ^= 1u;                      // the launch leaves the other set zeroed for the next dynamic one
-        if (c->ev_fused) HIPCHK(hipEventRecord(c->ev_fused, st));
-    }
-    if (timed) { HIPCHK(hipEventRecord(evp.second, st)); c->ev.push_back(evp); }
-    if (gh && po && po->done) return AESGCM_OK;                   // the launch finished the tag itself
-    if (gh && po) {
-        const u64 eA = (u64)64 * p.Tw;
-        if (C <= COMBINE_MAX_ITEMS && (C == 1 || (ptab_ptr(c, eA) && (C <= 4 || ptab_ptr(c, 4 * eA)) && (C <= 16 || ptab_ptr(c, 16 * eA))))) {
-            po->ptr = c->parts; po->np = C; po->kind = PARTS_ITEM; po->eA = eA;   // few chunks: k_combine folds them, no k_fold launch
-            return AESGCM_OK;
-        }
-        return enqueue_fold(c, c->parts, C, 1, eA, 0, st, po);
-    }
-    return AESGCM_OK;
-}
-
-
-// one k_body launch (dealt chunks or cyclic rows) with the context's timing and event bookkeeping
-int launch_body(aesgcm_ctx *c, int mode, BodyParams &p, u32 wgs, hipStream_t st) {
-    const bool cyc = p.cyc != 0, half = cyc && p.cw == BODY_CYC_WAVES_HALF;
-    if (cyc && mode == MODE_PROBE) return AESGCM_EARG;
-    if (half && !p.fuse) return AESGCM_EARG;                    // the half shape exists with the in-launch closing only
-    if (c->timing) { p.trace = c->d_trace; HIPCHK(hipMemsetAsync(c->d_trace, 0, sizeof(u64) * 4 * AESGCM_GMAX, st)); }
-    c->last_np = wgs;
-    std::pair<hipEvent_t, hipEvent_t> evp;
-    if (c->timing) {
-        if (!c->ev_pool.empty()) { evp = c->ev_pool.back(); c->ev_pool.pop_back(); }
-        else { HIPCHK(hipEventCreate(&evp.first)); HIPCHK(hipEventCreate(&evp.second)); }
-        HIPCHK(hipEventRecord(evp.first, st));
-    }
-    const hipError_t le = klaunch_body(mode, c->nr, cyc, half, wgs, st, c->km, c->tables, p);
-    if (le != hipSuccess) {
-        if (c->timing) c->ev_pool.push_back(evp);
-        return hip_fail(le, "k_body launch");
-    }
-    if (!cyc) c->qset ^= 1u;
-    if (c->timing) { HIPCHK(hipEventRecord(evp.second, st)); c->ev.push_back(evp); }
-    if (c->ev_fused) HIPCHK(hipEventRecord(c->ev_fused, st));
-    return AESGCM_OK;
-}
-// k_body over the planned split + the k_fold levels over its interleaved chunk items
-int enqueue_body(aesgcm_ctx *c, int mode, const uint8_t iv[12], const BodySplit &b, const void *d_in, void *d_out,
-                        u64 first_block, hipStream_t st, Partials *po, const FoldClose *close) {
-    BodyParams p;
-    memset(&p, 0, sizeof p);
-    int rc = grow_parts(c, (size_t)4 * b.S);
-    if (rc) return rc;
-    plan_body(p, b, iv, d_in, d_out, first_block, c->parts);
-    p.ej0 = c->d_tag + 3; po->ej0 = p.ej0;
-    const u32 waves_per_wg = AESGCM_BODY_WG / 64;
-    u32 wgs = (p.C + waves_per_wg - 1) / waves_per_wg;
-#if AESGCM_T4
-    if (wgs > (u32)c->G / 2) wgs = (u32)c->G / 2;                 // one 136 KiB workgroup per CU
-#else
-    if (wgs > (u32)c->G) wgs = (u32)c->G;
-#endif
-    plan_queues(p.C, &p.nq, &p.seg);
-    p.counter = c->d_counter + 16 * (1 + AESGCM_NQ * c->qset);
-    p.counter_zero = c->d_counter + 16 * (1 + AESGCM_NQ * (c->qset ^ 1u));
-    if ((rc = launch_body(c, mode, p, wgs, st))) return rc;
-    // items 4s + v: phases 64 blocks apart inside a super-chunk, super-chunks 256 T blocks apart
-    return enqueue_fold(c, c->parts, p.C, 4, 64, (u64)256 * b.T, st, po, close);
-}
-// A whole range -- AAD, data from any first block, ragged end -- as ONE k_body launch of cyclic rows (plan_body_cyc) and the k_fold level over its
-// 4096 items, when the range is of that size (*took says whether it was).  po describes the items and the partial last row for k_combine.
+// ---------------------------------------------------------------- single messages: plan (aesgcm_msgplan.h), then run
 bool cyc_capable(const aesgcm_ctx *c) {
 #if AESGCM_T4
     return (u32)c->G / 2 * (AESGCM_BODY_WG / 64) == BODY_CYC_WAVES && c->cyc_max_pieces > c->cyc_min_fused;
@@ -242,98 +102,77 @@ bool others_in_flight(const aesgcm_ctx *c) {
     }
     return false;
 }
-int enqueue_cyc(aesgcm_ctx *c, int mode, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out,
-                       u64 first_block, hipStream_t st, Partials *po, bool *took, bool whole_message_tag) {
-    *took = false;
-    const bool fused = whole_message_tag && c->cyc_fuse;
-    if (!cyc_capable(c) || len < (fused ? c->cyc_min_fused : c->cyc_min)) return AESGCM_OK;
-    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return AESGCM_OK;     // the caller's other path reports the alignment
-    int rc = grow_parts(c, (size_t)BODY_CYC_WAVES + 1);
-    if (rc) return rc;
-    BodyParams p;
-    // a range with pieces around its body (AAD, an odd first block, a ragged end) costs the other paths a launch pair per piece (+45 .. 80 us,
-    // profiles/archive/r03c/general_shape.txt): for those the cyclic launch stays ahead for longer
-    const bool pieces = aad_len || (first_block & 255) || (len & 1023);
-    const u64 lo = fused ? c->cyc_min_fused : c->cyc_min, hi = pieces ? c->cyc_max_pieces : fused ? c->cyc_max_fused : c->cyc_max;
-    const bool half = fused && len < c->cyc_half_max && (c->cyc_half == 1 || (c->cyc_half == 2 && others_in_flight(c)));   // two workgroups per CU: for messages in flight beside each other
-    if (!plan_body_cyc(p, mode, iv, d_aad, aad_len, d_in, len, d_out, first_block, c->parts, lo, hi, half ? BODY_CYC_WAVES_HALF : BODY_CYC_WAVES)) return AESGCM_OK;
-    *took = true;
-    *po = Partials();
-    p.prio_rows = c->cyc_prio;
-    if (fused) {                                                                // the launch closes the tag itself (cyc_close): nothing behind it
-        p.fuse = 1; p.aad_len = aad_len; p.ct_len = len; p.acc = c->d_cyc;
-        p.tag_out = c->d_tag; p.tag_host = c->h_tag_dev; p.gen = gen_take(c);
-        po->done = true;
-        c->last_shape = half ? AESGCM_LAUNCH_CYCLIC_HALF : AESGCM_LAUNCH_CYCLIC;
-        rc = launch_body(c, mode, p, half ? BODY_CYC_WAVES_HALF / (AESGCM_BODYH_WG / 64) : BODY_CYC_WAVES / (AESGCM_BODY_WG / 64), st);
-        if (rc) gen_give_back(c);
-        return rc;
-    }
-    p.ej0 = c->d_tag + 3; po->ej0 = p.ej0;
-    if ((rc = launch_body(c, mode, p, BODY_CYC_WAVES / (AESGCM_BODY_WG / 64), st))) return rc;
-    if ((rc = enqueue_fold(c, c->parts, BODY_CYC_WAVES, 1, 64, 0, st, po))) return rc;       // always BODY_CYC_WAVES items, 64 blocks apart
-    if (p.tb) { po->tail_item = c->parts + (size_t)BODY_CYC_WAVES * 64; po->tail_blocks = p.tb; }
-    return AESGCM_OK;
-}
 
-// Y' = Y * H^nb ^ P(aad, data) for a whole range, Y in *state (device).  Large ranges go head / k_body / tail,
-// each piece folded into the state in order; small ones are a single k_main launch.
-int absorb_range(aesgcm_ctx *c, int mode, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len,
-                        void *d_out, u64 first_block, hipStream_t st, uint4 *state, const uint4 **ej0) {
-    BodySplit b;
-    Partials pp;
-    int rc;
-    {   // mid-size ranges: the whole range in one k_body launch of cyclic rows
-        bool took;
-        if ((rc = enqueue_cyc(c, mode, iv, d_aad, aad_len, d_in, len, d_out, first_block, st, &pp, &took))) return rc;
-        if (took) {
-            if (ej0) *ej0 = pp.ej0;
-            const u64 nb = (aad_len + 15) / 16 + (len + 15) / 16;
-            return enqueue_combine(c, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.kind, state, nb), pp.eA, pp.tail_item, pp.tail_blocks), st);
-        }
-    }
-    if (!ctx_body_split(c, len, first_block, &b)) {
-        if ((rc = enqueue_main(c, mode, iv, d_aad, aad_len, d_in, len, d_out, first_block, st, &pp))) return rc;
-        const u64 nb = (aad_len + 15) / 16 + (len + 15) / 16;
-        return nb ? enqueue_combine(c, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.kind, state, nb), pp.eA), st) : AESGCM_OK;
-    }
-    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return AESGCM_EALIGN;
-    const u64 n_aad = (aad_len + 15) / 16;
-    if (n_aad + b.head_blocks) {
-        c->timing_mute = true;
-        rc = enqueue_main(c, mode, iv, d_aad, aad_len, d_in, 16 * b.head_blocks, d_out, first_block, st, &pp);
-        c->timing_mute = false;
-        if (rc) return rc;
-        if ((rc = enqueue_combine(c, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.kind, state, n_aad + b.head_blocks), pp.eA), st))) return rc;
-    }
-    if ((rc = enqueue_body(c, mode, iv, b, d_in, d_out, first_block, st, &pp))) return rc;
-    if (ej0) *ej0 = pp.ej0;                                      // valid until the next launch on this context overwrites the slot: consumed by the caller's final combine
-    if ((rc = enqueue_combine(c, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.kind, state, b.body_blocks), pp.eA), st))) return rc;
-    const u64 done = b.head_blocks + b.body_blocks, tail = len - 16 * done;
-    if (tail) {
-        c->timing_mute = true;
-        rc = enqueue_main(c, mode, iv, nullptr, 0, (const unsigned char *)d_in + 16 * done, tail, (unsigned char *)d_out + 16 * done,
-                          first_block + done, st, &pp);
-        c->timing_mute = false;
-        if (rc) return rc;
-        if ((rc = enqueue_combine(c, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.kind, state, (tail + 15) / 16), pp.eA), st))) return rc;
-    }
-    return AESGCM_OK;
-}
-
-int enqueue_combine(aesgcm_ctx *c, const CombineParams &p0, hipStream_t st) {
-    CombineParams p = p0;
+// k_combine on `st`; a result that goes to the tag slot is mirrored to the pinned host slot under a new generation number.  Beside the runner, for the calls whose
+// one launch is no message's plan: the tag from a chaining value (aesgcm_stream_final, the pipelined path) and from gathered partials (aesgcm_shard_finalize_*)
+int launch_combine(aesgcm_ctx *c, CombineParams p, hipStream_t st) {
     const bool to_slot = p.out == c->d_tag;
-    if (to_slot) { p.out_host = c->h_tag_dev; p.gen = gen_take(c); }          // results that go to the tag slot are mirrored to the pinned host slot
-    if (p.kind == PARTS_ITEM && p.np > 1) {                       // the launch folds the items itself: tables of H^eA, H^(8 eA)
-        p.tabA = ptab_ptr(c, p.eA);
-        p.tabB = p.np > 4 ? ptab_ptr(c, 4 * p.eA) : nullptr;
-        p.tabC = p.np > 16 ? ptab_ptr(c, 16 * p.eA) : nullptr;
-        if (p.np > COMBINE_MAX_ITEMS || !p.tabA || (p.np > 4 && !p.tabB) || (p.np > 16 && !p.tabC)) { if (to_slot) gen_give_back(c); snprintf(g_err, sizeof g_err, "k_combine: %u items, spacing %llu not foldable in the launch", p.np, (unsigned long long)p.eA); return AESGCM_EHIP; }
-    }
+    if (to_slot) { p.out_host = c->h_tag_dev; p.gen = gen_take(c); }
     const hipError_t le = klaunch_combine(st, c->km, c->tables, p);
     if (le != hipSuccess) { if (to_slot) gen_give_back(c); return hip_fail(le, "k_combine launch"); }
     return AESGCM_OK;
+}
+// k_main or k_body as the step says, with the context's timing (trace, event pair) around it when it is the measured launch
+static int launch_rows(aesgcm_ctx *c, MsgStep &t, hipStream_t st) {
+    const bool main = t.kind == MsgStep::MAIN, timed = c->timing && t.measured;
+    u64 **trace = main ? &t.m.trace : &t.b.trace;
+    u64 *gen = main ? &t.m.gen : &t.b.gen;
+    if (timed) { *trace = c->d_trace; HIPCHK(hipMemsetAsync(c->d_trace, 0, sizeof(u64) * 4 * AESGCM_GMAX, st)); }
+    if (t.measured) c->last_np = t.wgs;
+    std::pair<hipEvent_t, hipEvent_t> evp;
+    if (timed) {
+        if (!c->ev_pool.empty()) { evp = c->ev_pool.back(); c->ev_pool.pop_back(); }
+        else { HIPCHK(hipEventCreate(&evp.first)); HIPCHK(hipEventCreate(&evp.second)); }
+        HIPCHK(hipEventRecord(evp.first, st));
+    }
+    if (t.publishes) *gen = gen_take(c);
+    const hipError_t le = main ? klaunch_main(t.mode, c->nr, t.wgs, st, c->km, c->tables, t.m)
+                               : klaunch_body(t.mode, c->nr, t.b.cyc != 0, t.b.cyc && t.b.cw == BODY_CYC_WAVES_HALF, t.wgs, st, c->km, c->tables, t.b);
+    if (le != hipSuccess) {                          // nothing ran: the queues were not touched on the device
+        if (timed) c->ev_pool.push_back(evp);
+        if (t.publishes) gen_give_back(c);
+        return hip_fail(le, main ? "k_main launch" : "k_body launch");
+    }
+    if (t.dealt) c->qset ^= 1u;                       // the launch leaves the other set zeroed for the next dealt one
+    if (timed) { HIPCHK(hipEventRecord(evp.second, st)); c->ev.push_back(evp); }
+    if (c->ev_fused) HIPCHK(hipEventRecord(c->ev_fused, st));
+    return AESGCM_OK;
+}
+// The launches of a call on `st`: what msg_plan decides, step by step, up to the first that fails.  The plan is made against the context as it stands -- its options,
+// its scratch (parts grown first to what the plan needs), the queue set in turn -- and every launch that publishes takes its generation number as it is made.
+int msg_run(aesgcm_ctx *c, const MsgCall &call, hipStream_t st) {
+    const MsgRules rules = {(u32)c->G, c->tw_override, c->body_min, cyc_capable(c), c->cyc_fuse, c->fold_close, c->cyc_half, c->cyc_prio,
+                            c->cyc_min, c->cyc_min_fused, c->cyc_half_max, c->cyc_max, c->cyc_max_fused, c->cyc_max_pieces};
+    int in_flight = -1;                               // asked once at most, however often the plan is made
+    auto others = [&] { if (in_flight < 0) in_flight = others_in_flight(c); return in_flight != 0; };
+    MsgPlan pl;
+    for (;;) {
+        const MsgScratch s = {c->parts, c->fold_a, c->fold_b, c->d_tag, c->h_tag_dev, {c->d_counter + 16 * 1, c->d_counter + 16 * (1 + AESGCM_NQ)}, c->qset, c->d_cyc,
+                              reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(c->km) + offsetof(KeyMaterial, ptab))};
+        msg_plan(pl, call, rules, s, others);
+        if (pl.parts_need <= c->parts_cap) break;
+        const int rc = grow_parts(c, pl.parts_need);
+        if (rc) return rc;
+    }
+    if (call.goal == MSG_TAG) c->last_shape = pl.shape;
+    for (u32 k = 0; k < pl.n; k++) {
+        MsgStep &t = pl.step[k];
+        int rc = AESGCM_OK;
+        switch (t.kind) {
+        case MsgStep::CLEAR: HIPCHK(hipMemsetAsync(t.clear, 0, 16, st)); break;
+        case MsgStep::MAIN: case MsgStep::BODY: rc = launch_rows(c, t, st); break;
+        case MsgStep::FOLD: {
+            if (t.publishes) t.f.close.gen = gen_take(c);
+            const hipError_t le = klaunch_fold(t.wgs, t.publishes, st, c->km, t.f);
+            if (le != hipSuccess) { if (t.publishes) gen_give_back(c); rc = hip_fail(le, "k_fold launch"); }
+            break;
+        }
+        case MsgStep::COMBINE: rc = launch_combine(c, t.c, st); break;
+        }
+        if (rc) return rc;
+    }
+    if (pl.fold_overflow) snprintf(g_err, sizeof g_err, "k_fold: %u output items do not fit the level's buffer", pl.fold_overflow);
+    return pl.rc;
 }
 
 int check_lengths(u64 aad_len, u64 len) {
@@ -350,53 +189,7 @@ int crypt_dev(aesgcm_ctx *c, int dec, const uint8_t iv[12], const void *d_aad, u
     if (aad_len && !d_aad) return AESGCM_EARG;
     if (len && (!d_in || !d_out)) return AESGCM_EARG;
     HIPCHK(hipSetDevice(c->device));
-    {   // mid-size messages: k_body as cyclic rows takes AAD, data and the ragged end in one launch; its items go straight to the tag
-        Partials pc;
-        bool took;
-        if ((rc = enqueue_cyc(c, dec ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, 0, st, &pc, &took, true))) return rc;
-        if (took && pc.done) return AESGCM_OK;                   // the launch left the tag in d_tag and in the host slot
-        if (took) {
-            c->last_shape = AESGCM_LAUNCH_CYCLIC;
-            CombineParams q = combine_with_items(plan_combine_tag(pc.ptr, pc.np, pc.kind, iv, aad_len, len, c->d_tag), pc.eA, pc.tail_item, pc.tail_blocks);
-            q.ej0 = pc.ej0;
-            return enqueue_combine(c, q, st);
-        }
-    }
-    BodySplit b;
-    if (ctx_body_split(c, len, 0, &b)) {
-        c->last_shape = AESGCM_LAUNCH_DEALT;
-        if (!aad_len && !b.head_blocks && len == 16 * b.body_blocks) {
-            // the whole message is one aligned body (the benchmark's shape): no chaining value to carry, k_body's items go
-            // straight to the tag
-            Partials pb;
-            FoldClose fc = {};
-            if (c->fold_close) {                                 // k_fold's first level closes the tag (when there is a k_fold launch at all)
-                fc.aad_len = 0; fc.ct_len = len; fc.ej0 = c->d_tag + 3; fc.acc = c->d_cyc;
-                fc.tag_out = c->d_tag; fc.tag_host = c->h_tag_dev; fc.gen = gen_now(c) + 1;
-            }
-            if ((rc = enqueue_body(c, dec ? MODE_DEC : MODE_ENC, iv, b, d_in, d_out, 0, st, &pb, c->fold_close ? &fc : nullptr))) return rc;
-            if (pb.done) { gen_take(c); return AESGCM_OK; }
-            CombineParams q = combine_with_items(plan_combine_tag(pb.ptr, pb.np, pb.kind, iv, 0, len, c->d_tag), pb.eA);
-            q.ej0 = pb.ej0;
-            return enqueue_combine(c, q, st);
-        }
-        // large message: head / k_body / tail folded into a device-side chaining value, then the tag from it
-        uint4 *state = c->d_tag + 2;
-        HIPCHK(hipMemsetAsync(state, 0, 16, st));
-        const uint4 *ej0 = nullptr;
-        if ((rc = absorb_range(c, dec ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, 0, st, state, &ej0))) return rc;
-        CombineParams q = plan_combine_final(state, iv, aad_len, len, c->d_tag);
-        q.ej0 = ej0;                                             // left by k_body (every piece of this message writes the same value)
-        return enqueue_combine(c, q, st);
-    }
-    Partials pp;
-    c->last_shape = AESGCM_LAUNCH_MAIN;
-    rc = enqueue_main(c, dec ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, 0, st, &pp, true);
-    if (rc) return rc;
-    if (pp.done) return AESGCM_OK;                               // single chunk: k_main's tail left the tag in d_tag and in the host slot
-    CombineParams q = combine_with_items(plan_combine_tag(pp.ptr, pp.np, pp.kind, iv, aad_len, len, c->d_tag), pp.eA);
-    q.ej0 = pp.ej0;                                              // same IV, same stream: k_main left E_K(IV || 1) behind
-    return enqueue_combine(c, q, st);
+    return msg_run(c, MsgCall{MSG_TAG, dec ? MODE_DEC : MODE_ENC, iv, d_aad, aad_len, d_in, len, d_out, 0, nullptr, 0, false}, st);
 }
 
 // The tag of the last result enqueued for the host slot: the kernel stores it in pinned host memory and then publishes
@@ -641,21 +434,11 @@ int stream_open(aesgcm_ctx *c, const uint8_t iv[12], int decrypt, hipStream_t st
     return AESGCM_OK;
 }
 // Y' = Y * H^nb ^ P(aad, data) on `st` (NULL: the context's stream).  large: the range may be of any size on device pointers (aesgcm_stream_update_dev) -- it takes the
-// launch structure a shard of that size takes (cyclic rows, dealt chunks; absorb_range); else one k_main launch (chunks that came through the staging buffers).
+// launch structure a shard of that size takes (cyclic rows, dealt chunks: MSG_CARRY, aesgcm_msgplan.h); else one k_main launch (chunks that came through the staging buffers).
 int stream_absorb(aesgcm_ctx *c, const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, u64 first_block, hipStream_t st, bool large) {
-    if (!st) st = c->stream;
-    const u64 nb = (aad_len + 15) / 16 + (len + 15) / 16;
-    if (large) {
-        const int rc = absorb_range(c, c->s.dec ? MODE_DEC : MODE_ENC, c->s.iv, d_aad, aad_len, d_in, len, d_out, first_block, st, c->d_tag + 1);
-        if (rc) return rc;
-        c->s.blocks += nb;
-        return AESGCM_OK;
-    }
-    Partials pp;
-    int rc = enqueue_main(c, c->s.dec ? MODE_DEC : MODE_ENC, c->s.iv, d_aad, aad_len, d_in, len, d_out, first_block, st, &pp);
-    if (rc) return rc;
-    c->s.blocks += nb;
-    return enqueue_combine(c, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.kind, c->d_tag + 1, nb), pp.eA), st);       // Y' = Y * H^nb ^ P
+    const int rc = msg_run(c, MsgCall{MSG_CARRY, c->s.dec ? MODE_DEC : MODE_ENC, c->s.iv, d_aad, aad_len, d_in, len, d_out, first_block, c->d_tag + 1, 0, !large}, st ? st : c->stream);
+    if (!rc) c->s.blocks += (aad_len + 15) / 16 + (len + 15) / 16;
+    return rc;
 }
 
 
@@ -1086,7 +869,7 @@ int crypt_pipelined(aesgcm_ctx *c, int dec, const uint8_t iv[12], const uint8_t 
         HIPCHK(hipMemcpyAsync(out + off, c->pl_buf[s], m, hipMemcpyDeviceToHost, c->pl_out));
         HIPCHK(hipEventRecord(c->pl_ev_d2h[s], c->pl_out));
     }
-    if ((rc = enqueue_combine(c, plan_combine_final(c->d_tag + 1, iv, aad_len, len, c->d_tag), c->stream))) return rc;
+    if ((rc = launch_combine(c, plan_combine_final(c->d_tag + 1, iv, aad_len, len, c->d_tag), c->stream))) return rc;
     if ((rc = fetch_tag(c, c->stream, tag))) return rc;
     HIPCHK(hipStreamSynchronize(c->pl_out));
     return AESGCM_OK;

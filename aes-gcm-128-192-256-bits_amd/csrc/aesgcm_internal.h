@@ -3,8 +3,10 @@
 //   aesgcm_kernels.hip   the kernels and, at its end, the LAUNCHERS: one plain function per kernel family (klaunch_*) that picks the template instance by the rules of
 //                        aesgcm_dispatch.h (which a host compiler alone can check) and launches it.  Nothing outside that file names a kernel, so the other two units hold no device code at all -- the host side builds and runs against
 //                        a fake HIP runtime on a machine without a GPU (tests/fake_hip: which device is current at every allocation, stream, event and launch).
-//   aesgcm_host.hip      the host runtime: contexts and per-device state, the launch planners (which launches a message takes; packets_plan, the routed loop of
+//   aesgcm_host.hip      the host runtime: contexts and per-device state, the runner of a single message's plan (msg_run), the launch planners (packets_plan, the routed loop of
 //                        packets_rows and batch_plan for the packet paths), the scratch of the row path, the pipelined host-buffer path.
+//   aesgcm_msgplan.h     which launches a single message takes: from a call, the context's options and its scratch addresses to a list of finished launches; no HIP
+//                        call, no context; included by aesgcm_host.hip, aesgcm_abi.hip and the CPU harness only (no kernel source: no device listing can move).
 //   aesgcm_plan.h        the pure part of the packet paths' planning -- shape, ILP form, deal, `plain`, grid, from counts and lengths alone -- with the
 //                        measurements behind each rule; no HIP header, as aesgcm_dispatch.h.  The planners of aesgcm_host.hip call it.
 //   aesgcm_abi.hip       the C ABI of include/aesgcm.h: argument checks and the calls into the runtime.
@@ -202,22 +204,15 @@ static inline hipStream_t pick_stream(aesgcm_ctx *c, void *s) { return s ? (hipS
 static const u64 MAX_DATA = (((u64)1) << 36) - 32;      // aes_icb.vhd:114
 static const u64 MAX_SEQ_BLOCKS = ((u64)1) << 36;
 
-// What the fold stage needs to know about the partials a launch produced.
-struct Partials { const uint4 *ptr = nullptr; u32 np = 0; u32 kind = PARTS_NONE; const uint4 *ej0 = nullptr; u64 eA = 0; bool done = false; const uint4 *tail_item = nullptr; u32 tail_blocks = 0; };   // eA: blocks between chunk items when k_combine folds them itself (np > 1)
 struct RowsScratch;
 int set_lds_attrs(int device, DeviceState *ds);
 int device_state(int device, DeviceState **out);
 int grow_parts(aesgcm_ctx *c, size_t need);
-int enqueue_fold(aesgcm_ctx *c, const uint4 *items, u32 n, u32 period, u64 eA, u64 eB, hipStream_t st, Partials *po, const FoldClose *close = nullptr);
-bool ctx_body_split(const aesgcm_ctx *c, u64 len, u64 first_block, BodySplit *b);
-int enqueue_main(aesgcm_ctx *c, int mode, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, u64 first_block, hipStream_t st, Partials *po, bool want_tail = false);
-int launch_body(aesgcm_ctx *c, int mode, BodyParams &p, u32 wgs, hipStream_t st);
-int enqueue_body(aesgcm_ctx *c, int mode, const uint8_t iv[12], const BodySplit &b, const void *d_in, void *d_out, u64 first_block, hipStream_t st, Partials *po, const FoldClose *close = nullptr);
 bool cyc_capable(const aesgcm_ctx *c);
 bool others_in_flight(const aesgcm_ctx *c);
-int enqueue_cyc(aesgcm_ctx *c, int mode, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, u64 first_block, hipStream_t st, Partials *po, bool *took, bool whole_message_tag = false);
-int absorb_range(aesgcm_ctx *c, int mode, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, u64 first_block, hipStream_t st, uint4 *state, const uint4 **ej0 = nullptr);
-int enqueue_combine(aesgcm_ctx *c, const CombineParams &p0, hipStream_t st);
+struct MsgCall;                                                          // (aesgcm_msgplan.h: host only, never seen by a kernel source)
+int msg_run(aesgcm_ctx *c, const MsgCall &call, hipStream_t st);
+int launch_combine(aesgcm_ctx *c, CombineParams p, hipStream_t st);
 int check_lengths(u64 aad_len, u64 len);
 int crypt_dev(aesgcm_ctx *c, int dec, const uint8_t iv[12], const void *d_aad, u64 aad_len, const void *d_in, u64 len, void *d_out, hipStream_t st);
 int fetch_tag(aesgcm_ctx *c, hipStream_t st, uint8_t tag[16]);

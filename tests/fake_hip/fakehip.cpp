@@ -17,7 +17,10 @@
 //     driver gave it (fake_name_stream; a name ends with its stream), "null", or "side" for a live stream nobody named.  A driver that names every stream it can
 //     reach -- its own as "caller", each context's own as "own" (plan_drive.py does) -- leaves unnamed only what the library made for itself and hands to nobody:
 //     a context's side stream.  A scalar that is 0 is left out.  fake_log reads it, fake_reset clears it: what a call decided, as text a test can compare
-//     (tests/fake_hip/plan_drive.py, tests/golden/launch_plan.txt).
+//     (tests/fake_hip/plan_drive.py, tests/golden/launch_plan.txt).  The single-message launchers (k_main, k_body, k_fold, k_combine) name the context's own buffers
+//     instead (pname: parts+item, a / b, tag+word, q0 / q1, ptab+table, ...) and every hipMemsetAsync and hipEventRecord notes a line as well -- all of it after
+//     fake_log_runtime(1) only, by a single-threaded driver
+//     (tests/fake_hip/msg_drive.py, tests/golden/launch_plan_msg.txt).
 //   * CAPTURE DISCIPLINE: hipStreamBeginCapture / hipStreamEndCapture / hipStreamIsCapturing on the fake streams (the "graph" is a count of what was enqueued).  While
 //     any stream captures, what a capture cannot carry is noted with the HIP call's name in a list of its own (fake_capture_violations, fake_capture_clear; fake_reset
 //     leaves it alone): hipMalloc, hipFree, a synchronous copy or memset, hipStreamSynchronize, hipDeviceSynchronize, hipEventSynchronize, hipEventQuery.  An event
@@ -27,6 +30,7 @@
 // To keep the host logic running, a launch that would publish a tag and its generation number to the pinned host slot publishes the number (no tag).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <set>
@@ -62,7 +66,7 @@ std::map<const void *, std::map<const void *, long>> clocks;  // per stream: its
 const void *watched = nullptr;
 
 void note(const char *fmt, ...) {
-    char b[512]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
+    char b[1536]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
     // a field that is 0 is left out (most are, in most launches): what a line does not name is zero
     std::string line;
     for (const char *q = b; *q;) {
@@ -119,6 +123,40 @@ void chk_stream(const char *what, hipStream_t s) {
 }
 // (an atomic store: the library reads the slot's generation word with an atomic load from whatever thread polls for the tag -- round 5 wrote it plainly, the one report
 // of the judge's thread-sanitizer run)
+// A pointer of a single-message launch in the log: the context buffer it points into, as a name -- parts / a / b (the k_fold ping-pong) + the item, tag + the 16-byte
+// word of d_tag, q0 / q1 (the two sets of chunk queues), ptab + the table, cyc, trace, host (the pinned tag slot) -- "1" for anything else (the caller's data), "0"
+// for NULL.  Never an address.  Takes the library's registry mutex: call it BEFORE the fake's own (LAUNCH), the order the library itself keeps.
+std::atomic<bool> log_runtime{false};                         // fake_log_runtime: the single-message launchers, hipMemsetAsync and hipEventRecord note their lines.  Off, nothing here
+                                                              // looks at another thread's context (pname reads every registered context's fields: for single-threaded drivers only)
+std::string pname(const void *p) {
+    if (!log_runtime) return "";
+    if (!p) return "0";
+    std::lock_guard<std::mutex> lk(g_mu);
+    const char *q = (const char *)p;
+    char b[48];
+    for (const aesgcm_ctx *c : g_ctxs) {
+        auto at = [&](const void *base, size_t bytes, const char *name, size_t unit) {
+            if (!base || q < (const char *)base || q >= (const char *)base + bytes) return false;
+            if (unit) snprintf(b, sizeof b, "%s+%zu", name, (size_t)(q - (const char *)base) / unit); else snprintf(b, sizeof b, "%s", name);
+            return true;
+        };
+        if (at(c->parts, c->parts_cap * 1024, "parts", 1024) || at(c->fold_a, (size_t)1024 * FOLD_A_ITEMS, "a", 1024) || at(c->fold_b, (size_t)1024 * FOLD_B_ITEMS, "b", 1024) ||
+            at(c->d_tag, 64, "tag", 16) || at(c->h_tag, 64, "host", 0) || at(c->d_cyc, 8 * (2 * CYC_ACC_SLOTS + 1), "cyc", 0) || at(c->d_trace, sizeof(u64) * 4 * AESGCM_GMAX, "trace", 0) ||
+            at(c->km ? (const char *)c->km + offsetof(KeyMaterial, ptab) : nullptr, sizeof c->km->ptab, "ptab", 8192)) return b;
+        if (c->d_counter && q >= (const char *)c->d_counter + 64 && q < (const char *)c->d_counter + 64 * (1 + 2 * AESGCM_NQ)) { snprintf(b, sizeof b, "q%zu", (size_t)(q - (const char *)c->d_counter - 64) / (64 * AESGCM_NQ)); return b; }
+    }
+    return "1";
+}
+const char *ename(hipEvent_t e) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (const aesgcm_ctx *c : g_ctxs) {
+        if (e == c->ev_fused) return "fused";
+        if (e == c->ev_session) return "session";
+        if (e == c->ev_sync) return "sync";
+        for (int i = 0; i < 2; i++) { if (e == c->pl_ev_h2d[i]) return "h2d"; if (e == c->pl_ev_k[i]) return "k"; if (e == c->pl_ev_d2h[i]) return "d2h"; }
+    }
+    return "ev";
+}
 void publish(void *slot, unsigned long long gen) { if (slot) __atomic_store_n(reinterpret_cast<unsigned long long *>(slot) + 2, gen, __ATOMIC_RELEASE); }
 }  // namespace
 
@@ -167,6 +205,7 @@ EXPORT size_t fake_log(char *buf, size_t n) {
     if (buf && n) { strncpy(buf, s.c_str(), n - 1); buf[n - 1] = 0; }
     return s.size() + 1;
 }
+EXPORT void fake_log_runtime(int on) { log_runtime = on != 0; }
 EXPORT void fake_name_stream(hipStream_t s, const char *name) { std::lock_guard<std::mutex> lk(mu); if (s) stream_names[(const void *)s] = name; }
 // FAKEHIP_REPORT=1: one line on stderr when the process ends (for drivers that are not Python: bench.py as a child process)
 namespace { struct Report { ~Report() { if (getenv("FAKEHIP_REPORT")) fprintf(stderr, "fakehip: syncs=%ld launches=%ld collectives=%ld violations=%zu touched=%u\n", n_sync, n_launch, n_collective, violations.size(), touched); } } report; }
@@ -229,7 +268,9 @@ hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) { retu
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind, hipStream_t st) { return copy("hipMemcpyAsync", dst, src, n, st, true); }
 hipError_t hipMemset(void *dst, int v, size_t n) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipMemset"); chk_ptr("hipMemset", "dst", dst); memset(dst, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t st) {
+    const std::string dn = log_runtime ? pname(dst) : std::string();
     std::lock_guard<std::mutex> lk(mu);
+    if (log_runtime) note("hipMemsetAsync %s dst=%s v=%d n=%zu", sname(st), dn.c_str(), v, n);
     touch(); chk_ptr("hipMemsetAsync", "dst", dst); chk_stream("hipMemsetAsync", st); enqueue("hipMemsetAsync", st);
     memset(dst, v, n);
     return hipSuccess;
@@ -303,7 +344,9 @@ static void chk_event(const char *what, hipEvent_t e) {
     if (reinterpret_cast<FakeEvent *>(e)->dev != cur) bad("%s: event of device %d used while device %d is current", what, reinterpret_cast<FakeEvent *>(e)->dev, cur);
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
-    std::lock_guard<std::mutex> lk(mu); touch(); chk_event("hipEventRecord", e); chk_stream("hipEventRecord", s);
+    const char *en = log_runtime ? ename(e) : "";
+    std::lock_guard<std::mutex> lk(mu); touch();
+    if (log_runtime) note("hipEventRecord %s %s", sname(s), en); chk_event("hipEventRecord", e); chk_stream("hipEventRecord", s);
     if (live_events.count((void *)e)) { FakeEvent *f = reinterpret_cast<FakeEvent *>(e); f->clock = clocks[stream_key(s)]; f->in_capture = capturing(s); }
     return hipSuccess;
 }
@@ -345,19 +388,38 @@ hipError_t klaunch_setup(hipStream_t st, KeyMaterial *km, const DevTables *tb, c
 hipError_t klaunch_gfmul(const uint4 *h, const uint4 *x, uint4 *z, size_t) { LAUNCH("k_gfmul", nullptr); P(h); P(x); P(z); return hipSuccess; }
 hipError_t klaunch_copy16(hipStream_t st, uint4 *dst, const uint4 *src, u64) { LAUNCH("k_copy16", st); P(dst); P(src); return hipSuccess; }
 hipError_t klaunch_fill_splitmix64(hipStream_t st, unsigned, u64 *buf, size_t, size_t, u64, u64) { LAUNCH("k_fill_splitmix64", st); P(buf); return hipSuccess; }
-hipError_t klaunch_main(int, int, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const MainParams &p) {
+// The single-message launchers in the log: the launcher's arguments, p = the caller's pointers of the struct (set or not), the context's own buffers by name (pname),
+// then the struct's scalars under its own field names (iv: whether any IV word is set; in k_body's line f* / l* are the `front` and `last` pieces' C, n_seq, len, ctr0)
+#define ULL(x) (unsigned long long)(x)
+hipError_t klaunch_main(int mode, int nr, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const MainParams &p) {
+    const std::string parts = pname(p.parts), cn = pname(p.counter), cz = pname(p.counter_zero), ej0 = pname(p.ej0), to = pname(p.tag_out), th = pname(p.tag_host), tr = pname(p.trace);
     LAUNCH("k_main", st); BIG_LDS(); P(km); P(tb); P(p.in); P(p.out); P(p.aad); P(p.parts); P(p.counter); P(p.counter_zero); P(p.ej0); P(p.tag_out); P(p.trace);
+    if (log_runtime) note("%s %s mode=%d nr=%d w=%u p=%s parts=%s counter=%s zero=%s ej0=%s tag_out=%s tag_host=%s trace=%s nq=%u seg=%u aad_len=%llu n_aad=%llu len=%llu n_seq=%llu rows=%llu pad=%u Tw=%u C=%u R0=%u "
+         "row_lo=%u row_hi=%u ctr0=%u iv=%d aad_aligned=%u tail=%u gen=%llu", W, sname(st), mode, nr, wgs, bits(p.in, p.out, p.aad).c_str(), parts.c_str(), cn.c_str(), cz.c_str(), ej0.c_str(),
+         to.c_str(), th.c_str(), tr.c_str(), p.nq, p.seg, ULL(p.aad_len), ULL(p.n_aad), ULL(p.len), ULL(p.n_seq), ULL(p.rows), p.pad, p.Tw, p.C, p.R0, p.row_lo, p.row_hi, p.ctr0,
+         (p.iv0 | p.iv1 | p.iv2) != 0, p.aad_aligned, p.tail, ULL(p.gen));
     if (p.tail) publish(p.tag_host, p.gen);
     return hipSuccess;
 }
-hipError_t klaunch_body(int, int, bool, bool, unsigned, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const BodyParams &p) {
+hipError_t klaunch_body(int mode, int nr, bool cyc, bool half, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const BodyParams &p) {
+    const std::string parts = pname(p.parts), cn = pname(p.counter), cz = pname(p.counter_zero), ej0 = pname(p.ej0), acc = pname(p.acc), to = pname(p.tag_out), th = pname(p.tag_host), tr = pname(p.trace);
     LAUNCH("k_body", st); BIG_LDS(); P(km); P(tb); P(p.in); P(p.out); P(p.parts); P(p.counter); P(p.counter_zero); P(p.ej0); P(p.acc); P(p.tag_out); P(p.trace);
     P(p.front.in); P(p.front.out); P(p.front.aad); P(p.last.in); P(p.last.out);
+    if (log_runtime) note("%s %s mode=%d nr=%d cyc=%d half=%d w=%u p=%s parts=%s counter=%s zero=%s ej0=%s acc=%s tag_out=%s tag_host=%s trace=%s nq=%u seg=%u T=%u C=%u ctr_hi0=%u iv=%d p.cyc=%u cw=%u F=%u R=%u tb=%u "
+         "prio_rows=%u fuse=%u aad_len=%llu ct_len=%llu gen=%llu fC=%u fseq=%llu flen=%llu fctr0=%u lC=%u lseq=%llu llen=%llu lctr0=%u", W, sname(st), mode, nr, cyc, half, wgs,
+         bits(p.in, p.out, p.front.in, p.front.out, p.front.aad, p.last.in, p.last.out).c_str(), parts.c_str(), cn.c_str(), cz.c_str(), ej0.c_str(), acc.c_str(), to.c_str(), th.c_str(), tr.c_str(),
+         p.nq, p.seg, p.T, p.C, p.ctr_hi0, (p.iv0 | p.iv1 | p.iv2) != 0, p.cyc, p.cw, p.F, p.R, p.tb, p.prio_rows, p.fuse, ULL(p.aad_len), ULL(p.ct_len), ULL(p.gen),
+         p.front.C, ULL(p.front.n_seq), ULL(p.front.len), p.front.ctr0, p.last.C, ULL(p.last.n_seq), ULL(p.last.len), p.last.ctr0);
     if (p.fuse) publish(p.tag_host, p.gen);
     return hipSuccess;
 }
-hipError_t klaunch_fold(unsigned, bool, hipStream_t st, const KeyMaterial *km, const FoldParams &p) {
+hipError_t klaunch_fold(unsigned wgs, bool closing, hipStream_t st, const KeyMaterial *km, const FoldParams &p) {
+    const std::string in = pname(p.in), out = pname(p.out), ta = pname(p.tabA), tb = pname(p.tabB), tc = pname(p.tabC), ej0 = pname(p.close.ej0), acc = pname(p.close.acc), to = pname(p.close.tag_out),
+                      th = pname(p.close.tag_host);
     LAUNCH("k_fold", st); BIG_LDS(); P(km); P(p.in); P(p.out); P(p.tabA); P(p.tabB); P(p.tabC); P(p.close.ej0); P(p.close.acc); P(p.close.tag_out);
+    if (log_runtime) note("%s %s w=%u closing=%d in=%s out=%s n=%u period=%u group=%u eA=%llu eB=%llu eC=%llu tabA=%s tabB=%s tabC=%s on=%u step=%llu aad_len=%llu ct_len=%llu ej0=%s acc=%s tag_out=%s tag_host=%s gen=%llu",
+         W, sname(st), wgs, closing, in.c_str(), out.c_str(), p.n, p.period, p.group, ULL(p.eA), ULL(p.eB), ULL(p.eC), ta.c_str(), tb.c_str(), tc.c_str(), p.close.on, ULL(p.close.step),
+         ULL(p.close.aad_len), ULL(p.close.ct_len), ej0.c_str(), acc.c_str(), to.c_str(), th.c_str(), ULL(p.close.gen));
     if (p.close.on) publish(p.close.tag_host, p.close.gen);
     return hipSuccess;
 }
@@ -365,7 +427,15 @@ static void combine_one(const char *W, const KeyMaterial *km, const DevTables *t
     P(km); P(tb); P(p.parts); P(p.tail_item); P(p.tabA); P(p.tabB); P(p.tabC); P(p.carry); P(p.ej0); P(p.out);
     publish(p.out_host, p.gen);
 }
-hipError_t klaunch_combine(hipStream_t st, const KeyMaterial *km, const DevTables *tb, const CombineParams &p) { LAUNCH("k_combine", st); BIG_LDS(); combine_one(W, km, tb, p); return hipSuccess; }
+hipError_t klaunch_combine(hipStream_t st, const KeyMaterial *km, const DevTables *tb, const CombineParams &p) {
+    const std::string parts = pname(p.parts), ti = pname(p.tail_item), ta = pname(p.tabA), tB = pname(p.tabB), tc = pname(p.tabC), ca = pname(p.carry), ej0 = pname(p.ej0), out = pname(p.out), oh = pname(p.out_host);
+    LAUNCH("k_combine", st); BIG_LDS();
+    if (log_runtime) note("%s %s parts=%s np=%u kind=%u stride=%u eA=%llu tail_item=%s tail_blocks=%u tabA=%s tabB=%s tabC=%s want_tag=%u e=%llu carry=%s e_carry=%llu has_carry=%u aad_len=%llu ct_len=%llu iv=%d ej0=%s "
+         "out=%s out_host=%s gen=%llu", W, sname(st), parts.c_str(), p.np, p.kind, p.stride, ULL(p.eA), ti.c_str(), p.tail_blocks, ta.c_str(), tB.c_str(), tc.c_str(), p.want_tag, ULL(p.e), ca.c_str(),
+         ULL(p.e_carry), p.has_carry, ULL(p.aad_len), ULL(p.ct_len), (p.iv0 | p.iv1 | p.iv2) != 0, ej0.c_str(), out.c_str(), oh.c_str(), ULL(p.gen));
+    combine_one(W, km, tb, p);
+    return hipSuccess;
+}
 hipError_t klaunch_combine_batch(unsigned n, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const CombineBatch &b) {
     LAUNCH("k_combine_batch", st); BIG_LDS();
     for (unsigned i = 0; i < n; i++) combine_one(W, km, tb, b.p[i]);

@@ -3,8 +3,8 @@
 // with K, per-lane tail powers, workgroup fold, k_combine fold -- and compares ciphertext and tag with
 // the oracle (oracle/aesgcm_oracle.c, linked in).  It exists because the build container has no GPU:
 // it pins the arithmetic and the index algebra before any GPU minute is spent.  Test infrastructure only.
-#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_dev.h"
-#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_rows.h"
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_internal.h"      // (the kernels' launch geometry, as the launchers see it; the lane code through aesgcm_dev.h, aesgcm_rows.h)
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_msgplan.h"
 #include "aesgcm_bs.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -157,10 +157,8 @@ static G128 emu_pow_h(const KeyMaterial *km, u64 e) { return gf_pow_h_serial(km,
 // emulated k_combine: the same lane pieces (in-launch item fold, one level of per-lane table multiplies through km->ltab)
 static void emu_combine(const KeyMaterial *km, const CombineParams &p0) {
     static unsigned char smem[CMB_LDS_BYTES] __attribute__((aligned(16)));
-    CombineParams p = p0;
+    const CombineParams &p = p0;
     const bool tag = p.want_tag != 0, items = p.kind == PARTS_ITEM;
-    auto tp = [&](u64 e) -> const uint4 * { int k = ptab_index(e); return k < 0 ? nullptr : km->ptab[k]; };
-    if (items && p.np > 1) { p.tabA = tp(p.eA); p.tabB = p.np > 4 ? tp(4 * p.eA) : nullptr; p.tabC = p.np > 16 ? tp(16 * p.eA) : nullptr; }
     CHECK(!(items && p.np > 1) || (p.np <= COMBINE_MAX_ITEMS && p.tabA && (p.np <= 4 || p.tabB) && (p.np <= 16 || p.tabC)), "emu_combine: %u items not foldable", p.np);
     const u32 J1 = items ? fold4_groups(p.np) : 0, J2 = items ? fold4_groups(J1) : 0;
     if (items && p.np > 1) memcpy(smem + CMB_LDS_TABA, p.tabA, 8192);
@@ -197,194 +195,108 @@ static void emu_combine(const KeyMaterial *km, const CombineParams &p0) {
     *p.out = be_to_mo(acc);
 }
 
-struct Parts { const uint4 *ptr; u32 np; u32 gathered; u64 eA; const uint4 *tail_item = nullptr; u32 tail_blocks = 0; };   // gathered = PARTS_* kind; eA: item spacing when k_combine folds the items itself
+// An emulated context: key material, the planner's rules (the context's options) and host vectors for its scratch.  go() makes the PRODUCT's plan for a call
+// (msg_plan, csrc/aesgcm_msgplan.h -- the one aesgcm_host.hip runs on a stream) and walks it with the kernel emulators above.
 struct Emu {
-    KeyMaterial km; u32 tw; std::vector<uint4> parts, fold_a, fold_b;
-    u32 n_cyc = 0;                  // launches that went through run_cyc()
-    u32 n_fold_close = 0;           // messages whose tag came out of k_fold's closing
-    bool fuse = true;               // whole messages: the cyclic launch closes the tag itself (cyc_close)
-    bool cyc = false; u64 cyc_min = 1024;   // ranges with at least one whole body row as cyclic rows of k_body (every size) instead of the pieces
-    Emu(const uint8_t *key, int key_len, u32 tw_) : tw(tw_), parts(1 << 16), fold_a(1 << 16), fold_b(1 << 12) { emu_setup(&km, key, key_len, 0, 512); }
-    // mirrors enqueue_fold(): k_fold launches until one item is left
-    // mirrors k_fold's closing (FoldClose): the workgroups of the first level turn their output items into the tag
-    bool fold_close = true;
-    void fold_closing(const FoldParams &f, u32 G, u64 aad_len, u64 ct_len, uint4 ej0, uint4 *tag_out) {
+    KeyMaterial km;
+    // no cyclic rows and no k_body split unless a test asks: every size through k_main.  Cyclic rows, when on, from one whole body row (every size)
+    MsgRules rules = {512, 0, ~0ull, false, true, true, 0, 0, 1024, 1024, 0, ~0ull, ~0ull, ~0ull};
+    std::vector<uint4> parts, fold_a, fold_b;
+    uint4 slots[4];                 // the context's d_tag: tag, a session's chaining value, a large range's, E_K(IV || 1)
+    MsgPlan last;                   // the plan of the last call
+    Emu(const uint8_t *key, int key_len, u32 tw) : parts(64), fold_a((size_t)64 * FOLD_A_ITEMS), fold_b((size_t)64 * FOLD_B_ITEMS) { rules.tw = tw; emu_setup(&km, key, key_len, 0, 512); }
+    template <class F> u32 count(MsgStep::Kind kind, F f) const { u32 n = 0; for (u32 k = 0; k < last.n; k++) n += last.step[k].kind == kind && f(last.step[k]); return n; }
+    u32 n_cyc() const { return count(MsgStep::BODY, [](const MsgStep &t) { return t.b.cyc != 0; }); }             // cyclic launches of the last call
+    u32 n_body() const { return count(MsgStep::BODY, [](const MsgStep &) { return true; }); }                      // k_body launches of any kind
+    u32 n_fold_close() const { return count(MsgStep::FOLD, [](const MsgStep &t) { return t.f.close.on != 0; }); }   // k_fold levels that closed the tag
+    // what the launch's chunk-0 wave leaves in the slot for k_combine and the closings
+    void leave_ej0(uint4 *ej0, u32 iv0, u32 iv1, u32 iv2) {
+        CombineParams q = {};
+        q.iv0 = iv0; q.iv1 = iv1; q.iv2 = iv2;
+        if (ej0) *ej0 = be_to_mo(combine_ej0_bytes(&km, g_tb.sbox, q));
+    }
+    // k_fold's closing (FoldClose): the workgroups of the level turn their output items into the tag
+    void fold_closing(const FoldParams &f, u32 G) {
         static unsigned char lds[FOLD_LDS_CLOSE_BYTES] __attribute__((aligned(16)));
         for (u32 k = 0; k < 2048; k++) *reinterpret_cast<uint4 *>(lds + cyc_ltab_off(k, FOLD_LDS_LTAB)) = cyc_ltab_entry(&km, k, 0u);
-        const u64 step = fold_out_step(f);
         G128 slots[CYC_ACC_SLOTS];
         memset(slots, 0, sizeof slots);
         for (u32 gg = 0; gg < G; gg++) {
             const u32 g = (gg * 29u + 3u) % G == gg ? gg : G - 1 - gg;      // any arrival order
             G128 z = {{0, 0, 0, 0}};
             for (u32 lane = 0; lane < 64; lane++) xor_g(z, cyc_lane_term_lds(lds, f.out[(size_t)g * 64 + lane], lane, FOLD_LDS_LTAB));
-            const u64 e = step * (u64)(G - 1 - g);
+            const u64 e = f.close.step * (u64)(G - 1 - g);
             for (u32 d = 0; d < 4; d++) {
                 const u32 dig = (u32)(e >> (AESGCM_LOG_WG * d)) & (u32)(AESGCM_WG - 1);
                 if (!dig) continue;
                 for (u32 lane = 0; lane < 32; lane++) *reinterpret_cast<uint4 *>(lds + FOLD_LDS_WTAB + 16u * lane) = shoup2_entry(mo_to_be(km.pw[d][dig]), lane);
                 z = shoup2_gmul_lds(z, reinterpret_cast<const uint4 *>(lds + FOLD_LDS_WTAB));
             }
-            if (g + 1 == G) { xor_g(z, tag_len_term(&km, aad_len, ct_len)); xor_g(z, mo_to_be(ej0)); }
+            if (g + 1 == G) { xor_g(z, tag_len_term(&km, f.close.aad_len, f.close.ct_len)); xor_g(z, mo_to_be(*f.close.ej0)); }
             xor_g(slots[g & (CYC_ACC_SLOTS - 1u)], z);
         }
         G128 t = {{0, 0, 0, 0}};
         for (u32 k = 0; k < CYC_ACC_SLOTS; k++) xor_g(t, slots[k]);
-        *tag_out = be_to_mo(t);
+        *f.close.tag_out = be_to_mo(t);
     }
-    Parts fold(const uint4 *items, u32 n, u32 period, u64 eA, u64 eB, const CombineParams *close = nullptr, uint4 *close_tag = nullptr) {
+    // one k_fold level
+    void emu_fold(const FoldParams &f, u32 G) {
         static unsigned char smem[FOLD_LDS_BYTES] __attribute__((aligned(16)));
-        const uint4 *cur = items; int which = 0;
-        bool first = true;
-        while (n > 1) {
-            {   // mirrors enqueue_fold(): the last level(s) belong to k_combine when the spacing has tables
-                auto has = [&](u64 e) { return ptab_index(e) >= 0; };
-                if (period <= 1 && n <= COMBINE_MAX_ITEMS && has(eA) && (n <= 4 || has(4 * eA)) && (n <= 16 || has(16 * eA))) { Parts q = {cur, n, PARTS_ITEM, eA}; return q; }
-            }
-            std::vector<uint4> &ob = which ? fold_b : fold_a;
-            const u32 G = fold_wgs(n, fold_group(n, period));
-            if (ob.size() < (size_t)G * 64) ob.resize((size_t)G * 64);
-            FoldParams f;
-            plan_fold(f, cur, ob.data(), n, period, eA, eB);
-            auto tp = [&](u64 e) -> const uint4 * { int k = ptab_index(e); return k < 0 ? nullptr : km.ptab[k]; };
-            f.tabA = tp(f.eA); f.tabB = tp(f.eB); f.tabC = tp(f.eC);
-            for (u32 tid = 0; tid < FOLD_WG; tid++) {
-                fold_fill_lds(smem, &km, f.tabA, f.eA, 0u, tid, FOLD_WG);
-                if (period > 1) fold_fill_lds(smem, &km, f.tabB, f.eB, 8192u, tid, FOLD_WG);
-                fold_fill_lds(smem, &km, f.tabC, f.eC, 16384u, tid, FOLD_WG);
-            }
-            for (u32 g = 0; g < G; g++) {
-                u32 start, end;
-                const u32 J = fold_wg_range(n, f.group, g, &start, &end);
-                for (u32 w = 0; w < J; w++) for (u32 lane = 0; lane < 64; lane++)
-                    *reinterpret_cast<uint4 *>(smem + FOLD_LDS_TAB + w * 1024u + lane * 16u) = fold_wave_lane(f, smem, start, end, J, w, lane);
-                for (u32 lane = 0; lane < 64; lane++) f.out[(size_t)g * 64 + lane] = fold_wg_lane(smem, J, lane);
-            }
-            if (close && fold_close && G <= 512) {      // (first is kept for the bookkeeping below)      // mirrors enqueue_fold(): the first level closes a whole message itself
-                CHECK(close->ej0 != nullptr, "fold closing without E_K(J0)");
-                fold_closing(f, G, close->aad_len, close->ct_len, *close->ej0, close_tag);
-                Parts q = {nullptr, 0, PARTS_NONE, 0};
-                return q;
-            }
-            first = false;
-            eA = fold_out_step(f); eB = 0; period = 1; cur = f.out; n = G; which ^= 1;
+        for (u32 tid = 0; tid < FOLD_WG; tid++) {
+            fold_fill_lds(smem, &km, f.tabA, f.eA, 0u, tid, FOLD_WG);
+            if (f.period > 1) fold_fill_lds(smem, &km, f.tabB, f.eB, 8192u, tid, FOLD_WG);
+            fold_fill_lds(smem, &km, f.tabC, f.eC, 16384u, tid, FOLD_WG);
         }
-        Parts r = {cur, 1, PARTS_ITEM, 0};
-        return r;
+        for (u32 g = 0; g < G; g++) {
+            u32 start, end;
+            const u32 J = fold_wg_range(f.n, f.group, g, &start, &end);
+            for (u32 w = 0; w < J; w++) for (u32 lane = 0; lane < 64; lane++)
+                *reinterpret_cast<uint4 *>(smem + FOLD_LDS_TAB + w * 1024u + lane * 16u) = fold_wave_lane(f, smem, start, end, J, w, lane);
+            for (u32 lane = 0; lane < 64; lane++) f.out[(size_t)g * 64 + lane] = fold_wg_lane(smem, J, lane);
+        }
+        if (f.close.on) { CHECK(f.close.ej0 != nullptr, "fold closing without E_K(J0)"); fold_closing(f, G); }
     }
-    // mirrors enqueue_main(): launch + k_fold levels
-    Parts run(int mode, const uint8_t *iv, const void *aad, u64 aad_len, const void *in, u64 len, void *out, u64 first_block) {
-        MainParams p; memset(&p, 0, sizeof p);
-        u32 C = plan_main(p, mode, tw, iv, aad, aad_len, in, len, out, first_block, nullptr);
-        Parts r = {nullptr, 0, PARTS_NONE, 0};
-        if (!C) return r;
-        if (parts.size() < (size_t)C * 64) parts.resize((size_t)C * 64);
-        p.parts = parts.data();
-        emu_main(mode, &km, p);
-        if (mode != MODE_ENC && mode != MODE_DEC) return r;
-        // mirrors enqueue_main(): few chunks with table-backed spacing go to k_combine unfolded
-        const u64 eA = (u64)64 * p.Tw;
-        auto has = [&](u64 e) { return ptab_index(e) >= 0; };
-        if (C <= COMBINE_MAX_ITEMS && (C == 1 || (has(eA) && (C <= 4 || has(4 * eA)) && (C <= 16 || has(16 * eA))))) { Parts q = {parts.data(), C, PARTS_ITEM, eA}; return q; }
-        return fold(parts.data(), C, 1, eA, 0);
+    // k_main's tail (single-chunk message: no k_combine launch): every term one table multiply deep
+    void emu_main_tail(const MainParams &p) {
+        G128 P = {{0, 0, 0, 0}};
+        for (u32 lane = 0; lane < 64; lane++) xor_g(P, tag_lane_term(&km, p.parts[lane], lane));
+        xor_g(P, tag_len_term(&km, p.aad_len, p.len));
+        xor_g(P, mo_to_be(*p.ej0));
+        *p.tag_out = be_to_mo(P);
     }
-    // mirrors enqueue_body(): k_body + k_fold with the interleaved first level
-    Parts run_body(int mode, const uint8_t *iv, const BodySplit &b, const void *in, void *out, u64 first_block, const CombineParams *close = nullptr, uint4 *close_tag = nullptr) {
-        BodyParams p; memset(&p, 0, sizeof p);
-        if (parts.size() < 256 * (size_t)b.S) parts.resize(256 * (size_t)b.S);
-        plan_body(p, b, iv, in, out, first_block, parts.data());
-        emu_body(mode, &km, p);
-        return fold(parts.data(), p.C, 4, 64, (u64)256 * b.T, close, close_tag);
-    }
-    // mirrors enqueue_cyc(): the whole range as cyclic rows of k_body + one k_fold level; false = the range is not of that size
-    bool run_cyc(int mode, const uint8_t *iv, const void *aad, u64 aad_len, const void *in, u64 len, void *out, u64 first_block, Parts *po, uint4 *fused_tag = nullptr) {
-        if (!cyc) return false;
-        if (parts.size() < (size_t)64 * (BODY_CYC_WAVES + 1)) parts.resize((size_t)64 * (BODY_CYC_WAVES + 1));
-        BodyParams p;
-        if (!plan_body_cyc(p, mode, iv, aad, aad_len, in, len, out, first_block, parts.data(), cyc_min, ~0ull)) return false;
-        if (fused_tag && fuse) { p.fuse = 1; p.aad_len = aad_len; p.ct_len = len; p.tag_out = fused_tag; }
-        emu_body(mode, &km, p);
-        ++n_cyc;
-        if (p.fuse) { po->np = 0; return true; }
-        *po = fold(parts.data(), BODY_CYC_WAVES, 1, 64, 0);
-        if (p.tb) { po->tail_item = parts.data() + (size_t)BODY_CYC_WAVES * 64; po->tail_blocks = p.tb; }
-        return true;
-    }
-    // mirrors absorb_range()
-    bool absorb(int mode, const uint8_t *iv, const uint8_t *aad, u64 aad_len, const uint8_t *in, u64 len, uint8_t *out, u64 first_block, u64 body_min, uint4 *Y) {
-        BodySplit b;
-        {   // mirrors absorb_range(): cyclic rows first
-            Parts pc = {nullptr, 0, PARTS_NONE, 0};
-            if (run_cyc(mode, iv, aad, aad_len, in, len, out, first_block, &pc)) {
-                const u64 nb = (aad_len + 15) / 16 + (len + 15) / 16;
-                emu_combine(&km, combine_with_items(plan_combine_carry(pc.ptr, pc.np, pc.gathered, Y, nb), pc.eA, pc.tail_item, pc.tail_blocks));
-                return true;
+    // plan the call as the host runtime does (the scratch grown to what the plan needs, then planned again) and execute every step
+    const MsgPlan &go(const MsgCall &call) {
+        for (;;) {
+            const MsgScratch s = {parts.data(), fold_a.data(), fold_b.data(), slots, nullptr, {nullptr, nullptr}, 0, nullptr, &km.ptab[0][0]};
+            msg_plan(last, call, rules, s, [] { return false; });
+            if (last.parts_need * 64 <= parts.size()) break;
+            parts.resize(last.parts_need * 64);
+        }
+        CHECK(last.rc == AESGCM_OK, "the plan refuses the call: %d", last.rc);
+        for (u32 k = 0; k < last.n; k++) {
+            const MsgStep &t = last.step[k];
+            switch (t.kind) {
+            case MsgStep::CLEAR: *t.clear = make_uint4(0, 0, 0, 0); break;
+            case MsgStep::MAIN: emu_main(t.mode, &km, t.m); leave_ej0(t.m.ej0, t.m.iv0, t.m.iv1, t.m.iv2); if (t.m.tail) emu_main_tail(t.m); break;
+            case MsgStep::BODY: CHECK(!t.b.cyc || t.b.cw == BODY_CYC_WAVES, "the half shape has no emulator"); emu_body(t.mode, &km, t.b); leave_ej0(t.b.ej0, t.b.iv0, t.b.iv1, t.b.iv2); break;
+            case MsgStep::FOLD: emu_fold(t.f, t.wgs); break;
+            case MsgStep::COMBINE: emu_combine(&km, t.c); break;
             }
         }
-        if (!plan_body_split(len, first_block, tw, body_min, &b)) {
-            Parts pp = run(mode, iv, aad, aad_len, in, len, out, first_block);
-            const u64 nb = (aad_len + 15) / 16 + (len + 15) / 16;
-            if (nb) emu_combine(&km, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.gathered, Y, nb), pp.eA));
-            return false;
-        }
-        const u64 n_aad = (aad_len + 15) / 16;
-        if (n_aad + b.head_blocks) {
-            Parts pp = run(mode, iv, aad, aad_len, in, 16 * b.head_blocks, out, first_block);
-            emu_combine(&km, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.gathered, Y, n_aad + b.head_blocks), pp.eA));
-        }
-        Parts pb = run_body(mode, iv, b, in, out, first_block);
-        emu_combine(&km, combine_with_items(plan_combine_carry(pb.ptr, pb.np, pb.gathered, Y, b.body_blocks), pb.eA));
-        const u64 done = b.head_blocks + b.body_blocks, tail = len - 16 * done;
-        if (tail) {
-            Parts pp = run(mode, iv, nullptr, 0, in + 16 * done, tail, out + 16 * done, first_block + done);
-            emu_combine(&km, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.gathered, Y, (tail + 15) / 16), pp.eA));
-        }
-        return true;
+        return last;
     }
-    // mirrors crypt_dev() for a message that takes the split; returns whether the split applied
-    bool crypt_split(int dec, const uint8_t iv[12], const uint8_t *aad, u64 aad_len, const uint8_t *in, u64 len, uint8_t *out, uint8_t tag[16], u64 body_min) {
-        uint4 Y = make_uint4(0, 0, 0, 0), t;
-        {   // mirrors crypt_dev(): cyclic rows first, items straight to the tag
-            Parts pc = {nullptr, 0, PARTS_NONE, 0};
-            if (run_cyc(dec ? MODE_DEC : MODE_ENC, iv, aad, aad_len, in, len, out, 0, &pc, &t)) {
-                if (!fuse) emu_combine(&km, combine_with_items(plan_combine_tag(pc.ptr, pc.np, pc.gathered, iv, aad_len, len, &t), pc.eA, pc.tail_item, pc.tail_blocks));
-                memcpy(tag, &t, 16);
-                return true;
-            }
-        }
-        BodySplit b0;
-        if (plan_body_split(len, 0, tw, body_min, &b0) && !aad_len && !b0.head_blocks && len == 16 * b0.body_blocks) {
-            // the whole message is one aligned body: k_body's items go straight to the tag (no chaining value)
-            CombineParams q0 = plan_combine_tag(nullptr, 0, PARTS_NONE, iv, 0, len, &t);
-            const uint4 ej0 = be_to_mo(combine_ej0_bytes(&km, g_tb.sbox, q0));      // what k_body's chunk-0 wave leaves behind
-            q0.ej0 = &ej0;
-            Parts pb = run_body(dec ? MODE_DEC : MODE_ENC, iv, b0, in, out, 0, &q0, &t);
-            if (pb.gathered != PARTS_NONE || pb.np) emu_combine(&km, combine_with_items(plan_combine_tag(pb.ptr, pb.np, pb.gathered, iv, 0, len, &t), pb.eA));
-            else ++n_fold_close;
-            memcpy(tag, &t, 16);
-            return true;
-        }
-        const bool split = absorb(dec ? MODE_DEC : MODE_ENC, iv, aad, aad_len, in, len, out, 0, body_min, &Y);
-        emu_combine(&km, plan_combine_final(&Y, iv, aad_len, len, &t));
-        memcpy(tag, &t, 16);
-        return split;
-    }
+    // the calls of the tests: a whole message's tag; a range into a chaining value; a range's weighted polynomial value; keystream / ECB
     void crypt(int dec, const uint8_t iv[12], const uint8_t *aad, u64 aad_len, const uint8_t *in, u64 len, uint8_t *out, uint8_t tag[16]) {
-        Parts pp = run(dec ? MODE_DEC : MODE_ENC, iv, aad, aad_len, in, len, out, 0);
-        uint4 t;
-        if (pp.np == 1 && pp.gathered == PARTS_ITEM) {
-            // mirrors k_main's tail (single-chunk message: no k_combine launch): every term one table multiply deep
-            G128 P = {{0, 0, 0, 0}};
-            for (u32 lane = 0; lane < 64; lane++) xor_g(P, tag_lane_term(&km, pp.ptr[lane], lane));
-            xor_g(P, tag_len_term(&km, aad_len, len));
-            CombineParams q = plan_combine_tag(nullptr, 0, PARTS_NONE, iv, aad_len, len, &t);
-            xor_g(P, combine_ej0_bytes(&km, g_tb.sbox, q));
-            t = be_to_mo(P);
-        } else {
-            emu_combine(&km, combine_with_items(plan_combine_tag(pp.ptr, pp.np, pp.gathered, iv, aad_len, len, &t), pp.eA));
-        }
-        memcpy(tag, &t, 16);
+        go(MsgCall{MSG_TAG, dec ? MODE_DEC : MODE_ENC, iv, aad, aad_len, in, len, out, 0, nullptr, 0, false});
+        memcpy(tag, &slots[0], 16);
     }
+    void carry(int mode, const uint8_t *iv, const void *aad, u64 aad_len, const void *in, u64 len, void *out, u64 first_block, uint4 *Y, bool main_only) {
+        go(MsgCall{MSG_CARRY, mode, iv, aad, aad_len, in, len, out, first_block, Y, 0, main_only});
+    }
+    void poly(int mode, const uint8_t *iv, const void *aad, u64 aad_len, const void *in, u64 len, void *out, u64 first_block, u64 after, uint4 *W) {
+        go(MsgCall{MSG_POLY, mode, iv, aad, aad_len, in, len, out, first_block, W, after, false});
+    }
+    void raw(int mode, const uint8_t *iv, const void *in, u64 len, void *out, u64 first_block) { go(MsgCall{MSG_RAW, mode, iv, nullptr, 0, in, len, out, first_block, nullptr, 0, true}); }
 };
 
 static std::vector<uint8_t> rnd(size_t n, u64 seed) {
@@ -648,7 +560,7 @@ static void test_key(int key_len, u32 G /* rows per chunk override, 0 = producti
         const size_t nb = 700;
         ABuf in(16 * nb), out(16 * nb);
         orc_fill_splitmix64(in.p, 16 * nb, seed + 5, 0);
-        E.run(MODE_ECB, nullptr, nullptr, 0, in.p, 16 * nb, out.p, 0);
+        E.raw(MODE_ECB, nullptr, in.p, 16 * nb, out.p, 0);
         for (size_t i = 0; i < nb; i++) { uint8_t o[16]; orc_aes_encrypt_block(rk, nr, in.p + 16 * i, o); CHECK(memcmp(o, out.p + 16 * i, 16) == 0, "ecb block %zu", i); }
     }
     for (auto &sz : sizes) {
@@ -686,8 +598,7 @@ static void test_shards(int key_len, u32 G, u64 al, u64 n, int R, u64 seed) {
         u64 blocks = total_blocks / R + ((u64)r < total_blocks % R ? 1 : 0);
         u64 end = first + blocks;
         u64 len = (end == total_blocks ? n : 16 * end) - 16 * first;
-        Parts pp = E.run(MODE_ENC, iv.data(), r == 0 ? aad.data() : nullptr, r == 0 ? al : 0, pt.p + 16 * first, len, ct.p + 16 * first, first);
-        emu_combine(&E.km, combine_with_items(plan_combine_poly(pp.ptr, pp.np, pp.gathered, total_blocks - end, &gathered[r]), pp.eA));
+        E.poly(MODE_ENC, iv.data(), r == 0 ? aad.data() : nullptr, r == 0 ? al : 0, pt.p + 16 * first, len, ct.p + 16 * first, first, total_blocks - end, &gathered[r]);
         first = end;
     }
     uint4 t;
@@ -704,25 +615,25 @@ static void test_body(int key_len, u32 G, u64 al, u64 n, u64 seed, bool cyc = fa
     uint8_t rtag[16], tag[16], dtag[16];
     orc_gcm_crypt(0, key.data(), key_len, iv.data(), aad.data(), al, pt.p, n, ref.p, rtag);
     Emu E(key.data(), key_len, G);
-    E.cyc = cyc;
+    E.rules.cyc_capable = cyc; E.rules.body_min = 4096;
     if (cyc) {                                                          // first with k_fold / k_combine behind the launch, then (below) with the fused closing
         uint8_t utag[16];
-        E.fuse = false;
-        E.crypt_split(0, iv.data(), aad.data(), al, pt.p, n, ct.p, utag, 4096);
+        E.rules.cyc_fuse = false;
+        E.crypt(0, iv.data(), aad.data(), al, pt.p, n, ct.p, utag);
         CHECK(memcmp(utag, rtag, 16) == 0, "cyclic unfused tag key %d aad %llu len %llu", key_len, (unsigned long long)al, (unsigned long long)n);
-        E.fuse = true; E.n_cyc = 0;
+        E.rules.cyc_fuse = true;
         memset(ct.p, 0xA5, n);
     }
-    const bool split = E.crypt_split(0, iv.data(), aad.data(), al, pt.p, n, ct.p, tag, 4096);
-    CHECK(split, "body split did not apply: len %llu G %u", (unsigned long long)n, G);
-    CHECK(!cyc || E.n_cyc == 1, "cyclic rows did not take the message: len %llu", (unsigned long long)n);
-    CHECK(cyc || al || (n % 4096) || n < 16 * 256 * 40 || E.n_fold_close == 1, "k_fold did not close the message: len %llu", (unsigned long long)n);
+    E.crypt(0, iv.data(), aad.data(), al, pt.p, n, ct.p, tag);
+    CHECK(E.n_body() == 1, "body split did not apply: len %llu G %u", (unsigned long long)n, G);
+    CHECK(!cyc || E.n_cyc() == 1, "cyclic rows did not take the message: len %llu", (unsigned long long)n);
+    CHECK(cyc || al || (n % 4096) || n < 16 * 256 * 40 || E.n_fold_close() == 1, "k_fold did not close the message: len %llu", (unsigned long long)n);
     CHECK(memcmp(ct.p, ref.p, n) == 0, "body ct key %d G %u aad %llu len %llu", key_len, G, (unsigned long long)al, (unsigned long long)n);
     CHECK(memcmp(tag, rtag, 16) == 0, "body tag key %d G %u aad %llu len %llu", key_len, G, (unsigned long long)al, (unsigned long long)n);
     CHECK(ct.p[n] == 0xA5, "body overrun");
-    E.crypt_split(1, iv.data(), aad.data(), al, ct.p, n, back.p, dtag, 4096);
+    E.crypt(1, iv.data(), aad.data(), al, ct.p, n, back.p, dtag);
     CHECK(memcmp(back.p, pt.p, n) == 0 && memcmp(dtag, rtag, 16) == 0, "body dec key %d G %u", key_len, G);
-    // the same message as R shards, every shard through absorb() from its own first block
+    // the same message as R shards, every shard into a chaining value (MSG_CARRY) from its own first block
     for (int R : {2, 3}) {
         ABuf ct2(n);
         const u64 total_blocks = (n + 15) / 16;
@@ -732,7 +643,8 @@ static void test_body(int key_len, u32 G, u64 al, u64 n, u64 seed, bool cyc = fa
             u64 blocks = total_blocks / R + ((u64)r < total_blocks % R ? 1 : 0), end = first + blocks;
             u64 len = (end == total_blocks ? n : 16 * end) - 16 * first;
             uint4 Y = make_uint4(0, 0, 0, 0);
-            nsplit += E.absorb(MODE_ENC, iv.data(), r == 0 ? aad.data() : nullptr, r == 0 ? al : 0, pt.p + 16 * first, len, ct2.p + 16 * first, first, 4096, &Y);
+            E.carry(MODE_ENC, iv.data(), r == 0 ? aad.data() : nullptr, r == 0 ? al : 0, pt.p + 16 * first, len, ct2.p + 16 * first, first, &Y, false);
+            nsplit += E.n_body();
             CombineParams q = plan_combine_poly(nullptr, 0, PARTS_NONE, 0, &gathered[r]);
             q.carry = &Y; q.has_carry = 1; q.e_carry = total_blocks - end;
             emu_combine(&E.km, q);
@@ -756,13 +668,11 @@ static void test_stream(int key_len, u32 G, u64 al, u64 n, u64 chunk, u64 seed) 
     uint4 Y = make_uint4(0, 0, 0, 0);
     for (u64 off = 0; off < al; off += chunk) {
         u64 m = al - off < chunk ? al - off : chunk;
-        Parts pp = E.run(MODE_ENC, iv.data(), aad.data() + off, m, nullptr, 0, nullptr, 0);
-        emu_combine(&E.km, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.gathered, &Y, (m + 15) / 16), pp.eA));
+        E.carry(MODE_ENC, iv.data(), aad.data() + off, m, nullptr, 0, nullptr, 0, &Y, true);
     }
     for (u64 off = 0; off < n; off += chunk) {
         u64 m = n - off < chunk ? n - off : chunk;
-        Parts pp = E.run(MODE_ENC, iv.data(), nullptr, 0, pt.p + off, m, ct.p + off, off / 16);
-        emu_combine(&E.km, combine_with_items(plan_combine_carry(pp.ptr, pp.np, pp.gathered, &Y, (m + 15) / 16), pp.eA));
+        E.carry(MODE_ENC, iv.data(), nullptr, 0, pt.p + off, m, ct.p + off, off / 16, &Y, true);
     }
     uint4 t;
     emu_combine(&E.km, plan_combine_final(&Y, iv.data(), al, n, &t));
@@ -776,7 +686,7 @@ static void test_keystream_and_ghash(u64 seed) {
     uint8_t rk[240]; int nr; orc_key_expand(key.data(), 32, rk, &nr);
     const u64 first = 0x01FFFF00ull - 2, nb = 600;      // counter crosses a 2^8, 2^16, 2^24 carry boundary
     ABuf out(16 * nb);
-    E.run(MODE_KS, iv.data(), nullptr, 0, out.p, 16 * nb, out.p, first);
+    E.raw(MODE_KS, iv.data(), out.p, 16 * nb, out.p, first);
     for (u64 i = 0; i < nb; i++) {
         uint8_t cb[16], o[16]; memcpy(cb, iv.data(), 12);
         u32 c = (u32)(2 + first + i); cb[12] = c >> 24; cb[13] = c >> 16; cb[14] = c >> 8; cb[15] = c;
@@ -786,8 +696,7 @@ static void test_keystream_and_ghash(u64 seed) {
     // GHASH chaining value Y = P*H
     for (u64 n : {1ull, 16ull, 17ull, 8191ull, 20000ull}) {
         auto d = rnd(n, seed + n);
-        Parts pp = E.run(MODE_ENC, iv.data(), d.data(), n, nullptr, 0, nullptr, 0);
-        uint4 y; emu_combine(&E.km, combine_with_items(plan_combine_poly(pp.ptr, pp.np, pp.gathered, 1, &y), pp.eA));
+        uint4 y; E.poly(MODE_ENC, iv.data(), d.data(), n, nullptr, 0, nullptr, 0, 1, &y);
         uint8_t yo[16] = {0}; orc_ghash_update((const uint8_t *)&E.km.h, yo, d.data(), n);
         CHECK(memcmp(&y, yo, 16) == 0, "ghash len %llu", (unsigned long long)n);
     }

@@ -58,6 +58,28 @@ def test_launch_plan_is_the_recorded_one():
     assert len(got) == len(want), "the log has %d lines, the fixture %d; the first one without a partner: %s" % (len(got), len(want), (got + want)[min(len(got), len(want))])
 
 
+def test_single_message_launch_plan_is_the_recorded_one():
+    """tests/fake_hip/msg_drive.py: what a single-message call launches -- whole messages on device pointers, streaming sessions, shards, aesgcm_ghash, keystream, ECB,
+    the host-buffer and pipelined calls -- every k_main / k_body / k_fold / k_combine launch with its stream, workgroups, the parameter struct's scalars and the
+    context's buffers by name, every hipMemsetAsync and hipEventRecord between them, over a grid on both sides of every threshold of the planner and under the
+    options that move them, line by line against tests/golden/launch_plan_msg.txt.  The fixture was written by the commit before the planner moved into
+    csrc/aesgcm_msgplan.h (its csrc/ with this fake runtime and driver): a call that launches anything else shows here."""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s", "libaesgcm_fake.so"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"))
+    out = subprocess.run([sys.executable, os.path.join(d, "msg_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    got, want = out.stdout.splitlines(), open(os.path.join(HERE, "golden", "launch_plan_msg.txt")).read().splitlines()
+    call = "(before the first call)"
+    for i, (g, w) in enumerate(zip(got, want)):
+        if w.startswith("=="):
+            call = w
+        assert g == w, "line %d, in the call\n  %s\nthe launch log says\n  %s\nand the fixture\n  %s" % (i + 1, call, g, w)
+    assert len(got) == len(want), "the log has %d lines, the fixture %d; the first one without a partner: %s" % (len(got), len(want), (got + want)[min(len(got), len(want))])
+
+
 @pytest.mark.parametrize("so,line", [("libaesgcm_fake.so", "FAKE CAPTURE OK ("), ("libaesgcm_fake_dbg.so", "FAKE CAPTURE OK (forced order: ")])
 def test_captured_calls_keep_capture_discipline_on_the_fake_runtime(so, line):
     """tests/fake_hip/capture_drive.py: every key-table call, recover and commit, the receive loop and the five-array batch calls, once as an ordinary warm-up call and
