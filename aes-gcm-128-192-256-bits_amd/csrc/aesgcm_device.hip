@@ -11,3 +11,4 @@
 #include "aesgcm_srtp_kernels.hip"
 #include "aesgcm_rxwin_kernels.hip"
 #include "aesgcm_txnum_kernels.hip"
+#include "aesgcm_kdf_kernels.hip"

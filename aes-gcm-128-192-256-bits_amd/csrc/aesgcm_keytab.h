@@ -22,6 +22,11 @@ struct __attribute__((aligned(128))) KtSlot {
 static_assert(offsetof(KtSlot, xpn) == 368, "the XPN state fills what was padding: the slot's other fields stay where they were");
 static_assert(sizeof(KtSlot) == 384, "a slot is three 128-byte lines");
 
+// a table's slots for the units that fill them without going through aesgcm_keytab_set* (aesgcm_kdf.hip); defined in aesgcm_keytab.hip
+struct aesgcm_keytab;
+struct KtView { KtSlot *tab; u32 n_slots; int nr, device; };
+KtView kt_view(const aesgcm_keytab *t);
+
 struct KtSetupParams {
     const unsigned char *keys;             // n * key_len bytes
     const u32 *slots;                      // n slot numbers, or NULL = first, first + 1, ...

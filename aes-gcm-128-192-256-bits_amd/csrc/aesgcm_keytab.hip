@@ -24,6 +24,8 @@ struct aesgcm_keytab {
     KtSlot *tab = nullptr;
 };
 
+KtView kt_view(const aesgcm_keytab *t) { return KtView{t->tab, (u32)t->n_slots, t->nr, t->base.device}; }
+
 static int kt_setup(aesgcm_keytab *t, const unsigned char *d_keys, const u32 *d_slots, size_t first, size_t n, hipStream_t st) {
     DeviceState *ds;
     int rc = device_state(t->base.device, &ds);

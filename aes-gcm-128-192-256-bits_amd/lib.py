@@ -49,6 +49,8 @@ SYMBOLS = [
     "aesgcm_rxwin_create", "aesgcm_rxwin_set", "aesgcm_rxwin_get", "aesgcm_rxwin_fmt_check", "aesgcm_rxwin_recover_dev", "aesgcm_rxwin_commit_dev", "aesgcm_rxwin_status",
     "aesgcm_rxwin_destroy",
     "aesgcm_txnum_create", "aesgcm_txnum_set", "aesgcm_txnum_get", "aesgcm_txnum_fmt_check", "aesgcm_txnum_assign_dev", "aesgcm_txnum_status", "aesgcm_txnum_destroy",
+    "aesgcm_kdf_create", "aesgcm_kdf_set", "aesgcm_kdf_set_dev", "aesgcm_kdf_clear", "aesgcm_kdf_fmt_check", "aesgcm_kdf_install_dev", "aesgcm_kdf_update_dev", "aesgcm_kdf_status",
+    "aesgcm_kdf_destroy",
 ]
 
 
@@ -895,7 +897,7 @@ def _device_call(device, up, down, call):
 
 
 class _Table:
-    """what KeyTable, RxWindows and TxCounters share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
+    """what KeyTable, RxWindows, TxCounters and SecretTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
     context manager, status()"""
     _h = _lib = None
 
@@ -1379,6 +1381,129 @@ class TxCounters(_Table):
                                                      b["num"].ptr, b["hi"].ptr, b["slots"].ptr))
         out = None if packets is None else [got["data"][0][off[p]:off[p + 1]] for p in range(n)]
         return out, got["num"], got["hi"], [s == 0xFFFFFFFF for s in got["slots"]]
+
+
+# ---------------------------------------------------------------- on-device key derivation (aesgcm_kdf_*)
+def _kdf_typed(L):
+    """type the aesgcm_kdf_* symbols on first use, as _txnum_typed does: the fake runtime of tests/fake_hip links no such unit and still loads"""
+    if not getattr(L, "_kdf_typed", False):
+        L.aesgcm_kdf_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_kdf_set.argtypes = [vp, sz, sz, vp, vp]
+        L.aesgcm_kdf_set_dev.argtypes = [vp, sz, vp, vp, vp]
+        L.aesgcm_kdf_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_kdf_fmt_check.argtypes = [ctypes.POINTER(KdfFormat)]
+        L.aesgcm_kdf_install_dev.argtypes = [vp, ctypes.POINTER(KdfFormat), vp, sz, vp, vp, vp, vp]
+        L.aesgcm_kdf_update_dev.argtypes = [vp, ctypes.POINTER(KdfFormat), sz, vp, vp, vp]
+        L.aesgcm_kdf_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_kdf_destroy.argtypes = [vp]
+        L._kdf_typed = True
+    return L
+
+
+KDF_LABEL_MAX = 20                                                  # bytes of a full label: the bound under which an HMAC is four compressions
+KDF_NO_SLOT = 0xFFFFFFFF                                            # an entry of d_aux_slots that installs no auxiliary key
+
+
+class KdfFormat(_Format, ctypes.Structure):
+    """aesgcm_kdf_fmt: the four HKDF-Expand-Label labels of a protocol in full, prefix included -- 0 key, 1 iv, 2 aux (QUIC hp / DTLS 1.3 sn), 3 update; len 0 = absent
+    (include/aesgcm.h "ON-DEVICE KEY DERIVATION")"""
+    _fields_ = [("len", ctypes.c_uint8 * 4), ("label", (ctypes.c_uint8 * 20) * 4)]
+    _check, _typed = "aesgcm_kdf_fmt_check", staticmethod(_kdf_typed)
+
+    @classmethod
+    def custom(cls, key, iv=b"", aux=b"", update=b""):
+        """full labels as bytes (b"" or None = absent).  A label longer than 20 bytes keeps its length and its first 20 bytes: check() refuses it"""
+        f = cls()
+        for j, lab in enumerate((key, iv, aux, update)):
+            lab = bytes(lab or b"")
+            if len(lab) > 255:
+                raise AesGcmError(EARG, "a label's length is one byte")
+            f.len[j] = len(lab)
+            for i, c in enumerate(lab[:KDF_LABEL_MAX]):
+                f.label[j][i] = c
+        return f
+
+    def labels(self):
+        """-> the four labels as bytes (b"" = absent)"""
+        return tuple(bytes(self.label[j][:min(self.len[j], KDF_LABEL_MAX)]) for j in range(4))
+
+    def __repr__(self):
+        return "KdfFormat(%s)" % ", ".join(repr(x) for x in self.labels())
+
+    @classmethod
+    def tls13(cls):
+        """RFC 8446 7.3 (key, iv) and 7.2 (traffic upd); TLS has no auxiliary key"""
+        return cls.custom(b"tls13 key", b"tls13 iv", None, b"tls13 traffic upd")
+
+    @classmethod
+    def quic_v1(cls):
+        """RFC 9001 5.1 (quic key, quic iv, quic hp) and 6.1 (quic ku)"""
+        return cls.custom(b"tls13 quic key", b"tls13 quic iv", b"tls13 quic hp", b"tls13 quic ku")
+
+    @classmethod
+    def quic_v2(cls):
+        """RFC 9369 3.3.2: quicv2 key, quicv2 iv, quicv2 hp, quicv2 ku"""
+        return cls.custom(b"tls13 quicv2 key", b"tls13 quicv2 iv", b"tls13 quicv2 hp", b"tls13 quicv2 ku")
+
+    @classmethod
+    def dtls13(cls):
+        """RFC 9147 5.9: the prefix is "dtls13" with no blank; key, iv, sn (4.2.3) and traffic upd (RFC 8446 7.2 under that prefix)"""
+        return cls.custom(b"dtls13key", b"dtls13iv", b"dtls13sn", b"dtls13traffic upd")
+
+
+class SecretTable(_Table):
+    """aesgcm_kdf: n_secrets device-resident traffic secrets of one hash (hash_len 32 = SHA-256, 48 = SHA-384).  install_dev derives key, IV and auxiliary key of a
+    secret into key-table slots, update_dev steps a secret to its next generation; no secret is ever read back (include/aesgcm.h "ON-DEVICE KEY DERIVATION").  Protect
+    the table like keys."""
+    _prefix = "aesgcm_kdf"
+
+    def __init__(self, hash_len, n_secrets, device=0):
+        self._create(_kdf_typed, device, hash_len, n_secrets)
+        self.hash_len, self.n_secrets = hash_len, n_secrets
+
+    def set(self, first, secrets, stream=None):
+        """aesgcm_kdf_set: host secrets (one bytes-like of n * hash_len bytes, or a list of secrets) into records first, first + 1, ..."""
+        sb, n = _per_slot(secrets, self.hash_len, "secrets must be a multiple of %d bytes" % self.hash_len)
+        _chk(self._lib.aesgcm_kdf_set(self._h, first, n, sb, stream))
+        return self
+
+    def set_dev(self, n, d_idx, d_secrets, stream=None):
+        """aesgcm_kdf_set_dev: n secrets from device memory (n x hash_len bytes) into the records d_idx (n uint32, device memory)"""
+        _chk(self._lib.aesgcm_kdf_set_dev(self._h, n, d_idx, d_secrets, stream))
+        return self
+
+    def clear(self, first, n=1, stream=None):
+        """aesgcm_kdf_clear: records first .. first + n - 1 zeroed and unset (their entries are refused)"""
+        _chk(self._lib.aesgcm_kdf_clear(self._h, first, n, stream))
+        return self
+
+    def install_dev(self, fmt, keytab, n, d_idx, d_slots, d_aux_slots=None, stream=None):
+        """aesgcm_kdf_install_dev: entry i derives key and IV of record d_idx[i] into slot d_slots[i] of keytab (a KeyTable), and the auxiliary key into slot
+        d_aux_slots[i] where that array is given and the entry is not KDF_NO_SLOT (all uint32, device memory)"""
+        _chk(self._lib.aesgcm_kdf_install_dev(self._h, ctypes.byref(fmt), keytab._h, n, d_idx, d_slots, d_aux_slots, stream))
+
+    def update_dev(self, fmt, n, d_from, d_to, stream=None):
+        """aesgcm_kdf_update_dev: record d_to[i] = the next generation of record d_from[i] (uint32, device memory; d_to[i] == d_from[i]: in place)"""
+        _chk(self._lib.aesgcm_kdf_update_dev(self._h, ctypes.byref(fmt), n, d_from, d_to, stream))
+
+    def install(self, fmt, keytab, idx, slots, aux_slots=None):
+        """Host convenience (tests, examples): install_dev over host lists, waited for"""
+        n = len(idx)
+        if not n or len(slots) != n or (aux_slots is not None and len(aux_slots) != n):
+            raise AesGcmError(EARG, "idx, slots and aux_slots must be equally long and not empty")
+        up = {"idx": ("I", idx), "slots": ("I", slots)}
+        if aux_slots is not None:
+            up["aux"] = ("I", aux_slots)
+        _device_call(self.device, up, {}, lambda b: self.install_dev(fmt, keytab, n, b["idx"].ptr, b["slots"].ptr, b["aux"].ptr if aux_slots is not None else None))
+        return self
+
+    def update(self, fmt, frm, to):
+        """Host convenience (tests, examples): update_dev over host lists, waited for"""
+        n = len(frm)
+        if not n or len(to) != n:
+            raise AesGcmError(EARG, "frm and to must be equally long and not empty")
+        _device_call(self.device, {"frm": ("I", frm), "to": ("I", to)}, {}, lambda b: self.update_dev(fmt, n, b["frm"].ptr, b["to"].ptr))
+        return self
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

@@ -40,7 +40,7 @@ extern "C" {
 #define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
                                   aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
-                                  the send counters aesgcm_txnum_* / aesgcm_txnum_fmt)
+                                  the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -421,13 +421,15 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * back, no event.  They may run under hipStreamBeginCapture on `stream` (a created stream; thread-local capture mode suffices), several of them behind one another, and
  * the graph may be replayed over other slots, numbers, lengths, offsets and bytes in the same buffers; a receive loop's window state travels from replay to replay in
  * the window records.  (The five-array aesgcm_batch_crypt_dev / _var_dev plan their launch the same way and follow the same rules.)
+ * aesgcm_kdf_install_dev and aesgcm_kdf_update_dev ("ON-DEVICE KEY DERIVATION" below) belong to this list too: one launch each, no memset node, no dispenser; the
+ * graph holds the secret records beside the slots, and a replayed update in place steps its secrets one generation per replay.
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
  *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
  *   ORDERING         a captured call is never ordered by falling length class, whatever its count: the order's scratch belongs to the device, not to the graph.  The
  *                    packets are taken in array order -- the same bytes, slower from the counts at which an ordinary call is ordered.
  *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
- *                    that grow, events, synchronous copies, waits): call them outside the capture.
+ *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
  *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
@@ -837,6 +839,59 @@ AESGCM_API int aesgcm_txnum_assign_dev(aesgcm_txnum *t, const aesgcm_txnum_fmt *
                             uint64_t *d_num_out, uint32_t *d_hi_out, uint32_t *d_slots, void *stream);
 AESGCM_API int aesgcm_txnum_status(aesgcm_txnum *t, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_txnum_destroy(aesgcm_txnum *t);
+
+/* ---------------------------------------------------------------- ON-DEVICE KEY DERIVATION: TLS 1.3, QUIC and DTLS 1.3 keys from traffic secrets that never leave the device
+ * In TLS 1.3 (RFC 8446 7.3), QUIC (RFC 9001 5.1, RFC 9369 3.3.2) and DTLS 1.3 (RFC 9147 5.9) a direction's AEAD key, its IV and its header-protection / record-number
+ * key all come from ONE traffic secret by HKDF-Expand-Label, and the next generation's secret comes from this one the same way (RFC 8446 7.2, RFC 9001 6).
+ * aesgcm_kdf is a table of n_secrets such secrets on the device, of one hash: hash_len 32 = SHA-256, 48 = SHA-384.  No call reads a secret back.  THE TABLE HOLDS
+ * TRAFFIC SECRETS: PROTECT IT LIKE KEYS -- whoever holds a secret holds every key of its generation and of all later ones.
+ *   aesgcm_kdf_create     every record unset.  AESGCM_EARG for a hash_len other than 32 / 48, n_secrets == 0 or >= 2^31.
+ *   aesgcm_kdf_set        HOST secrets (n * hash_len bytes) into records first .. first + n - 1, through the table's staging buffer on `stream`, which is zeroed
+ *                         behind the copy as aesgcm_keytab_set zeroes its keys; the library's host copy is wiped before the call returns.
+ *   aesgcm_kdf_set_dev    n secrets from DEVICE memory (n * hash_len bytes, no alignment asked) into the records d_idx[i]; an index out of range is refused.
+ *   aesgcm_kdf_clear      records first .. first + n - 1 zeroed and unset.
+ *   aesgcm_kdf_status     as aesgcm_keytab_status: the LOWEST entry index an install, update or set_dev call refused since the last read, which clears it.
+ *   aesgcm_kdf_destroy    waits for the device, zeroes the records and the staging buffer, frees.
+ * A FORMAT names the four labels in full, prefix included ("tls13 key", "tls13 quic hp", "dtls13sn"): 0 the key, 1 the IV, 2 the auxiliary key (QUIC's hp, DTLS 1.3's
+ * sn), 3 the update; len 0 = the protocol has none.  aesgcm_kdf_fmt_check: AESGCM_EARG for NULL, a label longer than 20 bytes, no label 0.  It touches no device.
+ * THE BOUND: only HKDF-Expand-Label(secret, label, "", L) with L <= hash_len is computed.  With a label of at most 20 bytes the HMAC's message is at most 25 bytes and
+ * every HMAC is exactly four compressions (csrc/aesgcm_kdf.h); the kernels rely on the check and do not repeat it.
+ * INSTALL: aesgcm_kdf_install_dev(k, fmt, keytab, n, d_idx, d_slots, d_aux_slots, stream).  For entry i with the secret s of record d_idx[i]:
+ *   slot d_slots[i] of `keytab` becomes exactly what aesgcm_keytab_set_dev makes of Expand-Label(s, label 0, key_len) -- round keys, H, its powers, the set marker --
+ *   and its TLS-IV field what aesgcm_keytab_set_tls_iv makes of Expand-Label(s, label 1, 12);
+ *   with d_aux_slots != NULL and d_aux_slots[i] != 0xFFFFFFFF, slot d_aux_slots[i] is set from Expand-Label(s, label 2, key_len).
+ * The table's key size may be 16, 24 or 32 with either hash.  AESGCM_EARG for a format without label 1, for d_aux_slots with a format that has no label 2, and for a key
+ * table of another device.  A key update passes d_aux_slots = NULL: QUIC's hp key and DTLS 1.3's sn key do not change with the generation.
+ * UPDATE: aesgcm_kdf_update_dev(k, fmt, n, d_from, d_to, stream): rec[d_to[i]] = Expand-Label(rec[d_from[i]], label 3, hash_len), marked set.  d_to[i] == d_from[i] is the
+ * update in place (the lane holds the whole secret before it writes).  Two entries of one call that name the same d_to, or an entry whose d_from is another entry's d_to,
+ * are the caller's error: that record is unspecified.  An endpoint that keeps the current and the next generation uses two records.
+ * REFUSED ENTRIES are skipped whole -- NOTHING an entry names is written -- when d_idx[i], d_from[i] or d_to[i] is out of range, the source record is unset or
+ * cleared, d_slots[i] is out of range, or an aux slot other than 0xFFFFFFFF is out of range.  The lowest such index goes to the SECRET table's status word; the key
+ * table's status is not touched.
+ * NO DERIVED KEY IN MEMORY: a derived key or IV is stored nowhere but in the slot's fields (a new secret: in its record).  The lane that expands a key runs the key
+ * schedule itself, from its registers.
+ * One launch per call, a lane per derived value (k_kdf_install: entries x {key, iv, aux}, k_kdf_update); no allocation, no event, no host synchronisation, nothing
+ * read back: install and update are capture-safe (CAPTURE, under "key tables" above) and asynchronous on `stream`.  Every call is stream-ordered on `stream`; an
+ * install on one stream and a crypt call on another that names the slot are the caller's to order, as with aesgcm_keytab_set.  So the key-update loop runs as launches
+ * on one stream: aesgcm_txnum_assign_dev refuses at the limit, update, install into a fresh slot, reset the counter, encrypt (INTEGRATION.md "Key derivation").
+ * The host calls of one table are thread-safe; a table belongs to its device.
+ * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF; SRTP's AES-CM key derivation (RFC 3711 4.3);
+ * ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash. */
+typedef struct aesgcm_kdf aesgcm_kdf;
+typedef struct aesgcm_kdf_fmt {
+    uint8_t len[4];         /* bytes of each label, 0 = absent, at most 20                                  */
+    uint8_t label[4][20];   /* full labels, prefix included: 0 key, 1 iv, 2 aux (hp / sn), 3 update        */
+} aesgcm_kdf_fmt;           /* 84 bytes */
+AESGCM_API int aesgcm_kdf_create(aesgcm_kdf **out, int device, size_t hash_len, size_t n_secrets);
+AESGCM_API int aesgcm_kdf_set(aesgcm_kdf *k, size_t first, size_t n, const uint8_t *secrets, void *stream);
+AESGCM_API int aesgcm_kdf_set_dev(aesgcm_kdf *k, size_t n, const uint32_t *d_idx, const void *d_secrets, void *stream);
+AESGCM_API int aesgcm_kdf_clear(aesgcm_kdf *k, size_t first, size_t n, void *stream);
+AESGCM_API int aesgcm_kdf_fmt_check(const aesgcm_kdf_fmt *fmt);
+AESGCM_API int aesgcm_kdf_install_dev(aesgcm_kdf *k, const aesgcm_kdf_fmt *fmt, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const uint32_t *d_slots,
+                           const uint32_t *d_aux_slots, void *stream);
+AESGCM_API int aesgcm_kdf_update_dev(aesgcm_kdf *k, const aesgcm_kdf_fmt *fmt, size_t n, const uint32_t *d_from, const uint32_t *d_to, void *stream);
+AESGCM_API int aesgcm_kdf_status(aesgcm_kdf *k, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_kdf_destroy(aesgcm_kdf *k);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->

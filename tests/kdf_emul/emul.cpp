@@ -1,0 +1,68 @@
+// CPU harness for the key derivation's lane code (csrc/aesgcm_kdf.h is __host__ __device__): it runs the SAME compressions (kdf_sha256_block, kdf_sha512_block), the
+// same message block (kdf_msg) and the same four-compression expansion (kdf_expand) that k_kdf_install and k_kdf_update run, and prints what they give.
+// tests/test_kdf_cpu.py writes the scripts and holds every line to hashlib, to hmac and to the fixtures' HKDF-Expand-Label.  Test infrastructure only.
+//   H hl hex | H hl -                the hash (hl 32: SHA-256, 48: SHA-384) of a message that fits ONE block (at most 55 / 111 bytes)   -> "h hex"
+//   X hl secret label L              HKDF-Expand-Label(secret, full label, "", L): secret hl bytes, label 1 .. 20 bytes, both in hex      -> "x hex" (L bytes)
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_kdf.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+static std::vector<unsigned char> unhex(const char *s) {
+    std::vector<unsigned char> v;
+    if (s[0] == '-') return v;
+    for (size_t k = 0; s[2 * k] && s[2 * k + 1]; k++) { unsigned b; sscanf(s + 2 * k, "%2x", &b); v.push_back((unsigned char)b); }
+    return v;
+}
+static void put_words(const char *tag, const u32 *w, size_t bytes) {
+    printf("%s ", tag);
+    for (size_t k = 0; k < bytes; k++) printf("%02x", (w[k / 4] >> (24 - 8 * (k % 4))) & 0xFFu);
+    printf("\n");
+}
+
+int main() {
+    static char line[4096], a[2048], b[2048];
+    auto need = [&](bool ok) { if (!ok) { printf("bad script line: %s\n", line); exit(2); } };
+    while (fgets(line, sizeof line, stdin)) {
+        unsigned hl, L;
+        if (line[0] == 'H') {
+            need(sscanf(line + 1, "%u %2047s", &hl, a) == 2 && (hl == 32 || hl == 48));
+            const std::vector<unsigned char> m = unhex(a);
+            const size_t block = hl == 32 ? 64 : 128, lenbytes = hl == 32 ? 8 : 16;
+            need(m.size() + 1 + lenbytes <= block);
+            unsigned char blk[128] = {0};
+            if (!m.empty()) memcpy(blk, m.data(), m.size());
+            blk[m.size()] = 0x80;
+            const u64 bits = 8ull * m.size();
+            for (int k = 0; k < 8; k++) blk[block - 1 - k] = (unsigned char)(bits >> (8 * k));
+            u32 out[12];
+            if (hl == 32) {
+                u32 st[8], w[16];
+                for (int k = 0; k < 16; k++) w[k] = ((u32)blk[4 * k] << 24) | ((u32)blk[4 * k + 1] << 16) | ((u32)blk[4 * k + 2] << 8) | blk[4 * k + 3];
+                kdf_sha256_init(st);
+                kdf_sha256_block(st, w);
+                for (int k = 0; k < 8; k++) out[k] = st[k];
+            } else {
+                u64 st[8], w[16];
+                for (int k = 0; k < 16; k++) { w[k] = 0; for (int j = 0; j < 8; j++) w[k] = (w[k] << 8) | blk[8 * k + j]; }
+                kdf_sha384_init(st);
+                kdf_sha512_block(st, w);
+                for (int k = 0; k < 6; k++) { out[2 * k] = (u32)(st[k] >> 32); out[2 * k + 1] = (u32)st[k]; }
+            }
+            put_words("h", out, hl);
+        } else if (line[0] == 'X') {
+            need(sscanf(line + 1, "%u %2047s %2047s %u", &hl, a, b, &L) == 4 && (hl == 32 || hl == 48));
+            const std::vector<unsigned char> sec = unhex(a), lab = unhex(b);
+            need(sec.size() == hl && !lab.empty() && lab.size() <= KDF_LABEL_MAX && L && L <= hl);
+            u32 s[12], out[12];
+            for (unsigned k = 0; k < hl / 4; k++) s[k] = ((u32)sec[4 * k] << 24) | ((u32)sec[4 * k + 1] << 16) | ((u32)sec[4 * k + 2] << 8) | sec[4 * k + 3];
+            KdfMsg m;
+            kdf_msg(lab.data(), (u32)lab.size(), L, m);
+            if (hl == 32) kdf_expand<32>(s, m, out); else kdf_expand<48>(s, m, out);
+            put_words("x", out, L);
+        } else need(line[0] == '#' || line[0] == '\n');
+    }
+    return 0;
+}
