@@ -12,3 +12,4 @@
 #include "aesgcm_rxwin_kernels.hip"
 #include "aesgcm_txnum_kernels.hip"
 #include "aesgcm_kdf_kernels.hip"
+#include "aesgcm_srtp_kdf_kernels.hip"

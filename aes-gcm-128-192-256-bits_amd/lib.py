@@ -51,6 +51,8 @@ SYMBOLS = [
     "aesgcm_txnum_create", "aesgcm_txnum_set", "aesgcm_txnum_get", "aesgcm_txnum_fmt_check", "aesgcm_txnum_assign_dev", "aesgcm_txnum_status", "aesgcm_txnum_destroy",
     "aesgcm_kdf_create", "aesgcm_kdf_set", "aesgcm_kdf_set_dev", "aesgcm_kdf_clear", "aesgcm_kdf_fmt_check", "aesgcm_kdf_install_dev", "aesgcm_kdf_update_dev", "aesgcm_kdf_status",
     "aesgcm_kdf_destroy",
+    "aesgcm_srtp_kdf_create", "aesgcm_srtp_kdf_set", "aesgcm_srtp_kdf_set_dev", "aesgcm_srtp_kdf_clear", "aesgcm_srtp_kdf_install_dev", "aesgcm_srtp_kdf_status",
+    "aesgcm_srtp_kdf_destroy",
 ]
 
 
@@ -897,7 +899,7 @@ def _device_call(device, up, down, call):
 
 
 class _Table:
-    """what KeyTable, RxWindows, TxCounters and SecretTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
+    """what KeyTable, RxWindows, TxCounters, SecretTable and MasterKeyTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
     context manager, status()"""
     _h = _lib = None
 
@@ -1503,6 +1505,74 @@ class SecretTable(_Table):
         if not n or len(to) != n:
             raise AesGcmError(EARG, "frm and to must be equally long and not empty")
         _device_call(self.device, {"frm": ("I", frm), "to": ("I", to)}, {}, lambda b: self.update_dev(fmt, n, b["frm"].ptr, b["to"].ptr))
+        return self
+
+
+# ---------------------------------------------------------------- SRTP's on-device key derivation (aesgcm_srtp_kdf_*)
+def _srtp_kdf_typed(L):
+    """type the aesgcm_srtp_kdf_* symbols on first use, as _kdf_typed does: the fake runtime of tests/fake_hip links no such unit and still loads"""
+    if not getattr(L, "_srtp_kdf_typed", False):
+        L.aesgcm_srtp_kdf_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_srtp_kdf_set.argtypes = [vp, sz, sz, vp, vp, vp]
+        L.aesgcm_srtp_kdf_set_dev.argtypes = [vp, sz, vp, vp, vp, vp]
+        L.aesgcm_srtp_kdf_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_srtp_kdf_install_dev.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, vp, vp, vp]
+        L.aesgcm_srtp_kdf_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_srtp_kdf_destroy.argtypes = [vp]
+        L._srtp_kdf_typed = True
+    return L
+
+
+SRTP_MASTER_SALT_LEN = 14                                           # bytes of a master salt in the C ABI; an AEAD profile's 12 are padded on the right
+
+
+class MasterKeyTable(_Table):
+    """aesgcm_srtp_kdf: n_masters device-resident SRTP master keys (key_len 16 / 24 / 32) and master salts.  install_dev derives a master's SRTP or SRTCP session key
+    and session salt (RFC 3711 4.3.1, RFC 6188; labels 0x00 / 0x02 and 0x03 / 0x05) into key-table slots; no master is ever read back (include/aesgcm.h "SRTP KEY
+    DERIVATION").  Protect the table like keys."""
+    _prefix = "aesgcm_srtp_kdf"
+
+    def __init__(self, key_len, n_masters, device=0):
+        self._create(_srtp_kdf_typed, device, key_len, n_masters)
+        self.key_len, self.n_masters = key_len, n_masters
+
+    def set(self, first, keys, salts, stream=None):
+        """aesgcm_srtp_kdf_set: host master keys (one bytes-like of n * key_len bytes, or a list) and master salts (a list of 12- or 14-byte salts, a 12-byte one
+        padded with two zero bytes on the right as RFC 7714 11 enters it into the PRF; or one bytes-like of n * 14 bytes) into records first, first + 1, ..."""
+        kb, n = _per_slot(keys, self.key_len, "master keys must be a multiple of %d bytes" % self.key_len)
+        what = "a master salt is 12 or 14 bytes, one per master key"
+        if isinstance(salts, (list, tuple)) and any(len(x) not in (12, SRTP_MASTER_SALT_LEN) for x in salts):
+            raise AesGcmError(EARG, what)
+        sb, ns = _per_slot(salts, SRTP_MASTER_SALT_LEN, what, pad=True)
+        if ns != n:
+            raise AesGcmError(EARG, what)
+        _chk(self._lib.aesgcm_srtp_kdf_set(self._h, first, n, kb, sb, stream))
+        return self
+
+    def set_dev(self, n, d_idx, d_keys, d_salts, stream=None):
+        """aesgcm_srtp_kdf_set_dev: n master keys (n x key_len bytes) and salts (n x 14 bytes) from device memory into the records d_idx (n uint32, device memory)"""
+        _chk(self._lib.aesgcm_srtp_kdf_set_dev(self._h, n, d_idx, d_keys, d_salts, stream))
+        return self
+
+    def clear(self, first, n=1, stream=None):
+        """aesgcm_srtp_kdf_clear: records first .. first + n - 1 zeroed and unset (their entries are refused)"""
+        _chk(self._lib.aesgcm_srtp_kdf_clear(self._h, first, n, stream))
+        return self
+
+    def install_dev(self, kind, keytab, n, d_idx, d_slots, d_r=None, stream=None):
+        """aesgcm_srtp_kdf_install_dev: entry i derives the session key and salt of record d_idx[i] for kind (SRTP_RTP or SRTP_RTCP) under r = d_r[i] (uint64, device
+        memory; None: all 0) into slot d_slots[i] of keytab (a KeyTable of the same key size; d_idx and d_slots uint32, device memory)"""
+        _chk(self._lib.aesgcm_srtp_kdf_install_dev(self._h, kind, keytab._h, n, d_idx, d_slots, d_r, stream))
+
+    def install(self, kind, keytab, idx, slots, r=None):
+        """Host convenience (tests, examples): install_dev over host lists, waited for.  As SecretTable.install: refused entries are what status() reports"""
+        n = len(idx)
+        if not n or len(slots) != n or (r is not None and len(r) != n):
+            raise AesGcmError(EARG, "idx, slots and r must be equally long and not empty")
+        up = {"idx": ("I", idx), "slots": ("I", slots)}
+        if r is not None:
+            up["r"] = ("Q", r)
+        _device_call(self.device, up, {}, lambda b: self.install_dev(kind, keytab, n, b["idx"].ptr, b["slots"].ptr, b["r"].ptr if r is not None else None))
         return self
 
 

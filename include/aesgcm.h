@@ -40,7 +40,8 @@ extern "C" {
 #define AESGCM_ABI_VERSION 5   /* (additions since, the version unchanged: key tables, their frames in wire format, aesgcm_wire_xfmt / aesgcm_keytab_set_xpn / aesgcm_keytab_frames_crypt_x_dev,
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
                                   aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
-                                  the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt)
+                                  the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt,
+                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -422,14 +423,16 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * the graph may be replayed over other slots, numbers, lengths, offsets and bytes in the same buffers; a receive loop's window state travels from replay to replay in
  * the window records.  (The five-array aesgcm_batch_crypt_dev / _var_dev plan their launch the same way and follow the same rules.)
  * aesgcm_kdf_install_dev and aesgcm_kdf_update_dev ("ON-DEVICE KEY DERIVATION" below) belong to this list too: one launch each, no memset node, no dispenser; the
- * graph holds the secret records beside the slots, and a replayed update in place steps its secrets one generation per replay.
+ * graph holds the secret records beside the slots, and a replayed update in place steps its secrets one generation per replay.  So does aesgcm_srtp_kdf_install_dev
+ * ("SRTP KEY DERIVATION" below): one launch, and the graph holds the master records beside the slots.
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
  *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
  *   ORDERING         a captured call is never ordered by falling length class, whatever its count: the order's scratch belongs to the device, not to the graph.  The
  *                    packets are taken in array order -- the same bytes, slower from the counts at which an ordinary call is ordered.
  *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
- *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy.
+ *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy
+ *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
  *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
@@ -685,8 +688,8 @@ AESGCM_API int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const
  * d_in, d_pkt_off, d_out NULL; RTP without d_roc; decrypt without d_auth; n_pkts >= 2^31.
  * ONE k_kt_srtp launch: no scratch memory, no host synchronisation, capture-safe (CAPTURE, under "key tables" above) and asynchronous; shape, order and planning as aesgcm_keytab_dtls_crypt_dev's DTLS 1.2
  * mode.  Ordering and thread safety as the other key-table calls.
- * OUT OF SCOPE: ROC estimation and replay windows (not this call's: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_SRTP writes d_roc, aesgcm_rxwin_commit_dev keeps the window); key derivation (RFC 3711 4.3 KDF, the DTLS-SRTP exporter: INTEGRATION.md "SRTP and SRTCP packets" says which secret
- * becomes what); the AES-CM / HMAC-SHA1 transforms; double encryption (RFC 8723); RFC 6904 header-extension encryption; MKI lookup (the caller maps an MKI to a slot, and one
+ * OUT OF SCOPE: ROC estimation and replay windows (not this call's: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_SRTP writes d_roc, aesgcm_rxwin_commit_dev keeps the window); the DTLS-SRTP exporter (the master key and salt are the caller's: INTEGRATION.md "SRTP and SRTCP packets" says which secret
+ * becomes what -- the session key derivation from them, RFC 3711 4.3, is aesgcm_srtp_kdf_* under "SRTP KEY DERIVATION" below); the AES-CM / HMAC-SHA1 transforms; double encryption (RFC 8723); RFC 6904 header-extension encryption; MKI lookup (the caller maps an MKI to a slot, and one
  * call has one mki_len); splitting reduced-size or multiplexed datagrams (one entry of d_pkt_off per packet; a compound RTCP packet is ONE packet). */
 #define AESGCM_SRTP_RTP  1u
 #define AESGCM_SRTP_RTCP 2u
@@ -875,8 +878,8 @@ AESGCM_API int aesgcm_txnum_destroy(aesgcm_txnum *t);
  * install on one stream and a crypt call on another that names the slot are the caller's to order, as with aesgcm_keytab_set.  So the key-update loop runs as launches
  * on one stream: aesgcm_txnum_assign_dev refuses at the limit, update, install into a fresh slot, reset the counter, encrypt (INTEGRATION.md "Key derivation").
  * The host calls of one table are thread-safe; a table belongs to its device.
- * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF; SRTP's AES-CM key derivation (RFC 3711 4.3);
- * ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash. */
+ * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF; ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash.  (SRTP's AES-CM key
+ * derivation, RFC 3711 4.3, is no HKDF and has a table of its own: aesgcm_srtp_kdf_*, "SRTP KEY DERIVATION" below.) */
 typedef struct aesgcm_kdf aesgcm_kdf;
 typedef struct aesgcm_kdf_fmt {
     uint8_t len[4];         /* bytes of each label, 0 = absent, at most 20                                  */
@@ -892,6 +895,54 @@ AESGCM_API int aesgcm_kdf_install_dev(aesgcm_kdf *k, const aesgcm_kdf_fmt *fmt, 
 AESGCM_API int aesgcm_kdf_update_dev(aesgcm_kdf *k, const aesgcm_kdf_fmt *fmt, size_t n, const uint32_t *d_from, const uint32_t *d_to, void *stream);
 AESGCM_API int aesgcm_kdf_status(aesgcm_kdf *k, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_kdf_destroy(aesgcm_kdf *k);
+
+/* ---------------------------------------------------------------- SRTP KEY DERIVATION: SRTP and SRTCP session keys from master keys that never leave the device
+ * An SRTP stream has ONE master key and master salt (from the DTLS-SRTP exporter or SDES: the caller's) and two derived sets of session keys, one for SRTP and one for
+ * SRTCP, which a non-zero key_derivation_rate derives anew periodically (RFC 3711 4.3).  aesgcm_srtp_kdf is a table of n_masters such master keys and salts on the
+ * device, of one key size: key_len 16, 24 or 32.  No call reads a master back.  THE TABLE HOLDS MASTER KEYS: PROTECT IT LIKE KEYS.
+ * THE DERIVATION (RFC 3711 4.3.1; RFC 6188 for AES-192 / AES-256 master keys; labels as RFC 7714 11 uses them): with the master key mk, the 14-byte master salt ms, a
+ * label byte and the 48-bit r = index DIV key_derivation_rate (0 where the rate is 0),
+ *   x = ms XOR (0^56 | label | be48(r)), 14 bytes: the label XORs into byte 7, r into bytes 8 .. 13;
+ *   output = E_mk(x | be16(0)) | E_mk(x | be16(1)) | ..., truncated.
+ * Labels: SRTP key 0x00, SRTP salt 0x02, SRTCP key 0x03, SRTCP salt 0x05; the GCM transforms have no authentication key.  The session key is key_len bytes (two blocks
+ * for AES-192 / AES-256), the session salt the first 12 bytes of its block -- what aesgcm_keytab_set_tls_iv holds and aesgcm_keytab_srtp_crypt_dev reads.  The PRF's AES
+ * size is the master key's, which must be the key table's: AES_128_CM for 16-byte slots, AES_192_CM / AES_256_CM (RFC 6188) otherwise.
+ * THE MASTER SALT IS 14 BYTES HERE, ALWAYS.  The AEAD profiles of RFC 7714 carry a 12-byte master salt; as this library reads RFC 7714 11, the PRF takes it multiplied
+ * by 2^16, that is, WITH TWO ZERO BYTES APPENDED on the right: a caller with a 12-byte salt passes those 14 bytes (the Python binding pads).
+ *   aesgcm_srtp_kdf_create   every record unset.  AESGCM_EARG for a key_len other than 16 / 24 / 32, n_masters == 0 or >= 2^31.
+ *   aesgcm_srtp_kdf_set      HOST master keys (n * key_len bytes) and salts (n * 14 bytes) into records first .. first + n - 1, through the table's staging buffer on
+ *                            `stream`, zeroed behind the copy; the library's host copy is wiped before the call returns (as aesgcm_kdf_set).
+ *   aesgcm_srtp_kdf_set_dev  n master keys and salts from DEVICE memory (n * key_len and n * 14 bytes, no alignment asked) into the records d_idx[i]; an index out
+ *                            of range is refused.
+ *   aesgcm_srtp_kdf_clear    records first .. first + n - 1 zeroed and unset.
+ *   aesgcm_srtp_kdf_status   as aesgcm_keytab_status: the LOWEST entry index an install or set_dev call refused since the last read, which clears it.
+ *   aesgcm_srtp_kdf_destroy  waits for the device, zeroes the records and the staging buffer, frees.
+ * INSTALL: aesgcm_srtp_kdf_install_dev(k, kind, keytab, n, d_idx, d_slots, d_r, stream), kind = AESGCM_SRTP_RTP or AESGCM_SRTP_RTCP.  For entry i with the master of
+ * record d_idx[i] and r = d_r[i] (DEVICE memory, n uint64; d_r = NULL: every r is 0):
+ *   slot d_slots[i] of `keytab` becomes exactly what aesgcm_keytab_set_dev makes of the session key under the kind's key label -- round keys, H, its powers, the set
+ *   marker -- and its TLS-IV field what aesgcm_keytab_set_tls_iv makes of the first 12 bytes of the session salt under the kind's salt label.
+ * An SRTP and an SRTCP slot of one stream are two calls over the same d_idx.  A new key-derivation period is the same call with the new r, into fresh slots where packets
+ * of the old period are still in flight (INTEGRATION.md "Key derivation").
+ * AESGCM_EARG, before a device is touched: a kind that is neither constant; k or keytab NULL; (n == 0 is AESGCM_OK;) d_idx or d_slots NULL; n >= 2^31; a key table of
+ * another device; a key table whose key size is not the master table's.
+ * REFUSED ENTRIES are skipped whole -- NOTHING an entry names is written -- when d_idx[i] is out of range, the record is unset or cleared, d_slots[i] is out of range,
+ * or d_r[i] >= 2^48.  The lowest such index goes to the MASTER table's status word; the key table's status is not touched.
+ * NO DERIVED KEY IN MEMORY: the lane that derives a session key loads the master key into registers, runs its key schedule there, encrypts the counter blocks and runs
+ * the session key's schedule from the output words; neither the master key's schedule nor the PRF's output is stored anywhere, a session key and salt nowhere but in
+ * the slot's fields.
+ * One launch per install, a lane per derived value (k_srtp_kdf_install: entries x {key, salt}); no allocation, no event, no host synchronisation, nothing read back:
+ * install is capture-safe (CAPTURE, under "key tables" above) and asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
+ * OUT OF SCOPE: the DTLS-SRTP exporter and SDES; the authentication-key labels (0x01, 0x04) and the AES-CM / HMAC-SHA1 transforms they serve; RFC 6904's header
+ * labels; counting packets to the next period (r is the caller's, per entry); the TLS 1.2 / DTLS 1.2 PRF. */
+typedef struct aesgcm_srtp_kdf aesgcm_srtp_kdf;
+AESGCM_API int aesgcm_srtp_kdf_create(aesgcm_srtp_kdf **out, int device, size_t key_len, size_t n_masters);
+AESGCM_API int aesgcm_srtp_kdf_set(aesgcm_srtp_kdf *k, size_t first, size_t n, const uint8_t *keys, const uint8_t *salts, void *stream);
+AESGCM_API int aesgcm_srtp_kdf_set_dev(aesgcm_srtp_kdf *k, size_t n, const uint32_t *d_idx, const void *d_keys, const void *d_salts, void *stream);
+AESGCM_API int aesgcm_srtp_kdf_clear(aesgcm_srtp_kdf *k, size_t first, size_t n, void *stream);
+AESGCM_API int aesgcm_srtp_kdf_install_dev(aesgcm_srtp_kdf *k, uint32_t kind, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const uint32_t *d_slots,
+                                const uint64_t *d_r, void *stream);
+AESGCM_API int aesgcm_srtp_kdf_status(aesgcm_srtp_kdf *k, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_srtp_kdf_destroy(aesgcm_srtp_kdf *k);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
