@@ -210,7 +210,14 @@ AESGCM_API int aesgcm_decrypt(aesgcm_ctx *ctx, const uint8_t iv[12], const uint8
  * copies see it complete as always.  Pass tag = NULL to skip the wait: the call only enqueues, and
  * aesgcm_last_tag() later collects the tag of the context's most recent message the same way (a poll of
  * the host slot) -- several contexts of one key, each with its own stream, keep several messages in
- * flight that way (bench.py --inflight). */
+ * flight that way (bench.py --inflight).
+ * What the call touches, in every launch structure the library may choose: it reads exactly `len`
+ * bytes of d_in and `aad_len` bytes of d_aad, and writes exactly `len` bytes of d_out -- nothing in
+ * front of either range and nothing behind a ragged end, so no slack up to the next 16 bytes (or row,
+ * or vector store) is needed and neighbouring buffers may touch.  Out of place, d_in and d_aad are
+ * left as they were.  aesgcm_decrypt_dev with expect_tag that fails verification under the context
+ * option "wipe_on_auth_fail" zeroes exactly those `len` bytes of d_pt.  aesgcm_keystream_dev writes
+ * exactly 16 * nblocks bytes; a refused call writes nothing.  (tests/test_gpu_msg_grid.py) */
 AESGCM_API int aesgcm_encrypt_dev(aesgcm_ctx *ctx, const uint8_t iv[12], const void *d_aad, size_t aad_len,
                        const void *d_pt, size_t len, void *d_ct, uint8_t tag[16], void *stream);
 AESGCM_API int aesgcm_decrypt_dev(aesgcm_ctx *ctx, const uint8_t iv[12], const void *d_aad, size_t aad_len,
@@ -234,7 +241,10 @@ AESGCM_API int aesgcm_keystream_dev(aesgcm_ctx *ctx, const uint8_t iv[12], uint6
  *    W_g = (sum_{i in shard} X_i * H^(end_g-1-i)) * H^(n_total_blocks - end_g)
  * to d_partial (device memory).  Partials of all ranks are exchanged by the caller (one 16-byte
  * all-gather, e.g. RCCL) and handed to aesgcm_shard_finalize, which XOR-folds them on the device and
- * produces tag = GHASH xor E_K(IV||1). */
+ * produces tag = GHASH xor E_K(IV||1).
+ * A shard reads exactly `len` bytes of d_in (rank 0: and aad_len of d_aad) and writes exactly `len`
+ * bytes of d_out and the 16 bytes of d_partial, from whatever first block: the ranks of one message
+ * may write one buffer in any order, each leaves its neighbours' ranges alone. */
 AESGCM_API int aesgcm_shard_crypt_dev(aesgcm_ctx *ctx, int decrypt, const uint8_t iv[12],
                            const void *d_aad, size_t aad_len,
                            const void *d_in, size_t len, void *d_out,
@@ -956,7 +966,8 @@ AESGCM_API int aesgcm_stream_update(aesgcm_ctx *ctx, const uint8_t *in, size_t l
 AESGCM_API int aesgcm_stream_final(aesgcm_ctx *ctx, uint8_t tag[16]);
 /* The same step on DEVICE pointers (round 6): d_in / d_out 16-byte aligned, may alias; asynchronous on `stream` (NULL = the context's own).  The steps of one session
  * may come on different streams: the library orders them itself (each step's stream waits on the device for the session's previous step; no host synchronisation).  A chunk of any size takes the launch structure a shard of that size takes, so a message of unknown total length that is
- * already on the GPU runs at the rate of aesgcm_shard_crypt_dev.  Every chunk but the last a multiple of 16 bytes. */
+ * already on the GPU runs at the rate of aesgcm_shard_crypt_dev.  Every chunk but the last a multiple of 16 bytes.  As a shard, a chunk reads exactly `len` bytes of d_in and
+ * writes exactly `len` bytes of d_out: no slack behind the ragged last chunk, and chunks may go to buffers that touch. */
 AESGCM_API int aesgcm_stream_update_dev(aesgcm_ctx *ctx, const void *d_in, size_t len, void *d_out, void *stream);
 /* The state of the open session as 64 bytes the caller can keep, move and pick up again -- in another context of the same key, on another device, in another process
  * (SURVEY.md 5 "checkpoint / resume", 8(f2)): what the RTL holds in its Y register (src/gcm_ghash.vhd:174-186) and its counter (src/aes_icb.vhd:97-100) and cannot hand out.
