@@ -285,6 +285,29 @@ int devtab_stage(DevTable *b, size_t bytes, hipStream_t st) {
     return AESGCM_OK;
 }
 
+int devtab_put(DevTable *b, void *dst, const void *host, size_t bytes, hipStream_t st, bool secret) {
+    return devtab_staged(*b, bytes, st, secret, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(b->stage, host, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dst, b->stage, bytes, hipMemcpyDeviceToDevice, st));
+        return AESGCM_OK;
+    });
+}
+
+int devtab_get(DevTable *b, void *host, const void *src, size_t bytes, hipStream_t st) {
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return AESGCM_OK;
+}
+
+int devtab_clear(DevTable *b, void *at, size_t bytes, hipStream_t st) {
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemsetAsync(at, 0, bytes, st));
+    return AESGCM_OK;
+}
+
+void host_wipe(void *p, size_t n) { volatile unsigned char *v = (volatile unsigned char *)p; while (n--) *v++ = 0; }
+
 int devtab_status(DevTable *b, int *code, uint64_t *detail) {
     HIPCHK(hipSetDevice(b->device));
     u32 w = ~0u;

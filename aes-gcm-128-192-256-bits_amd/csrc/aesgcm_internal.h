@@ -248,9 +248,11 @@ void pipeline_release(aesgcm_ctx *c);
 int pipeline_prepare(aesgcm_ctx *c, size_t chunk);
 int crypt_pipelined(aesgcm_ctx *c, int dec, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out, uint8_t tag[16], size_t chunk);
 
-// ---------------------------------------------------------------- device tables: what the host sides of a key table (aesgcm_keytab.hip) and of receive windows
-// (aesgcm_rxwin.hip) share.  A table is one device allocation of state (slots, window records), a status word that its kernels lower to the first entry they refuse,
-// and a staging buffer through which host data reaches the state.  Each table struct holds a DevTable beside its own fields.
+// ---------------------------------------------------------------- device tables: what the host sides of the five tables share -- a key table (aesgcm_keytab.hip),
+// receive windows (aesgcm_rxwin.hip), send counters (aesgcm_txnum.hip), traffic secrets (aesgcm_kdf.hip) and SRTP master keys (aesgcm_srtp_kdf.hip).  A table is one
+// device allocation of state (slots, records), a status word that its kernels lower to the first entry they refuse, and a staging buffer through which host data
+// reaches the state.  Each table struct holds a DevTable beside its own fields; its unit keeps its argument checks and the packing of its records, the base owns
+// every runtime call of set, get and clear.
 struct DevTable {
     int device = 0;
     u32 *status = nullptr;             // device: the lowest refused packet (or set entry) since the last devtab_status, ~0 = none
@@ -263,8 +265,33 @@ struct DevTable {
 // AESGCM_EHIP with `who` in the message (without a device: from device_state)
 int devtab_create(DevTable *b, int device, size_t state_bytes, void **state, const char *who);
 // `bytes` of the staging buffer for a host-to-device copy on `st`, behind the buffer's previous user on whatever stream that ran; the caller holds b->mu and
-// records b->stage_done behind its own last use
+// records b->stage_done behind its own last use (devtab_staged is that caller)
 int devtab_stage(DevTable *b, size_t bytes, hipStream_t st);
+// One staged set, which every host-to-table setter is: under the table's mutex, on its device, `bytes` of the stage (devtab_stage); `body()` -- host data into the
+// stage and from there into the state, on `st`, returning an AESGCM code --; `secret`: the stage zeroed behind it whatever body returned (key material does not
+// outlive the call there); the stage's event recorded -- on every path once the stage is there, so that its next user, on whatever stream, is ordered behind a
+// failed call's copies and zeroing as behind a good one's.  The first error is the one returned.  The caller has checked its arguments.
+template <class Body>
+static int devtab_staged(DevTable &b, size_t bytes, hipStream_t st, bool secret, Body body) {
+    std::lock_guard<std::mutex> lk(b.mu);
+    HIPCHK(hipSetDevice(b.device));
+    int rc = devtab_stage(&b, bytes, st);
+    if (rc) return rc;
+    rc = body();
+    const hipError_t ez = secret ? hipMemsetAsync(b.stage, 0, bytes, st) : hipSuccess;
+    const hipError_t er = hipEventRecord(b.stage_done, st);
+    if (rc) return rc;
+    HIPCHK(ez);
+    HIPCHK(er);
+    return AESGCM_OK;
+}
+// the set of a table of records: `bytes` at `host` through the stage to `dst` (pageable memory: copied out of `host` when the call returns)
+int devtab_put(DevTable *b, void *dst, const void *host, size_t bytes, hipStream_t st, bool secret);
+int devtab_get(DevTable *b, void *host, const void *src, size_t bytes, hipStream_t st);      // state to host on `st`, waited for
+int devtab_clear(DevTable *b, void *at, size_t bytes, hipStream_t st);                        // that much of the state zeroed on `st`
+// a host copy of secrets on its way into a table: zeroed when it goes out of scope, on every return path (volatile stores: not optimised away)
+void host_wipe(void *p, size_t n);
+struct SecretWords : std::vector<u32> { using std::vector<u32>::vector; ~SecretWords() { host_wipe(data(), size() * sizeof(u32)); } };
 int devtab_status(DevTable *b, int *code, uint64_t *detail);          // read and clear; the caller has checked its pointers
 // waits for the device, then frees the state, the status word, the stage and the event.  wipe_bytes != 0: that much of the state and the whole stage are zeroed
 // first, and waited for (a key table: both held key material)

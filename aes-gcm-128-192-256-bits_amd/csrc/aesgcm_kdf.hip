@@ -1,7 +1,7 @@
 // aesgcm_kdf.hip -- on-device key derivation (include/aesgcm.h "ON-DEVICE KEY DERIVATION"): the host side of aesgcm_kdf_*.  The kernels are in aesgcm_kdf_kernels.hip,
 // the lane code and the layout of the state in aesgcm_kdf.h.  A table is a DevTable (aesgcm_internal.h; defined in aesgcm_host.hip) whose state is n_secrets records of
-// 64 bytes.  Host secrets reach the records through the staging buffer, zeroed behind its use as aesgcm_keytab_set zeroes its keys; the host's own copy is wiped before
-// the call returns; destroy wipes the records and the stage.  install and update are ONE launch each on the caller's stream: they neither synchronise nor allocate nor
+// 64 bytes.  Host secrets reach the records through the staging buffer (devtab_put), zeroed behind its use as aesgcm_keytab_set zeroes its keys; the host's own copy
+// is wiped before the call returns (SecretWords); clear is devtab_clear; destroy wipes the records and the stage.  install and update are ONE launch each on the caller's stream: they neither synchronise nor allocate nor
 // record an event nor read anything back -- capture-safe (include/aesgcm.h, CAPTURE).  The key table is reached through kt_view (aesgcm_keytab.h) and nothing else.
 #include "aesgcm_internal.h"
 #include "aesgcm_keytab.h"
@@ -13,8 +13,6 @@ struct aesgcm_kdf {
     DevTable base;                     // base.stage: host secrets wait there for their copy into the records, zeroed behind it; base.stage_done: behind that zeroing
     KdfTable t = {};                   // t.status == base.status: the kernels' copy of the pointer
 };
-
-static void wipe(void *p, size_t n) { volatile unsigned char *v = (volatile unsigned char *)p; while (n--) *v++ = 0; }
 
 int aesgcm_kdf_create(aesgcm_kdf **out, int device, size_t hash_len, size_t n_secrets) {
     if (!out) return AESGCM_EARG;
@@ -35,23 +33,10 @@ int aesgcm_kdf_set(aesgcm_kdf *k, size_t first, size_t n, const uint8_t *secrets
     if (!k) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!secrets || !devtab_in_range(first, n, k->t.n_secrets)) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t hl = k->t.hash_len, bytes = n * KDF_REC_WORDS * sizeof(u32);
-    std::vector<u32> rec(n * KDF_REC_WORDS, 0);
+    const size_t hl = k->t.hash_len;
+    SecretWords rec(n * KDF_REC_WORDS, 0);                                                  // (wiped on every return path)
     for (size_t i = 0; i < n; i++) { memcpy(&rec[i * KDF_REC_WORDS], secrets + i * hl, hl); rec[i * KDF_REC_WORDS + KDF_REC_WORDS - 1u] = KDF_SET; }
-    struct Wipe { std::vector<u32> &v; ~Wipe() { wipe(v.data(), v.size() * sizeof(u32)); } } wiper{rec};
-    DevTable &b = k->base;
-    std::lock_guard<std::mutex> lk(b.mu);
-    HIPCHK(hipSetDevice(b.device));
-    int rc = devtab_stage(&b, bytes, st);                                                   // (behind the previous set's copy and zeroing)
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(b.stage, rec.data(), bytes, hipMemcpyHostToDevice, st);   // (pageable memory: copied out of `rec` when the call returns)
-    if (e == hipSuccess) e = hipMemcpyAsync(k->t.rec + first * KDF_REC_WORDS, b.stage, bytes, hipMemcpyDeviceToDevice, st);
-    const hipError_t ez = hipMemsetAsync(b.stage, 0, bytes, st);                            // whatever the copies returned: no secret outlives the call in the stage
-    HIPCHK(e);
-    HIPCHK(ez);
-    HIPCHK(hipEventRecord(b.stage_done, st));
-    return AESGCM_OK;
+    return devtab_put(&k->base, k->t.rec + first * KDF_REC_WORDS, rec.data(), rec.size() * sizeof(u32), (hipStream_t)stream, true);
 }
 
 int aesgcm_kdf_set_dev(aesgcm_kdf *k, size_t n, const uint32_t *d_idx, const void *d_secrets, void *stream) {
@@ -69,9 +54,7 @@ int aesgcm_kdf_clear(aesgcm_kdf *k, size_t first, size_t n, void *stream) {
     if (!k) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!devtab_in_range(first, n, k->t.n_secrets)) return AESGCM_EARG;
-    HIPCHK(hipSetDevice(k->base.device));
-    HIPCHK(hipMemsetAsync(k->t.rec + first * KDF_REC_WORDS, 0, n * KDF_REC_WORDS * sizeof(u32), (hipStream_t)stream));
-    return AESGCM_OK;
+    return devtab_clear(&k->base, k->t.rec + first * KDF_REC_WORDS, n * KDF_REC_WORDS * sizeof(u32), (hipStream_t)stream);
 }
 
 // label 0 (the key) is what every format has; a label is at most KDF_LABEL_MAX bytes -- the bound under which an HMAC is four compressions (aesgcm_kdf.h)

@@ -1,7 +1,7 @@
 // aesgcm_keytab.hip -- key tables (include/aesgcm.h "key tables"): the host side of aesgcm_keytab_*.  The kernels are in aesgcm_<family>_kernels.hip, one source per family.
-// A table is a DevTable (aesgcm_internal.h: create, the staging buffer, status, destroy, the range check; defined in aesgcm_host.hip) whose state is n_slots KtSlot
-// records (aesgcm_keytab.h).  Host data reaches the slots through the staging buffer, zeroed behind every use (kt_stage_set): keys by k_kt_setup, the other fields
-// (salt, XPN state, TLS IV) by strided copies.  A crypt call is one launch of a kernel that runs k_batch3's body,
+// A table is a DevTable (aesgcm_internal.h: create, the staged set, clear, status, destroy, the range check; defined in aesgcm_host.hip) whose state is n_slots KtSlot
+// records (aesgcm_keytab.h).  Host data reaches the slots through the staging buffer, zeroed behind every use (kt_stage_set, on devtab_staged): keys by k_kt_setup,
+// the other fields (salt, XPN state, TLS IV) by strided copies.  A crypt call is one launch of a kernel that runs k_batch3's body,
 // planned by batch_plan (aesgcm_host.hip) as the batch path's: the shape by batch_pick_lg, the same dispenser ring, order and deal.
 //   family   entry point                          kernel       the format's cut (aesgcm_wirecut.h)
 //   keytab   aesgcm_keytab_crypt_dev              k_kt_batch   -                       packets as five arrays
@@ -49,9 +49,9 @@ int aesgcm_keytab_create(aesgcm_keytab **out, int device, size_t key_len, size_t
     return AESGCM_OK;
 }
 
-// What every host-to-slot setter does, under the base's mutex: `parts` side by side through the table's staging buffer (devtab_stage) on `st` -- the host copies into the
-// stage, `into_slots` (the expansion kernel, or a strided copy per part) from there into the slots, the stage zeroed behind it whatever into_slots returned (raw key
-// material does not outlive the call), the stage's event recorded.  The caller has checked its arguments.
+// What every host-to-slot setter does: one staged set (devtab_staged: the stage holds key material, so it is zeroed behind the call) whose body copies `parts` side
+// by side into the stage and has `into_slots` (the expansion kernel, or a strided copy per part) take them from there into the slots.  The caller has checked its
+// arguments.
 struct KtPart {
     const uint8_t *src;                // host: n * width bytes; NULL = the field becomes zero (nothing staged)
     size_t width, field;               // bytes per slot; offset inside KtSlot
@@ -59,20 +59,13 @@ struct KtPart {
 template <size_t N, class F>
 static int kt_stage_set(aesgcm_keytab *t, size_t n, const KtPart (&parts)[N], hipStream_t st, F into_slots) {
     DevTable &b = t->base;
-    std::lock_guard<std::mutex> lk(b.mu);
-    HIPCHK(hipSetDevice(b.device));
     size_t bytes = 0;
     for (const KtPart &p : parts) if (p.src) bytes += n * p.width;
-    int rc = devtab_stage(&b, bytes, st);                                       // (behind the previous set's kernel and zeroing)
-    if (rc) return rc;
-    size_t at = 0;
-    for (const KtPart &p : parts) if (p.src) { HIPCHK(hipMemcpyAsync(b.stage + at, p.src, n * p.width, hipMemcpyHostToDevice, st)); at += n * p.width; }
-    rc = into_slots();
-    const hipError_t ez = hipMemsetAsync(b.stage, 0, bytes, st);
-    if (rc) return rc;
-    HIPCHK(ez);
-    HIPCHK(hipEventRecord(b.stage_done, st));
-    return AESGCM_OK;
+    return devtab_staged(b, bytes, st, true, [&]() -> int {
+        size_t at = 0;
+        for (const KtPart &p : parts) if (p.src) { HIPCHK(hipMemcpyAsync(b.stage + at, p.src, n * p.width, hipMemcpyHostToDevice, st)); at += n * p.width; }
+        return into_slots();
+    });
 }
 
 // the fields that k_kt_setup leaves alone (salt, xpn): each part from the stage into its field of slots first_slot, ... by one 2-D copy (the slots are 384 bytes apart)
@@ -110,9 +103,7 @@ int aesgcm_keytab_clear(aesgcm_keytab *t, size_t first_slot, size_t n, void *str
     if (!t) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!devtab_in_range(first_slot, n, t->n_slots)) return AESGCM_EARG;
-    HIPCHK(hipSetDevice(t->base.device));
-    HIPCHK(hipMemsetAsync(t->tab + first_slot, 0, n * sizeof(KtSlot), (hipStream_t)stream));
-    return AESGCM_OK;
+    return devtab_clear(&t->base, t->tab + first_slot, n * sizeof(KtSlot), (hipStream_t)stream);
 }
 
 // Batches with a slot per packet: the argument checks and KtParams here, the dispenser, shape, order and deal by batch_plan, as batch_launch does for k_batch3

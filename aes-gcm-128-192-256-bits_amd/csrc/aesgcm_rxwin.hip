@@ -1,7 +1,7 @@
 // aesgcm_rxwin.hip -- receive windows (include/aesgcm.h "RECEIVE WINDOWS"): the host side of aesgcm_rxwin_*.  The kernels are in aesgcm_rxwin_kernels.hip, the lane code and
-// the layout of the state in aesgcm_rxwin.h.  A table is a DevTable (aesgcm_internal.h: create, the staging buffer, status, destroy, the range check; defined in
-// aesgcm_host.hip) whose state is n_wins window records.  Host state reaches the records through the staging buffer, which is not zeroed behind a set and not wiped
-// by destroy (it holds numbers, no keys); aesgcm_rxwin_get copies records back and waits.  The normalised form of set / get and the records' ring are converted
+// the layout of the state in aesgcm_rxwin.h.  A table is a DevTable (aesgcm_internal.h: create, put, get, status, destroy, the range check; defined in
+// aesgcm_host.hip) whose state is n_wins window records.  Host state reaches the records through the staging buffer (devtab_put), which is not zeroed behind a set and
+// not wiped by destroy (it holds numbers, no keys); aesgcm_rxwin_get copies records back and waits (devtab_get).  The normalised form of set / get and the records' ring are converted
 // into one another here, on the host (rx_norm_to_ring, rx_ring_to_norm).  recover is one launch, commit three; neither synchronises or allocates: capture-safe (include/aesgcm.h, CAPTURE).
 #include "aesgcm_internal.h"
 #include "aesgcm_rxwin.h"
@@ -32,23 +32,13 @@ int aesgcm_rxwin_set(aesgcm_rxwin *w, size_t first, size_t n, const uint64_t *ne
     if (!next || !devtab_in_range(first, n, w->t.n_wins)) return AESGCM_EARG;
     const u32 W = w->t.window, stride = w->t.stride, sw = W / 64u;
     for (size_t k = 0; k < n; k++) if (!rx_norm_valid(next[k], seen ? seen + k * sw : nullptr, W)) return AESGCM_EARG;      // a bit for a number below 0
-    hipStream_t st = (hipStream_t)stream;
     std::vector<u64> rec(n * stride, 0);
     for (size_t k = 0; k < n; k++) {
         u64 *r = rec.data() + k * stride;
         r[0] = r[1] = next[k];
         rx_norm_to_ring(next[k], seen ? seen + k * sw : nullptr, W, r + RX_HDR_WORDS);
     }
-    const size_t bytes = rec.size() * sizeof(u64);
-    DevTable &b = w->base;
-    std::lock_guard<std::mutex> lk(b.mu);
-    HIPCHK(hipSetDevice(b.device));
-    const int rc = devtab_stage(&b, bytes, st);                                          // (behind the previous set's copy out of the stage)
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(b.stage, rec.data(), bytes, hipMemcpyHostToDevice, st));       // (pageable memory: copied out of `rec` when the call returns)
-    HIPCHK(hipMemcpyAsync(w->t.state + first * stride, b.stage, bytes, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipEventRecord(b.stage_done, st));
-    return AESGCM_OK;
+    return devtab_put(&w->base, w->t.state + first * stride, rec.data(), rec.size() * sizeof(u64), (hipStream_t)stream, false);
 }
 
 int aesgcm_rxwin_get(aesgcm_rxwin *w, size_t first, size_t n, uint64_t *next, uint64_t *seen, void *stream) {
@@ -56,11 +46,9 @@ int aesgcm_rxwin_get(aesgcm_rxwin *w, size_t first, size_t n, uint64_t *next, ui
     if (!n) return AESGCM_OK;
     if (!next || !devtab_in_range(first, n, w->t.n_wins)) return AESGCM_EARG;
     const u32 W = w->t.window, stride = w->t.stride, sw = W / 64u;
-    hipStream_t st = (hipStream_t)stream;
     std::vector<u64> rec(n * stride);
-    HIPCHK(hipSetDevice(w->base.device));
-    HIPCHK(hipMemcpyAsync(rec.data(), w->t.state + first * stride, rec.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const int rc = devtab_get(&w->base, rec.data(), w->t.state + first * stride, rec.size() * sizeof(u64), (hipStream_t)stream);
+    if (rc) return rc;
     for (size_t k = 0; k < n; k++) {
         const u64 *r = rec.data() + k * stride;
         next[k] = r[0];

@@ -1,7 +1,7 @@
 // aesgcm_srtp_kdf.hip -- SRTP / SRTCP session keys derived on the device (include/aesgcm.h "SRTP KEY DERIVATION"): the host side of aesgcm_srtp_kdf_*.  The kernels are in
 // aesgcm_srtp_kdf_kernels.hip, the lane code and the layout of the state in aesgcm_srtp_kdf.h.  A table is a DevTable (aesgcm_internal.h; defined in aesgcm_host.hip)
-// whose state is n_masters records of 64 bytes.  Host masters reach the records through the staging buffer, zeroed behind its use as aesgcm_kdf_set zeroes its secrets;
-// the host's own copy is wiped before the call returns; destroy wipes the records and the stage.  install is ONE launch on the caller's stream: it neither synchronises
+// whose state is n_masters records of 64 bytes.  Host masters reach the records through the staging buffer (devtab_put), zeroed behind its use as aesgcm_kdf_set zeroes
+// its secrets; the host's own copy is wiped before the call returns (SecretWords); clear is devtab_clear; destroy wipes the records and the stage.  install is ONE launch on the caller's stream: it neither synchronises
 // nor allocates nor records an event nor reads anything back -- capture-safe (include/aesgcm.h, CAPTURE).  The key table is reached through kt_view (aesgcm_keytab.h) and
 // nothing else.
 #include "aesgcm_internal.h"
@@ -14,8 +14,6 @@ struct aesgcm_srtp_kdf {
     DevTable base;                     // base.stage: host masters wait there for their copy into the records, zeroed behind it; base.stage_done: behind that zeroing
     SkdfTable t = {};                  // t.status == base.status: the kernels' copy of the pointer
 };
-
-static void wipe(void *p, size_t n) { volatile unsigned char *v = (volatile unsigned char *)p; while (n--) *v++ = 0; }
 
 int aesgcm_srtp_kdf_create(aesgcm_srtp_kdf **out, int device, size_t key_len, size_t n_masters) {
     if (!out) return AESGCM_EARG;
@@ -36,25 +34,11 @@ int aesgcm_srtp_kdf_set(aesgcm_srtp_kdf *k, size_t first, size_t n, const uint8_
     if (!k) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!keys || !salts || !devtab_in_range(first, n, k->t.n_masters)) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = n * KDF_REC_WORDS * sizeof(u32);
-    std::vector<u32> rec(n * KDF_REC_WORDS, 0);
+    SecretWords rec(n * KDF_REC_WORDS, 0);                                                  // (wiped on every return path)
     SkdfTable host = k->t;                                                                  // the same record layout, by the same function, over the host's copy
     host.rec = rec.data();
     for (size_t i = 0; i < n; i++) skdf_store(host, (u32)i, keys + i * k->t.key_len, salts + i * SKDF_SALT_LEN);
-    struct Wipe { std::vector<u32> &v; ~Wipe() { wipe(v.data(), v.size() * sizeof(u32)); } } wiper{rec};
-    DevTable &b = k->base;
-    std::lock_guard<std::mutex> lk(b.mu);
-    HIPCHK(hipSetDevice(b.device));
-    int rc = devtab_stage(&b, bytes, st);                                                   // (behind the previous set's copy and zeroing)
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(b.stage, rec.data(), bytes, hipMemcpyHostToDevice, st);   // (pageable memory: copied out of `rec` when the call returns)
-    if (e == hipSuccess) e = hipMemcpyAsync(k->t.rec + first * KDF_REC_WORDS, b.stage, bytes, hipMemcpyDeviceToDevice, st);
-    const hipError_t ez = hipMemsetAsync(b.stage, 0, bytes, st);                            // whatever the copies returned: no master outlives the call in the stage
-    HIPCHK(e);
-    HIPCHK(ez);
-    HIPCHK(hipEventRecord(b.stage_done, st));
-    return AESGCM_OK;
+    return devtab_put(&k->base, k->t.rec + first * KDF_REC_WORDS, rec.data(), rec.size() * sizeof(u32), (hipStream_t)stream, true);
 }
 
 int aesgcm_srtp_kdf_set_dev(aesgcm_srtp_kdf *k, size_t n, const uint32_t *d_idx, const void *d_keys, const void *d_salts, void *stream) {
@@ -72,9 +56,7 @@ int aesgcm_srtp_kdf_clear(aesgcm_srtp_kdf *k, size_t first, size_t n, void *stre
     if (!k) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!devtab_in_range(first, n, k->t.n_masters)) return AESGCM_EARG;
-    HIPCHK(hipSetDevice(k->base.device));
-    HIPCHK(hipMemsetAsync(k->t.rec + first * KDF_REC_WORDS, 0, n * KDF_REC_WORDS * sizeof(u32), (hipStream_t)stream));
-    return AESGCM_OK;
+    return devtab_clear(&k->base, k->t.rec + first * KDF_REC_WORDS, n * KDF_REC_WORDS * sizeof(u32), (hipStream_t)stream);
 }
 
 int aesgcm_srtp_kdf_install_dev(aesgcm_srtp_kdf *k, uint32_t kind, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const uint32_t *d_slots, const uint64_t *d_r,

@@ -1,8 +1,8 @@
 // aesgcm_txnum.hip -- send counters (include/aesgcm.h "SEND COUNTERS"): the host side of aesgcm_txnum_*.  The kernels are in aesgcm_txnum_kernels.hip, the lane code and
-// the layout of the state in aesgcm_txnum.h.  A table is a DevTable (aesgcm_internal.h: create, the staging buffer, status, destroy, the range check; defined in
+// the layout of the state in aesgcm_txnum.h.  A table is a DevTable (aesgcm_internal.h: create, put, get, status, destroy, the range check; defined in
 // aesgcm_host.hip) whose state is ONE allocation: n_ctrs counter records, then the scratch of an assign call -- the sort's TX_ENTRIES counts and its one or two
-// arrays of max_pkts packet indices -- so that a call allocates nothing.  Host state reaches the records through the staging buffer, which is not wiped by destroy (it
-// holds numbers, no keys); aesgcm_txnum_get copies records back and waits.  assign is 3 * passes + 2 launches on the caller's stream; it neither synchronises nor
+// arrays of max_pkts packet indices -- so that a call allocates nothing.  Host state reaches the records through the staging buffer (devtab_put), which is not zeroed behind
+// a set and not wiped by destroy (it holds numbers, no keys); aesgcm_txnum_get copies records back and waits (devtab_get).  assign is 3 * passes + 2 launches on the caller's stream; it neither synchronises nor
 // allocates nor reads anything back: capture-safe (include/aesgcm.h, CAPTURE).
 #include "aesgcm_internal.h"
 #include "aesgcm_txnum.h"
@@ -39,30 +39,18 @@ int aesgcm_txnum_set(aesgcm_txnum *c, size_t first, size_t n, const uint64_t *ne
     if (!n) return AESGCM_OK;
     if (!next || !limit || !devtab_in_range(first, n, c->t.n_ctrs)) return AESGCM_EARG;
     for (size_t k = 0; k < n; k++) if (next[k] > limit[k]) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
     std::vector<u64> rec(n * TX_REC_WORDS, 0);
     for (size_t k = 0; k < n; k++) { rec[k * TX_REC_WORDS] = next[k]; rec[k * TX_REC_WORDS + 1] = limit[k]; }
-    const size_t bytes = rec.size() * sizeof(u64);
-    DevTable &b = c->base;
-    std::lock_guard<std::mutex> lk(b.mu);
-    HIPCHK(hipSetDevice(b.device));
-    const int rc = devtab_stage(&b, bytes, st);                                          // (behind the previous set's copy out of the stage)
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(b.stage, rec.data(), bytes, hipMemcpyHostToDevice, st));       // (pageable memory: copied out of `rec` when the call returns)
-    HIPCHK(hipMemcpyAsync(c->t.rec + first * TX_REC_WORDS, b.stage, bytes, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipEventRecord(b.stage_done, st));
-    return AESGCM_OK;
+    return devtab_put(&c->base, c->t.rec + first * TX_REC_WORDS, rec.data(), rec.size() * sizeof(u64), (hipStream_t)stream, false);
 }
 
 int aesgcm_txnum_get(aesgcm_txnum *c, size_t first, size_t n, uint64_t *next, uint64_t *limit, void *stream) {
     if (!c) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!next || !devtab_in_range(first, n, c->t.n_ctrs)) return AESGCM_EARG;
-    hipStream_t st = (hipStream_t)stream;
     std::vector<u64> rec(n * TX_REC_WORDS);
-    HIPCHK(hipSetDevice(c->base.device));
-    HIPCHK(hipMemcpyAsync(rec.data(), c->t.rec + first * TX_REC_WORDS, rec.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const int rc = devtab_get(&c->base, rec.data(), c->t.rec + first * TX_REC_WORDS, rec.size() * sizeof(u64), (hipStream_t)stream);
+    if (rc) return rc;
     for (size_t k = 0; k < n; k++) {
         next[k] = rec[k * TX_REC_WORDS];
         if (limit) limit[k] = rec[k * TX_REC_WORDS + 1];

@@ -1,5 +1,5 @@
-"""Drives the calls that include/aesgcm.h names capture-safe (CAPTURE: key tables and receive windows; the five-array batch calls plan their launch the same way)
-through the fake HIP runtime (fakehip.cpp) twice each: an ordinary warm-up call, then the same call while the caller's stream captures.  Asserted per call:
+"""Drives the calls that include/aesgcm.h names capture-safe (CAPTURE: key tables, receive windows, send counters' assign, the key derivations' install and update;
+the five-array batch calls plan their launch as a key table's) through the fake HIP runtime (fakehip.cpp) twice each: an ordinary warm-up call, then the same call while the caller's stream captures.  Asserted per call:
   * nothing a capture cannot carry was done while the stream captured -- no hipMalloc or hipFree, no synchronous copy or memset, no host synchronisation, and no
     stream outside the capture waits on an event the capture recorded (fake_capture_violations: each entry names the HIP call);
   * the captured call launches what the warm-up call launched, line by line of the launch log -- except that a captured call is never ordered by length class: where
@@ -78,7 +78,7 @@ def in_array_order(log):
     return out
 
 
-def calls(kt, rw, n, key_len):
+def calls(kt, rw, tx, sec, mk, n, key_len):
     """every device call of the families, by name; all on the caller's stream"""
     W, X, T, D, S, R = lib.WireFormat, lib.WireFormatX, lib.TlsFormat, lib.DtlsFormat, lib.SrtpFormat, lib.RxFormat
     c = {}
@@ -102,6 +102,10 @@ def calls(kt, rw, n, key_len):
     c["rxwin recover", 1] = lambda: rw.recover_dev(R.esp_esn(), n, d_slots, d_in, d_off, d_num, d_hi, stream=caller)
     c["rxwin recover expect", 1] = lambda: rw.recover_dev(R.expect(), n, d_slots, None, None, d_num, None, stream=caller)
     c["rxwin commit", 1] = lambda: rw.commit_dev(n, d_slots, d_num, d_auth, d_auth, d_why, stream=caller)
+    c["txnum assign", 0] = lambda: tx.assign_dev(lib.TxFormat.esp_esn(), n, d_slots, d_in, d_off, d_num, d_hi, stream=caller)
+    c["kdf install", 0] = lambda: sec.install_dev(lib.KdfFormat.quic_v1(), kt, n, d_slots, d_hp, d_pn_off, stream=caller)
+    c["kdf update", 0] = lambda: sec.update_dev(lib.KdfFormat.tls13(), n, d_slots, d_hp, stream=caller)
+    c["srtp_kdf install", 0] = lambda: mk.install_dev(lib.SRTP_RTP, kt, n, d_slots, d_hp, d_num, stream=caller)
 
     def loop():                                                         # the receive loop of INTEGRATION.md: four stream-ordered steps
         rw.recover_dev(R.esp_esn(), n, d_slots, d_in, d_off, d_num, d_hi, stream=caller)
@@ -113,11 +117,11 @@ def calls(kt, rw, n, key_len):
 
 
 def drive(n, key_len, want_ordered, label):
-    with lib.KeyTable(key_len, 16) as kt, lib.RxWindows(4, 64) as rw:
+    with lib.KeyTable(key_len, 16) as kt, lib.RxWindows(4, 64) as rw, lib.TxCounters(4, n) as tx, lib.SecretTable(32, 4) as sec, lib.MasterKeyTable(key_len, 4) as mk:
         kt.set(0, bytes(key_len * 16))
         F.fake_capture_clear()
         ordered_seen = 0
-        for (name, dec), call in calls(kt, rw, n, key_len).items():
+        for (name, dec), call in calls(kt, rw, tx, sec, mk, n, key_len).items():
             what = "%s, %s %s n=%d AES-%d" % (label, name, "dec" if dec else "enc", n, 8 * key_len)
             warm, _ = logged(call)
             assert warm and not violations(), (what, "the warm-up call", warm, violations())

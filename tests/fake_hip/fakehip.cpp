@@ -11,7 +11,8 @@
 //   * host synchronisations are counted (the queued multi-GPU path must have none per message), device-wide ones apart;
 //   * STREAM ORDER: every stream keeps a vector clock (its own count of enqueued operations, and what it has waited for through events), so a test can ask whether
 //     one stream is ordered behind another (fake_ordered_behind), or have every operation on another stream checked against a watched one (fake_watch);
-//   * fault injection: fake_fail_launch(k) makes the k-th kernel launch after a reset fail, to drive the library's error paths.
+//   * fault injection: fake_fail_launch(k) makes the k-th kernel launch after a reset fail, fake_fail_copy(k) the k-th hipMemcpyAsync, to drive the library's
+//     error paths.
 //   * THE LAUNCH LOG: every launcher the packet, message and batch calls reach notes one line -- the kernel, the stream, its scalar arguments and the scalar fields
 //     of its parameter struct; every pointer as 0 or 1 (p=..., in the order of the note's own argument list), never as an address; the stream as the name the
 //     driver gave it (fake_name_stream; a name ends with its stream), "null", or "side" for a live stream nobody named.  A driver that names every stream it can
@@ -25,8 +26,10 @@
 //     any stream captures, what a capture cannot carry is noted with the HIP call's name in a list of its own (fake_capture_violations, fake_capture_clear; fake_reset
 //     leaves it alone): hipMalloc, hipFree, a synchronous copy or memset, hipStreamSynchronize, hipDeviceSynchronize, hipEventSynchronize, hipEventQuery.  An event
 //     remembers whether its last record was inside a capture; a hipStreamWaitEvent on such an event from a stream that is not capturing is noted too, also after the
-//     capture has ended.  The key tables' and receive windows' host sides (csrc/aesgcm_keytab.hip, aesgcm_rxwin.hip) are linked in for this, with launchers that note a
+//     capture has ended.  The five device tables' host sides (csrc/aesgcm_keytab.hip, _rxwin, _txnum, _kdf, _srtp_kdf) are linked in for this, with launchers that note a
 //     log line as the others do (tests/fake_hip/capture_drive.py).
+//   * THE CALL LIST: after fake_log_runtime(1), every runtime call and launch by name with its byte count (fake_calls): what one call into the library costs
+//     (tests/fake_hip/table_drive.py, tests/golden/table_calls.txt).
 // To keep the host logic running, a launch that would publish a tag and its generation number to the pinned host slot publishes the number (no tag).
 #include <hip/hip_runtime.h>
 
@@ -44,6 +47,8 @@
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_internal.h"
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_keytab.h"
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_rxwin.h"
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_txnum.h"
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_srtp_kdf.h"
 #include <rccl/rccl.h>
 
 #define FAKE_DEVICES 4
@@ -58,10 +63,10 @@ struct FakeStream { int dev; bool capturing = false; long captured = 0; };      
 struct FakeEvent { int dev; std::map<const void *, long> clock; bool in_capture = false; };      // clock: the stream clock it captured when it was last recorded; in_capture: ... inside a capture
 std::set<void *> live_streams, live_events;
 FakeStream null_stream[FAKE_DEVICES] = {{0}, {1}, {2}, {3}};
-std::vector<std::string> violations, log_lines, cap_violations;
+std::vector<std::string> violations, log_lines, cap_violations, call_lines;
 int n_capturing = 0;                                          // streams between hipStreamBeginCapture and hipStreamEndCapture
 unsigned touched = 0, attrs = 0;                              // bit masks of devices
-long n_sync = 0, n_dev_sync = 0, n_launch = 0, n_collective = 0, fail_at = 0;
+long n_sync = 0, n_dev_sync = 0, n_launch = 0, n_collective = 0, fail_at = 0, n_copy = 0, fail_copy_at = 0;
 std::map<const void *, std::map<const void *, long>> clocks;  // per stream: its own count of enqueued operations and the counts of the others it is ordered behind
 const void *watched = nullptr;
 
@@ -128,6 +133,13 @@ void chk_stream(const char *what, hipStream_t s) {
 // for NULL.  Never an address.  Takes the library's registry mutex: call it BEFORE the fake's own (LAUNCH), the order the library itself keeps.
 std::atomic<bool> log_runtime{false};                         // fake_log_runtime: the single-message launchers, hipMemsetAsync and hipEventRecord note their lines.  Off, nothing here
                                                               // looks at another thread's context (pname reads every registered context's fields: for single-threaded drivers only)
+// THE CALL LIST (after fake_log_runtime(1)): every runtime call and launch by name, with its byte count where it has one, never an address -- what one call into the
+// library costs in allocations, copies, waits and synchronisations (fake_calls; tests/fake_hip/table_drive.py, tests/golden/table_calls.txt).  Under the fake's mutex.
+void rt(const char *fmt, ...) {
+    if (!log_runtime) return;
+    char b[96]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof b, fmt, ap); va_end(ap);
+    call_lines.push_back(b);
+}
 std::string pname(const void *p) {
     if (!log_runtime) return "";
     if (!p) return "0";
@@ -161,13 +173,14 @@ void publish(void *slot, unsigned long long gen) { if (slot) __atomic_store_n(re
 }  // namespace
 
 // ---------------------------------------------------------------- what the test reads
-EXPORT void fake_reset(void) { std::lock_guard<std::mutex> lk(mu); violations.clear(); log_lines.clear(); last_params.clear(); touched = 0; n_sync = n_dev_sync = n_launch = n_collective = fail_at = 0; clocks.clear(); watched = nullptr; }   // (attrs stays: set once per device and process)
+EXPORT void fake_reset(void) { std::lock_guard<std::mutex> lk(mu); violations.clear(); log_lines.clear(); call_lines.clear(); last_params.clear(); touched = 0; n_sync = n_dev_sync = n_launch = n_collective = fail_at = n_copy = fail_copy_at = 0; clocks.clear(); watched = nullptr; }   // (attrs stays: set once per device and process)
 EXPORT unsigned fake_touched(void) { return touched; }
 EXPORT unsigned fake_attrs(void) { return attrs; }
 EXPORT long fake_syncs(void) { return n_sync; }
 EXPORT long fake_launches(void) { return n_launch; }
 EXPORT long fake_device_syncs(void) { return n_dev_sync; }                    // hipDeviceSynchronize calls (also counted in fake_syncs)
 EXPORT void fake_fail_launch(long k) { std::lock_guard<std::mutex> lk(mu); fail_at = k; }      // the k-th launch from now on (counted since the last reset) fails; 0 = none
+EXPORT void fake_fail_copy(long k) { std::lock_guard<std::mutex> lk(mu); fail_copy_at = k; }      // the k-th hipMemcpyAsync from now on (counted since the last reset) fails before it is enqueued; 0 = none
 // 1: stream a is ordered behind every operation enqueued on stream b since the last reset (NULL: the current device's null stream)
 EXPORT int fake_ordered_behind(hipStream_t a, hipStream_t b) { std::lock_guard<std::mutex> lk(mu); return clocks[stream_key(a)][stream_key(b)] >= clocks[stream_key(b)][stream_key(b)] ? 1 : 0; }
 // from now on every operation enqueued on another stream must be ordered behind what s holds at that moment (a violation otherwise); NULL: stop watching
@@ -205,6 +218,14 @@ EXPORT size_t fake_log(char *buf, size_t n) {
     if (buf && n) { strncpy(buf, s.c_str(), n - 1); buf[n - 1] = 0; }
     return s.size() + 1;
 }
+// the call list since the last reset, a line per runtime call or launch; returns the bytes it needs, as fake_log
+EXPORT size_t fake_calls(char *buf, size_t n) {
+    std::lock_guard<std::mutex> lk(mu);
+    std::string s;
+    for (auto &v : call_lines) s += v + "\n";
+    if (buf && n) { strncpy(buf, s.c_str(), n - 1); buf[n - 1] = 0; }
+    return s.size() + 1;
+}
 EXPORT void fake_log_runtime(int on) { log_runtime = on != 0; }
 EXPORT void fake_name_stream(hipStream_t s, const char *name) { std::lock_guard<std::mutex> lk(mu); if (s) stream_names[(const void *)s] = name; }
 // FAKEHIP_REPORT=1: one line on stderr when the process ends (for drivers that are not Python: bench.py as a child process)
@@ -215,7 +236,7 @@ extern "C" {
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "fake error"; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 hipError_t hipGetDeviceCount(int *n) { *n = FAKE_DEVICES; return hipSuccess; }
-hipError_t hipSetDevice(int d) { if (d < 0 || d >= FAKE_DEVICES) return hipErrorInvalidDevice; cur = d; return hipSuccess; }
+hipError_t hipSetDevice(int d) { if (d < 0 || d >= FAKE_DEVICES) return hipErrorInvalidDevice; cur = d; if (log_runtime) { std::lock_guard<std::mutex> lk(mu); rt("hipSetDevice"); } return hipSuccess; }
 hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int d) {
     if (d < 0 || d >= FAKE_DEVICES) return hipErrorInvalidDevice;
     memset(p, 0, sizeof *p);
@@ -224,10 +245,10 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int d) {
     p->multiProcessorCount = 256;
     return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipDeviceSynchronize"); ++n_sync; ++n_dev_sync; return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { std::lock_guard<std::mutex> lk(mu); touch(); rt("hipDeviceSynchronize"); cap_bad("hipDeviceSynchronize"); ++n_sync; ++n_dev_sync; return hipSuccess; }
 hipError_t hipMalloc(void **p, size_t n) {
     std::lock_guard<std::mutex> lk(mu);
-    touch(); cap_bad("hipMalloc");
+    touch(); rt("hipMalloc n=%zu", n); cap_bad("hipMalloc");
     void *q = calloc(1, n ? n : 1);
     if (!q) return hipErrorOutOfMemory;
     allocs[(uintptr_t)q] = {n ? n : 1, cur};
@@ -237,7 +258,7 @@ hipError_t hipMalloc(void **p, size_t n) {
 hipError_t hipFree(void *p) {
     std::lock_guard<std::mutex> lk(mu);
     if (!p) return hipSuccess;
-    cap_bad("hipFree");
+    rt("hipFree"); cap_bad("hipFree");
     auto it = allocs.find((uintptr_t)p);
     if (it == allocs.end()) { bad("hipFree of an unknown pointer"); return hipErrorInvalidValue; }
     if (it->second.dev != cur) bad("hipFree: memory of device %d freed while device %d is current", it->second.dev, cur);
@@ -257,8 +278,9 @@ hipError_t hipHostFree(void *p) { std::lock_guard<std::mutex> lk(mu); allocs.era
 hipError_t hipHostGetDevicePointer(void **d, void *h, unsigned) { *d = h; return hipSuccess; }
 static hipError_t copy(const char *what, void *dst, const void *src, size_t n, hipStream_t st, bool async) {
     std::lock_guard<std::mutex> lk(mu);
-    touch();
+    touch(); rt("%s n=%zu", what, n);
     chk_ptr(what, "dst", dst); chk_ptr(what, "src", src);
+    if (async && fail_copy_at && ++n_copy == fail_copy_at) return hipErrorInvalidValue;
     if (async) { chk_stream(what, st); enqueue(what, st); }
     else cap_bad(what);
     if (n) memmove(dst, src, n);
@@ -266,25 +288,25 @@ static hipError_t copy(const char *what, void *dst, const void *src, size_t n, h
 }
 hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) { return copy("hipMemcpy", dst, src, n, nullptr, false); }
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind, hipStream_t st) { return copy("hipMemcpyAsync", dst, src, n, st, true); }
-hipError_t hipMemset(void *dst, int v, size_t n) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipMemset"); chk_ptr("hipMemset", "dst", dst); memset(dst, v, n); return hipSuccess; }
+hipError_t hipMemset(void *dst, int v, size_t n) { std::lock_guard<std::mutex> lk(mu); touch(); rt("hipMemset n=%zu", n); cap_bad("hipMemset"); chk_ptr("hipMemset", "dst", dst); memset(dst, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t st) {
     const std::string dn = log_runtime ? pname(dst) : std::string();
     std::lock_guard<std::mutex> lk(mu);
     if (log_runtime) note("hipMemsetAsync %s dst=%s v=%d n=%zu", sname(st), dn.c_str(), v, n);
-    touch(); chk_ptr("hipMemsetAsync", "dst", dst); chk_stream("hipMemsetAsync", st); enqueue("hipMemsetAsync", st);
+    touch(); rt("hipMemsetAsync n=%zu", n); chk_ptr("hipMemsetAsync", "dst", dst); chk_stream("hipMemsetAsync", st); enqueue("hipMemsetAsync", st);
     memset(dst, v, n);
     return hipSuccess;
 }
 // (the strided forms: a key table's setters move their fields from the staging buffer into the slots with them)
 hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t st) {
     std::lock_guard<std::mutex> lk(mu);
-    touch(); chk_ptr("hipMemcpy2DAsync", "dst", dst); chk_ptr("hipMemcpy2DAsync", "src", src); chk_stream("hipMemcpy2DAsync", st); enqueue("hipMemcpy2DAsync", st);
+    touch(); rt("hipMemcpy2DAsync %zux%zu", width, height); chk_ptr("hipMemcpy2DAsync", "dst", dst); chk_ptr("hipMemcpy2DAsync", "src", src); chk_stream("hipMemcpy2DAsync", st); enqueue("hipMemcpy2DAsync", st);
     for (size_t r = 0; r < height; r++) memmove((char *)dst + r * dpitch, (const char *)src + r * spitch, width);
     return hipSuccess;
 }
 hipError_t hipMemset2DAsync(void *dst, size_t pitch, int v, size_t width, size_t height, hipStream_t st) {
     std::lock_guard<std::mutex> lk(mu);
-    touch(); chk_ptr("hipMemset2DAsync", "dst", dst); chk_stream("hipMemset2DAsync", st); enqueue("hipMemset2DAsync", st);
+    touch(); rt("hipMemset2DAsync %zux%zu", width, height); chk_ptr("hipMemset2DAsync", "dst", dst); chk_stream("hipMemset2DAsync", st); enqueue("hipMemset2DAsync", st);
     for (size_t r = 0; r < height; r++) memset((char *)dst + r * pitch, v, width);
     return hipSuccess;
 }
@@ -307,7 +329,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {
     delete reinterpret_cast<FakeStream *>(s);
     return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t s) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipStreamSynchronize"); chk_stream("hipStreamSynchronize", s); ++n_sync; return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) { std::lock_guard<std::mutex> lk(mu); touch(); rt("hipStreamSynchronize"); cap_bad("hipStreamSynchronize"); chk_stream("hipStreamSynchronize", s); ++n_sync; return hipSuccess; }
 // Capture: a created stream (never the null stream) notes what is enqueued on it; the graph that comes back is the count, as an opaque handle
 hipError_t hipStreamBeginCapture(hipStream_t s, hipStreamCaptureMode) {
     std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamBeginCapture", s);
@@ -331,7 +353,7 @@ hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus *st) {
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
     std::lock_guard<std::mutex> lk(mu);
-    touch();
+    touch(); rt("hipEventCreateWithFlags");
     FakeEvent *f = new FakeEvent{cur, {}, false};
     live_events.insert(f);
     *e = reinterpret_cast<hipEvent_t>(f);
@@ -345,7 +367,7 @@ static void chk_event(const char *what, hipEvent_t e) {
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     const char *en = log_runtime ? ename(e) : "";
-    std::lock_guard<std::mutex> lk(mu); touch();
+    std::lock_guard<std::mutex> lk(mu); touch(); rt("hipEventRecord");
     if (log_runtime) note("hipEventRecord %s %s", sname(s), en); chk_event("hipEventRecord", e); chk_stream("hipEventRecord", s);
     if (live_events.count((void *)e)) { FakeEvent *f = reinterpret_cast<FakeEvent *>(e); f->clock = clocks[stream_key(s)]; f->in_capture = capturing(s); }
     return hipSuccess;
@@ -354,7 +376,7 @@ hipError_t hipEventSynchronize(hipEvent_t e) { std::lock_guard<std::mutex> lk(mu
 hipError_t hipEventQuery(hipEvent_t e) { std::lock_guard<std::mutex> lk(mu); touch(); cap_bad("hipEventQuery"); chk_event("hipEventQuery", e); return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { std::lock_guard<std::mutex> lk(mu); chk_event("hipEventElapsedTime", a); chk_event("hipEventElapsedTime", b); *ms = 1.0f; return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
-    std::lock_guard<std::mutex> lk(mu); touch(); chk_stream("hipStreamWaitEvent", s); chk_event("hipStreamWaitEvent", e);
+    std::lock_guard<std::mutex> lk(mu); touch(); rt("hipStreamWaitEvent"); chk_stream("hipStreamWaitEvent", s); chk_event("hipStreamWaitEvent", e);
     if (live_events.count((void *)e)) {
         // an event whose last record belongs to a capture is a node of that graph: a stream outside it cannot wait for it (now, or once the capture has ended)
         if (reinterpret_cast<FakeEvent *>(e)->in_capture && !capturing(s))
@@ -373,7 +395,7 @@ EXPORT long fake_end_capture(hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- launchers (csrc/aesgcm_internal.h): record, check, launch nothing
-#define LAUNCH(what, st) std::lock_guard<std::mutex> lk(mu); touch(); ++n_launch; if (fail_at && n_launch == fail_at) return hipErrorLaunchFailure; \
+#define LAUNCH(what, st) std::lock_guard<std::mutex> lk(mu); touch(); rt("launch %s", what); ++n_launch; if (fail_at && n_launch == fail_at) return hipErrorLaunchFailure; \
                          chk_stream(what, st); enqueue(what, st); const char *W = what; (void)W
 // kernels that ask for more dynamic LDS than the default cap: the attribute must have been set on THIS device
 #define BIG_LDS() do { if (!((attrs >> cur) & 1u)) bad("%s launched on device %d before its LDS attributes were set there", W, cur); } while (0)
@@ -579,6 +601,67 @@ hipError_t klaunch_rxwin_recover(hipStream_t st, const RxRecoverParams &p) {
 hipError_t klaunch_rxwin_commit(hipStream_t st, const RxCommitParams &p) {
     LAUNCH("k_rxwin_commit*", st); P(p.t.state); P(p.t.status); P(p.win); P(p.num); P(p.auth); P(p.accept); P(p.why);
     note("%s %s %s p=%s n=%u", W, sname(st), rx_txt(p.t).c_str(), bits(p.win, p.num, p.auth, p.accept, p.why).c_str(), p.n_pkts);
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- send counters and the two key derivations (csrc/aesgcm_txnum.h, aesgcm_kdf.h, aesgcm_srtp_kdf.h)
+static std::string tx_txt(const TxTable &t) {
+    char b[128];
+    snprintf(b, sizeof b, "t=%s ctrs=%u max=%u passes=%u", bits(t.rec, t.status, t.counts, t.idx[0], t.idx[1]).c_str(), t.n_ctrs, t.max_pkts, t.passes);
+    return b;
+}
+hipError_t klaunch_txnum_assign(hipStream_t st, const TxAssignParams &p) {
+    LAUNCH("k_tx_assign*", st); P(p.t.rec); P(p.t.status); P(p.t.counts); P(p.t.idx[0]); P(p.t.idx[1]); P(p.ctr); P(p.pkts); P(p.pkt_off); P(p.num_out); P(p.hi_out); P(p.slots); P(p.sorted);
+    note("%s %s %s off=%u len=%u dup=%u flags=%u p=%s n=%u", W, sname(st), tx_txt(p.t).c_str(), p.f.num_off, p.f.num_len, p.f.dup_off, p.f.flags,
+         bits(p.ctr, p.pkts, p.pkt_off, p.num_out, p.hi_out, p.slots, p.sorted).c_str(), p.n_pkts);
+    return hipSuccess;
+}
+// The records of the two derivation tables are 64 bytes and no ABI call reads them back: an install notes the 64-bit FNV-1a of the record its first entry names (the
+// fake's device memory is host memory), which is how a driver sees what a set stored.  0: no entry, or one outside the table.
+static unsigned long long rec_hash(const u32 *rec, const u32 *idx, u32 n, u32 n_recs) {
+    if (!rec || !idx || !n || idx[0] >= n_recs) return 0;
+    const unsigned char *q = (const unsigned char *)(rec + (size_t)idx[0] * KDF_REC_WORDS);
+    unsigned long long h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < KDF_REC_WORDS * sizeof(u32); i++) h = (h ^ q[i]) * 0x100000001b3ull;
+    return h;
+}
+static std::string kdf_txt(const KdfTable &t) {
+    char b[96];
+    snprintf(b, sizeof b, "t=%s secrets=%u hash=%u", bits(t.rec, t.status).c_str(), t.n_secrets, t.hash_len);
+    return b;
+}
+hipError_t klaunch_kdf_attributes() { std::lock_guard<std::mutex> lk(mu); touch(); note("k_kdf_attributes dev=%d", cur + 1); return hipSuccess; }
+hipError_t klaunch_kdf_set(hipStream_t st, const KdfSetParams &p) {
+    LAUNCH("k_kdf_set", st); P(p.t.rec); P(p.t.status); P(p.idx); P(p.secrets);
+    note("%s %s %s p=%s n=%u", W, sname(st), kdf_txt(p.t).c_str(), bits(p.idx, p.secrets).c_str(), p.n);
+    return hipSuccess;
+}
+hipError_t klaunch_kdf_install(int nr, hipStream_t st, const DevTables *tb, const KdfInstallParams &p) {
+    LAUNCH("k_kdf_install", st); P(tb); P(p.t.rec); P(p.t.status); P(p.idx); P(p.slots); P(p.aux_slots); P(p.tab);
+    note("%s %s nr=%d %s p=%s n=%u slots=%u msg=%u/%u/%u rec=%016llx", W, sname(st), nr, kdf_txt(p.t).c_str(), bits(tb, p.idx, p.slots, p.aux_slots, p.tab).c_str(), p.n, p.n_slots,
+         p.msg[0].len, p.msg[1].len, p.msg[2].len, rec_hash(p.t.rec, p.idx, p.n, p.t.n_secrets));
+    return hipSuccess;
+}
+hipError_t klaunch_kdf_update(hipStream_t st, const KdfUpdateParams &p) {
+    LAUNCH("k_kdf_update", st); P(p.t.rec); P(p.t.status); P(p.from); P(p.to);
+    note("%s %s %s p=%s n=%u msg=%u", W, sname(st), kdf_txt(p.t).c_str(), bits(p.from, p.to).c_str(), p.n, p.msg.len);
+    return hipSuccess;
+}
+static std::string skdf_txt(const SkdfTable &t) {
+    char b[96];
+    snprintf(b, sizeof b, "t=%s masters=%u key=%u", bits(t.rec, t.status).c_str(), t.n_masters, t.key_len);
+    return b;
+}
+hipError_t klaunch_srtp_kdf_attributes() { std::lock_guard<std::mutex> lk(mu); touch(); note("k_srtp_kdf_attributes dev=%d", cur + 1); return hipSuccess; }
+hipError_t klaunch_srtp_kdf_set(hipStream_t st, const SkdfSetParams &p) {
+    LAUNCH("k_srtp_kdf_set", st); P(p.t.rec); P(p.t.status); P(p.idx); P(p.keys); P(p.salts);
+    note("%s %s %s p=%s n=%u", W, sname(st), skdf_txt(p.t).c_str(), bits(p.idx, p.keys, p.salts).c_str(), p.n);
+    return hipSuccess;
+}
+hipError_t klaunch_srtp_kdf_install(int nr, hipStream_t st, const DevTables *tb, const SkdfInstallParams &p) {
+    LAUNCH("k_srtp_kdf_install", st); P(tb); P(p.t.rec); P(p.t.status); P(p.idx); P(p.slots); P(p.r); P(p.tab);
+    note("%s %s nr=%d %s p=%s n=%u slots=%u label=%u/%u rec=%016llx", W, sname(st), nr, skdf_txt(p.t).c_str(), bits(tb, p.idx, p.slots, p.r, p.tab).c_str(), p.n, p.n_slots,
+         p.label[0], p.label[1], rec_hash(p.t.rec, p.idx, p.n, p.t.n_masters));
     return hipSuccess;
 }
 

@@ -5,8 +5,8 @@
 // fake HIP runtime of this directory (fakehip.cpp: no GPU, launches launch nothing) and driven through the C ABI by eight threads over four fake devices, every
 // thread for itself: create, messages queued with tag = NULL and collected with aesgcm_last_tag, packets (fixed-size records by rows and through the packet kernels,
 // offset arrays: the routed call with its fork to the side stream), messages wherever they live, a streaming session exported and imported into a second context,
-// rekey, status, destroy; one thread more drives the four-device object; and the two threads of each device set their halves of the device's shared key table and
-// receive windows (csrc/aesgcm_keytab.hip, aesgcm_rxwin.hip: table_sets below).  asan.mk / tsan.mk build it; tests/test_fake_hip.py runs both.  The fake records device
+// rekey, status, destroy; one thread more drives the four-device object; and the two threads of each device set their halves of the device's five shared tables -- key table,
+// receive windows, send counters, traffic secrets, SRTP master keys (csrc/aesgcm_keytab.hip, _rxwin, _txnum, _kdf, _srtp_kdf: table_sets below).  asan.mk / tsan.mk build it; tests/test_fake_hip.py runs both.  The fake records device
 // discipline as always: its violation count must be zero at the end.
 #include <pthread.h>
 #include <stdint.h>
@@ -23,12 +23,16 @@ extern "C" int fake_violations(char *buf, size_t n);
 static const size_t MB = 1 << 20;
 static int g_rounds = 6;
 
-// The device tables: a key table (AES-256) and receive windows (64 bits) per fake device, made by main and shared by the two threads of the device.  Each thread sets
+// The device tables: a key table (AES-256), receive windows (64 bits), send counters, traffic secrets (SHA-384) and master keys (AES-256) per fake device, made by main and shared by the two threads of the device.  Each thread sets
 // its own TAB_PER entries twenty times on a stream of its own, in pieces whose sizes make the shared staging buffer grow again and again -- the tables' mutex and
-// the stage's cross-stream event under the sanitizers; main then reads the windows back (aesgcm_rxwin_get: the fake copies for real) and compares.
+// the stage's cross-stream event under the sanitizers; the counters are read back at once, secrets and masters cleared every other time and their status read; main
+// then reads the windows and counters back (aesgcm_rxwin_get, aesgcm_txnum_get: the fake copies for real) and compares.
 static const size_t TAB_PER = 32;
 static aesgcm_keytab *g_kt[4];
 static aesgcm_rxwin *g_rw[4];
+static aesgcm_txnum *g_tx[4];
+static aesgcm_kdf *g_kdf[4];
+static aesgcm_srtp_kdf *g_skdf[4];
 static uint64_t g_want_next[8][TAB_PER], g_want_seen[8][TAB_PER];
 
 static void table_sets(int t, aesgcm_ctx *c) {
@@ -36,12 +40,23 @@ static void table_sets(int t, aesgcm_ctx *c) {
     const size_t base = (size_t)(t / 4) * TAB_PER;
     void *st = nullptr;
     CHECK(aesgcm_ctx_stream(c, &st));
-    std::vector<unsigned char> bytes(32 * TAB_PER, (unsigned char)t);
+    std::vector<unsigned char> bytes(48 * TAB_PER, (unsigned char)t);
     for (int i = 0; i < 20; i++) {
         const size_t n = i == 19 ? TAB_PER : 1 + (size_t)(i * 7 + t) % TAB_PER, first = (size_t)(i * 5) % (TAB_PER - n + 1);
         uint64_t *next = g_want_next[t] + first, *seen = g_want_seen[t] + first;
         for (size_t k = 0; k < n; k++) { next[k] = 1000 + 64 * (uint64_t)i + k; seen[k] = 0x8000000000000001ull ^ ((uint64_t)t << 32) ^ (k << 8) ^ (uint64_t)i; }
         CHECK(aesgcm_rxwin_set(g_rw[dev], base + first, n, next, seen, st));
+        uint64_t got[TAB_PER], limit[TAB_PER];
+        for (size_t k = 0; k < n; k++) limit[k] = next[k] + 1;
+        CHECK(aesgcm_txnum_set(g_tx[dev], base + first, n, next, limit, st));
+        CHECK(aesgcm_txnum_get(g_tx[dev], base + first, n, got, limit, st));
+        if (memcmp(got, next, n * sizeof(uint64_t)) || limit[n - 1] != next[n - 1] + 1) { fprintf(stderr, "thread %d: the counters it has just set read back otherwise\n", t); exit(1); }
+        CHECK(aesgcm_kdf_set(g_kdf[dev], base + first, n, bytes.data(), st));
+        CHECK(aesgcm_srtp_kdf_set(g_skdf[dev], base + first, n, bytes.data(), bytes.data(), st));
+        if (i & 1) { CHECK(aesgcm_kdf_clear(g_kdf[dev], base + first, n, st)); CHECK(aesgcm_srtp_kdf_clear(g_skdf[dev], base + first, n, st)); }
+        int code = -1; uint64_t detail = 0;
+        CHECK(aesgcm_kdf_status(g_kdf[dev], &code, &detail)); CHECK(code);
+        CHECK(aesgcm_srtp_kdf_status(g_skdf[dev], &code, &detail)); CHECK(code);
         switch (i % 4) {
         case 0: CHECK(aesgcm_keytab_set(g_kt[dev], base + first, n, bytes.data(), st)); break;
         case 1: CHECK(aesgcm_keytab_set_salt(g_kt[dev], base + first, n, bytes.data(), st)); break;
@@ -54,21 +69,26 @@ static void table_sets(int t, aesgcm_ctx *c) {
 static void tables_create(void) {
     const int t = -1;
     for (int d = 0; d < 4; d++) { CHECK(aesgcm_keytab_create(&g_kt[d], d, 32, 2 * TAB_PER)); CHECK(aesgcm_rxwin_create(&g_rw[d], d, 2 * TAB_PER, 64)); }
+    for (int d = 0; d < 4; d++) { CHECK(aesgcm_txnum_create(&g_tx[d], d, 2 * TAB_PER, 64)); CHECK(aesgcm_kdf_create(&g_kdf[d], d, 48, 2 * TAB_PER)); CHECK(aesgcm_srtp_kdf_create(&g_skdf[d], d, 32, 2 * TAB_PER)); }
 }
 
 static void tables_compare_and_destroy(void) {
     const int t = -1;
     for (int d = 0; d < 4; d++) {
         uint64_t next[2 * TAB_PER], seen[2 * TAB_PER];
+        uint64_t ctr[2 * TAB_PER];
         CHECK(aesgcm_rxwin_get(g_rw[d], 0, 2 * TAB_PER, next, seen, nullptr));
+        CHECK(aesgcm_txnum_get(g_tx[d], 0, 2 * TAB_PER, ctr, nullptr, nullptr));
         for (size_t k = 0; k < 2 * TAB_PER; k++) {
             const int w = d + 4 * (int)(k / TAB_PER);
-            if (next[k] != g_want_next[w][k % TAB_PER] || seen[k] != g_want_seen[w][k % TAB_PER]) { fprintf(stderr, "device %d, window %zu: not what thread %d set last\n", d, k, w); exit(1); }
+            if (next[k] != g_want_next[w][k % TAB_PER] || seen[k] != g_want_seen[w][k % TAB_PER] || ctr[k] != next[k]) { fprintf(stderr, "device %d, window or counter %zu: not what thread %d set last\n", d, k, w); exit(1); }
         }
         int code = -1; uint64_t detail = 0;
         CHECK(aesgcm_keytab_status(g_kt[d], &code, &detail)); CHECK(code);
         CHECK(aesgcm_rxwin_status(g_rw[d], &code, &detail)); CHECK(code);
+        CHECK(aesgcm_txnum_status(g_tx[d], &code, &detail)); CHECK(code);
         CHECK(aesgcm_keytab_destroy(g_kt[d])); CHECK(aesgcm_rxwin_destroy(g_rw[d]));
+        CHECK(aesgcm_txnum_destroy(g_tx[d])); CHECK(aesgcm_kdf_destroy(g_kdf[d])); CHECK(aesgcm_srtp_kdf_destroy(g_skdf[d]));
     }
 }
 

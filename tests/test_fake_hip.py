@@ -110,10 +110,11 @@ def test_the_fake_runtime_reports_what_a_capture_cannot_carry():
 
 
 def test_device_tables_stage_check_and_free_as_recorded_on_the_fake_runtime():
-    """tests/fake_hip/table_drive.py: a key table and receive windows of both sizes through create, every host-to-table setter on three fresh streams (the second
-    grows the staging buffer; each is ordered behind the one before), set -> get through the stage and both conversions, the range check of every entry point at its
-    edges, status, destroy (allocations back where they were, the recorded number of device synchronisations) and a set whose launch fails -- every answer a literal
-    recorded from the commit before both host sides moved onto one base"""
+    """tests/fake_hip/table_drive.py: all five device tables -- a key table, receive windows of both sizes, send counters, traffic secrets of both hashes, SRTP master
+    keys of the three key sizes -- through create, every host-to-table setter on three fresh streams (the second grows the staging buffer; each is ordered behind the
+    one before), set -> get through the stage (windows: and both conversions), what an install finds in a record that was set, the range check of every entry point at
+    its edges, status, destroy (allocations back where they were, the recorded number of device synchronisations), a set whose launch or copy fails, and the runtime
+    calls of one set against tests/golden/table_calls.txt -- every answer a literal recorded from the commit before the tables' host sides moved onto one base"""
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc (the HIP headers)")
     d = os.path.join(HERE, "fake_hip")
@@ -121,6 +122,28 @@ def test_device_tables_stage_check_and_free_as_recorded_on_the_fake_runtime():
     env = dict(os.environ, AESGCM_LIB=os.path.join(d, "libaesgcm_fake.so"))
     out = subprocess.run([sys.executable, os.path.join(d, "table_drive.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert out.returncode == 0 and "FAKE TABLE OK" in out.stdout, out.stdout[-3000:]
+
+
+def test_the_fake_libraries_export_the_abi_of_the_real_ones_exactly():
+    """libaesgcm_fake.so and libaesgcm_fake_dbg.so link every host unit of the library (tests/fake_hip/Makefile, UNITS), so each exports exactly the aesgcm_* symbols
+    of libaesgcm_hip.so / libaesgcm_hip_dbg.so and loads through the ordinary binding with every declared symbol: a host unit the fake does not link, or a launcher
+    fakehip.cpp does not have, fails here (at the link, or as a missing symbol)"""
+    import re
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc (the HIP headers)")
+    from aesgcm_amd.build import build, SO, SO_DEBUG
+    build()
+    d = os.path.join(HERE, "fake_hip")
+    subprocess.run(["make", "-C", d, "-s", "libaesgcm_fake.so", "dbg"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+
+    def exported(path):
+        return set(re.findall(r" T (aesgcm_\w+)", subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)))
+    for fake, real in (("libaesgcm_fake.so", SO), ("libaesgcm_fake_dbg.so", SO_DEBUG)):
+        assert exported(os.path.join(d, fake)) == exported(real), (fake, sorted(exported(os.path.join(d, fake)) ^ exported(real)))
+        out = subprocess.run([sys.executable, "-c", "from aesgcm_amd import lib; L = lib.load(); print(sum(hasattr(L, s) for s in lib.SYMBOLS), len(lib.SYMBOLS), L.aesgcm_abi_version())"],
+                             cwd=os.path.dirname(HERE), env=dict(os.environ, AESGCM_LIB=os.path.join(d, fake)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+        n, total, version = (out.stdout.split() + ["", "", ""])[:3]
+        assert out.returncode == 0 and n == total and version == "5", (fake, out.stdout[-2000:])
 
 
 def test_the_host_side_loads_over_a_runtime_without_stream_capture():

@@ -92,13 +92,6 @@ def test_argument_errors_before_any_table_or_device():
     assert L.aesgcm_srtp_kdf_destroy(None) == lib.OK
 
 
-def test_the_host_units_the_fake_runtime_links_do_not_name_the_new_unit():
-    for f in ("aesgcm_host.hip", "aesgcm_abi.hip", "aesgcm_keytab.hip", "aesgcm_rxwin.hip"):
-        text = open(os.path.join(CSRC, f)).read()
-        assert "srtp_kdf" not in text and "Skdf" not in text, f
-    assert "srtp_kdf" not in open(os.path.join(ROOT, "tests", "fake_hip", "Makefile")).read()
-
-
 # ---------------------------------------------------------------- the reference
 def test_reference_reproduces_the_published_vectors():
     vs = K.vectors()
