@@ -13,3 +13,4 @@
 #include "aesgcm_txnum_kernels.hip"
 #include "aesgcm_kdf_kernels.hip"
 #include "aesgcm_srtp_kdf_kernels.hip"
+#include "aesgcm_prf12_kernels.hip"

@@ -90,3 +90,6 @@ int aesgcm_srtp_kdf_destroy(aesgcm_srtp_kdf *k) {
     delete k;
     return rc;
 }
+
+// the TLS 1.2 PRF's host side (aesgcm_prf12_*): its exporter fills this unit's master records, so it is compiled here, behind the struct it needs
+#include "aesgcm_prf12.hip"

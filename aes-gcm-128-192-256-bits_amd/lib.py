@@ -53,6 +53,8 @@ SYMBOLS = [
     "aesgcm_kdf_destroy",
     "aesgcm_srtp_kdf_create", "aesgcm_srtp_kdf_set", "aesgcm_srtp_kdf_set_dev", "aesgcm_srtp_kdf_clear", "aesgcm_srtp_kdf_install_dev", "aesgcm_srtp_kdf_status",
     "aesgcm_srtp_kdf_destroy",
+    "aesgcm_prf12_create", "aesgcm_prf12_set", "aesgcm_prf12_set_dev", "aesgcm_prf12_clear", "aesgcm_prf12_install_dev", "aesgcm_prf12_export_srtp_dev", "aesgcm_prf12_status",
+    "aesgcm_prf12_destroy",
 ]
 
 
@@ -1574,6 +1576,89 @@ class MasterKeyTable(_Table):
             up["r"] = ("Q", r)
         _device_call(self.device, up, {}, lambda b: self.install_dev(kind, keytab, n, b["idx"].ptr, b["slots"].ptr, b["r"].ptr if r is not None else None))
         return self
+
+
+# ---------------------------------------------------------------- the TLS 1.2 PRF on the device (aesgcm_prf12_*)
+def _prf12_typed(L):
+    """type the aesgcm_prf12_* symbols on first use, as _kdf_typed does: a library that lacks them still loads"""
+    if not getattr(L, "_prf12_typed", False):
+        L.aesgcm_prf12_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_prf12_set.argtypes = [vp, sz, sz, vp, vp, vp, vp]
+        L.aesgcm_prf12_set_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+        L.aesgcm_prf12_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_prf12_install_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.aesgcm_prf12_export_srtp_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.aesgcm_prf12_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_prf12_destroy.argtypes = [vp]
+        L._prf12_typed = True
+    return L
+
+
+PRF12_MASTER_LEN, PRF12_RANDOM_LEN = 48, 32                         # bytes of a master secret and of a hello random
+PRF12_NONE = 0xFFFFFFFF                                             # an entry of a slot / record array that installs nothing for that direction
+
+
+class MasterSecretTable(_Table):
+    """aesgcm_prf12: n_masters device-resident TLS 1.2 / DTLS 1.2 master secrets with their client and server randoms, of one PRF hash (hash_len 32 = SHA-256, 48 =
+    SHA-384).  install_dev cuts a connection's AES-GCM key block (RFC 5246 6.3) into key-table slots, export_srtp_dev the DTLS-SRTP exporter's output (RFC 5764 4.2)
+    into a MasterKeyTable; no record is ever read back (include/aesgcm.h "TLS 1.2 PRF").  Protect the table like keys."""
+    _prefix = "aesgcm_prf12"
+
+    def __init__(self, hash_len, n_masters, device=0):
+        self._create(_prf12_typed, device, hash_len, n_masters)
+        self.hash_len, self.n_masters = hash_len, n_masters
+
+    def set(self, first, masters, client_randoms, server_randoms, stream=None):
+        """aesgcm_prf12_set: host master secrets (one bytes-like of n * 48 bytes, or a list) and the connections' randoms (n * 32 bytes each, or lists) into records
+        first, first + 1, ..."""
+        mb, n = _per_slot(masters, PRF12_MASTER_LEN, "master secrets must be a multiple of 48 bytes")
+        what = "a random is 32 bytes, one client random and one server random per master secret"
+        cb, nc = _per_slot(client_randoms, PRF12_RANDOM_LEN, what)
+        sb, ns = _per_slot(server_randoms, PRF12_RANDOM_LEN, what)
+        if nc != n or ns != n:
+            raise AesGcmError(EARG, what)
+        _chk(self._lib.aesgcm_prf12_set(self._h, first, n, mb, cb, sb, stream))
+        return self
+
+    def set_dev(self, n, d_idx, d_masters, d_client_randoms, d_server_randoms, stream=None):
+        """aesgcm_prf12_set_dev: n master secrets (n x 48 bytes) and randoms (n x 32 bytes each) from device memory into the records d_idx (n uint32, device memory)"""
+        _chk(self._lib.aesgcm_prf12_set_dev(self._h, n, d_idx, d_masters, d_client_randoms, d_server_randoms, stream))
+        return self
+
+    def clear(self, first, n=1, stream=None):
+        """aesgcm_prf12_clear: records first .. first + n - 1 zeroed and unset (their entries are refused)"""
+        _chk(self._lib.aesgcm_prf12_clear(self._h, first, n, stream))
+        return self
+
+    def install_dev(self, keytab, n, d_idx, d_client_slots, d_server_slots, stream=None):
+        """aesgcm_prf12_install_dev: entry i cuts the key block of record d_idx[i] into slot d_client_slots[i] (client_write_key, client_write_IV) and slot
+        d_server_slots[i] (the server's) of keytab (a KeyTable); either array may be None, an entry PRF12_NONE installs nothing (all uint32, device memory)"""
+        _chk(self._lib.aesgcm_prf12_install_dev(self._h, keytab._h, n, d_idx, d_client_slots, d_server_slots, stream))
+
+    def export_srtp_dev(self, master_table, n, d_idx, d_client_recs, d_server_recs, stream=None):
+        """aesgcm_prf12_export_srtp_dev: entry i writes the DTLS-SRTP exporter's client key and salt of record d_idx[i] into record d_client_recs[i] of master_table
+        (a MasterKeyTable of key_len 16 or 32) and the server's into d_server_recs[i]; None and PRF12_NONE as install_dev"""
+        _chk(self._lib.aesgcm_prf12_export_srtp_dev(self._h, master_table._h, n, d_idx, d_client_recs, d_server_recs, stream))
+
+    def _both(self, idx, a, b, call):
+        n = len(idx)
+        if not n or (a is None and b is None) or any(x is not None and len(x) != n for x in (a, b)):
+            raise AesGcmError(EARG, "idx and the client / server arrays (at least one) must be equally long and not empty")
+        up = {"idx": ("I", idx)}
+        if a is not None:
+            up["c"] = ("I", a)
+        if b is not None:
+            up["s"] = ("I", b)
+        _device_call(self.device, up, {}, lambda m: call(n, m["idx"].ptr, m["c"].ptr if a is not None else None, m["s"].ptr if b is not None else None))
+        return self
+
+    def install(self, keytab, idx, client_slots, server_slots):
+        """Host convenience (tests, examples): install_dev over host lists, waited for.  Refused entries are what status() reports"""
+        return self._both(idx, client_slots, server_slots, lambda n, i, c, s: self.install_dev(keytab, n, i, c, s))
+
+    def export_srtp(self, master_table, idx, client_recs, server_recs):
+        """Host convenience (tests, examples): export_srtp_dev over host lists, waited for"""
+        return self._both(idx, client_recs, server_recs, lambda n, i, c, s: self.export_srtp_dev(master_table, n, i, c, s))
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

@@ -41,7 +41,7 @@ extern "C" {
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
                                   aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
                                   the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt,
-                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*)
+                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*, the TLS 1.2 PRF aesgcm_prf12_*)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -434,7 +434,8 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * the window records.  (The five-array aesgcm_batch_crypt_dev / _var_dev plan their launch the same way and follow the same rules.)
  * aesgcm_kdf_install_dev and aesgcm_kdf_update_dev ("ON-DEVICE KEY DERIVATION" below) belong to this list too: one launch each, no memset node, no dispenser; the
  * graph holds the secret records beside the slots, and a replayed update in place steps its secrets one generation per replay.  So does aesgcm_srtp_kdf_install_dev
- * ("SRTP KEY DERIVATION" below): one launch, and the graph holds the master records beside the slots.
+ * ("SRTP KEY DERIVATION" below): one launch, and the graph holds the master records beside the slots.  So do aesgcm_prf12_install_dev and aesgcm_prf12_export_srtp_dev
+ * ("TLS 1.2 PRF" below): one launch each, and the graph holds the master-secret records beside the slots (install) or beside the SRTP master records (export).
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
  *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
@@ -442,7 +443,7 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  *                    packets are taken in array order -- the same bytes, slower from the counts at which an ordinary call is ordered.
  *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
  *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy
- *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy.
+ *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_prf12_create, _set, _set_dev, _clear, _status, _destroy.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
  *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
@@ -698,7 +699,7 @@ AESGCM_API int aesgcm_keytab_dtls_crypt_dev(aesgcm_keytab *t, int decrypt, const
  * d_in, d_pkt_off, d_out NULL; RTP without d_roc; decrypt without d_auth; n_pkts >= 2^31.
  * ONE k_kt_srtp launch: no scratch memory, no host synchronisation, capture-safe (CAPTURE, under "key tables" above) and asynchronous; shape, order and planning as aesgcm_keytab_dtls_crypt_dev's DTLS 1.2
  * mode.  Ordering and thread safety as the other key-table calls.
- * OUT OF SCOPE: ROC estimation and replay windows (not this call's: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_SRTP writes d_roc, aesgcm_rxwin_commit_dev keeps the window); the DTLS-SRTP exporter (the master key and salt are the caller's: INTEGRATION.md "SRTP and SRTCP packets" says which secret
+ * OUT OF SCOPE: ROC estimation and replay windows (not this call's: aesgcm_rxwin_recover_dev with AESGCM_RXWIN_SRTP writes d_roc, aesgcm_rxwin_commit_dev keeps the window); the DTLS-SRTP exporter (not this call's: aesgcm_prf12_export_srtp_dev under "TLS 1.2 PRF" below fills the master table on the device; without it the master key and salt are the caller's: INTEGRATION.md "SRTP and SRTCP packets" says which secret
  * becomes what -- the session key derivation from them, RFC 3711 4.3, is aesgcm_srtp_kdf_* under "SRTP KEY DERIVATION" below); the AES-CM / HMAC-SHA1 transforms; double encryption (RFC 8723); RFC 6904 header-extension encryption; MKI lookup (the caller maps an MKI to a slot, and one
  * call has one mki_len); splitting reduced-size or multiplexed datagrams (one entry of d_pkt_off per packet; a compound RTCP packet is ONE packet). */
 #define AESGCM_SRTP_RTP  1u
@@ -888,7 +889,7 @@ AESGCM_API int aesgcm_txnum_destroy(aesgcm_txnum *t);
  * install on one stream and a crypt call on another that names the slot are the caller's to order, as with aesgcm_keytab_set.  So the key-update loop runs as launches
  * on one stream: aesgcm_txnum_assign_dev refuses at the limit, update, install into a fresh slot, reset the counter, encrypt (INTEGRATION.md "Key derivation").
  * The host calls of one table are thread-safe; a table belongs to its device.
- * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF; ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash.  (SRTP's AES-CM key
+ * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF (not this table's: aesgcm_prf12_* under "TLS 1.2 PRF" below); ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash.  (SRTP's AES-CM key
  * derivation, RFC 3711 4.3, is no HKDF and has a table of its own: aesgcm_srtp_kdf_*, "SRTP KEY DERIVATION" below.) */
 typedef struct aesgcm_kdf aesgcm_kdf;
 typedef struct aesgcm_kdf_fmt {
@@ -942,8 +943,8 @@ AESGCM_API int aesgcm_kdf_destroy(aesgcm_kdf *k);
  * the slot's fields.
  * One launch per install, a lane per derived value (k_srtp_kdf_install: entries x {key, salt}); no allocation, no event, no host synchronisation, nothing read back:
  * install is capture-safe (CAPTURE, under "key tables" above) and asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
- * OUT OF SCOPE: the DTLS-SRTP exporter and SDES; the authentication-key labels (0x01, 0x04) and the AES-CM / HMAC-SHA1 transforms they serve; RFC 6904's header
- * labels; counting packets to the next period (r is the caller's, per entry); the TLS 1.2 / DTLS 1.2 PRF. */
+ * OUT OF SCOPE: the DTLS-SRTP exporter (not this table's: aesgcm_prf12_export_srtp_dev below fills these records on the device) and SDES; the authentication-key labels (0x01, 0x04) and the AES-CM / HMAC-SHA1 transforms they serve; RFC 6904's header
+ * labels; counting packets to the next period (r is the caller's, per entry); the TLS 1.2 / DTLS 1.2 PRF (not this table's: aesgcm_prf12_* under "TLS 1.2 PRF" below). */
 typedef struct aesgcm_srtp_kdf aesgcm_srtp_kdf;
 AESGCM_API int aesgcm_srtp_kdf_create(aesgcm_srtp_kdf **out, int device, size_t key_len, size_t n_masters);
 AESGCM_API int aesgcm_srtp_kdf_set(aesgcm_srtp_kdf *k, size_t first, size_t n, const uint8_t *keys, const uint8_t *salts, void *stream);
@@ -953,6 +954,62 @@ AESGCM_API int aesgcm_srtp_kdf_install_dev(aesgcm_srtp_kdf *k, uint32_t kind, ae
                                 const uint64_t *d_r, void *stream);
 AESGCM_API int aesgcm_srtp_kdf_status(aesgcm_srtp_kdf *k, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_srtp_kdf_destroy(aesgcm_srtp_kdf *k);
+
+/* ---------------------------------------------------------------- TLS 1.2 PRF: TLS 1.2 and DTLS 1.2 AES-GCM keys, and DTLS-SRTP master keys, from master secrets that never leave the device
+ * In TLS 1.2 and DTLS 1.2 every key of a connection comes from its 48-byte master secret and the two hello randoms by the PRF of RFC 5246 section 5:
+ *   PRF(secret, label, seed) = P_hash(secret, label | seed) = T(1) | T(2) | ..., A(0) = label | seed, A(j) = HMAC(secret, A(j - 1)), T(j) = HMAC(secret, A(j) | label | seed),
+ * over HMAC-SHA-256, or HMAC-SHA-384 for the suites that name SHA384.  aesgcm_prf12 is a table of n_masters records on the device, each a master secret and its
+ * connection's client random and server random (32 bytes each), of one PRF hash: hash_len 32 = SHA-256, 48 = SHA-384.  No call reads a record back.  THE TABLE HOLDS
+ * MASTER SECRETS: PROTECT IT LIKE KEYS -- whoever holds a master secret holds every key of its connection, and of every connection resumed from its session.
+ *   aesgcm_prf12_create    every record unset.  AESGCM_EARG for a hash_len other than 32 / 48, n_masters == 0 or >= 2^31.
+ *   aesgcm_prf12_set       HOST master secrets (n * 48 bytes), client randoms and server randoms (n * 32 bytes each) into records first .. first + n - 1, through the
+ *                          table's staging buffer on `stream`, zeroed behind the copy; the library's host copy is wiped before the call returns (as aesgcm_kdf_set).
+ *   aesgcm_prf12_set_dev   n masters and randoms from DEVICE memory (n * 48, n * 32 and n * 32 bytes, no alignment asked) into the records d_idx[i]; an index out of
+ *                          range is refused.
+ *   aesgcm_prf12_clear     records first .. first + n - 1 zeroed and unset.
+ *   aesgcm_prf12_status    as aesgcm_keytab_status: the LOWEST entry index an install, export or set_dev call refused since the last read, which clears it.
+ *   aesgcm_prf12_destroy   waits for the device, zeroes the records and the staging buffer, frees.
+ * INSTALL: aesgcm_prf12_install_dev(p, keytab, n, d_idx, d_client_slots, d_server_slots, stream).  For entry i with the record d_idx[i]:
+ *   key_block = P_hash(master, "key expansion" | server_random | client_random) = client_write_key | server_write_key | client_write_IV[4] | server_write_IV[4], the keys
+ *   of the key table's key_len (RFC 5246 6.3; RFC 5288 3: an AEAD suite has no MAC keys, and its fixed IV is four bytes);
+ *   slot d_client_slots[i] of `keytab` becomes exactly what aesgcm_keytab_set_dev makes of client_write_key -- round keys, H, its powers, the set marker -- and its
+ *   TLS-IV field what aesgcm_keytab_set_tls_iv makes of client_write_IV | 8 zero bytes: what aesgcm_keytab_records_crypt_dev (TLS 1.2) and aesgcm_keytab_dtls_crypt_dev
+ *   (DTLS 1.2) read; slot d_server_slots[i] gets server_write_key and server_write_IV the same way.
+ * Either array may be NULL (not both: AESGCM_EARG), and an entry of 0xFFFFFFFF installs nothing for that direction: an endpoint installs its write key into its
+ * sending table and the peer's into its receiving one, in two calls or in one.  The table's key size may be 16, 24 or 32 with either hash.  AESGCM_EARG for p or
+ * keytab NULL, d_idx NULL, n >= 2^31 and a key table of another device; n == 0 is AESGCM_OK.
+ * EXPORT: aesgcm_prf12_export_srtp_dev(p, masters, n, d_idx, d_client_recs, d_server_recs, stream).  For entry i:
+ *   out = P_hash(master, "EXTRACTOR-dtls_srtp" | client_random | server_random), 2 * key_len + 24 bytes = client key | server key | client salt[12] | server salt[12]
+ *   with the SRTP master table's key_len (RFC 5705 4 without a context; RFC 5764 4.2; the AEAD profiles' 12-byte salts, RFC 7714 12).  THE RANDOMS STAND IN THE
+ *   OTHER ORDER than in key expansion;
+ *   record d_client_recs[i] of `masters` becomes exactly what aesgcm_srtp_kdf_set_dev makes of the client's key and of its salt with two zero bytes appended (the 14
+ *   bytes that table takes, "SRTP KEY DERIVATION" above); record d_server_recs[i] gets the server's.  NULL and 0xFFFFFFFF as install.
+ * AESGCM_EARG as install, and for a master table of another device or of key_len 24 (DTLS-SRTP has no AES-192 profile).  From there aesgcm_srtp_kdf_install_dev derives
+ * the session keys: master secret -> exporter -> master table -> install -> aesgcm_keytab_srtp_crypt_dev, as launches on one stream (INTEGRATION.md "Key derivation").
+ * REFUSED ENTRIES are skipped whole -- NOTHING an entry names is written, in either direction -- when d_idx[i] is out of range, the record is unset or cleared, or a
+ * slot / record it names (other than 0xFFFFFFFF) is out of range.  The lowest such index goes to THIS table's status word; the key table's and the SRTP master
+ * table's status words are not touched.
+ * THE BOUND: both labels are shorter than 20 bytes, so the seed is at most 84 bytes and every HMAC has a block count that no datum changes (csrc/aesgcm_prf12.h); the
+ * ipad and opad states of the master secret are computed once per lane.  A lane computes only as many T(j) as cover the bytes it takes.
+ * NO DERIVED KEY IN MEMORY: a derived key, IV or salt is stored nowhere but in the slot's fields or the SRTP master record.  The lane that derives a key runs the key
+ * schedule itself, from its registers.
+ * One launch per call, a lane per derived value (k_prf12_install: entries x {client key, server key, client IV, server IV}; k_prf12_export: entries x {client,
+ * server}); no allocation, no event, no host synchronisation, nothing read back: install and export are capture-safe (CAPTURE, under "key tables" above) and
+ * asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
+ * OUT OF SCOPE: deriving the master secret itself from the premaster secret, with or without the extended master secret of RFC 7627 (the master secret is the
+ * caller's); verify_data; the MAC keys of CBC suites (only AEAD key blocks are cut); exporters with a context or other labels; IKEv2's prf+ and MACsec's MKA KDF. */
+typedef struct aesgcm_prf12 aesgcm_prf12;
+AESGCM_API int aesgcm_prf12_create(aesgcm_prf12 **out, int device, size_t hash_len, size_t n_masters);
+AESGCM_API int aesgcm_prf12_set(aesgcm_prf12 *p, size_t first, size_t n, const uint8_t *masters, const uint8_t *client_randoms, const uint8_t *server_randoms, void *stream);
+AESGCM_API int aesgcm_prf12_set_dev(aesgcm_prf12 *p, size_t n, const uint32_t *d_idx, const void *d_masters, const void *d_client_randoms, const void *d_server_randoms,
+                             void *stream);
+AESGCM_API int aesgcm_prf12_clear(aesgcm_prf12 *p, size_t first, size_t n, void *stream);
+AESGCM_API int aesgcm_prf12_install_dev(aesgcm_prf12 *p, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const uint32_t *d_client_slots,
+                                 const uint32_t *d_server_slots, void *stream);
+AESGCM_API int aesgcm_prf12_export_srtp_dev(aesgcm_prf12 *p, aesgcm_srtp_kdf *masters, size_t n, const uint32_t *d_idx, const uint32_t *d_client_recs,
+                                     const uint32_t *d_server_recs, void *stream);
+AESGCM_API int aesgcm_prf12_status(aesgcm_prf12 *p, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_prf12_destroy(aesgcm_prf12 *p);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
