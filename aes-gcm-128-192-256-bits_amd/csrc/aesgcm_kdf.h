@@ -8,7 +8,7 @@
 // THE ONE CASE.  HKDF-Expand-Label(secret, label, "", L) with L <= hash_len is T(1) = HMAC(secret, HkdfLabel | 0x01), HkdfLabel = be16(L) | len | label | 0x00
 // (RFC 8446 7.1, RFC 5869 2.3).  With a full label of at most KDF_LABEL_MAX = 20 bytes the message is at most 25 bytes, and the key (the secret: hash_len bytes) is at
 // most one block.  So EVERY HMAC HERE IS EXACTLY FOUR COMPRESSIONS: the ipad block, one message block (message | 0x80 | zeros | bit length), the opad block, one
-// digest block.  There is no multi-block and no multi-T(i) path; aesgcm_kdf_fmt_check holds the labels to the bound, the kernels do not look at it again.  The message
+// digest block (kdf_hmac_pad, kdf_hmac_msg, kdf_hmac_outer: each shape written once, over KdfHash<HL>; aesgcm_prf12.h builds its HMACs from the same three).  There is no multi-block and no multi-T(i) path; aesgcm_kdf_fmt_check holds the labels to the bound, the kernels do not look at it again.  The message
 // block's first 32 bytes are made on the HOST (kdf_msg: a KdfMsg per label, passed by value), so no lane indexes its message schedule by a length.
 //
 // The rounds are fully unrolled (by template recursion) over a 16-word rolling schedule with constant indices (registers, no private memory); rotates are funnel shifts (v_alignbit_b32; a 64-bit
@@ -136,6 +136,73 @@ HD void kdf_sha384_init(u64 *st) {
     st[4] = 0x67332667ffc00b31ull; st[5] = 0x8eb44a8768581511ull; st[6] = 0xdb0c2e0d64f98fa7ull; st[7] = 0x47b5481dbefa4fa4ull;
 }
 
+// ---------------------------------------------------------------- the two hashes by digest length, and the shapes of an HMAC
+// HL = 32: SHA-256, HL = 48: SHA-384.  A message is handed over as big-endian 32-bit words (NW of them, zeros behind); at(m, k) is word k of the block's sixteen
+// in the state's width: m[k] itself, or m[2k] | m[2k + 1].  A block is BLOCK bytes and ends with the message's bit length in LEN_BYTES bytes, of which all but the
+// low word -- w[15] in either width -- are zero here; the padding's 0x80 is KDF_PAD_BIT in the 32-bit word behind the message's last
+template <int HL> struct KdfHash;
+template <> struct KdfHash<32> {
+    typedef u32 word;
+    static constexpr u32 BLOCK = 64u, LEN_BYTES = 8u;
+    static HD void init(word *st) { kdf_sha256_init(st); }
+    static HD void block(word *st, word *w) { kdf_sha256_block(st, w); }
+    template <int NW> static HD word at(const u32 *m, int k) { return k < NW ? m[k] : 0u; }
+    static HD void digest(const word *st, u32 *out) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) out[k] = st[k];
+    }
+};
+template <> struct KdfHash<48> {
+    typedef u64 word;
+    static constexpr u32 BLOCK = 128u, LEN_BYTES = 16u;
+    static HD void init(word *st) { kdf_sha384_init(st); }
+    static HD void block(word *st, word *w) { kdf_sha512_block(st, w); }
+    template <int NW> static HD word at(const u32 *m, int k) { return ((u64)(2 * k < NW ? m[2 * k] : 0u) << 32) | (2 * k + 1 < NW ? m[2 * k + 1] : 0u); }
+    static HD void digest(const word *st, u32 *out) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) { out[2 * k] = (u32)(st[k] >> 32); out[2 * k + 1] = (u32)st[k]; }
+    }
+};
+#define KDF_IPAD 0x3636363636363636ull     /* RFC 2104; cut to the state's width */
+#define KDF_OPAD 0x5c5c5c5c5c5c5c5cull
+#define KDF_PAD_BIT 0x80000000u
+// how many blocks a message of len bytes takes behind whole blocks: the 0x80 and the length field go in with it
+template <int HL> constexpr u32 kdf_blocks(u32 len) { return (len + 1u + KdfHash<HL>::LEN_BYTES + KdfHash<HL>::BLOCK - 1u) / KdfHash<HL>::BLOCK; }
+
+// st = the state behind the pad block of a key of KW 32-bit words (at most one block): one compression from init; pad = KDF_IPAD or KDF_OPAD
+template <int HL, int KW> HD void kdf_hmac_pad(const u32 *key, u64 pad, typename KdfHash<HL>::word *st) {
+    typedef KdfHash<HL> H;
+    static_assert(4u * KW <= H::BLOCK, "a longer key would have to be hashed first");
+    typename H::word w[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = H::template at<KW>(key, k) ^ (typename H::word)pad;
+    H::init(st);
+    H::block(st, w);
+}
+// st, which stands behind ONE block (a pad state), takes the NB blocks of a message of len bytes: m = the message with its KDF_PAD_BIT, NW words.  Block B of NB, by
+// recursion: every index is a constant
+template <int HL, int NB, int NW, int B = 0> HD void kdf_hmac_msg(typename KdfHash<HL>::word *st, const u32 *m, u32 len) {
+    typedef KdfHash<HL> H;
+    static_assert(4u * NW + H::LEN_BYTES <= NB * H::BLOCK, "the message and its 0x80 must end before the length field of block NB");
+    typename H::word w[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = H::template at<NW>(m, 16 * B + k);
+    if constexpr (B + 1 == NB) w[15] = (H::BLOCK + len) * 8u;
+    H::block(st, w);
+    if constexpr (B + 1 < NB) kdf_hmac_msg<HL, NB, NW, B + 1>(st, m, len);
+}
+// the outer hash: opad = the opad state, in = the inner hash's final state -> res, the HMAC as HL / 4 big-endian 32-bit words
+template <int HL> HD void kdf_hmac_outer(const typename KdfHash<HL>::word *opad, const typename KdfHash<HL>::word *in, u32 *res) {
+    typename KdfHash<HL>::word o[8];
+    u32 d[HL / 4 + 1];
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = opad[k];
+    KdfHash<HL>::digest(in, d);
+    d[HL / 4] = KDF_PAD_BIT;
+    kdf_hmac_msg<HL, 1, HL / 4 + 1>(o, d, (u32)HL);
+    KdfHash<HL>::digest(o, res);
+}
+
 // ---------------------------------------------------------------- HKDF-Expand-Label, the one case
 // The message of the HMAC, HkdfLabel | 0x01, with the padding's 0x80 behind it, as eight big-endian words, and its length.  Made on the host from a full label of at
 // most KDF_LABEL_MAX bytes (len <= 25: the 0x80 is byte 25 at the latest, inside the 32)
@@ -150,53 +217,16 @@ HD void kdf_msg(const unsigned char *label, u32 label_len, u32 L, KdfMsg &m) {
     for (u32 k = 0; k < 8u; k++) m.w[k] = ((u32)b[4 * k] << 24) | ((u32)b[4 * k + 1] << 16) | ((u32)b[4 * k + 2] << 8) | b[4 * k + 3];
 }
 
-// sec: the secret as HL / 4 big-endian 32-bit words -> out: T(1), HL / 4 big-endian 32-bit words, of which the caller takes the first L bytes
-template <int HL> HD void kdf_expand(const u32 *sec, const KdfMsg &m, u32 *out);
-template <> HD void kdf_expand<32>(const u32 *sec, const KdfMsg &m, u32 *out) {
-    u32 st[8], in[8], w[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = (k < 8 ? sec[k] : 0u) ^ 0x36363636u;
-    kdf_sha256_init(st);
-    kdf_sha256_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = k < 8 ? m.w[k] : 0u;
-    w[15] = (64u + m.len) * 8u;
-    kdf_sha256_block(st, w);
+// sec: the secret as HL / 4 big-endian 32-bit words -> out: T(1), HL / 4 big-endian 32-bit words, of which the caller takes the first L bytes.  The compressions in
+// this order -- ipad, message, opad, digest -- so that only the inner digest is live across the opad block
+template <int HL> HD void kdf_expand(const u32 *sec, const KdfMsg &m, u32 *out) {
+    typename KdfHash<HL>::word st[8], in[8];
+    kdf_hmac_pad<HL, HL / 4>(sec, KDF_IPAD, st);
+    kdf_hmac_msg<HL, 1, 8>(st, m.w, m.len);
 #pragma unroll
     for (int k = 0; k < 8; k++) in[k] = st[k];
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = (k < 8 ? sec[k] : 0u) ^ 0x5c5c5c5cu;
-    kdf_sha256_init(st);
-    kdf_sha256_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = k < 8 ? in[k] : 0u;
-    w[8] = 0x80000000u; w[15] = (64u + 32u) * 8u;
-    kdf_sha256_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 8; k++) out[k] = st[k];
-}
-template <> HD void kdf_expand<48>(const u32 *sec, const KdfMsg &m, u32 *out) {
-    u64 st[8], in[6], w[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = (k < 6 ? ((u64)sec[2 * k] << 32) | sec[2 * k + 1] : 0ull) ^ 0x3636363636363636ull;
-    kdf_sha384_init(st);
-    kdf_sha512_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = k < 4 ? ((u64)m.w[2 * k] << 32) | m.w[2 * k + 1] : 0ull;
-    w[15] = (128u + m.len) * 8u;
-    kdf_sha512_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 6; k++) in[k] = st[k];
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = (k < 6 ? ((u64)sec[2 * k] << 32) | sec[2 * k + 1] : 0ull) ^ 0x5c5c5c5c5c5c5c5cull;
-    kdf_sha384_init(st);
-    kdf_sha512_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 16; k++) w[k] = k < 6 ? in[k] : 0ull;
-    w[6] = 0x8000000000000000ull; w[15] = (128u + 48u) * 8u;
-    kdf_sha512_block(st, w);
-#pragma unroll
-    for (int k = 0; k < 6; k++) { out[2 * k] = (u32)(st[k] >> 32); out[2 * k + 1] = (u32)st[k]; }
+    kdf_hmac_pad<HL, HL / 4>(sec, KDF_OPAD, st);
+    kdf_hmac_outer<HL>(st, in, out);
 }
 
 // ---------------------------------------------------------------- the table and what a lane decides

@@ -7,13 +7,11 @@
 //
 // THE SHAPE.  P_hash(secret, seed) = T(1) | T(2) | ..., A(1) = HMAC(secret, seed), A(j) = HMAC(secret, A(j - 1)), T(j) = HMAC(secret, A(j) | seed), with
 // seed = label | random | random.  The secret is 48 bytes, less than a block of either hash, so the ipad and the opad state are ONE compression each, made once per
-// lane (Prf12Key).  With a label of 1 .. PRF12_LABEL_MAX = 20 bytes the seed is 65 .. 84 bytes and every message has a block count that no datum changes:
-//                      seed     A(j)     A(j) | seed
-//     SHA-256           2        1           2            (65 + 9 > 64, 84 + 9 <= 128;  32 + 9 <= 64;  97 + 9 > 64, 116 + 9 <= 128)
-//     SHA-384           1        1           2            (84 + 17 <= 128;  48 + 17 <= 128;  113 + 17 > 128, 132 + 17 <= 256)
-// plus one compression for the outer hash of each HMAC.  The label's LENGTH is a template argument: where the randoms fall in the blocks is known to the compiler, so
+// lane (Prf12Key).  With a label of 1 .. PRF12_LABEL_MAX = 20 bytes the seed is 65 .. 84 bytes and every message has a block count that no datum changes: the seed
+// two blocks of SHA-256 and one of SHA-384, A(j) one, A(j) | seed two (the static_asserts under "the three HMACs" compute them; a label bound that breaks one fails the
+// compile), plus one compression for the outer hash of each HMAC.  The label's LENGTH is a template argument: where the randoms fall in the blocks is known to the compiler, so
 // no lane indexes its message schedule by a length.  The label's bytes are made into words on the HOST (prf12_label: a Prf12Label, passed by value), the randoms are
-// shifted in behind them by constant amounts (prf12_seed), and the seed with its padding bit is 22 words in registers.  The compressions are aesgcm_kdf.h's, as they are.
+// shifted in behind them by constant amounts (prf12_seed), and the seed with its padding bit is 22 words in registers.  The compressions and the HMAC's pieces (kdf_hmac_pad, kdf_hmac_msg, kdf_hmac_outer) are aesgcm_kdf.h's, as they are.
 //
 // WHAT A LANE TAKES.  A lane wants some 32-bit words of the output stream (a key: words first .. first + NK - 1; an IV: one word; a salt: three).  The T(j) come in a
 // loop that is NOT unrolled; inside it prf12_pick copies the words of T(j) that fall into the lane's window by compares of the loop counter with constants -- selects,
@@ -60,131 +58,46 @@ template <int LL> HD void prf12_seed(const Prf12Label &m, const u32 *r, u32 *sw)
 }
 template <int LL> constexpr u32 prf12_seed_len() { return (u32)LL + 2u * PRF12_RANDOM_LEN; }
 
-// ---------------------------------------------------------------- the three HMACs of fixed shape, per hash
+// ---------------------------------------------------------------- the three HMACs of fixed shape
+// the block counts of THE SHAPE, from the hashes' own block and length-field sizes: no label of 1 .. PRF12_LABEL_MAX bytes changes one
+template <int HL> constexpr bool prf12_shapes_fixed() {
+    return kdf_blocks<HL>(1u + 2u * PRF12_RANDOM_LEN) == kdf_blocks<HL>(PRF12_LABEL_MAX + 2u * PRF12_RANDOM_LEN) && kdf_blocks<HL>(HL) == 1u &&
+           kdf_blocks<HL>(HL + 1u + 2u * PRF12_RANDOM_LEN) == 2u && kdf_blocks<HL>(HL + PRF12_LABEL_MAX + 2u * PRF12_RANDOM_LEN) == 2u;
+}
+static_assert(prf12_shapes_fixed<32>() && kdf_blocks<32>(PRF12_LABEL_MAX + 2u * PRF12_RANDOM_LEN) == 2u, "SHA-256: seed 2 blocks, A(j) 1, A(j) | seed 2");
+static_assert(prf12_shapes_fixed<48>() && kdf_blocks<48>(PRF12_LABEL_MAX + 2u * PRF12_RANDOM_LEN) == 1u, "SHA-384: seed 1 block, A(j) 1, A(j) | seed 2");
+static_assert(4u * PRF12_SEED_WORDS >= PRF12_LABEL_MAX + 2u * PRF12_RANDOM_LEN + 1u, "the longest seed and its 0x80");
+
 // the ipad and the opad state of the 48-byte secret (ms: twelve big-endian words)
-template <int HL> struct Prf12Key;
-template <> struct Prf12Key<32> { u32 in[8], out[8]; };
-template <> struct Prf12Key<48> { u64 in[8], out[8]; };
-
-HD void prf12_key(const u32 *ms, Prf12Key<32> &k) {
-    u32 w[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = (j < 12 ? ms[j] : 0u) ^ 0x36363636u;
-    kdf_sha256_init(k.in);
-    kdf_sha256_block(k.in, w);
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = (j < 12 ? ms[j] : 0u) ^ 0x5c5c5c5cu;
-    kdf_sha256_init(k.out);
-    kdf_sha256_block(k.out, w);
+template <int HL> struct Prf12Key { typename KdfHash<HL>::word in[8], out[8]; };
+template <int HL> HD void prf12_key(const u32 *ms, Prf12Key<HL> &k) {
+    kdf_hmac_pad<HL, (int)PRF12_MASTER_LEN / 4>(ms, KDF_IPAD, k.in);
+    kdf_hmac_pad<HL, (int)PRF12_MASTER_LEN / 4>(ms, KDF_OPAD, k.out);
 }
-HD void prf12_key(const u32 *ms, Prf12Key<48> &k) {
-    u64 w[16];
+// HMAC(secret, message): m = the message of len bytes with its KDF_PAD_BIT, NW big-endian words -> res, HL / 4 words
+template <int HL, int NW> HD void prf12_hmac(const Prf12Key<HL> &k, const u32 *m, u32 len, u32 *res) {
+    typename KdfHash<HL>::word st[8];
 #pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = (j < 6 ? ((u64)ms[2 * j] << 32) | ms[2 * j + 1] : 0ull) ^ 0x3636363636363636ull;
-    kdf_sha384_init(k.in);
-    kdf_sha512_block(k.in, w);
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = (j < 6 ? ((u64)ms[2 * j] << 32) | ms[2 * j + 1] : 0ull) ^ 0x5c5c5c5c5c5c5c5cull;
-    kdf_sha384_init(k.out);
-    kdf_sha512_block(k.out, w);
+    for (int j = 0; j < 8; j++) st[j] = k.in[j];
+    kdf_hmac_msg<HL, (int)kdf_blocks<HL>(4u * NW - 1u), NW>(st, m, len);                    // (4 NW - 1 bytes: the longest message whose 0x80 is in word NW - 1)
+    kdf_hmac_outer<HL>(k.out, st, res);
 }
-// the outer hash: st = the inner digest's state -> res, HL / 4 big-endian 32-bit words
-HD void prf12_outer(const Prf12Key<32> &k, const u32 *st, u32 *res) {
-    u32 o[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = k.out[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = j < 8 ? st[j] : 0u;
-    w[8] = 0x80000000u; w[15] = (64u + 32u) * 8u;
-    kdf_sha256_block(o, w);
-#pragma unroll
-    for (int j = 0; j < 8; j++) res[j] = o[j];
-}
-HD void prf12_outer(const Prf12Key<48> &k, const u64 *st, u32 *res) {
-    u64 o[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = k.out[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = j < 6 ? st[j] : 0ull;
-    w[6] = 0x8000000000000000ull; w[15] = (128u + 48u) * 8u;
-    kdf_sha512_block(o, w);
-#pragma unroll
-    for (int j = 0; j < 6; j++) { res[2 * j] = (u32)(o[j] >> 32); res[2 * j + 1] = (u32)o[j]; }
-}
-HD u64 prf12_pair(const u32 *w, int k) { return ((u64)w[2 * k] << 32) | w[2 * k + 1]; }
-
 // HMAC(secret, seed): sw from prf12_seed, SL = the seed's bytes
-HD void prf12_hmac_seed(const Prf12Key<32> &k, const u32 *sw, u32 SL, u32 *res) {
-    u32 st[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) st[j] = k.in[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = sw[j];
-    kdf_sha256_block(st, w);
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = 16 + j < PRF12_SEED_WORDS ? sw[16 + j] : 0u;
-    w[15] = (64u + SL) * 8u;
-    kdf_sha256_block(st, w);
-    prf12_outer(k, st, res);
-}
-HD void prf12_hmac_seed(const Prf12Key<48> &k, const u32 *sw, u32 SL, u32 *res) {
-    u64 st[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) st[j] = k.in[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = 2 * j < PRF12_SEED_WORDS ? prf12_pair(sw, j) : 0ull;
-    w[15] = (128u + SL) * 8u;
-    kdf_sha512_block(st, w);
-    prf12_outer(k, st, res);
-}
+template <int HL> HD void prf12_hmac_seed(const Prf12Key<HL> &k, const u32 *sw, u32 SL, u32 *res) { prf12_hmac<HL, PRF12_SEED_WORDS>(k, sw, SL, res); }
 // HMAC(secret, A): a = HL / 4 big-endian words
-HD void prf12_hmac_a(const Prf12Key<32> &k, const u32 *a, u32 *res) {
-    u32 st[8], w[16];
+template <int HL> HD void prf12_hmac_a(const Prf12Key<HL> &k, const u32 *a, u32 *res) {
+    u32 m[HL / 4 + 1];
 #pragma unroll
-    for (int j = 0; j < 8; j++) st[j] = k.in[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = j < 8 ? a[j] : 0u;
-    w[8] = 0x80000000u; w[15] = (64u + 32u) * 8u;
-    kdf_sha256_block(st, w);
-    prf12_outer(k, st, res);
-}
-HD void prf12_hmac_a(const Prf12Key<48> &k, const u32 *a, u32 *res) {
-    u64 st[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) st[j] = k.in[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = j < 6 ? prf12_pair(a, j) : 0ull;
-    w[6] = 0x8000000000000000ull; w[15] = (128u + 48u) * 8u;
-    kdf_sha512_block(st, w);
-    prf12_outer(k, st, res);
+    for (int j = 0; j < HL / 4; j++) m[j] = a[j];
+    m[HL / 4] = KDF_PAD_BIT;
+    prf12_hmac<HL, HL / 4 + 1>(k, m, (u32)HL, res);
 }
 // HMAC(secret, A | seed)
-HD void prf12_hmac_a_seed(const Prf12Key<32> &k, const u32 *a, const u32 *sw, u32 SL, u32 *res) {
-    u32 st[8], w[16];
+template <int HL> HD void prf12_hmac_a_seed(const Prf12Key<HL> &k, const u32 *a, const u32 *sw, u32 SL, u32 *res) {
+    u32 m[HL / 4 + PRF12_SEED_WORDS];
 #pragma unroll
-    for (int j = 0; j < 8; j++) st[j] = k.in[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = j < 8 ? a[j] : sw[j - 8];
-    kdf_sha256_block(st, w);
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = 8 + j < PRF12_SEED_WORDS ? sw[8 + j] : 0u;       // words 8 .. 21 of the seed: the 0x80 is in word 21 at the latest, w[14] stays 0
-    w[15] = (64u + 32u + SL) * 8u;
-    kdf_sha256_block(st, w);
-    prf12_outer(k, st, res);
-}
-HD void prf12_hmac_a_seed(const Prf12Key<48> &k, const u32 *a, const u32 *sw, u32 SL, u32 *res) {
-    u64 st[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) st[j] = k.in[j];
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = j < 6 ? prf12_pair(a, j) : prf12_pair(sw, j - 6);    // seed words 0 .. 19
-    kdf_sha512_block(st, w);
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = 0ull;
-    w[0] = prf12_pair(sw, 10);                                                                // seed words 20, 21 (zero where the seed ended in the first block)
-    w[15] = (128u + 48u + SL) * 8u;
-    kdf_sha512_block(st, w);
-    prf12_outer(k, st, res);
+    for (int j = 0; j < HL / 4 + PRF12_SEED_WORDS; j++) m[j] = j < HL / 4 ? a[j] : sw[j - HL / 4];
+    prf12_hmac<HL, HL / 4 + PRF12_SEED_WORDS>(k, m, (u32)HL + SL, res);
 }
 
 // ---------------------------------------------------------------- P_hash, and what a lane takes of it

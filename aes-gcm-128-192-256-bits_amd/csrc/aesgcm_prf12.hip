@@ -3,16 +3,12 @@
 // 128 bytes.  Host masters reach the records through the staging buffer (devtab_put), zeroed behind its use as aesgcm_kdf_set zeroes its secrets; the host's own copy
 // is wiped before the call returns (SecretWords); clear is devtab_clear; destroy wipes the records and the stage.  install and export are ONE launch each on the
 // caller's stream: they neither synchronise nor allocate nor record an event nor read anything back -- capture-safe (include/aesgcm.h, CAPTURE).  The key table is
-// reached through kt_view (aesgcm_keytab.h) and nothing else.
-// THIS FILE IS PART OF THE UNIT aesgcm_srtp_kdf: aesgcm_srtp_kdf.hip includes it at its end.  The exporter writes SRTP master records, so it needs that unit's table
-// struct, which no header shows; and a library made of the host units alone (tests/fake_hip links them against a fake runtime) gets these entry points with the unit
-// it already links.  Such a library has no kernels' object: the launchers below are the weak ones, and every call that would launch fails with AESGCM_EHIP.
+// reached through kt_view (aesgcm_keytab.h), the SRTP master table that the exporter fills through skdf_view (aesgcm_srtp_kdf.h), and nothing else.
+#include "aesgcm_internal.h"
+#include "aesgcm_keytab.h"
 #include "aesgcm_prf12.h"
 
-__attribute__((weak)) hipError_t klaunch_prf12_attributes() { return hipErrorNotSupported; }
-__attribute__((weak)) hipError_t klaunch_prf12_install(int, hipStream_t, const DevTables *, const Prf12InstallParams &) { return hipErrorNotSupported; }
-__attribute__((weak)) hipError_t klaunch_prf12_export(hipStream_t, const Prf12ExportParams &) { return hipErrorNotSupported; }
-__attribute__((weak)) hipError_t klaunch_prf12_set(hipStream_t, const Prf12SetParams &) { return hipErrorNotSupported; }
+#include <string.h>
 
 struct aesgcm_prf12 {
     DevTable base;                     // base.stage: host masters wait there for their copy into the records, zeroed behind it; base.stage_done: behind that zeroing
@@ -91,10 +87,11 @@ int aesgcm_prf12_export_srtp_dev(aesgcm_prf12 *k, aesgcm_srtp_kdf *masters, size
     if (!k || !masters) return AESGCM_EARG;
     if (!n) return AESGCM_OK;
     if (!d_idx || (!d_client_recs && !d_server_recs) || n >= ((size_t)1 << 31)) return AESGCM_EARG;
-    if (masters->base.device != k->base.device || masters->t.key_len == 24u) return AESGCM_EARG;      // DTLS-SRTP has AEAD_AES_128_GCM and AEAD_AES_256_GCM (RFC 7714 14.2)
+    const SkdfView mv = skdf_view(masters);
+    if (mv.device != k->base.device || mv.t.key_len == 24u) return AESGCM_EARG;      // DTLS-SRTP has AEAD_AES_128_GCM and AEAD_AES_256_GCM (RFC 7714 14.2)
     Prf12ExportParams p;
     memset(&p, 0, sizeof p);
-    p.t = k->t; p.idx = d_idx; p.recs[PRF12_CLIENT] = d_client_recs; p.recs[PRF12_SERVER] = d_server_recs; p.m = masters->t; p.n = (u32)n;
+    p.t = k->t; p.idx = d_idx; p.recs[PRF12_CLIENT] = d_client_recs; p.recs[PRF12_SERVER] = d_server_recs; p.m = mv.t; p.n = (u32)n;
     prf12_label(PRF12_EXPORTER, PRF12_LL_EXPORTER, p.label);
     HIPCHK(hipSetDevice(k->base.device));
     HIPCHK(klaunch_prf12_export((hipStream_t)stream, p));

@@ -27,6 +27,10 @@ struct SkdfTable {
     u32 *status;                           // lowest refused entry (atomic min, kdf_refuse), ~0 = none
     u32 n_masters, key_len;
 };
+// a table's records for the units that fill them without going through aesgcm_srtp_kdf_set* (aesgcm_prf12.hip: the DTLS-SRTP exporter); defined in aesgcm_srtp_kdf.hip
+struct aesgcm_srtp_kdf;
+struct SkdfView { SkdfTable t; int device; };
+SkdfView skdf_view(const aesgcm_srtp_kdf *k);
 struct KtSlot;
 struct SkdfInstallParams {
     SkdfTable t;

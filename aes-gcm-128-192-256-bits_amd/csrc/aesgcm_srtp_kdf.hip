@@ -15,6 +15,8 @@ struct aesgcm_srtp_kdf {
     SkdfTable t = {};                  // t.status == base.status: the kernels' copy of the pointer
 };
 
+SkdfView skdf_view(const aesgcm_srtp_kdf *k) { return SkdfView{k->t, k->base.device}; }
+
 int aesgcm_srtp_kdf_create(aesgcm_srtp_kdf **out, int device, size_t key_len, size_t n_masters) {
     if (!out) return AESGCM_EARG;
     *out = nullptr;
@@ -90,6 +92,3 @@ int aesgcm_srtp_kdf_destroy(aesgcm_srtp_kdf *k) {
     delete k;
     return rc;
 }
-
-// the TLS 1.2 PRF's host side (aesgcm_prf12_*): its exporter fills this unit's master records, so it is compiled here, behind the struct it needs
-#include "aesgcm_prf12.hip"

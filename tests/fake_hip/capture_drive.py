@@ -1,4 +1,4 @@
-"""Drives the calls that include/aesgcm.h names capture-safe (CAPTURE: key tables, receive windows, send counters' assign, the key derivations' install and update;
+"""Drives the calls that include/aesgcm.h names capture-safe (CAPTURE: key tables, receive windows, send counters' assign, the key derivations' install and update, the TLS 1.2 PRF's install and export;
 the five-array batch calls plan their launch as a key table's) through the fake HIP runtime (fakehip.cpp) twice each: an ordinary warm-up call, then the same call while the caller's stream captures.  Asserted per call:
   * nothing a capture cannot carry was done while the stream captured -- no hipMalloc or hipFree, no synchronous copy or memset, no host synchronisation, and no
     stream outside the capture waits on an event the capture recorded (fake_capture_violations: each entry names the HIP call);
@@ -78,7 +78,7 @@ def in_array_order(log):
     return out
 
 
-def calls(kt, rw, tx, sec, mk, n, key_len):
+def calls(kt, rw, tx, sec, mk, ms, n, key_len):
     """every device call of the families, by name; all on the caller's stream"""
     W, X, T, D, S, R = lib.WireFormat, lib.WireFormatX, lib.TlsFormat, lib.DtlsFormat, lib.SrtpFormat, lib.RxFormat
     c = {}
@@ -106,6 +106,8 @@ def calls(kt, rw, tx, sec, mk, n, key_len):
     c["kdf install", 0] = lambda: sec.install_dev(lib.KdfFormat.quic_v1(), kt, n, d_slots, d_hp, d_pn_off, stream=caller)
     c["kdf update", 0] = lambda: sec.update_dev(lib.KdfFormat.tls13(), n, d_slots, d_hp, stream=caller)
     c["srtp_kdf install", 0] = lambda: mk.install_dev(lib.SRTP_RTP, kt, n, d_slots, d_hp, d_num, stream=caller)
+    c["prf12 install", 0] = lambda: ms.install_dev(kt, n, d_slots, d_hp, d_pn_off, stream=caller)
+    c["prf12 export_srtp", 0] = lambda: ms.export_srtp_dev(mk, n, d_slots, d_hp, d_pn_off, stream=caller)
 
     def loop():                                                         # the receive loop of INTEGRATION.md: four stream-ordered steps
         rw.recover_dev(R.esp_esn(), n, d_slots, d_in, d_off, d_num, d_hi, stream=caller)
@@ -117,11 +119,12 @@ def calls(kt, rw, tx, sec, mk, n, key_len):
 
 
 def drive(n, key_len, want_ordered, label):
-    with lib.KeyTable(key_len, 16) as kt, lib.RxWindows(4, 64) as rw, lib.TxCounters(4, n) as tx, lib.SecretTable(32, 4) as sec, lib.MasterKeyTable(key_len, 4) as mk:
+    with lib.KeyTable(key_len, 16) as kt, lib.RxWindows(4, 64) as rw, lib.TxCounters(4, n) as tx, lib.SecretTable(32, 4) as sec, lib.MasterKeyTable(key_len, 4) as mk, \
+            lib.MasterSecretTable(48, 4) as ms:
         kt.set(0, bytes(key_len * 16))
         F.fake_capture_clear()
         ordered_seen = 0
-        for (name, dec), call in calls(kt, rw, tx, sec, mk, n, key_len).items():
+        for (name, dec), call in calls(kt, rw, tx, sec, mk, ms, n, key_len).items():
             what = "%s, %s %s n=%d AES-%d" % (label, name, "dec" if dec else "enc", n, 8 * key_len)
             warm, _ = logged(call)
             assert warm and not violations(), (what, "the warm-up call", warm, violations())
@@ -150,7 +153,7 @@ def selftest():
         b = ctypes.create_string_buffer(1 << 16)
         F.fake_capture_violations(b, len(b))
         return [v.split()[0] for v in b.value.decode().splitlines()]
-    with lib.KeyTable(16, 4) as kt, lib.RxWindows(2, 64) as rw:
+    with lib.KeyTable(16, 4) as kt, lib.RxWindows(2, 64) as rw, lib.MasterSecretTable(32, 4) as ms:
         kt.set(0, bytes(64))
         clean = lambda: kt.frames_crypt_dev(0, lib.WireFormat.macsec(), 300, d_slots, d_in, d_off, d_out, stream=caller)
         assert listed(clean) == [] and listed(clean, capture=False) == []
@@ -168,6 +171,10 @@ def selftest():
         assert listed(lambda: kt.set(1, bytes(16), stream=caller)) == []
         assert listed(lambda: kt.set(2, bytes(16)), capture=False) == ["hipStreamWaitEvent"]
         assert listed(lambda: kt.set(3, bytes(16)), capture=False) == []                  # (that setter recorded it again, outside)
+        ms.set(0, bytes(48), bytes(32), bytes(32))                                        # (the stage and its event are made: an ordinary call before a capture)
+        assert listed(lambda: ms.set(1, bytes(48), bytes(32), bytes(32), stream=caller)) == []
+        assert listed(lambda: ms.set(2, bytes(48), bytes(32), bytes(32)), capture=False) == ["hipStreamWaitEvent"]
+        assert listed(lambda: ms.set(3, bytes(48), bytes(32), bytes(32)), capture=False) == []
     F.fake_capture_clear()
     print("FAKE CAPTURE SELFTEST OK")
 

@@ -26,7 +26,7 @@
 //     any stream captures, what a capture cannot carry is noted with the HIP call's name in a list of its own (fake_capture_violations, fake_capture_clear; fake_reset
 //     leaves it alone): hipMalloc, hipFree, a synchronous copy or memset, hipStreamSynchronize, hipDeviceSynchronize, hipEventSynchronize, hipEventQuery.  An event
 //     remembers whether its last record was inside a capture; a hipStreamWaitEvent on such an event from a stream that is not capturing is noted too, also after the
-//     capture has ended.  The five device tables' host sides (csrc/aesgcm_keytab.hip, _rxwin, _txnum, _kdf, _srtp_kdf) are linked in for this, with launchers that note a
+//     capture has ended.  The six device tables' host sides (csrc/aesgcm_keytab.hip, _rxwin, _txnum, _kdf, _srtp_kdf, _prf12) are linked in for this, with launchers that note a
 //     log line as the others do (tests/fake_hip/capture_drive.py).
 //   * THE CALL LIST: after fake_log_runtime(1), every runtime call and launch by name with its byte count (fake_calls): what one call into the library costs
 //     (tests/fake_hip/table_drive.py, tests/golden/table_calls.txt).
@@ -48,7 +48,7 @@
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_keytab.h"
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_rxwin.h"
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_txnum.h"
-#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_srtp_kdf.h"
+#include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_prf12.h"
 #include <rccl/rccl.h>
 
 #define FAKE_DEVICES 4
@@ -604,7 +604,7 @@ hipError_t klaunch_rxwin_commit(hipStream_t st, const RxCommitParams &p) {
     return hipSuccess;
 }
 
-// ---------------------------------------------------------------- send counters and the two key derivations (csrc/aesgcm_txnum.h, aesgcm_kdf.h, aesgcm_srtp_kdf.h)
+// ---------------------------------------------------------------- send counters and the three key derivations (csrc/aesgcm_txnum.h, aesgcm_kdf.h, aesgcm_srtp_kdf.h, aesgcm_prf12.h)
 static std::string tx_txt(const TxTable &t) {
     char b[128];
     snprintf(b, sizeof b, "t=%s ctrs=%u max=%u passes=%u", bits(t.rec, t.status, t.counts, t.idx[0], t.idx[1]).c_str(), t.n_ctrs, t.max_pkts, t.passes);
@@ -616,13 +616,13 @@ hipError_t klaunch_txnum_assign(hipStream_t st, const TxAssignParams &p) {
          bits(p.ctr, p.pkts, p.pkt_off, p.num_out, p.hi_out, p.slots, p.sorted).c_str(), p.n_pkts);
     return hipSuccess;
 }
-// The records of the two derivation tables are 64 bytes and no ABI call reads them back: an install notes the 64-bit FNV-1a of the record its first entry names (the
-// fake's device memory is host memory), which is how a driver sees what a set stored.  0: no entry, or one outside the table.
-static unsigned long long rec_hash(const u32 *rec, const u32 *idx, u32 n, u32 n_recs) {
+// The records of the derivation tables are 64 bytes (the TLS 1.2 PRF's: 128) and no ABI call reads them back: an install notes the 64-bit FNV-1a of the record its first
+// entry names (the fake's device memory is host memory), which is how a driver sees what a set stored.  0: no entry, or one outside the table.
+static unsigned long long rec_hash(const u32 *rec, const u32 *idx, u32 n, u32 n_recs, u32 rec_words = KDF_REC_WORDS) {
     if (!rec || !idx || !n || idx[0] >= n_recs) return 0;
-    const unsigned char *q = (const unsigned char *)(rec + (size_t)idx[0] * KDF_REC_WORDS);
+    const unsigned char *q = (const unsigned char *)(rec + (size_t)idx[0] * rec_words);
     unsigned long long h = 0xcbf29ce484222325ull;
-    for (size_t i = 0; i < KDF_REC_WORDS * sizeof(u32); i++) h = (h ^ q[i]) * 0x100000001b3ull;
+    for (size_t i = 0; i < rec_words * sizeof(u32); i++) h = (h ^ q[i]) * 0x100000001b3ull;
     return h;
 }
 static std::string kdf_txt(const KdfTable &t) {
@@ -662,6 +662,29 @@ hipError_t klaunch_srtp_kdf_install(int nr, hipStream_t st, const DevTables *tb,
     LAUNCH("k_srtp_kdf_install", st); P(tb); P(p.t.rec); P(p.t.status); P(p.idx); P(p.slots); P(p.r); P(p.tab);
     note("%s %s nr=%d %s p=%s n=%u slots=%u label=%u/%u rec=%016llx", W, sname(st), nr, skdf_txt(p.t).c_str(), bits(tb, p.idx, p.slots, p.r, p.tab).c_str(), p.n, p.n_slots,
          p.label[0], p.label[1], rec_hash(p.t.rec, p.idx, p.n, p.t.n_masters));
+    return hipSuccess;
+}
+static std::string prf12_txt(const Prf12Table &t) {
+    char b[96];
+    snprintf(b, sizeof b, "t=%s masters=%u hash=%u", bits(t.rec, t.status).c_str(), t.n_masters, t.hash_len);
+    return b;
+}
+hipError_t klaunch_prf12_attributes() { std::lock_guard<std::mutex> lk(mu); touch(); note("k_prf12_attributes dev=%d", cur + 1); return hipSuccess; }
+hipError_t klaunch_prf12_set(hipStream_t st, const Prf12SetParams &p) {
+    LAUNCH("k_prf12_set", st); P(p.t.rec); P(p.t.status); P(p.idx); P(p.masters); P(p.client_randoms); P(p.server_randoms);
+    note("%s %s %s p=%s n=%u", W, sname(st), prf12_txt(p.t).c_str(), bits(p.idx, p.masters, p.client_randoms, p.server_randoms).c_str(), p.n);
+    return hipSuccess;
+}
+hipError_t klaunch_prf12_install(int nr, hipStream_t st, const DevTables *tb, const Prf12InstallParams &p) {
+    LAUNCH("k_prf12_install", st); P(tb); P(p.t.rec); P(p.t.status); P(p.idx); P(p.slots[PRF12_CLIENT]); P(p.slots[PRF12_SERVER]); P(p.tab);
+    note("%s %s nr=%d %s p=%s n=%u slots=%u rec=%016llx", W, sname(st), nr, prf12_txt(p.t).c_str(), bits(tb, p.idx, p.slots[PRF12_CLIENT], p.slots[PRF12_SERVER], p.tab).c_str(), p.n,
+         p.n_slots, rec_hash(p.t.rec, p.idx, p.n, p.t.n_masters, PRF12_REC_WORDS));
+    return hipSuccess;
+}
+hipError_t klaunch_prf12_export(hipStream_t st, const Prf12ExportParams &p) {
+    LAUNCH("k_prf12_export", st); P(p.t.rec); P(p.t.status); P(p.idx); P(p.recs[PRF12_CLIENT]); P(p.recs[PRF12_SERVER]); P(p.m.rec); P(p.m.status);
+    note("%s %s %s p=%s n=%u m=[%s] rec=%016llx", W, sname(st), prf12_txt(p.t).c_str(), bits(p.idx, p.recs[PRF12_CLIENT], p.recs[PRF12_SERVER]).c_str(), p.n, skdf_txt(p.m).c_str(),
+         rec_hash(p.t.rec, p.idx, p.n, p.t.n_masters, PRF12_REC_WORDS));
     return hipSuccess;
 }
 

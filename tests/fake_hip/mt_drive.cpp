@@ -5,7 +5,7 @@
 // fake HIP runtime of this directory (fakehip.cpp: no GPU, launches launch nothing) and driven through the C ABI by eight threads over four fake devices, every
 // thread for itself: create, messages queued with tag = NULL and collected with aesgcm_last_tag, packets (fixed-size records by rows and through the packet kernels,
 // offset arrays: the routed call with its fork to the side stream), messages wherever they live, a streaming session exported and imported into a second context,
-// rekey, status, destroy; one thread more drives the four-device object; and the two threads of each device set their halves of the device's five shared tables -- key table,
+// rekey, status, destroy; one thread more drives the four-device object, another a TLS 1.2 master-secret table of its own (csrc/aesgcm_prf12.hip: prf12_worker); and the two threads of each device set their halves of the device's five shared tables -- key table,
 // receive windows, send counters, traffic secrets, SRTP master keys (csrc/aesgcm_keytab.hip, _rxwin, _txnum, _kdf, _srtp_kdf: table_sets below).  asan.mk / tsan.mk build it; tests/test_fake_hip.py runs both.  The fake records device
 // discipline as always: its violation count must be zero at the end.
 #include <pthread.h>
@@ -143,6 +143,34 @@ static void *worker(void *arg) {
     return nullptr;
 }
 
+// The sixth table, on its own: a thread makes an aesgcm_prf12 and a key table on device 3, sets master secrets on a stream of its own in pieces that make the stage
+// grow, installs them (the launcher launches nothing: the call's checks, device_state and the table's pointers under the sanitizers) and clears every other time,
+// while the two threads of that device work the shared tables
+static void *prf12_worker(void *arg) {
+    const int t = (int)(intptr_t)arg, dev = 3;
+    unsigned char key[16] = {7};
+    aesgcm_ctx *c = nullptr;
+    aesgcm_prf12 *ms = nullptr;
+    aesgcm_keytab *kt = nullptr;
+    void *st = nullptr, *d_idx = nullptr;
+    CHECK(aesgcm_ctx_create(&c, dev, key, 16)); CHECK(aesgcm_ctx_stream(c, &st));
+    CHECK(aesgcm_prf12_create(&ms, dev, 48, TAB_PER)); CHECK(aesgcm_keytab_create(&kt, dev, 32, 2 * TAB_PER));
+    CHECK(aesgcm_dev_alloc(dev, &d_idx, 4 * TAB_PER));
+    std::vector<unsigned char> bytes(48 * TAB_PER, (unsigned char)t);
+    for (int r = 0; r < g_rounds; r++)
+        for (int i = 0; i < 20; i++) {
+            const size_t n = i == 19 ? TAB_PER : 1 + (size_t)(i * 7 + r) % TAB_PER, first = (size_t)(i * 5) % (TAB_PER - n + 1);
+            CHECK(aesgcm_prf12_set(ms, first, n, bytes.data(), bytes.data(), bytes.data(), st));
+            CHECK(aesgcm_prf12_install_dev(ms, kt, n, (const uint32_t *)d_idx, (const uint32_t *)d_idx, (i & 2) ? (const uint32_t *)d_idx : nullptr, st));
+            if (i & 1) CHECK(aesgcm_prf12_clear(ms, first, n, st));
+            int code = -1; uint64_t detail = 0;
+            CHECK(aesgcm_prf12_status(ms, &code, &detail)); CHECK(code);
+        }
+    CHECK(aesgcm_dev_free(dev, d_idx));
+    CHECK(aesgcm_prf12_destroy(ms)); CHECK(aesgcm_keytab_destroy(kt)); CHECK(aesgcm_ctx_destroy(c));
+    return nullptr;
+}
+
 static void *mgpu_worker(void *arg) {
     const int t = (int)(intptr_t)arg;
     unsigned char key[32] = {9}, iv[12] = {0}, tags[16 * 8];
@@ -166,15 +194,16 @@ static void *mgpu_worker(void *arg) {
 int main(int argc, char **argv) {
     if (argc > 1) g_rounds = atoi(argv[1]);
     const int T = 8;
-    pthread_t th[T + 1];
+    pthread_t th[T + 2];
     tables_create();
     for (int t = 0; t < T; t++) pthread_create(&th[t], nullptr, worker, (void *)(intptr_t)t);
     pthread_create(&th[T], nullptr, mgpu_worker, (void *)(intptr_t)T);
-    for (int t = 0; t <= T; t++) pthread_join(th[t], nullptr);
+    pthread_create(&th[T + 1], nullptr, prf12_worker, (void *)(intptr_t)(T + 1));
+    for (int t = 0; t <= T + 1; t++) pthread_join(th[t], nullptr);
     tables_compare_and_destroy();
     static char buf[1 << 16];
     const int bad = fake_violations(buf, sizeof buf);
     if (bad) { fprintf(stderr, "%d violations of device discipline\n%s", bad, buf); return 1; }
-    printf("MT DRIVE OK (%d threads x %d rounds over 4 fake devices)\n", T + 1, g_rounds);
+    printf("MT DRIVE OK (%d threads x %d rounds over 4 fake devices)\n", T + 2, g_rounds);
     return 0;
 }

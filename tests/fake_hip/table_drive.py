@@ -1,5 +1,5 @@
-"""Drives the five device tables -- a key table (16 slots, AES-256), receive windows (16 windows of 64 bits, 16 of 4096), send counters (16, calls of 64 packets), traffic
-secrets (16 of SHA-256, 16 of SHA-384) and SRTP master keys (16 each of AES-128, -192, -256) -- through the fake HIP runtime (fakehip.cpp) for what their host sides
+"""Drives the six device tables -- a key table (16 slots, AES-256), receive windows (16 windows of 64 bits, 16 of 4096), send counters (16, calls of 64 packets), traffic
+secrets (16 of SHA-256, 16 of SHA-384), SRTP master keys (16 each of AES-128, -192, -256) and TLS 1.2 master secrets (16 of SHA-256, 16 of SHA-384) -- through the fake HIP runtime (fakehip.cpp) for what their host sides
 share: create, the staged set that every host-to-table setter is, get, clear, status, the range check, destroy.  EVERYTHING below was recorded from the parent commit
 of the one that folded set, get and clear onto the base (DevTable, csrc/aesgcm_internal.h: devtab_staged, devtab_put, devtab_get, devtab_clear): the literals --
 allocation counts, synchronisation counts, record hashes, the ordering bits -- and tests/golden/table_calls.txt; this driver passed on that commit's five host units,
@@ -21,6 +21,11 @@ unchanged, with one difference, the last point.  Per table and setter, on a tabl
     and the next set on another stream succeeds and IS ordered behind the failed one's copies and zeroing.  THE ONE DELIBERATE CHANGE: the parent commit returned
     from a failed set before it recorded the stage's event, so the bit was 0 there in all three cases (this driver recorded it "as it is, not as it should be");
     devtab_staged records the event on every path once the stage is there.
+THE SIXTH TABLE (MasterSecretTable, csrc/aesgcm_prf12.hip) came later and its literals were recorded the same way: on the host code of the commit before the one that
+made aesgcm_prf12 a unit of its own, with nothing but the fake's klaunch_prf12_* added.  Its record hashes (128-byte records: an install_dev's and an
+export_srtp_dev's launch line) are also the FNV-1a of the record as include/aesgcm.h lays it out; beyond the points above it has every AESGCM_EARG of the two device
+calls (no direction array, a key table or master-key table on another device, a master-key table of AES-192), none of which launches; a set that fails at its second
+copy; and, since the host's set launches nothing, the failed launch of set_dev.
 No device discipline violation anywhere.  Without AESGCM_LIB it runs itself on libaesgcm_fake.so.
 
     make -C tests/fake_hip -s libaesgcm_fake.so && python tests/fake_hip/table_drive.py"""
@@ -52,7 +57,7 @@ OK, EARG, EHIP = lib.OK, lib.EARG, lib.EHIP
 N = 16                                                                  # slots, windows, counters, secrets, masters
 
 # every stream of the run, made before the first table: a context's allocations would otherwise stand between a table's create and its destroy
-_ctxs = [lib.Context(bytes(32)) for _ in range(64)]
+_ctxs = [lib.Context(bytes(32)) for _ in range(80)]
 _streams = [c.stream() for c in _ctxs]
 assert len(set(_streams)) == len(_streams)
 
@@ -228,12 +233,12 @@ destroyed(what, tx, live, 1)
 d_idx, d_slots = lib.DeviceBuffer(16), lib.DeviceBuffer(16)
 
 
-def installed_record(install, i):
-    """the record hash in the launch log's line of one install with idx = [i]"""
+def installed_record(install, i, kernel="_install "):
+    """the record hash in the launch log's line of one install (or export) with idx = [i]"""
     d_idx.upload(struct.pack("<I", i))
     F.fake_reset()
     install()
-    line, = [ln for ln in text(F.fake_log) if "_install " in ln]
+    line, = [ln for ln in text(F.fake_log) if kernel in ln]
     return line.split(" rec=")[1]
 
 
@@ -280,6 +285,44 @@ for kl in (16, 24, 32):
     range_check(what + ".set", N, mk_set)
     range_check(what + ".clear", N, lambda first, n: mk.clear(first, n))
     destroyed(what, mk, live, 2)
+
+# ---------------------------------------------------------------- TLS 1.2 master secrets: set, and what an install and an export find in the record
+Z128 = "8421ae126c7ced25"                                                            # 128 zero bytes: entry 12 was never set
+lib.KeyTable(16, 1, device=1).close()                                   # (device 1's own state is made on first use: not an allocation of the tables below)
+PRF12_RECORDS = {0: "4266d1521611c19d", 10: "dfca7ff05712211d", 11: "5a4dd056cd27682d", 12: Z128}            # a record is the 48-byte master and the two randoms, whatever the hash
+for hl in (32, 48):
+    what = "MasterSecretTable(hash_len=%d)" % hl
+    live = F.fake_live_allocations()
+    ms = lib.MasterSecretTable(hl, N)
+    assert F.fake_live_allocations() == live + 2 and ms.status() == (OK, 0), what       # the records and the status word
+
+    def ms_set(first, n, st=None, ms=ms):
+        r = range(first, first + n)
+        ms.set(first, b"".join(bytes([k + 1]) * 48 for k in r), b"".join(bytes([0x40 + k]) * 32 for k in r), b"".join(bytes([0x80 + k]) * 32 for k in r), stream=st)
+    three_sets(what, ms, ms_set)
+    other = lib.MasterSecretTable(hl, N)
+    record_calls(what, other, lambda first, n, st: ms_set(first, n, st, other))
+    with lib.KeyTable(16, N) as kt, lib.MasterKeyTable(16, N) as mk, lib.KeyTable(16, N, device=1) as kt1, lib.MasterKeyTable(16, N, device=1) as mk1, lib.MasterKeyTable(24, N) as mk24:
+        got = {i: installed_record(lambda: ms.install_dev(kt, 1, d_idx.ptr, d_slots.ptr, None), i) for i in PRF12_RECORDS}
+        assert got == PRF12_RECORDS, (what, "install_dev", got)
+        got = {i: installed_record(lambda: ms.export_srtp_dev(mk, 1, d_idx.ptr, None, d_slots.ptr), i, "k_prf12_export ") for i in PRF12_RECORDS}
+        assert got == PRF12_RECORDS, (what, "export_srtp_dev", got)
+        # every AESGCM_EARG of the two device calls: no direction array, a table on another device, a master table of AES-192; none of them launches
+        F.fake_reset()
+        assert rc(lambda: ms.install_dev(kt, 1, d_idx.ptr, None, None)) == EARG and rc(lambda: ms.export_srtp_dev(mk, 1, d_idx.ptr, None, None)) == EARG, what
+        assert rc(lambda: ms.install_dev(kt1, 1, d_idx.ptr, d_slots.ptr, d_slots.ptr)) == EARG and rc(lambda: ms.export_srtp_dev(mk1, 1, d_idx.ptr, d_slots.ptr, d_slots.ptr)) == EARG, what
+        assert rc(lambda: ms.export_srtp_dev(mk24, 1, d_idx.ptr, d_slots.ptr, d_slots.ptr)) == EARG, what
+        assert rc(lambda: ms.install_dev(kt, 0, None, None, None)) == OK and rc(lambda: ms.export_srtp_dev(mk, 0, None, None, None)) == OK, (what, "n == 0")
+        assert text(F.fake_log) == [] and ms.status() == (OK, 0) and violations() == [], (what, text(F.fake_log), violations())
+    failed_set(what, ms, ms_set, F.fake_fail_copy, 1)                                   # the copy into the stage
+    failed_set(what, ms, ms_set, lambda k: F.fake_fail_copy(k + 1), 1)                  # the copy out of it
+    # the host's set launches nothing; the set that does is set_dev, and its failed launch is EHIP, the first error, with the next set as ever
+    F.fake_reset()
+    F.fake_fail_launch(1)
+    assert rc(lambda: ms.set_dev(1, d_idx.ptr, d_slots.ptr, d_slots.ptr, d_slots.ptr)) == EHIP and rc(lambda: ms_set(2, 1)) == OK and ms.status() == (OK, 0), what
+    range_check(what + ".set", N, ms_set)
+    range_check(what + ".clear", N, lambda first, n: ms.clear(first, n))
+    destroyed(what, ms, live, 2)
 
 assert violations() == []
 golden = os.path.join(os.path.dirname(HERE), "golden", "table_calls.txt")

@@ -4,23 +4,12 @@
 //   H hl hex | H hl -                the hash (hl 32: SHA-256, 48: SHA-384) of a message that fits ONE block (at most 55 / 111 bytes)   -> "h hex"
 //   X hl secret label L              HKDF-Expand-Label(secret, full label, "", L): secret hl bytes, label 1 .. 20 bytes, both in hex      -> "x hex" (L bytes)
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_kdf.h"
+#include "../emul_hex.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
-
-static std::vector<unsigned char> unhex(const char *s) {
-    std::vector<unsigned char> v;
-    if (s[0] == '-') return v;
-    for (size_t k = 0; s[2 * k] && s[2 * k + 1]; k++) { unsigned b; sscanf(s + 2 * k, "%2x", &b); v.push_back((unsigned char)b); }
-    return v;
-}
-static void put_words(const char *tag, const u32 *w, size_t bytes) {
-    printf("%s ", tag);
-    for (size_t k = 0; k < bytes; k++) printf("%02x", (w[k / 4] >> (24 - 8 * (k % 4))) & 0xFFu);
-    printf("\n");
-}
 
 int main() {
     static char line[4096], a[2048], b[2048];
@@ -51,17 +40,17 @@ int main() {
                 kdf_sha512_block(st, w);
                 for (int k = 0; k < 6; k++) { out[2 * k] = (u32)(st[k] >> 32); out[2 * k + 1] = (u32)st[k]; }
             }
-            put_words("h", out, hl);
+            printf("h "); put_be(out, hl); printf("\n");
         } else if (line[0] == 'X') {
             need(sscanf(line + 1, "%u %2047s %2047s %u", &hl, a, b, &L) == 4 && (hl == 32 || hl == 48));
             const std::vector<unsigned char> sec = unhex(a), lab = unhex(b);
             need(sec.size() == hl && !lab.empty() && lab.size() <= KDF_LABEL_MAX && L && L <= hl);
             u32 s[12], out[12];
-            for (unsigned k = 0; k < hl / 4; k++) s[k] = ((u32)sec[4 * k] << 24) | ((u32)sec[4 * k + 1] << 16) | ((u32)sec[4 * k + 2] << 8) | sec[4 * k + 3];
+            be_words(sec, s);
             KdfMsg m;
             kdf_msg(lab.data(), (u32)lab.size(), L, m);
             if (hl == 32) kdf_expand<32>(s, m, out); else kdf_expand<48>(s, m, out);
-            put_words("x", out, L);
+            printf("x "); put_be(out, L); printf("\n");
         } else need(line[0] == '#' || line[0] == '\n');
     }
     return 0;

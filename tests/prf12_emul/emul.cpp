@@ -12,21 +12,11 @@
 //                                      aesgcm_srtp_kdf's own store packs the same key and salt | 00 00 (compared here)            -> "e crecord srecord" | "e refused"
 //   S                                  the status word, read and cleared                                                            -> "s index" | "s none"
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_prf12.h"
+#include "../emul_hex.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-
-static std::vector<unsigned char> unhex(const char *s) {
-    std::vector<unsigned char> v;
-    for (size_t k = 0; s[2 * k] && s[2 * k + 1]; k++) { unsigned b; sscanf(s + 2 * k, "%2x", &b); v.push_back((unsigned char)b); }
-    return v;
-}
-static void put_be(const u32 *w, size_t bytes) { for (size_t k = 0; k < bytes; k++) printf("%02x", (w[k / 4] >> (24 - 8 * (k % 4))) & 0xFFu); }
-static void put_mo(const u32 *w, size_t bytes) { for (size_t k = 0; k < bytes; k++) printf("%02x", (w[k / 4] >> (8 * (k % 4))) & 0xFFu); }
-static void be_words(const std::vector<unsigned char> &b, u32 *w) {
-    for (size_t k = 0; k < b.size() / 4; k++) w[k] = ((u32)b[4 * k] << 24) | ((u32)b[4 * k + 1] << 16) | ((u32)b[4 * k + 2] << 8) | b[4 * k + 3];
-}
 
 // P_hash with the label's length as the template argument the lane code wants.  The lengths compiled here: the two edges of the bound, 1 and 20, and the two labels
 // the library uses, 13 and 19 (each instance unrolls every compression: twenty of them per hash would take the compiler many minutes)

@@ -9,6 +9,7 @@
 //   I kind n_slots i idx slot r|-     entry i of an install call (r = '-': the call has no d_r), both roles                        -> "i key salt12" | "i refused"
 //   S                                 the status word, read and cleared                                                            -> "s index" | "s none"
 #include "../../aes-gcm-128-192-256-bits_amd/csrc/aesgcm_srtp_kdf.h"
+#include "../emul_hex.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,15 +17,6 @@
 
 static DevTables g_tb;
 static unsigned char g_smem[AESGCM_LDS_AES_OFF + AESGCM_LDS_AES] __attribute__((aligned(16)));
-
-static std::vector<unsigned char> unhex(const char *s) {
-    std::vector<unsigned char> v;
-    for (size_t k = 0; s[2 * k] && s[2 * k + 1]; k++) { unsigned b; sscanf(s + 2 * k, "%2x", &b); v.push_back((unsigned char)b); }
-    return v;
-}
-static void put_mo(const u32 *w, size_t bytes) {                     // memory-order words: byte k is bits 8 (k % 4) .. of word k / 4
-    for (size_t k = 0; k < bytes; k++) printf("%02x", (w[k / 4] >> (8 * (k % 4))) & 0xFFu);
-}
 
 // what both lanes of entry i do, short of the slot's fields: the verdict (role 0 reports), then each role's derivation
 template <int NR> static void install_entry(const SkdfInstallParams &p, u32 i) {

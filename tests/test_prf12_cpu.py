@@ -7,6 +7,7 @@ with scratch, with the register counts DESIGN.md records."""
 import ctypes
 import os
 import random
+import re
 import subprocess
 
 import pytest
@@ -242,8 +243,9 @@ def test_prf12_source_is_a_unit_of_its_own():
         assert "k_prf12_" not in open(os.path.join(CSRC, f)).read(), f
     assert '#include "aesgcm_prf12_kernels.hip"' in open(os.path.join(CSRC, "aesgcm_device.hip")).read()
     mk = open(os.path.join(CSRC, "Makefile")).read().splitlines()
-    assert "prf12" in [w for ln in mk if ln.startswith("FAMILIES") for w in ln.split()]
-    assert '#include "aesgcm_prf12.hip"' in open(os.path.join(CSRC, "aesgcm_srtp_kdf.hip")).read()      # the host side: part of the unit whose records the exporter fills
+    assert "prf12" in [w for ln in mk if ln.startswith("FAMILIES") for w in ln.split()] and "aesgcm_prf12" in [w for ln in mk if ln.startswith("UNITS") for w in ln.split()]
+    for f in os.listdir(CSRC):                                                # the host side: compiled once, as that unit, and included nowhere
+        assert not f.endswith(".hip") or not re.search(r'#\s*include\s*"aesgcm_prf12\.hip"', open(os.path.join(CSRC, f)).read()), f
     for f in ("aesgcm_prf12.h", "aesgcm_prf12_kernels.hip"):
         code = "\n".join(ln.split("//")[0] for ln in open(os.path.join(CSRC, f)).read().splitlines())
         assert "atomic" not in code, f                                        # the only atomic is kdf_refuse's, in aesgcm_kdf.h
