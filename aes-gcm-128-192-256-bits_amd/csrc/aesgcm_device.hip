@@ -14,3 +14,4 @@
 #include "aesgcm_kdf_kernels.hip"
 #include "aesgcm_srtp_kdf_kernels.hip"
 #include "aesgcm_prf12_kernels.hip"
+#include "aesgcm_prfplus_kernels.hip"

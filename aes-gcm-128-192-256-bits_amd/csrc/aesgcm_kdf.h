@@ -135,9 +135,13 @@ HD void kdf_sha384_init(u64 *st) {
     st[0] = 0xcbbb9d5dc1059ed8ull; st[1] = 0x629a292a367cd507ull; st[2] = 0x9159015a3070dd17ull; st[3] = 0x152fecd8f70e5939ull;
     st[4] = 0x67332667ffc00b31ull; st[5] = 0x8eb44a8768581511ull; st[6] = 0xdb0c2e0d64f98fa7ull; st[7] = 0x47b5481dbefa4fa4ull;
 }
+HD void kdf_sha512_init(u64 *st) {
+    st[0] = 0x6a09e667f3bcc908ull; st[1] = 0xbb67ae8584caa73bull; st[2] = 0x3c6ef372fe94f82bull; st[3] = 0xa54ff53a5f1d36f1ull;
+    st[4] = 0x510e527fade682d1ull; st[5] = 0x9b05688c2b3e6c1full; st[6] = 0x1f83d9abfb41bd6bull; st[7] = 0x5be0cd19137e2179ull;
+}
 
-// ---------------------------------------------------------------- the two hashes by digest length, and the shapes of an HMAC
-// HL = 32: SHA-256, HL = 48: SHA-384.  A message is handed over as big-endian 32-bit words (NW of them, zeros behind); at(m, k) is word k of the block's sixteen
+// ---------------------------------------------------------------- the hashes by digest length, and the shapes of an HMAC
+// HL = 32: SHA-256, HL = 48: SHA-384, HL = 64: SHA-512 (aesgcm_prfplus.h only: SHA-384's compression from its own initial state, all eight state words out).  A message is handed over as big-endian 32-bit words (NW of them, zeros behind); at(m, k) is word k of the block's sixteen
 // in the state's width: m[k] itself, or m[2k] | m[2k + 1].  A block is BLOCK bytes and ends with the message's bit length in LEN_BYTES bytes, of which all but the
 // low word -- w[15] in either width -- are zero here; the padding's 0x80 is KDF_PAD_BIT in the 32-bit word behind the message's last
 template <int HL> struct KdfHash;
@@ -161,6 +165,17 @@ template <> struct KdfHash<48> {
     static HD void digest(const word *st, u32 *out) {
 #pragma unroll
         for (int k = 0; k < 6; k++) { out[2 * k] = (u32)(st[k] >> 32); out[2 * k + 1] = (u32)st[k]; }
+    }
+};
+template <> struct KdfHash<64> {
+    typedef u64 word;
+    static constexpr u32 BLOCK = 128u, LEN_BYTES = 16u;
+    static HD void init(word *st) { kdf_sha512_init(st); }
+    static HD void block(word *st, word *w) { kdf_sha512_block(st, w); }
+    template <int NW> static HD word at(const u32 *m, int k) { return KdfHash<48>::at<NW>(m, k); }
+    static HD void digest(const word *st, u32 *out) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) { out[2 * k] = (u32)(st[k] >> 32); out[2 * k + 1] = (u32)st[k]; }
     }
 };
 #define KDF_IPAD 0x3636363636363636ull     /* RFC 2104; cut to the state's width */

@@ -109,3 +109,6 @@ int aesgcm_prf12_destroy(aesgcm_prf12 *k) {
     delete k;
     return rc;
 }
+
+// IKEv2's prf+ (aesgcm_prfplus_*): its host side is compiled here, inside this unit (aesgcm_prfplus.hip says why)
+#include "aesgcm_prfplus.hip"

@@ -55,6 +55,7 @@ SYMBOLS = [
     "aesgcm_srtp_kdf_destroy",
     "aesgcm_prf12_create", "aesgcm_prf12_set", "aesgcm_prf12_set_dev", "aesgcm_prf12_clear", "aesgcm_prf12_install_dev", "aesgcm_prf12_export_srtp_dev", "aesgcm_prf12_status",
     "aesgcm_prf12_destroy",
+    "aesgcm_prfplus_create", "aesgcm_prfplus_set", "aesgcm_prfplus_set_dev", "aesgcm_prfplus_clear", "aesgcm_prfplus_install_dev", "aesgcm_prfplus_status", "aesgcm_prfplus_destroy",
 ]
 
 
@@ -901,7 +902,7 @@ def _device_call(device, up, down, call):
 
 
 class _Table:
-    """what KeyTable, RxWindows, TxCounters, SecretTable and MasterKeyTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
+    """what KeyTable, RxWindows, TxCounters, SecretTable, MasterKeyTable, MasterSecretTable and IkeSaTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
     context manager, status()"""
     _h = _lib = None
 
@@ -1659,6 +1660,76 @@ class MasterSecretTable(_Table):
     def export_srtp(self, master_table, idx, client_recs, server_recs):
         """Host convenience (tests, examples): export_srtp_dev over host lists, waited for"""
         return self._both(idx, client_recs, server_recs, lambda n, i, c, s: self.export_srtp_dev(master_table, n, i, c, s))
+
+
+# ---------------------------------------------------------------- IKEv2's prf+ on the device (aesgcm_prfplus_*)
+def _prfplus_typed(L):
+    """type the aesgcm_prfplus_* symbols on first use, as _kdf_typed does: a library that lacks them still loads"""
+    if not getattr(L, "_prfplus_typed", False):
+        L.aesgcm_prfplus_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_prfplus_set.argtypes = [vp, sz, sz, vp, vp]
+        L.aesgcm_prfplus_set_dev.argtypes = [vp, sz, vp, vp, vp]
+        L.aesgcm_prfplus_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_prfplus_install_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_prfplus_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_prfplus_destroy.argtypes = [vp]
+        L._prfplus_typed = True
+    return L
+
+
+PRFP_SEED_MAX = 2048                                                # bytes of the longest seed an install entry may name
+PRFP_NONE = 0xFFFFFFFF                                              # an entry of a slot array that installs nothing for that direction
+
+
+class IkeSaTable(_Table):
+    """aesgcm_prfplus: n_keys device-resident SK_d values of IKE SAs, of one prf (hash_len 32 = HMAC-SHA-256, 48 = -384, 64 = -512).  install_dev cuts the ESP AES-GCM
+    keying material of Child SAs, prf+(SK_d, seed) of RFC 7296 2.13 / 2.17, into key-table slots: key and four salt bytes per direction; no SK_d is ever read back
+    (include/aesgcm.h "IKEv2 PRF+").  Protect the table like keys."""
+    _prefix = "aesgcm_prfplus"
+
+    def __init__(self, hash_len, n_keys, device=0):
+        self._create(_prfplus_typed, device, hash_len, n_keys)
+        self.hash_len, self.n_keys = hash_len, n_keys
+
+    def set(self, first, keys, stream=None):
+        """aesgcm_prfplus_set: host SK_d values (one bytes-like of n * hash_len bytes, or a list) into records first, first + 1, ..."""
+        kb, n = _per_slot(keys, self.hash_len, "SK_d values must be a multiple of %d bytes" % self.hash_len)
+        _chk(self._lib.aesgcm_prfplus_set(self._h, first, n, kb, stream))
+        return self
+
+    def set_dev(self, n, d_idx, d_keys, stream=None):
+        """aesgcm_prfplus_set_dev: n SK_d values from device memory (n x hash_len bytes) into the records d_idx (n uint32, device memory)"""
+        _chk(self._lib.aesgcm_prfplus_set_dev(self._h, n, d_idx, d_keys, stream))
+        return self
+
+    def clear(self, first, n=1, stream=None):
+        """aesgcm_prfplus_clear: records first .. first + n - 1 zeroed and unset (their entries are refused)"""
+        _chk(self._lib.aesgcm_prfplus_clear(self._h, first, n, stream))
+        return self
+
+    def install_dev(self, keytab, n, d_idx, d_seed, d_seed_off, d_i2r_slots, d_r2i_slots, stream=None):
+        """aesgcm_prfplus_install_dev: entry i derives KEYMAT = prf+(record d_idx[i], seed i) with seed i = bytes [d_seed_off[i], d_seed_off[i + 1]) of d_seed, and
+        installs key_i2r | salt_i2r into slot d_i2r_slots[i] and key_r2i | salt_r2i into slot d_r2i_slots[i] of keytab (a KeyTable); either slot array may be None,
+        an entry PRFP_NONE installs nothing (d_idx, d_seed_off and the slots uint32, all device memory)"""
+        _chk(self._lib.aesgcm_prfplus_install_dev(self._h, keytab._h, n, d_idx, d_seed, d_seed_off, d_i2r_slots, d_r2i_slots, stream))
+
+    def install(self, keytab, idx, seeds, i2r_slots=None, r2i_slots=None, stream=None):
+        """Host convenience (tests, examples): install_dev over host lists, waited for; seeds is a list of bytes, packed side by side here.  Refused entries are what
+        status() reports"""
+        n = len(idx)
+        if not n or len(seeds) != n or (i2r_slots is None and r2i_slots is None) or any(x is not None and len(x) != n for x in (i2r_slots, r2i_slots)):
+            raise AesGcmError(EARG, "idx, seeds and the i2r / r2i slot arrays (at least one) must be equally long and not empty")
+        packed, off = _joined(seeds)
+        if off[-1] >= 1 << 32:
+            raise AesGcmError(EARG, "the seeds' offsets are 32-bit")
+        up = {"idx": ("I", idx), "seed": packed, "off": ("I", off)}
+        if i2r_slots is not None:
+            up["i2r"] = ("I", i2r_slots)
+        if r2i_slots is not None:
+            up["r2i"] = ("I", r2i_slots)
+        _device_call(self.device, up, {}, lambda b: self.install_dev(keytab, n, b["idx"].ptr, b["seed"].ptr, b["off"].ptr, b["i2r"].ptr if i2r_slots is not None else None,
+                                                                     b["r2i"].ptr if r2i_slots is not None else None, stream))
+        return self
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

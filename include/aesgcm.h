@@ -41,7 +41,7 @@ extern "C" {
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
                                   aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
                                   the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt,
-                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*, the TLS 1.2 PRF aesgcm_prf12_*)
+                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*, the TLS 1.2 PRF aesgcm_prf12_*, IKEv2's prf+ aesgcm_prfplus_*)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -435,7 +435,8 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * aesgcm_kdf_install_dev and aesgcm_kdf_update_dev ("ON-DEVICE KEY DERIVATION" below) belong to this list too: one launch each, no memset node, no dispenser; the
  * graph holds the secret records beside the slots, and a replayed update in place steps its secrets one generation per replay.  So does aesgcm_srtp_kdf_install_dev
  * ("SRTP KEY DERIVATION" below): one launch, and the graph holds the master records beside the slots.  So do aesgcm_prf12_install_dev and aesgcm_prf12_export_srtp_dev
- * ("TLS 1.2 PRF" below): one launch each, and the graph holds the master-secret records beside the slots (install) or beside the SRTP master records (export).
+ * ("TLS 1.2 PRF" below): one launch each, and the graph holds the master-secret records beside the slots (install) or beside the SRTP master records (export).  So does
+ * aesgcm_prfplus_install_dev ("IKEv2 PRF+" below): one launch, and the graph holds the SK_d records and the caller's seed buffer and offsets beside the slots.
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
  *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
@@ -443,7 +444,8 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  *                    packets are taken in array order -- the same bytes, slower from the counts at which an ordinary call is ordered.
  *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
  *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy
- *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_prf12_create, _set, _set_dev, _clear, _status, _destroy.
+ *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_prf12_create, _set, _set_dev, _clear, _status, _destroy,
+ *                    and aesgcm_prfplus_create, _set, _set_dev, _clear, _status, _destroy.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
  *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
@@ -889,7 +891,7 @@ AESGCM_API int aesgcm_txnum_destroy(aesgcm_txnum *t);
  * install on one stream and a crypt call on another that names the slot are the caller's to order, as with aesgcm_keytab_set.  So the key-update loop runs as launches
  * on one stream: aesgcm_txnum_assign_dev refuses at the limit, update, install into a fresh slot, reset the counter, encrypt (INTEGRATION.md "Key derivation").
  * The host calls of one table are thread-safe; a table belongs to its device.
- * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF (not this table's: aesgcm_prf12_* under "TLS 1.2 PRF" below); ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash.  (SRTP's AES-CM key
+ * OUT OF SCOPE: HKDF-Extract and the handshake key schedule (the traffic secrets are the caller's); the TLS 1.2 PRF (not this table's: aesgcm_prf12_* under "TLS 1.2 PRF" below); IKEv2's prf+ (not this table's: aesgcm_prfplus_* under "IKEv2 PRF+" below); ChaCha20 and CCM suites; the QUIC Initial salt step (RFC 9001 5.2); labels with a context; outputs longer than the hash.  (SRTP's AES-CM key
  * derivation, RFC 3711 4.3, is no HKDF and has a table of its own: aesgcm_srtp_kdf_*, "SRTP KEY DERIVATION" below.) */
 typedef struct aesgcm_kdf aesgcm_kdf;
 typedef struct aesgcm_kdf_fmt {
@@ -944,7 +946,7 @@ AESGCM_API int aesgcm_kdf_destroy(aesgcm_kdf *k);
  * One launch per install, a lane per derived value (k_srtp_kdf_install: entries x {key, salt}); no allocation, no event, no host synchronisation, nothing read back:
  * install is capture-safe (CAPTURE, under "key tables" above) and asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
  * OUT OF SCOPE: the DTLS-SRTP exporter (not this table's: aesgcm_prf12_export_srtp_dev below fills these records on the device) and SDES; the authentication-key labels (0x01, 0x04) and the AES-CM / HMAC-SHA1 transforms they serve; RFC 6904's header
- * labels; counting packets to the next period (r is the caller's, per entry); the TLS 1.2 / DTLS 1.2 PRF (not this table's: aesgcm_prf12_* under "TLS 1.2 PRF" below). */
+ * labels; counting packets to the next period (r is the caller's, per entry); the TLS 1.2 / DTLS 1.2 PRF (not this table's: aesgcm_prf12_* under "TLS 1.2 PRF" below); IKEv2's prf+ (not this table's: aesgcm_prfplus_* under "IKEv2 PRF+" below). */
 typedef struct aesgcm_srtp_kdf aesgcm_srtp_kdf;
 AESGCM_API int aesgcm_srtp_kdf_create(aesgcm_srtp_kdf **out, int device, size_t key_len, size_t n_masters);
 AESGCM_API int aesgcm_srtp_kdf_set(aesgcm_srtp_kdf *k, size_t first, size_t n, const uint8_t *keys, const uint8_t *salts, void *stream);
@@ -997,7 +999,7 @@ AESGCM_API int aesgcm_srtp_kdf_destroy(aesgcm_srtp_kdf *k);
  * server}); no allocation, no event, no host synchronisation, nothing read back: install and export are capture-safe (CAPTURE, under "key tables" above) and
  * asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
  * OUT OF SCOPE: deriving the master secret itself from the premaster secret, with or without the extended master secret of RFC 7627 (the master secret is the
- * caller's); verify_data; the MAC keys of CBC suites (only AEAD key blocks are cut); exporters with a context or other labels; IKEv2's prf+ and MACsec's MKA KDF. */
+ * caller's); verify_data; the MAC keys of CBC suites (only AEAD key blocks are cut); exporters with a context or other labels; IKEv2's prf+ (not this table's: aesgcm_prfplus_* below) and MACsec's MKA KDF. */
 typedef struct aesgcm_prf12 aesgcm_prf12;
 AESGCM_API int aesgcm_prf12_create(aesgcm_prf12 **out, int device, size_t hash_len, size_t n_masters);
 AESGCM_API int aesgcm_prf12_set(aesgcm_prf12 *p, size_t first, size_t n, const uint8_t *masters, const uint8_t *client_randoms, const uint8_t *server_randoms, void *stream);
@@ -1010,6 +1012,55 @@ AESGCM_API int aesgcm_prf12_export_srtp_dev(aesgcm_prf12 *p, aesgcm_srtp_kdf *ma
                                      const uint32_t *d_server_recs, void *stream);
 AESGCM_API int aesgcm_prf12_status(aesgcm_prf12 *p, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_prf12_destroy(aesgcm_prf12 *p);
+
+/* ---------------------------------------------------------------- IKEv2 PRF+: ESP keys of Child SAs from SK_d values that never leave the device
+ * An IKEv2 gateway holds one SK_d per IKE SA and cuts the keys of every Child SA from it, at creation and again at every rekey (RFC 7296 2.17):
+ *   KEYMAT = prf+(SK_d, Ni | Nr), or prf+(SK_d, g^ir (new) | Ni | Nr) where the exchange carried a Diffie-Hellman (PFS),
+ * with prf+ of RFC 7296 2.13:
+ *   prf+(K, S) = T1 | T2 | ...,   T1 = prf(K, S | 0x01),   Tn = prf(K, T(n-1) | S | n)   (n one byte),
+ * and prf = HMAC-SHA-256, HMAC-SHA-384 or HMAC-SHA-512 (PRF_HMAC_SHA2_256 / _384 / _512, RFC 4868).  aesgcm_prfplus is a table of n_keys SK_d values on the device, of
+ * one prf: hash_len 32, 48 or 64, which is also SK_d's length (the prf's preferred key length).  No call reads a record back.  THE TABLE HOLDS SK_d VALUES: PROTECT IT
+ * LIKE KEYS -- whoever holds an SK_d holds the keys of every Child SA its IKE SA makes without PFS, and those of the IKE SAs rekeyed from it.
+ *   aesgcm_prfplus_create    every record unset.  AESGCM_EARG for a hash_len other than 32 / 48 / 64, n_keys == 0 or >= 2^31.
+ *   aesgcm_prfplus_set       HOST SK_d values (n * hash_len bytes) into records first .. first + n - 1, through the table's staging buffer on `stream`, zeroed behind
+ *                            the copy; the library's host copy is wiped before the call returns (as aesgcm_kdf_set).
+ *   aesgcm_prfplus_set_dev   n SK_d values from DEVICE memory (n * hash_len bytes, no alignment asked) into the records d_idx[i]; an index out of range is refused.
+ *   aesgcm_prfplus_clear     records first .. first + n - 1 zeroed and unset.
+ *   aesgcm_prfplus_status    as aesgcm_keytab_status: the LOWEST entry index an install or set_dev call refused since the last read, which clears it.
+ *   aesgcm_prfplus_destroy   waits for the device, zeroes the records and the staging buffer, frees.
+ * INSTALL: aesgcm_prfplus_install_dev(p, keytab, n, d_idx, d_seed, d_seed_off, d_i2r_slots, d_r2i_slots, stream).  For entry i with the SK_d of record d_idx[i]:
+ *   THE SEED S is the bytes [d_seed_off[i], d_seed_off[i + 1]) of d_seed (DEVICE memory; d_seed_off: n + 1 uint32 byte offsets): byte-packed, at any alignment, 1 ..
+ *   2048 bytes (g^ir of MODP-8192 and two 256-byte nonces).  The seeds are the caller's, per entry, and not the table's: many Child SAs share one IKE SA's SK_d and each
+ *   has its own Ni | Nr, so many entries of one call may name the same d_idx, and a rekey is a new seed, not a new record.  WITH PFS THE SEED HOLDS THE DIFFIE-HELLMAN
+ *   SHARED SECRET: the buffer is then the caller's to protect and to wipe;
+ *   KEYMAT = prf+(SK_d, S) = key_i2r | salt_i2r[4] | key_r2i | salt_r2i[4] (RFC 7296 2.17: the initiator-to-responder SA first; RFC 4106 8.1: within an SA the key, then
+ *   its four salt bytes), the keys of the key table's key_len, 16, 24 or 32, with any of the three hashes: direction d's bytes start at d * (key_len + 4);
+ *   slot d_i2r_slots[i] of `keytab` becomes exactly what aesgcm_keytab_set_dev makes of key_i2r -- round keys, H, its powers, nr, the set marker -- and its 8-byte salt
+ *   field what aesgcm_keytab_set_salt makes of salt_i2r | 00 00 00 00: what the ESP format {8, 16, 8, 4, tag, 0} reads, with or without ESN; xpn and the TLS-IV field
+ *   are left alone.  Slot d_r2i_slots[i] gets key_r2i and salt_r2i the same way.  AES-GMAC ESP (ENCR_NULL_AUTH_AES_GMAC, RFC 4543) takes the same KEYMAT.
+ * Either slot array may be NULL (not both: AESGCM_EARG), and an entry of 0xFFFFFFFF installs nothing for that direction: an endpoint installs its outbound SA into its
+ * sending table and its inbound SA into its receiving one, in two calls or in one.  AESGCM_EARG, before a device is touched, for p or keytab NULL, d_idx, d_seed or
+ * d_seed_off NULL, n >= 2^31 and a key table of another device; n == 0 is AESGCM_OK and looks at nothing.
+ * REFUSED ENTRIES are skipped whole -- NOTHING an entry names is written, in either direction -- when d_idx[i] is out of range, the record is unset or cleared, a slot
+ * it names (other than 0xFFFFFFFF) is out of range, or its seed's offsets fall, or the seed is empty or longer than 2048 bytes.  The lowest such index goes to THIS
+ * table's status word; the key table's status word is not touched.
+ * NO DERIVED KEY IN MEMORY: a derived key or salt is stored nowhere but in the slot's fields, no T(n) anywhere.  The lane that derives a key runs the key schedule
+ * itself, from its registers.
+ * One launch per call, a lane per direction (k_prfp_install: entries x {i2r, r2i}; a lane derives its key and salt together and computes only as many T(n) as cover
+ * them); no allocation, no event, no host synchronisation, nothing read back: install is capture-safe (CAPTURE, under "key tables" above) and asynchronous on
+ * `stream`.  Ordering and thread safety as aesgcm_kdf_*.  So an ESP rekey runs as launches on one stream: aesgcm_txnum_assign_dev refuses at the limit, install with
+ * the new nonces into fresh slots, reset the counter, encrypt (INTEGRATION.md "Key derivation").
+ * OUT OF SCOPE: the IKE SA's own keys -- SKEYSEED and the SK_d | SK_ai | SK_ar | SK_ei | SK_er | SK_pi | SK_pr split (SK_d is the caller's); IKEv1; PRF_HMAC_SHA1,
+ * AES-XCBC and AES-CMAC as prf; ENCR suites with a separate integrity key (only AEAD KEYMAT is cut); MACsec's MKA KDF (AES-CMAC in counter mode: another feature). */
+typedef struct aesgcm_prfplus aesgcm_prfplus;
+AESGCM_API int aesgcm_prfplus_create(aesgcm_prfplus **out, int device, size_t hash_len, size_t n_keys);
+AESGCM_API int aesgcm_prfplus_set(aesgcm_prfplus *p, size_t first, size_t n, const uint8_t *keys, void *stream);
+AESGCM_API int aesgcm_prfplus_set_dev(aesgcm_prfplus *p, size_t n, const uint32_t *d_idx, const void *d_keys, void *stream);
+AESGCM_API int aesgcm_prfplus_clear(aesgcm_prfplus *p, size_t first, size_t n, void *stream);
+AESGCM_API int aesgcm_prfplus_install_dev(aesgcm_prfplus *p, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const void *d_seed, const uint32_t *d_seed_off,
+                                   const uint32_t *d_i2r_slots, const uint32_t *d_r2i_slots, void *stream);
+AESGCM_API int aesgcm_prfplus_status(aesgcm_prfplus *p, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_prfplus_destroy(aesgcm_prfplus *p);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
