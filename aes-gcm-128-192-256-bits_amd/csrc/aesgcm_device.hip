@@ -15,3 +15,4 @@
 #include "aesgcm_srtp_kdf_kernels.hip"
 #include "aesgcm_prf12_kernels.hip"
 #include "aesgcm_prfplus_kernels.hip"
+#include "aesgcm_mka_kernels.hip"

@@ -96,3 +96,5 @@ int aesgcm_prfplus_destroy(aesgcm_prfplus *k) {
     delete k;
     return rc;
 }
+
+#include "aesgcm_mka.hip"

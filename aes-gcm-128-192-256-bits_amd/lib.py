@@ -56,6 +56,7 @@ SYMBOLS = [
     "aesgcm_prf12_create", "aesgcm_prf12_set", "aesgcm_prf12_set_dev", "aesgcm_prf12_clear", "aesgcm_prf12_install_dev", "aesgcm_prf12_export_srtp_dev", "aesgcm_prf12_status",
     "aesgcm_prf12_destroy",
     "aesgcm_prfplus_create", "aesgcm_prfplus_set", "aesgcm_prfplus_set_dev", "aesgcm_prfplus_clear", "aesgcm_prfplus_install_dev", "aesgcm_prfplus_status", "aesgcm_prfplus_destroy",
+    "aesgcm_mka_create", "aesgcm_mka_set", "aesgcm_mka_set_dev", "aesgcm_mka_clear", "aesgcm_mka_install_dev", "aesgcm_mka_unwrap_dev", "aesgcm_mka_status", "aesgcm_mka_destroy",
 ]
 
 
@@ -902,7 +903,7 @@ def _device_call(device, up, down, call):
 
 
 class _Table:
-    """what KeyTable, RxWindows, TxCounters, SecretTable, MasterKeyTable, MasterSecretTable and IkeSaTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
+    """what KeyTable, RxWindows, TxCounters, SecretTable, MasterKeyTable, MasterSecretTable, IkeSaTable and CakTable share: the handle of a device table made by <_prefix>_create, which belongs to the library that made it (_lib); close, the
     context manager, status()"""
     _h = _lib = None
 
@@ -1730,6 +1731,103 @@ class IkeSaTable(_Table):
         _device_call(self.device, up, {}, lambda b: self.install_dev(keytab, n, b["idx"].ptr, b["seed"].ptr, b["off"].ptr, b["i2r"].ptr if i2r_slots is not None else None,
                                                                      b["r2i"].ptr if r2i_slots is not None else None, stream))
         return self
+
+
+# ---------------------------------------------------------------- MACsec's MKA on the device (aesgcm_mka_*)
+def _mka_typed(L):
+    """type the aesgcm_mka_* symbols on first use, as _kdf_typed does: a library that lacks them still loads"""
+    if not getattr(L, "_mka_typed", False):
+        L.aesgcm_mka_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz]
+        L.aesgcm_mka_set.argtypes = [vp, sz, sz, vp, vp, vp]
+        L.aesgcm_mka_set_dev.argtypes = [vp, sz, vp, vp, vp, vp]
+        L.aesgcm_mka_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_mka_install_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_mka_unwrap_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+        L.aesgcm_mka_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_mka_destroy.argtypes = [vp]
+        L._mka_typed = True
+    return L
+
+
+MKA_CTX_MAX = 2048                                                  # bytes of the longest context an install entry may name
+MKA_KEYID_LEN = 16                                                  # bytes of a Keyid in the C ABI: the CKN's first 16, zero-padded on the right
+MKA_INSTALLED, MKA_REFUSED, MKA_BAD_ICV = 0, 1, 2                   # an unwrap entry's verdict byte
+
+
+def mka_sak_context(ks_nonce, mis, kn):
+    """the SAK's KDF context of IEEE 802.1X-2010 9.8.1: KS-nonce | MI-value list | be32(KN) -- the key server's nonce (of the SAK's length), the 12-byte member
+    identifiers of the live peers in the order the standard gives them, and the key number"""
+    if any(len(mi) != 12 for mi in mis) or not 0 <= kn < 1 << 32:
+        raise AesGcmError(EARG, "a member identifier is 12 bytes, a key number 32 bits")
+    return bytes(ks_nonce) + b"".join(bytes(mi) for mi in mis) + struct.pack(">I", kn)
+
+
+class CakTable(_Table):
+    """aesgcm_mka: n_caks device-resident MACsec CAKs (cak_len 16 / 32) with their Keyids.  install_dev (the key server) derives SAKs by the AES-CMAC KDF of IEEE
+    802.1X-2010 6.2 into key-table slots and, if asked, emits them wrapped under the KEK (RFC 3394); unwrap_dev (any other station) turns a received wrapped SAK into a
+    slot or refuses it; no CAK is ever read back (include/aesgcm.h "MACSEC MKA").  Protect the table like keys."""
+    _prefix = "aesgcm_mka"
+
+    def __init__(self, cak_len, n_caks, device=0):
+        self._create(_mka_typed, device, cak_len, n_caks)
+        self.cak_len, self.n_caks = cak_len, n_caks
+
+    def set(self, first, caks, ckns, stream=None):
+        """aesgcm_mka_set: host CAKs (one bytes-like of n * cak_len bytes, or a list) and their CKNs (a list, 1 .. 32 bytes each: the Keyid is formed here) into
+        records first, first + 1, ..."""
+        kb, n = _per_slot(caks, self.cak_len, "CAKs must be a multiple of %d bytes" % self.cak_len)
+        if not isinstance(ckns, (list, tuple)) or len(ckns) != n or any(not 1 <= len(c) <= 32 for c in ckns):
+            raise AesGcmError(EARG, "a CKN is 1 to 32 bytes, one per CAK")
+        ib = b"".join(bytes(c)[:MKA_KEYID_LEN].ljust(MKA_KEYID_LEN, b"\0") for c in ckns)
+        _chk(self._lib.aesgcm_mka_set(self._h, first, n, kb, ib, stream))
+        return self
+
+    def set_dev(self, n, d_idx, d_caks, d_keyids, stream=None):
+        """aesgcm_mka_set_dev: n CAKs (n x cak_len bytes) and Keyids (n x 16 bytes) from device memory into the records d_idx (n uint32, device memory)"""
+        _chk(self._lib.aesgcm_mka_set_dev(self._h, n, d_idx, d_caks, d_keyids, stream))
+        return self
+
+    def clear(self, first, n=1, stream=None):
+        """aesgcm_mka_clear: records first .. first + n - 1 zeroed and unset (their entries are refused)"""
+        _chk(self._lib.aesgcm_mka_clear(self._h, first, n, stream))
+        return self
+
+    def install_dev(self, keytab, n, d_idx, d_ctx, d_ctx_off, d_slots, d_wrapped=None, stream=None):
+        """aesgcm_mka_install_dev: entry i derives SAK = KDF(record d_idx[i], "IEEE8021 SAK", context i) with context i = bytes [d_ctx_off[i], d_ctx_off[i + 1]) of
+        d_ctx into slot d_slots[i] of keytab (a KeyTable of key_len 16 or 32) and, where d_wrapped is not None, its key_len + 8 wrapped bytes to d_wrapped + i *
+        (key_len + 8) (d_idx, d_ctx_off and d_slots uint32, all device memory)"""
+        _chk(self._lib.aesgcm_mka_install_dev(self._h, keytab._h, n, d_idx, d_ctx, d_ctx_off, d_slots, d_wrapped, stream))
+
+    def unwrap_dev(self, keytab, n, d_idx, d_wrapped, d_slots, d_verdict=None, stream=None):
+        """aesgcm_mka_unwrap_dev: entry i unwraps the key_len + 8 bytes at d_wrapped + i * (key_len + 8) under the KEK of record d_idx[i] into slot d_slots[i] of
+        keytab, or refuses; d_verdict (n bytes, device memory, or None) gets MKA_INSTALLED, MKA_REFUSED or MKA_BAD_ICV per entry"""
+        _chk(self._lib.aesgcm_mka_unwrap_dev(self._h, keytab._h, n, d_idx, d_wrapped, d_slots, d_verdict, stream))
+
+    def install(self, keytab, idx, contexts, slots, wrapped=False, stream=None):
+        """Host convenience (tests, examples): install_dev over host lists, waited for; contexts is a list of bytes, packed side by side here.  -> the list of wrapped
+        SAKs where wrapped is true (a refused entry's bytes are what the buffer held: zeros), else self.  Refused entries are what status() reports"""
+        n = len(idx)
+        if not n or len(contexts) != n or len(slots) != n:
+            raise AesGcmError(EARG, "idx, contexts and slots must be equally long and not empty")
+        packed, off = _joined(contexts)
+        if off[-1] >= 1 << 32:
+            raise AesGcmError(EARG, "the contexts' offsets are 32-bit")
+        w = keytab.key_len + 8
+        up = {"idx": ("I", idx), "ctx": packed, "off": ("I", off), "slots": ("I", slots)}
+        if wrapped:
+            up["wrapped"] = bytes(n * w)
+        got = _device_call(self.device, up, {"wrapped": ("%ds" % w, n)} if wrapped else {},
+                           lambda b: self.install_dev(keytab, n, b["idx"].ptr, b["ctx"].ptr, b["off"].ptr, b["slots"].ptr, b["wrapped"].ptr if wrapped else None, stream))
+        return got["wrapped"] if wrapped else self
+
+    def unwrap(self, keytab, idx, wrapped, slots, stream=None):
+        """Host convenience (tests, examples): unwrap_dev over host lists, waited for; wrapped is a list of key_len + 8 bytes each.  -> the list of verdicts"""
+        n = len(idx)
+        if not n or len(wrapped) != n or len(slots) != n or any(len(x) != keytab.key_len + 8 for x in wrapped):
+            raise AesGcmError(EARG, "idx, wrapped and slots must be equally long and not empty, a wrapped SAK key_len + 8 bytes")
+        got = _device_call(self.device, {"idx": ("I", idx), "wrapped": b"".join(bytes(x) for x in wrapped), "slots": ("I", slots), "verdict": b"\xff" * n}, {"verdict": ("B", n)},
+                           lambda b: self.unwrap_dev(keytab, n, b["idx"].ptr, b["wrapped"].ptr, b["slots"].ptr, b["verdict"].ptr, stream))
+        return got["verdict"]
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

@@ -41,7 +41,8 @@ extern "C" {
                                   aesgcm_tls_fmt / aesgcm_keytab_set_tls_iv / aesgcm_keytab_records_crypt_dev, aesgcm_keytab_quic_crypt_dev,
                                   aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
                                   the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt,
-                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*, the TLS 1.2 PRF aesgcm_prf12_*, IKEv2's prf+ aesgcm_prfplus_*)
+                                  SRTP's on-device key derivation aesgcm_srtp_kdf_*, the TLS 1.2 PRF aesgcm_prf12_*, IKEv2's prf+ aesgcm_prfplus_*,
+                                  MACsec's MKA aesgcm_mka_*)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -437,6 +438,8 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * ("SRTP KEY DERIVATION" below): one launch, and the graph holds the master records beside the slots.  So do aesgcm_prf12_install_dev and aesgcm_prf12_export_srtp_dev
  * ("TLS 1.2 PRF" below): one launch each, and the graph holds the master-secret records beside the slots (install) or beside the SRTP master records (export).  So does
  * aesgcm_prfplus_install_dev ("IKEv2 PRF+" below): one launch, and the graph holds the SK_d records and the caller's seed buffer and offsets beside the slots.
+ * So do aesgcm_mka_install_dev and aesgcm_mka_unwrap_dev ("MACSEC MKA" below): one launch each, and the graph holds the CAK records and the caller's context buffer and
+ * offsets, wrapped-key buffer and verdict bytes beside the slots.
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
  *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
@@ -445,7 +448,7 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
  *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy
  *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_prf12_create, _set, _set_dev, _clear, _status, _destroy,
- *                    and aesgcm_prfplus_create, _set, _set_dev, _clear, _status, _destroy.
+ *                    and aesgcm_prfplus_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_mka_create, _set, _set_dev, _clear, _status, _destroy.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
  *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
@@ -999,7 +1002,7 @@ AESGCM_API int aesgcm_srtp_kdf_destroy(aesgcm_srtp_kdf *k);
  * server}); no allocation, no event, no host synchronisation, nothing read back: install and export are capture-safe (CAPTURE, under "key tables" above) and
  * asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
  * OUT OF SCOPE: deriving the master secret itself from the premaster secret, with or without the extended master secret of RFC 7627 (the master secret is the
- * caller's); verify_data; the MAC keys of CBC suites (only AEAD key blocks are cut); exporters with a context or other labels; IKEv2's prf+ (not this table's: aesgcm_prfplus_* below) and MACsec's MKA KDF. */
+ * caller's); verify_data; the MAC keys of CBC suites (only AEAD key blocks are cut); exporters with a context or other labels; IKEv2's prf+ (not this table's: aesgcm_prfplus_* below) and MACsec's MKA KDF (AES-CMAC, not this table's either: aesgcm_mka_* under "MACSEC MKA" below). */
 typedef struct aesgcm_prf12 aesgcm_prf12;
 AESGCM_API int aesgcm_prf12_create(aesgcm_prf12 **out, int device, size_t hash_len, size_t n_masters);
 AESGCM_API int aesgcm_prf12_set(aesgcm_prf12 *p, size_t first, size_t n, const uint8_t *masters, const uint8_t *client_randoms, const uint8_t *server_randoms, void *stream);
@@ -1051,7 +1054,7 @@ AESGCM_API int aesgcm_prf12_destroy(aesgcm_prf12 *p);
  * `stream`.  Ordering and thread safety as aesgcm_kdf_*.  So an ESP rekey runs as launches on one stream: aesgcm_txnum_assign_dev refuses at the limit, install with
  * the new nonces into fresh slots, reset the counter, encrypt (INTEGRATION.md "Key derivation").
  * OUT OF SCOPE: the IKE SA's own keys -- SKEYSEED and the SK_d | SK_ai | SK_ar | SK_ei | SK_er | SK_pi | SK_pr split (SK_d is the caller's); IKEv1; PRF_HMAC_SHA1,
- * AES-XCBC and AES-CMAC as prf; ENCR suites with a separate integrity key (only AEAD KEYMAT is cut); MACsec's MKA KDF (AES-CMAC in counter mode: another feature). */
+ * AES-XCBC and AES-CMAC as prf; ENCR suites with a separate integrity key (only AEAD KEYMAT is cut); MACsec's MKA KDF (AES-CMAC in counter mode; not this table's: aesgcm_mka_* under "MACSEC MKA" below). */
 typedef struct aesgcm_prfplus aesgcm_prfplus;
 AESGCM_API int aesgcm_prfplus_create(aesgcm_prfplus **out, int device, size_t hash_len, size_t n_keys);
 AESGCM_API int aesgcm_prfplus_set(aesgcm_prfplus *p, size_t first, size_t n, const uint8_t *keys, void *stream);
@@ -1061,6 +1064,65 @@ AESGCM_API int aesgcm_prfplus_install_dev(aesgcm_prfplus *p, aesgcm_keytab *keyt
                                    const uint32_t *d_i2r_slots, const uint32_t *d_r2i_slots, void *stream);
 AESGCM_API int aesgcm_prfplus_status(aesgcm_prfplus *p, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_prfplus_destroy(aesgcm_prfplus *p);
+
+/* ---------------------------------------------------------------- MACSEC MKA: SAKs from CAKs that never leave the device, by the AES-CMAC KDF and AES Key Wrap
+ * MKA (IEEE 802.1X-2010 6.2, 9.3, 9.8) keys a MACsec connectivity association from its CAK.  The KEY SERVER derives the SAK, uses it, and distributes it to the peers
+ * wrapped by AES Key Wrap (RFC 3394) under the KEK; EVERY OTHER STATION derives the same KEK and unwraps the SAK it received.  A switch plays both roles.
+ *   PRF = AES-CMAC (RFC 4493; SP 800-38B) with a 16- or 32-byte key, 16 bytes of output
+ *   KDF(Key, Label, Context, Length) = first Length bits of  PRF(Key, 0x01 | Label | 0x00 | Context | be16(Length)) | PRF(Key, 0x02 | ...) | ...
+ *   KEK = KDF(CAK, "IEEE8021 KEK", Keyid, 8 * cak_len)      Keyid = the first 16 bytes of the CKN, zero-padded on the right where it is shorter
+ *   SAK = KDF(CAK, "IEEE8021 SAK", KS-nonce | MI-value list | KN, 8 * key_len)
+ * The counter is one byte; Length is in bits, two bytes, big-endian; both labels are 12 bytes without a terminator (the 0x00 that follows is the formula's).  The KEK has
+ * the CAK's length, the SAK the key table's: a 16-byte CAK may produce a 32-byte SAK (two iterations), and the other way round.  The wrapped SAK is RFC 3394 2.2.1 with
+ * the default initial value A6A6A6A6A6A6A6A6: key_len + 8 bytes, so 24 or 40.  aesgcm_mka is a table of n_caks CAKs on the device, of one cak_len (16 or 32), each with
+ * its 16-byte Keyid.  No call reads a record back.  THE TABLE HOLDS CAKs: PROTECT IT
+ * LIKE KEYS -- whoever holds a CAK derives the KEK, unwraps every SAK its association distributes, and may act as its key server.
+ *   aesgcm_mka_create        every record unset.  AESGCM_EARG for a cak_len other than 16 / 32, n_caks == 0 or >= 2^31.
+ *   aesgcm_mka_set           HOST CAKs (n * cak_len bytes) and Keyids (n * 16 bytes) into records first .. first + n - 1, through the table's staging buffer on `stream`,
+ *                            zeroed behind the copy; the library's host copy is wiped before the call returns (as aesgcm_kdf_set).
+ *   aesgcm_mka_set_dev       n CAKs and Keyids from DEVICE memory (n * cak_len and n * 16 bytes, no alignment asked) into the records d_idx[i]; an index out of range
+ *                            is refused.
+ *   aesgcm_mka_clear         records first .. first + n - 1 zeroed and unset.
+ *   aesgcm_mka_status        as aesgcm_keytab_status: the LOWEST entry index an install, unwrap or set_dev call refused since the last read, which clears it.
+ *   aesgcm_mka_destroy       waits for the device, zeroes the records and the staging buffer, frees.
+ * INSTALL (the key server): aesgcm_mka_install_dev(m, keytab, n, d_idx, d_ctx, d_ctx_off, d_slots, d_wrapped, stream).  For entry i with the CAK of record d_idx[i]:
+ *   THE CONTEXT is the bytes [d_ctx_off[i], d_ctx_off[i + 1]) of d_ctx (DEVICE memory; d_ctx_off: n + 1 uint32 byte offsets): byte-packed, at any alignment, 1 .. 2048
+ *   bytes.  The caller assembles KS-nonce | MI list | be32(KN); the library does not parse it;
+ *   slot d_slots[i] of `keytab` (key_len 16 or 32) becomes exactly what aesgcm_keytab_set_dev makes of the SAK -- round keys, H, its powers, nr, the set marker.  The
+ *   salt, xpn and TLS-IV fields are left alone: the SCI goes in by aesgcm_keytab_set_salt, the XPN salt by aesgcm_keytab_set_xpn, and both are the caller's;
+ *   if d_wrapped is not NULL, entry i's key_len + 8 wrapped bytes go to d_wrapped + i * (key_len + 8) (no alignment asked): what the MKPDU's Distributed SAK parameter
+ *   set carries.  A refused entry's bytes there are not written.
+ * Many entries may name one record: one SAK serves several SCs, so several slots are several entries.
+ * UNWRAP (any other station): aesgcm_mka_unwrap_dev(m, keytab, n, d_idx, d_wrapped, d_slots, d_verdict, stream).  The KEK is derived from record d_idx[i] and unwraps
+ *   the key_len + 8 bytes at d_wrapped + i * (key_len + 8) (RFC 3394 2.2.2).  If all eight bytes of the recovered A equal the default initial value, slot d_slots[i] is
+ *   built as above; if not, the entry is refused.  Where d_verdict is not NULL, entry i's byte there becomes 0 (installed), 1 (refused for what it names) or 2 (the
+ *   integrity check failed).
+ * AESGCM_EARG, before a device is touched, for m or keytab NULL, d_idx, d_ctx, d_ctx_off, d_slots (install) or d_idx, d_wrapped, d_slots (unwrap) NULL, n >= 2^31, a key
+ * table of another device and a key table of key size 24 (MACsec has no AES-192); n == 0 is AESGCM_OK and looks at nothing.
+ * REFUSED ENTRIES are skipped whole -- NOTHING an entry names is written; the verdict byte, where one was asked for, is the only byte a refused entry gets -- when
+ * d_idx[i] is out of range, the record is unset or cleared, the slot is out of range, the context's offsets fall, or the context is empty or longer than 2048 bytes, or
+ * the unwrap check fails.  The lowest such index goes to THIS table's status word; the key table's status word is not touched.
+ * NO DERIVED KEY IN MEMORY: neither the CAK's schedule, the KEK, its schedule, a CMAC subkey nor an unwrapped candidate is stored anywhere; the SAK goes nowhere but
+ * the slot's fields.  The lane that derives a key runs the key schedule itself, from its registers.  The wrapped SAK is public and goes to the caller's buffer.
+ * One launch per call, a lane per entry (k_mka_install: the same lane derives the SAK and, where asked, the KEK and the wrap; k_mka_unwrap: KEK, the inverse cipher,
+ * the check, the slot); no scratch memory, no allocation, no event, no host synchronisation, nothing read back: install and unwrap are capture-safe (CAPTURE, under
+ * "key tables" above) and asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.  So a MACsec rekey runs as launches on one stream:
+ * aesgcm_txnum_assign_dev refuses at PN exhaustion, install with KN + 1 into the next AN's slot, set_salt, reset the counter, encrypt; the peer runs unwrap, then its
+ * receive windows (INTEGRATION.md "Key derivation").
+ * OUT OF SCOPE: CAK and CKN from an EAP MSK ("IEEE8021 EAP CAK" / "IEEE8021 EAP CKN"); the ICK and the ICV of MKPDUs; building or parsing MKPDUs, the KS-nonce's
+ * randomness, MI and KN bookkeeping; the XPN salt from MI and KN (the caller's aesgcm_keytab_set_xpn does it: no text of 802.1AEbw is on hand to pin its byte order);
+ * AES-192; key wrap with padding (RFC 5649). */
+typedef struct aesgcm_mka aesgcm_mka;
+AESGCM_API int aesgcm_mka_create(aesgcm_mka **out, int device, size_t cak_len, size_t n_caks);
+AESGCM_API int aesgcm_mka_set(aesgcm_mka *m, size_t first, size_t n, const uint8_t *caks, const uint8_t *keyids, void *stream);
+AESGCM_API int aesgcm_mka_set_dev(aesgcm_mka *m, size_t n, const uint32_t *d_idx, const void *d_caks, const void *d_keyids, void *stream);
+AESGCM_API int aesgcm_mka_clear(aesgcm_mka *m, size_t first, size_t n, void *stream);
+AESGCM_API int aesgcm_mka_install_dev(aesgcm_mka *m, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const void *d_ctx, const uint32_t *d_ctx_off,
+                               const uint32_t *d_slots, void *d_wrapped, void *stream);
+AESGCM_API int aesgcm_mka_unwrap_dev(aesgcm_mka *m, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const void *d_wrapped, const uint32_t *d_slots,
+                              uint8_t *d_verdict, void *stream);
+AESGCM_API int aesgcm_mka_status(aesgcm_mka *m, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_mka_destroy(aesgcm_mka *m);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
