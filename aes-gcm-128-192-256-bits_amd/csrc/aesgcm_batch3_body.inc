@@ -14,7 +14,7 @@
     static_assert(!WIRE || SLOTS, "frames in wire format name a slot each");
     static_assert(!WIREX || WIRE, "the number that is not on the wire belongs to a frame in wire format");
     static_assert(WIREX == 0u || WIREX == AESGCM_WIREX_XPN || WIREX == AESGCM_WIREX_ESN || WIREX == KT_WIREX_TLS13 || WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_QUIC || WIREX == KT_WIREX_DTLS13 || WIREX == KT_WIREX_DTLS12 ||
-                  WIREX == KT_WIREX_SRTP || WIREX == KT_WIREX_SRTCP, "one extension or none");
+                  WIREX == KT_WIREX_SRTP || WIREX == KT_WIREX_SRTCP || WIREX == KT_WIREX_SSH, "one extension or none");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr u32 G = 1u << LG, P = 64u >> LG;
     // LDS behind the T-tables: one (8 lanes per packet) or two 512-byte table slots per packet, 256-byte aligned (shoup2_mul_dr ORs the entry offset into

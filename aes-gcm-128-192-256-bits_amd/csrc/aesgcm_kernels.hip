@@ -1420,7 +1420,8 @@ hipError_t klaunch_set_attributes() {
     if (!e) e = klaunch_tls_attributes();
     if (!e) e = klaunch_quic_attributes();
     if (!e) e = klaunch_dtls_attributes();
-    return e ? e : klaunch_srtp_attributes();
+    if (!e) e = klaunch_srtp_attributes();
+    return e ? e : klaunch_ssh_attributes();
 }
 hipError_t klaunch_main(int mode, int nr, unsigned wgs, hipStream_t st, const KeyMaterial *km, const DevTables *tb, const MainParams &p) {
     return launch(set_pick(MainSet{}, main_instance, nr, mode), wgs, st, km, tb, p);

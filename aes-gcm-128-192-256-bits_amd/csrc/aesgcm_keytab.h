@@ -1,6 +1,6 @@
 // aesgcm_keytab.h -- key tables (aesgcm_keytab_*): device-resident slots of key material that a batch call names per packet.
 // Shared by the kernels -- aesgcm_keytab_kernels.hip: k_kt_setup, and k_kt_batch, which runs k_batch3's body (aesgcm_batch3_body.inc) with the key material read from
-// slots; aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip, aesgcm_quic_kernels.hip, aesgcm_dtls_kernels.hip, aesgcm_srtp_kernels.hip: the same body on packets in wire format, one source per
+// slots; aesgcm_wire_kernels.hip, aesgcm_wirex_kernels.hip, aesgcm_tls_kernels.hip, aesgcm_quic_kernels.hip, aesgcm_dtls_kernels.hip, aesgcm_srtp_kernels.hip, aesgcm_ssh_kernels.hip: the same body on packets in wire format, one source per
 // family (aesgcm_keytab.hip lists them), what each format decides in aesgcm_wirecut.h -- and the host (aesgcm_keytab.hip, which launches each as aesgcm_host.hip's batch_plan plans k_batch3).  Every launcher below
 // picks its instance by aesgcm_dispatch.h.
 #pragma once
@@ -51,7 +51,7 @@ struct KtWireParams {
 
 // ... with an extension (k_kt_wirex): hi[p] = the upper half of frame p's 64-bit packet / sequence number, which is not in the frame
 // The body's WIREX modes that the ABI does not name (aesgcm_wire_xfmt_check refuses them as it refuses every unknown bit): TLS records, aesgcm_keytab_records_crypt_dev;
-// QUIC packets, aesgcm_keytab_quic_crypt_dev; DTLS records, aesgcm_keytab_dtls_crypt_dev; SRTP and SRTCP packets, aesgcm_keytab_srtp_crypt_dev
+// QUIC packets, aesgcm_keytab_quic_crypt_dev; DTLS records, aesgcm_keytab_dtls_crypt_dev; SRTP and SRTCP packets, aesgcm_keytab_srtp_crypt_dev; SSH binary packets, aesgcm_keytab_ssh_crypt_dev
 #define KT_WIREX_TLS13 0x10u
 #define KT_WIREX_TLS12 0x20u
 #define KT_WIREX_QUIC  0x40u
@@ -59,6 +59,7 @@ struct KtWireParams {
 #define KT_WIREX_DTLS12 0x100u
 #define KT_WIREX_SRTP 0x200u
 #define KT_WIREX_SRTCP 0x400u
+#define KT_WIREX_SSH 0x800u
 struct KtWireXParams {
     KtWireParams w;
     union {
@@ -67,6 +68,7 @@ struct KtWireXParams {
                                            // k_kt_quic: n_pkts full packet numbers (decrypt: as k_kt_quic_hp decoded them); w.f = {0, 0, 0, 0, 16, 0}, the header's length is per packet
                                            // k_kt_dtls, 1.3: n_pkts full record sequence numbers (decrypt: as k_kt_dtls_sn decoded them); w.f as k_kt_quic's.  1.2: unused;
                                            // w.f = {13, 21, 13, 4, 16, 0}
+                                           // k_kt_ssh: n_pkts counts of the packets sent under the slot's key before this one; w.f = {4, 4, 4, 0, 16, 0}
     };
     union {
         u32 mki_len;                       // k_kt_srtp only, in the place of a pointer it does not use: the bytes of MKI that end every packet (the parameters' size stays what it was)
@@ -106,3 +108,5 @@ hipError_t klaunch_kt_dtls(unsigned version, int nr, int dec, int lg, unsigned w
 hipError_t klaunch_kt_dtls_sn(int nr, int dec, hipStream_t st, const DevTables *tb, const KtQuicHpParams &p);
 hipError_t klaunch_srtp_attributes();
 hipError_t klaunch_kt_srtp(unsigned kind, int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);  // kind: AESGCM_SRTP_RTP or _RTCP
+hipError_t klaunch_ssh_attributes();
+hipError_t klaunch_kt_ssh(int nr, int dec, int lg, unsigned wgs, hipStream_t st, const DevTables *tb, const KtWireXParams &p);

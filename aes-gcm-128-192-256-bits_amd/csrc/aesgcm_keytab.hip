@@ -11,6 +11,7 @@
 //   quic     aesgcm_keytab_quic_crypt_dev         k_kt_quic    cut_quic                QUIC packets, and a second launch, k_kt_quic_hp (header protection, a lane per packet)
 //   dtls     aesgcm_keytab_dtls_crypt_dev         k_kt_dtls    cut_dtls13, cut_wire    DTLS records; 1.3: and a second launch, k_kt_dtls_sn (record-number encryption, a lane per record)
 //   srtp     aesgcm_keytab_srtp_crypt_dev         k_kt_srtp    (body text), cut_srtcp    SRTP and SRTCP packets (RFC 7714)
+//   ssh      aesgcm_keytab_ssh_crypt_dev          k_kt_ssh     cut_ssh                 SSH binary packets (RFC 5647) with the number of packets sent before each
 // The calls in wire format all go through kt_wire_crypt.
 #include "aesgcm_keytab.h"
 
@@ -327,6 +328,25 @@ int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srt
         xp.hi = rtp ? d_roc : nullptr;
         xp.mki_len = fmt->mki_len;
         return klaunch_kt_srtp(fmt->kind, b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
+    });
+}
+
+// ---------------------------------------------------------------- SSH binary packets
+// One k_kt_ssh launch, planned as a TLS call: the packet's cut and its nonce are the kernel's (cut_ssh, nonce_iv_add_num); of a wire format it takes the tag's length and,
+// for the bytes that pass through out of place, the four length bytes in front of the body.
+// A library made of the host units alone (tests/fake_hip links them against a fake runtime whose launcher list is fixed) has no launcher for this family: the one
+// below is the weak one, as aesgcm_prfplus.hip's are, and the call fails there with AESGCM_EHIP behind its argument checks and its plan; in the product the kernels'
+// object defines the strong one
+__attribute__((weak)) hipError_t klaunch_kt_ssh(int, int, int, unsigned, hipStream_t, const DevTables *, const KtWireXParams &) { return hipErrorNotSupported; }
+
+int aesgcm_keytab_ssh_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint64_t *d_seq, const void *d_in, const uint64_t *d_pkt_off,
+                                void *d_out, int *d_auth, void *stream) {
+    if (!d_seq) return AESGCM_EARG;
+    static const aesgcm_wire_fmt f = {4, 4, 4, 0, 16, 0};                             // {aad_len, hdr_len, iv_off, salt_len, tag_len, flags}
+    return kt_wire_crypt(t, decrypt, n_pkts, true, d_slots, d_in, d_pkt_off, d_out, d_auth, stream, nullptr, [&](const BatchPlan &b, KtWireXParams &xp) {
+        xp.w.f = f;
+        xp.seq = d_seq;
+        return klaunch_kt_ssh(b.nr, decrypt, b.lg, b.wgs, b.st, b.tables, xp);
     });
 }
 

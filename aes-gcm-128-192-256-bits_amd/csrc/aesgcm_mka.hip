@@ -121,3 +121,5 @@ int aesgcm_mka_destroy(aesgcm_mka *m) {
     delete m;
     return rc;
 }
+
+#include "aesgcm_sshkdf.hip"

@@ -136,6 +136,23 @@ HD void cut_srtcp(const BatchParams &p, const KtWireXParams *wx, const KtSlot *k
     doff = b + (enc ? 8u : body);
 }
 
+// An SSH binary packet under AES-GCM (RFC 5647 7.2 / 7.3; OpenSSH PROTOCOL 1.6): packet_length[4] | body | tag[16].  AAD = the four length bytes, which stay in the
+// clear; payload = the body (padding_length, payload, padding: not interpreted), a whole number of cipher blocks and at least one; the tag last.  Refused, in this
+// order: the slot, falling offsets, 2^28 bytes or more, fewer than 4 + 16 + 16, a body that is no multiple of 16, the slot unset -- and only then is the length field
+// read, in both directions (on encrypt the caller wrote it): it must say the body's length.  A refused packet's number is not read (wire_nonce)
+HD void cut_ssh(const BatchParams &p, const KtSlot *ks, u32 pkt, bool &bad, u64 &aoff, u64 &doff, u32 &aad_len, u32 &pkt_len) {
+    const u64 b = p.data_off[pkt], e = p.data_off[pkt + 1];
+    bad |= e < b || e - b >= ((u64)1 << 28) || e - b < 36u || ((e - b - 20u) & 15u) != 0;
+    bad |= ks->set != KT_SET;
+    const u32 body = bad ? 0u : (u32)(e - b) - 20u;
+    const u32 field = bad ? 0u : bswap32(gload4_any(p.in + b));
+    bad |= field != body;
+    aoff = b;
+    aad_len = bad ? 0u : 4u;
+    pkt_len = bad ? 0u : body;
+    doff = b + (bad ? 0u : 4u);
+}
+
 // ---------------------------------------------------------------- the nonces, as three memory-order words.  `bad`: a refused packet's bytes and numbers are not read
 // salt_len (0, 4 or 8) bytes of the slot's salt, then the frame's bytes at ivp -- whole words either way (the formats without an extension, and ESP with ESN)
 HD void nonce_salted(const KtSlot *ks, const unsigned char *ivp, u32 sw, bool bad, u32 &iv0, u32 &iv1, u32 &iv2) {
@@ -158,6 +175,12 @@ HD void nonce_tls12(const KtSlot *ks, const unsigned char *ivp, bool bad, u32 &i
 // with the packet number; DTLS 1.3 (RFC 9147 4.2.1 -> RFC 8446 5.3): with the record's sequence number
 HD void nonce_iv_xor_num(const KtSlot *ks, u64 num, u32 &iv0, u32 &iv1, u32 &iv2) {
     iv0 = ks->xpn[0]; iv1 = ks->xpn[1] ^ bswap32((u32)(num >> 32)); iv2 = ks->xpn[2] ^ bswap32((u32)num);
+}
+// SSH (RFC 5647 7.1): the slot's 12-byte IV = fixed[4] | invocation_counter[8], the counter a big-endian integer that is INCREMENTED once per packet: the nonce is
+// fixed | be64(counter + num mod 2^64), num = the packets sent under the key before this one.  The carry runs through the counter's 64 bits and never into the fixed field
+HD void nonce_iv_add_num(const KtSlot *ks, u64 num, u32 &iv0, u32 &iv1, u32 &iv2) {
+    const u64 c = (((u64)bswap32(ks->xpn[1]) << 32) | bswap32(ks->xpn[2])) + num;
+    iv0 = ks->xpn[0]; iv1 = bswap32((u32)(c >> 32)); iv2 = bswap32((u32)c);
 }
 // SRTCP (RFC 7714 9.1): the salt XOR (00 00 | SSRC | 00 00 | 0, the 31-bit index) -- SSRC = the packet's bytes 4 .. 7, the index = W without its E bit (the top bit of
 // W's first byte); w_at = where W lies: 16 bytes behind the payload, or behind the AAD's packet bytes when there is none
@@ -196,6 +219,7 @@ HD void wire_cut(const BatchParams &p, const KtParams *kt, const aesgcm_wire_fmt
     if constexpr (WIREX == KT_WIREX_QUIC) cut_quic(p, kt, wx, ks, pkt, dec, bad, aoff, doff, aad_len, pkt_len, num);
     else if constexpr (WIREX == KT_WIREX_DTLS13) cut_dtls13(p, kt, wx, ks, pkt, bad, aoff, doff, aad_len, pkt_len, num);
     else if constexpr (WIREX == KT_WIREX_SRTCP) cut_srtcp(p, wx, ks, pkt, bad, aoff, doff, aad_len, pkt_len);
+    else if constexpr (WIREX == KT_WIREX_SSH) cut_ssh(p, ks, pkt, bad, aoff, doff, aad_len, pkt_len);
     else cut_wire<WIREX>(p, wf, pkt, bad, aoff, doff, aad_len, pkt_len, ivp);
 }
 
@@ -207,6 +231,7 @@ HD void wire_nonce(const aesgcm_wire_fmt *wf, const KtWireXParams *wx, const KtS
     else if constexpr (WIREX == KT_WIREX_TLS12 || WIREX == KT_WIREX_DTLS12) nonce_tls12(ks, ivp, bad, iv0, iv1, iv2);
     else if constexpr (WIREX == KT_WIREX_TLS13) nonce_iv_xor_num(ks, bad ? (u64)0 : wx->seq[pkt], iv0, iv1, iv2);         // (a refused record's number is not read)
     else if constexpr (WIREX == KT_WIREX_QUIC || WIREX == KT_WIREX_DTLS13) nonce_iv_xor_num(ks, num, iv0, iv1, iv2);
+    else if constexpr (WIREX == KT_WIREX_SSH) nonce_iv_add_num(ks, bad ? (u64)0 : wx->seq[pkt], iv0, iv1, iv2);           // (likewise)
     else if constexpr (WIREX == KT_WIREX_SRTCP) nonce_srtcp(ks, pk, in + pkt_len + 16u, bad, iv0, iv1, iv2);
     else nonce_salted(ks, ivp, wf->salt_len >> 2, bad, iv0, iv1, iv2);
 }

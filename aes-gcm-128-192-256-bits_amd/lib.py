@@ -57,6 +57,8 @@ SYMBOLS = [
     "aesgcm_prf12_destroy",
     "aesgcm_prfplus_create", "aesgcm_prfplus_set", "aesgcm_prfplus_set_dev", "aesgcm_prfplus_clear", "aesgcm_prfplus_install_dev", "aesgcm_prfplus_status", "aesgcm_prfplus_destroy",
     "aesgcm_mka_create", "aesgcm_mka_set", "aesgcm_mka_set_dev", "aesgcm_mka_clear", "aesgcm_mka_install_dev", "aesgcm_mka_unwrap_dev", "aesgcm_mka_status", "aesgcm_mka_destroy",
+    "aesgcm_keytab_ssh_crypt_dev",
+    "aesgcm_sshkdf_create", "aesgcm_sshkdf_set", "aesgcm_sshkdf_set_dev", "aesgcm_sshkdf_clear", "aesgcm_sshkdf_install_dev", "aesgcm_sshkdf_status", "aesgcm_sshkdf_destroy",
 ]
 
 
@@ -741,6 +743,7 @@ def _keytab_typed(L):
         L.aesgcm_keytab_dtls_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(DtlsFormat), sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.aesgcm_srtp_fmt_check.argtypes = [ctypes.POINTER(SrtpFormat)]
         L.aesgcm_keytab_srtp_crypt_dev.argtypes = [vp, cint, ctypes.POINTER(SrtpFormat), sz, vp, vp, vp, vp, vp, vp, vp]
+        L.aesgcm_keytab_ssh_crypt_dev.argtypes = [vp, cint, sz, vp, vp, vp, vp, vp, vp, vp]
         L._keytab_typed = True
     return L
 
@@ -1030,6 +1033,24 @@ class KeyTable(_Table):
         def call(b):
             self.records_crypt_dev(decrypt, fmt, n, b["slots"].ptr, b["seq"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_auth=b["auth"].ptr if decrypt else None)
         outs, got = self._packed_call(records, {"slots": ("I", slots), "seq": ("Q", seqs)}, {"auth": "i"} if decrypt else {}, call)
+        return outs, got.get("auth")
+
+    def ssh_crypt_dev(self, decrypt, n_pkts, d_slots, d_seq, d_in, d_pkt_off, d_out, d_auth=None, stream=None):
+        """aesgcm_keytab_ssh_crypt_dev: SSH binary packet p (packet_length[4] | body | tag[16], RFC 5647) = bytes [d_pkt_off[p], d_pkt_off[p + 1]) of d_in / d_out under
+        slot d_slots[p] (key by set, initial IV by set_tls_iv); d_seq[p] (uint64, device memory) = the packets sent under that key before this one, added to the IV's
+        invocation counter"""
+        _chk(self._lib.aesgcm_keytab_ssh_crypt_dev(self._h, int(bool(decrypt)), n_pkts, d_slots, d_seq, d_in, d_pkt_off, d_out, d_auth, stream))
+
+    def crypt_ssh(self, slots, seqs, packets, decrypt=False):
+        """Host convenience (tests, examples), crypt_records' counterpart: whole SSH packets (packet_length | body | tag; on encrypt the length field is written and the
+        tag's bytes are placeholders) with a packet count each through one call, in place.  -> (packets_out, auth); auth is None on encrypt."""
+        n = len(slots)
+        if len(packets) != n or len(seqs) != n or not n:
+            raise AesGcmError(EARG, "slots, seqs and packets must be equally long and not empty")
+
+        def call(b):
+            self.ssh_crypt_dev(decrypt, n, b["slots"].ptr, b["seq"].ptr, b["data"].ptr, b["off"].ptr, b["data"].ptr, d_auth=b["auth"].ptr if decrypt else None)
+        outs, got = self._packed_call(packets, {"slots": ("I", slots), "seq": ("Q", seqs)}, {"auth": "i"} if decrypt else {}, call)
         return outs, got.get("auth")
 
     def quic_crypt_dev(self, decrypt, n_pkts, d_slots, d_hp_slots, d_pn, d_pn_off, d_in, d_pkt_off, d_out, d_pn_out=None, d_auth=None, stream=None):
@@ -1828,6 +1849,80 @@ class CakTable(_Table):
         got = _device_call(self.device, {"idx": ("I", idx), "wrapped": b"".join(bytes(x) for x in wrapped), "slots": ("I", slots), "verdict": b"\xff" * n}, {"verdict": ("B", n)},
                            lambda b: self.unwrap_dev(keytab, n, b["idx"].ptr, b["wrapped"].ptr, b["slots"].ptr, b["verdict"].ptr, stream))
         return got["verdict"]
+
+
+# ---------------------------------------------------------------- SSH's key derivation on the device (aesgcm_sshkdf_*)
+def _sshkdf_typed(L):
+    """type the aesgcm_sshkdf_* symbols on first use, as _kdf_typed does: a library that lacks them still loads"""
+    if not getattr(L, "_sshkdf_typed", False):
+        L.aesgcm_sshkdf_create.argtypes = [ctypes.POINTER(vp), cint, sz, sz, sz]
+        L.aesgcm_sshkdf_set.argtypes = [vp, sz, sz, vp, vp, vp, vp]
+        L.aesgcm_sshkdf_set_dev.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+        L.aesgcm_sshkdf_clear.argtypes = [vp, sz, sz, vp]
+        L.aesgcm_sshkdf_install_dev.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.aesgcm_sshkdf_status.argtypes = [vp, ctypes.POINTER(cint), ctypes.POINTER(u64)]
+        L.aesgcm_sshkdf_destroy.argtypes = [vp]
+        L._sshkdf_typed = True
+    return L
+
+
+SSHK_SECRET_MAX = 2048                                              # the most that max_secret_len may be
+SSHK_NONE = 0xFFFFFFFF                                              # an entry of a slot array that installs nothing for that direction
+
+
+class SshKexTable(_Table):
+    """aesgcm_sshkdf: n_recs device-resident key-exchange outputs of SSH connections -- secret = K_enc | H (K as the exchange encodes it: mpint or string, with its
+    length prefix) and the session identifier --, of one hash (hash_len 32 = SHA-256, 48 = SHA-384, 64 = SHA-512).  install_dev derives the AES-GCM key and the initial
+    IV of either direction by RFC 4253 7.2 into key-table slots, which crypt_ssh then uses; no record is ever read back (include/aesgcm.h "SSH KEY DERIVATION").
+    Protect the table like keys."""
+    _prefix = "aesgcm_sshkdf"
+
+    def __init__(self, hash_len, n_recs, max_secret_len=SSHK_SECRET_MAX, device=0):
+        self._create(_sshkdf_typed, device, hash_len, max_secret_len, n_recs)
+        self.hash_len, self.n_recs, self.max_secret_len = hash_len, n_recs, max_secret_len
+
+    def set(self, first, secrets, session_ids, stream=None):
+        """aesgcm_sshkdf_set: host secrets (a list of bytes, K_enc | H each, 1 .. max_secret_len bytes) and session identifiers (one bytes-like of n * hash_len bytes,
+        or a list) into records first, first + 1, ..."""
+        sb, n = _per_slot(session_ids, self.hash_len, "a session identifier is %d bytes" % self.hash_len)
+        if len(secrets) != n:
+            raise AesGcmError(EARG, "one secret and one session identifier per record")
+        packed, off = _joined(secrets)
+        if off[-1] >= 1 << 32:
+            raise AesGcmError(EARG, "the secrets' offsets are 32-bit")
+        _chk(self._lib.aesgcm_sshkdf_set(self._h, first, n, packed, struct.pack("<%dI" % (n + 1), *off), sb, stream))
+        return self
+
+    def set_dev(self, n, d_idx, d_secrets, d_secret_off, d_session_ids, stream=None):
+        """aesgcm_sshkdf_set_dev: n secrets (byte-packed, secret i = bytes [d_secret_off[i], d_secret_off[i + 1]) of d_secrets) and session identifiers (n x hash_len
+        bytes) from device memory into the records d_idx (d_idx and d_secret_off uint32, device memory)"""
+        _chk(self._lib.aesgcm_sshkdf_set_dev(self._h, n, d_idx, d_secrets, d_secret_off, d_session_ids, stream))
+        return self
+
+    def clear(self, first, n=1, stream=None):
+        """aesgcm_sshkdf_clear: records first .. first + n - 1 zeroed and unset (their entries are refused)"""
+        _chk(self._lib.aesgcm_sshkdf_clear(self._h, first, n, stream))
+        return self
+
+    def install_dev(self, keytab, n, d_idx, d_c2s_slots, d_s2c_slots, stream=None):
+        """aesgcm_sshkdf_install_dev: entry i derives, from record d_idx[i], key HASH(K | H | "C" | session_id) and IV HASH(K | H | "A" | session_id) into slot
+        d_c2s_slots[i] of keytab (a KeyTable) and those of "D" / "B" into slot d_s2c_slots[i]; either slot array may be None, an entry SSHK_NONE installs nothing
+        (all uint32, device memory)"""
+        _chk(self._lib.aesgcm_sshkdf_install_dev(self._h, keytab._h, n, d_idx, d_c2s_slots, d_s2c_slots, stream))
+
+    def install(self, keytab, idx, c2s_slots=None, s2c_slots=None, stream=None):
+        """Host convenience (tests, examples): install_dev over host lists, waited for.  Refused entries are what status() reports"""
+        n = len(idx)
+        if not n or (c2s_slots is None and s2c_slots is None) or any(x is not None and len(x) != n for x in (c2s_slots, s2c_slots)):
+            raise AesGcmError(EARG, "idx and the c2s / s2c slot arrays (at least one) must be equally long and not empty")
+        up = {"idx": ("I", idx)}
+        if c2s_slots is not None:
+            up["c2s"] = ("I", c2s_slots)
+        if s2c_slots is not None:
+            up["s2c"] = ("I", s2c_slots)
+        _device_call(self.device, up, {}, lambda b: self.install_dev(keytab, n, b["idx"].ptr, b["c2s"].ptr if c2s_slots is not None else None,
+                                                                     b["s2c"].ptr if s2c_slots is not None else None, stream))
+        return self
 
 
 # ---------------------------------------------------------------- the exchange step (RCCL inside the library)

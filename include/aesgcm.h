@@ -42,7 +42,7 @@ extern "C" {
                                   aesgcm_dtls_fmt / aesgcm_keytab_dtls_crypt_dev, aesgcm_srtp_fmt / aesgcm_keytab_srtp_crypt_dev, the receive windows aesgcm_rxwin_*,
                                   the send counters aesgcm_txnum_* / aesgcm_txnum_fmt, the on-device key derivation aesgcm_kdf_* / aesgcm_kdf_fmt,
                                   SRTP's on-device key derivation aesgcm_srtp_kdf_*, the TLS 1.2 PRF aesgcm_prf12_*, IKEv2's prf+ aesgcm_prfplus_*,
-                                  MACsec's MKA aesgcm_mka_*)
+                                  MACsec's MKA aesgcm_mka_*, SSH packets aesgcm_keytab_ssh_crypt_dev, SSH's key derivation aesgcm_sshkdf_*)
                                   5 (round 6): calls with offset arrays and aesgcm_messages_crypt_dev are ROUTED per message on the device (AESGCM_SHAPE_MIXED; pkt_len is no longer a hint),
                                   aesgcm_ctx_status (what an asynchronous call could not say when it returned), aesgcm_stream_export / _import / _update_dev, aesgcm_frames_ceiling_probe_dev,
                                   aesgcm_mgpu_last_tags collects the OLDEST queued messages;
@@ -439,7 +439,8 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  * ("TLS 1.2 PRF" below): one launch each, and the graph holds the master-secret records beside the slots (install) or beside the SRTP master records (export).  So does
  * aesgcm_prfplus_install_dev ("IKEv2 PRF+" below): one launch, and the graph holds the SK_d records and the caller's seed buffer and offsets beside the slots.
  * So do aesgcm_mka_install_dev and aesgcm_mka_unwrap_dev ("MACSEC MKA" below): one launch each, and the graph holds the CAK records and the caller's context buffer and
- * offsets, wrapped-key buffer and verdict bytes beside the slots.
+ * offsets, wrapped-key buffer and verdict bytes beside the slots.  So does aesgcm_sshkdf_install_dev ("SSH KEY DERIVATION" below): one launch, and the graph holds
+ * the secret records beside the slots.
  *   PRECONDITION     one ordinary call on that device, with that table (or window table) and key size, before the capture: per-device state is made on first use.
  *   A GRAPH HOLDS    the caller's pointers and n, the table's slots and status word, the window records, the counter records and the counter table's scratch, and ONE of the device's 256 launch dispensers (a word the
  *                    lane groups draw packets from, zeroed by the graph's memset node).  Destroy the graph before the table; the caller's buffers are the caller's.
@@ -448,7 +449,8 @@ AESGCM_API int aesgcm_batch_crypt_var_dev(int device, int decrypt, size_t n_pkts
  *   NOT CAPTURE-SAFE aesgcm_keytab_create, every aesgcm_keytab_set*, aesgcm_keytab_status, _destroy; aesgcm_rxwin_create, _set, _get, _status, _destroy; aesgcm_txnum_create, _set, _get, _status, _destroy (staging buffers
  *                    that grow, events, synchronous copies, waits): call them outside the capture.  So are aesgcm_kdf_create, _set, _set_dev, _clear, _status, _destroy
  *                    and aesgcm_srtp_kdf_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_prf12_create, _set, _set_dev, _clear, _status, _destroy,
- *                    and aesgcm_prfplus_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_mka_create, _set, _set_dev, _clear, _status, _destroy.
+ *                    and aesgcm_prfplus_create, _set, _set_dev, _clear, _status, _destroy, and aesgcm_mka_create, _set, _set_dev, _clear, _status, _destroy,
+ *                    and aesgcm_sshkdf_create, _set, _set_dev, _clear, _status, _destroy.
  *   DISPENSERS       a replay shares its dispenser with every 256th later crypt call on the device.  On one stream that is harmless (each zeroes it before use).
  *                    Such a call must not run CONCURRENTLY with the replay on another stream: a caller who replays graphs beside ordinary calls on other streams
  *                    orders them, or keeps fewer than 256 crypt calls between a graph's capture and its last replay.
@@ -717,6 +719,37 @@ AESGCM_API int aesgcm_srtp_fmt_check(const aesgcm_srtp_fmt *fmt);
 AESGCM_API int aesgcm_keytab_srtp_crypt_dev(aesgcm_keytab *t, int decrypt, const aesgcm_srtp_fmt *fmt, size_t n_pkts,
                                  const uint32_t *d_slots, const uint32_t *d_roc,
                                  const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
+
+/* ---------------------------------------------------------------- key tables on SSH BINARY PACKETS in wire format: RFC 5647 AEAD_AES_128_GCM / AEAD_AES_256_GCM
+ * An SSH bastion, an SFTP front end or a Git host holds thousands of connections, each with its own key, and one buffer of short packets.  Under
+ * aes128-gcm@openssh.com / aes256-gcm@openssh.com (OpenSSH PROTOCOL 1.6) and RFC 5647's AEAD_AES_128_GCM / AEAD_AES_256_GCM (7.2, 7.3) a packet is
+ *   packet_length[4] | body[B] | tag[16]        B = L - 20
+ * packet_length in the clear, the AAD's four bytes; body = padding_length, payload and padding, not interpreted; B a whole number of cipher blocks and at least one.
+ * No other call can express it: no nonce byte is on the wire, and the nonce is not an XOR.  aesgcm_keytab_ssh_crypt_dev takes the buffer as it is: packet p is bytes
+ * [d_pkt_off[p], d_pkt_off[p + 1]) of d_in and of d_out (the same n_pkts + 1 offsets for both; d_in == d_out allowed; any byte alignment), L bytes long, under slot
+ * d_slots[p].  The slot holds the direction's encryption key (aesgcm_keytab_set) and its 12-byte initial IV (aesgcm_keytab_set_tls_iv: the slot state that TLS, QUIC,
+ * DTLS and SRTP use): fixed[4] | invocation_counter[8] (RFC 5647 7.1).
+ *   NONCE = fixed[4] | be64((be64(invocation_counter) + d_seq[p]) mod 2^64)
+ * d_seq[p] (DEVICE memory, n_pkts numeric 64-bit values, as TLS 1.3's) is the number of packets sent under this key before this one.  It is ADDED, with its carries
+ * through all 64 bits of the counter; the carry never runs into the fixed field.  (SSH's 32-bit implicit sequence number is not used by AES-GCM and is not this value:
+ * d_seq restarts at 0 with every key.)
+ * Encrypt writes the body and the tag; THE CALLER WROTE packet_length, as it writes a TLS header.  Decrypt writes the body and d_auth[p] = 1 iff the packet's tag equals
+ * the computed one (d_auth is required for decrypt and ignored for encrypt).  Out of place every byte of an accepted packet in d_out is defined: the length field is
+ * copied, and on decrypt the tag.  No byte outside an accepted packet is written.
+ * A packet is REFUSED on its own.  The tests, in this order: the slot is n_slots or more; the offsets fall; L >= 2^28; L < 36 (the body is at least one cipher block, RFC
+ * 5647 7.2); B % 16 != 0; the slot is unset or cleared; be32(packet_length) != B -- ONLY HERE IS THE FIELD READ, in both directions.  Nothing of a refused packet is read
+ * past the test that refuses it, nothing of it is written, d_seq[p] is not read, d_auth[p] = 0 on decrypt, and the LOWEST such index goes to aesgcm_keytab_status.
+ * FAIL-CLOSED: aesgcm_wipe_failed_dev(device, n_pkts, d_out, 0, d_pkt_off, d_auth, stream) behind a decrypt, as for TLS.
+ * AESGCM_EARG for d_seq == NULL, before the call looks at the table; then, in aesgcm_keytab_records_crypt_dev's order: t NULL; decrypt not 0 / 1; (n_pkts == 0 is
+ * AESGCM_OK;) any of d_slots, d_in, d_pkt_off, d_out NULL; decrypt without d_auth; n_pkts >= 2^31.
+ * ONE k_kt_ssh launch: no scratch memory, no host synchronisation, capture-safe (CAPTURE, under "key tables" above) and asynchronous; shape, order and planning as
+ * aesgcm_keytab_records_crypt_dev.  Ordering and thread safety as the other key-table calls.
+ * OUT OF SCOPE: chacha20-poly1305@openssh.com; encrypt-then-MAC, CBC and CTR suites; SSH's 32-bit implicit sequence number; finding the packets' boundaries in a TCP
+ * stream (the clear length fields are the caller's to walk: one entry of d_pkt_off per packet); compression; the key exchange and the computation of H (the keys from
+ * K and H: aesgcm_sshkdf_* under "SSH KEY DERIVATION" below); counting packets (the send counters' business: aesgcm_txnum_assign_dev under "SEND COUNTERS" below gives d_seq --
+ * INTEGRATION.md "SSH packets"); routing long packets to the row kernels. */
+AESGCM_API int aesgcm_keytab_ssh_crypt_dev(aesgcm_keytab *t, int decrypt, size_t n_pkts, const uint32_t *d_slots, const uint64_t *d_seq,
+                                const void *d_in, const uint64_t *d_pkt_off, void *d_out, int *d_auth, void *stream);
 
 /* ---------------------------------------------------------------- RECEIVE WINDOWS: anti-replay and number recovery on the device, for every wire format above
  * A receiver needs, BEFORE a decrypt call, a per-packet value that depends on per-association state -- ESN's seq-hi, XPN's upper PN half, SRTP's rollover counter, the
@@ -1123,6 +1156,52 @@ AESGCM_API int aesgcm_mka_unwrap_dev(aesgcm_mka *m, aesgcm_keytab *keytab, size_
                               uint8_t *d_verdict, void *stream);
 AESGCM_API int aesgcm_mka_status(aesgcm_mka *m, int *code, uint64_t *detail);
 AESGCM_API int aesgcm_mka_destroy(aesgcm_mka *m);
+
+/* ---------------------------------------------------------------- SSH KEY DERIVATION: AES-GCM keys and initial IVs from K and H that never leave the device (RFC 4253 7.2)
+ * An SSH key exchange ends with a shared secret K and an exchange hash H; the first H of a connection is its session identifier.  RFC 4253 7.2 derives
+ *   initial IV client to server   = HASH(K | H | "A" | session_id)        encryption key client to server = HASH(K | H | "C" | session_id)
+ *   initial IV server to client   = HASH(K | H | "B" | session_id)        encryption key server to client = HASH(K | H | "D" | session_id)
+ * each cut to the length needed, HASH the key exchange's own: SHA-256, SHA-384 or SHA-512.  It is a PLAIN HASH, no HMAC.  ("E" / "F", the integrity keys, have no use
+ * under AES-GCM.)  aesgcm_sshkdf is a table of n_recs records on the device, of one hash_len (32 / 48 / 64), each
+ *   secret = K_enc | H         1 .. max_secret_len bytes (max_secret_len <= 2048, fixed at create).  K_enc is K EXACTLY AS THE KEY EXCHANGE ENCODES IT INTO THE HASH: an
+ *                              mpint with its four length bytes (the DH and ECDH exchanges), or a string with its four length bytes (the hybrid exchanges such as
+ *                              sntrup761x25519-sha512 and mlkem768x25519-sha256).  The caller says which by passing the bytes; the library does not parse them.
+ *   session_id[hash_len]
+ * No call reads a record back.  THE TABLE HOLDS KEY-EXCHANGE SECRETS: PROTECT IT LIKE KEYS -- whoever holds K and H derives every key of the connection.
+ *   aesgcm_sshkdf_create     every record unset.  AESGCM_EARG for a hash_len other than 32 / 48 / 64, max_secret_len == 0 or > 2048, n_recs == 0 or >= 2^31.
+ *   aesgcm_sshkdf_set        HOST secrets (byte-packed: record first + i takes bytes [secret_off[i], secret_off[i + 1]) of `secrets`; secret_off: n + 1 uint32 in HOST
+ *                            memory) and session identifiers (n * hash_len bytes) into records first .. first + n - 1, through the table's staging buffer on `stream`,
+ *                            zeroed behind the copy; the library's host copy is wiped before the call returns (as aesgcm_kdf_set).  AESGCM_EARG, and nothing stored,
+ *                            where offsets fall or a secret is empty or longer than max_secret_len.
+ *   aesgcm_sshkdf_set_dev    the same from DEVICE memory (d_secret_off: n + 1 uint32; no alignment asked) into the records d_idx[i]; an index out of range, falling
+ *                            offsets, an empty secret or one longer than max_secret_len is refused.
+ *   aesgcm_sshkdf_clear      records first .. first + n - 1 zeroed and unset.
+ *   aesgcm_sshkdf_status     as aesgcm_keytab_status: the LOWEST entry index an install or set_dev call refused since the last read, which clears it.
+ *   aesgcm_sshkdf_destroy    waits for the device, zeroes the records and the staging buffer, frees.
+ * INSTALL: aesgcm_sshkdf_install_dev(s, keytab, n, d_idx, d_c2s_slots, d_s2c_slots, stream).  For entry i with record d_idx[i], slot d_c2s_slots[i] of `keytab` becomes
+ * exactly what aesgcm_keytab_set_dev makes of the "C" key's first key_len bytes and aesgcm_keytab_set_tls_iv of the "A" value's first 12 -- round keys, H, its powers,
+ * nr, the set marker, the IV field -- which is what aesgcm_keytab_ssh_crypt_dev reads; slot d_s2c_slots[i] the same of "D" and "B".  Either array may be NULL (not
+ * both); an entry 0xFFFFFFFF installs nothing for that direction.  key_len is the key table's, 16 / 24 / 32 <= hash_len: RFC 4253's extension K2 = HASH(K | H | K1),
+ * for values longer than the digest, is NEVER NEEDED AND NOT BUILT.
+ * A RE-EXCHANGE (RFC 4253 9) is a set of the new K | H with the SAME session_id, then an install into fresh slots; d_seq starts at 0 under the new key.
+ * AESGCM_EARG, before a device is touched, for s or keytab NULL, d_idx NULL, both slot arrays NULL, n >= 2^31, a key table of another device; n == 0 is AESGCM_OK and
+ * looks at nothing.
+ * REFUSED ENTRIES are skipped whole -- NOTHING an entry names is written -- when d_idx[i] is out of range, the record is unset or cleared, or a slot is out of range.
+ * The lowest such index goes to THIS table's status word; the key table's status word is not touched.
+ * NO DERIVED KEY IN MEMORY: the lane that derives a key runs the key schedule itself, from its registers; the key goes nowhere but the slot's fields.
+ * One launch per call, a lane per entry and letter (k_sshk_install); no scratch memory, no allocation, no event, no host synchronisation, nothing read back: install is
+ * capture-safe (CAPTURE, under "key tables" above) and asynchronous on `stream`.  Ordering and thread safety as aesgcm_kdf_*.
+ * OUT OF SCOPE: the key exchange itself and the computation of H; RFC 4253's key extension; the integrity keys; chacha20-poly1305@openssh.com's 64-byte keys. */
+typedef struct aesgcm_sshkdf aesgcm_sshkdf;
+AESGCM_API int aesgcm_sshkdf_create(aesgcm_sshkdf **out, int device, size_t hash_len, size_t max_secret_len, size_t n_recs);
+AESGCM_API int aesgcm_sshkdf_set(aesgcm_sshkdf *s, size_t first, size_t n, const uint8_t *secrets, const uint32_t *secret_off, const uint8_t *session_ids, void *stream);
+AESGCM_API int aesgcm_sshkdf_set_dev(aesgcm_sshkdf *s, size_t n, const uint32_t *d_idx, const void *d_secrets, const uint32_t *d_secret_off, const void *d_session_ids,
+                              void *stream);
+AESGCM_API int aesgcm_sshkdf_clear(aesgcm_sshkdf *s, size_t first, size_t n, void *stream);
+AESGCM_API int aesgcm_sshkdf_install_dev(aesgcm_sshkdf *s, aesgcm_keytab *keytab, size_t n, const uint32_t *d_idx, const uint32_t *d_c2s_slots,
+                                  const uint32_t *d_s2c_slots, void *stream);
+AESGCM_API int aesgcm_sshkdf_status(aesgcm_sshkdf *s, int *code, uint64_t *detail);
+AESGCM_API int aesgcm_sshkdf_destroy(aesgcm_sshkdf *s);
 
 /* ---------------------------------------------------------------- streaming (beat-by-beat) interface
  * Mirrors the call order the reference harness drives its model with (tb/gcm_test.py:76-85 ->
